@@ -4,8 +4,10 @@
 One bench "step" = ONE complete 512x512 edit of BASELINE.json configs[1]: batch 1, 50 scheduler steps, each step =
 BlobNet (batch 1) + patched UNet (CFG batch 2) + crop/CFG/scheduler update, hipGraph-replayed, inputs resident in HBM.
 metric = edits/s over all ranks (weak scaling: every rank runs its own K edits, no data-path collective).
-Also emits `roofline` for the dominant kernel (HIP-event timed on the launch stream) and `cpu_baseline` (the CPU oracle,
-one denoise step of the same workload on the host cores, rank 0 / N=1 only).
+A plain run times only that: set-up, warm-up, the timed edits, the result line.  `--full` adds the optional blocks: `roofline` for
+the dominant kernel (HIP-event timed on the launch stream), `cpu_baseline` (the CPU oracle, one denoise step of the same workload on
+the host cores, rank 0 / N=1 only), `box_calibration`, the other configurations and the end-to-end timings.  `--dump-outputs DIR`
+writes what the last timed edit returned (rank 0) as DIR/latents.npy.
 """
 import argparse
 import json
@@ -722,8 +724,17 @@ def main():
     ap.add_argument("--requests", type=int, default=0,
                     help="BASELINE configs[3]: this many independent edit requests in total, sharded round-robin over the ranks "
                          "(dist.shard_requests) and run `--batch` at a time as per-request batches; 0 = `--steps` edits per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the optional blocks (CPU baseline, box calibration, roofline, other configurations, end to end); each "
+                         "can still be left out by its --no-* option.  Without --full only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the final latents of the last timed edit (rank 0) as DIR/latents.npy (float32)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:                                  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_calibration = args.no_roofline = args.no_configs = args.no_e2e = True
 
     if args.cpu_baseline_worker:                       # child of a bench run: CPU only (see start_cpu_baseline)
         return cpu_baseline_worker(args.res // 8, args.res // 8, args.denoise_steps)
@@ -801,14 +812,18 @@ def main():
     t0 = time.perf_counter()
     if args.requests:
         for rb in batches:
-            run_requests(rb)
+            out = run_requests(rb)
     else:
         for i in range(args.steps):
-            one_edit(rank * 1000 + i + 1)
+            out = one_edit(rank * 1000 + i + 1)
     torch.cuda.synchronize()
     if world > 1:
         tdist.barrier()
     dt = bdist.barrier_max_seconds(time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), out.detach().float().cpu().numpy())
     # The CPU baseline runs beside the optional blocks below (never beside the timed region above).  Its worker is pinned to socket 0:
     # move this process (host side of the roofline / configs / end-to-end blocks) OFF those CPUs first, and say in the line what ran
     # beside what.
