@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .engine import TrunkConfig, TrunkPlan
 from .launch import Recorder
-from .schedulers import DDIMTable, UniPCTable
+from .schedulers import DDIMTable, UniPCTable, draw_variance_noise, randn_tensor
 from .weights import PackedTrunk, pad8
 
 
@@ -77,10 +77,12 @@ class BlobCtrlEngine:
         self.text_encoder = text_encoder                              # optional blobctrl_amd.clip_text.CLIPTextModel
 
     # ------------------------------------------------------------------------------------------------ planning
-    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False):
+    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
-        conditioning scales) instead of B variations of one edit."""
-        key = (B, h, w, T, ctx_dim, nsteps, per_request)
+        conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 - the plan owns the named buffer
+        `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are per-call
+        contents of the coefficient table and of that buffer, so one plan and its graphs serve every eta > 0 and every seed)."""
+        key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic))
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -113,6 +115,8 @@ class BlobCtrlEngine:
         P.scale_table = rec.zeros(nsteps * Bi, dtype=f32, name="scale_table")   # [step][image] conditioning_scale * keep
         P.hist = rec.zeros(3, B * 4 * h * w, dtype=f32, name="hist")
         P.eps_guided = rec.zeros(B, 4, h, w, dtype=f32, name="eps_guided")
+        P.stochastic = bool(stochastic)
+        P.variance_noise = rec.zeros(nsteps, B, 4, h, w, dtype=f32, name="variance_noise") if stochastic else None
         P.guidance = [7.5]
 
         # rank-1 collapse of the BlobNet feature channels (per-edit weight; round 6: per-IMAGE weights for a batch of independent requests -
@@ -188,8 +192,12 @@ class BlobCtrlEngine:
             else:
                 eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=True)   # (images b and b + B: the CFG pair)
             P.eps = eps
-            rec.call("bc_cfg_scheduler_step", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.eps_guided, 1,
-                     kind="cfg_step")
+            if P.stochastic:
+                rec.call("bc_cfg_scheduler_step_noise", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.variance_noise,
+                         nsteps, P.eps_guided, 1, kind="cfg_step")
+            else:
+                rec.call("bc_cfg_scheduler_step", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.eps_guided, 1,
+                         kind="cfg_step")
 
         # ---- step A: BlobNet + UNet
         # The BlobNet branch is recorded for the side stream: fork (side waits for the start of the step on main), every
@@ -238,17 +246,36 @@ class BlobCtrlEngine:
         if params is not None:
             self.scheduler_params = (int(params[0]), float(params[1]), float(params[2]))
 
-    def _scheduler_table(self, n):
-        """Coefficient tables depend only on (scheduler, its beta configuration, steps)."""
-        key = (self.scheduler_kind, self.scheduler_params, n)
+    def _scheduler_table(self, n, eta=0.0):
+        """Coefficient tables depend only on (scheduler, its beta configuration, steps, DDIM eta)."""
+        key = (self.scheduler_kind, self.scheduler_params, n, float(eta))
         sched = self._sched_cache.get(key)
         if sched is None:
             nt, b0, b1 = self.scheduler_params
             cls = UniPCTable if self.scheduler_kind == "unipc" else DDIMTable
             sched = cls(num_train_timesteps=nt, beta_start=b0, beta_end=b1)
-            sched.set_timesteps(n)
+            if eta:
+                sched.set_timesteps(n, eta=float(eta))
+            else:
+                sched.set_timesteps(n)
             self._sched_cache[key] = sched
         return sched
+
+    def _check_eta(self, eta):
+        """eta > 0 is stochastic DDIM; UniPC has no eta (its step takes none, so the reference ignores it: refused here)."""
+        if eta < 0:
+            raise NotImplementedError(f"eta = {eta}: a negative eta is not a DDIM variance")
+        if eta != 0.0 and self.scheduler_kind != "ddim":
+            raise NotImplementedError(f"eta != 0 is supported with DDIM only (stochastic DDIM); the {self.scheduler_kind} scheduler "
+                                      "has no eta")
+        return eta > 0
+
+    @staticmethod
+    def variance_noise(num_steps, batch, h, w, generator=None, device="cuda"):
+        """The per-step `variance_noise` of a stochastic DDIM edit, [num_steps, batch, 4, h, w] fp32: drawn as DDIMScheduler.step draws
+        it (one randn_tensor per step, in step order; a CPU generator on the CPU, a list of generators one sample each, None = the global
+        RNG of `device`)."""
+        return draw_variance_noise(num_steps, (batch, 4, h, w), generator, device)
 
     def set_weights(self, unet_w=None, blob_w=None):
         """New packed weights (LoRA loaded / unloaded, conv_in edited): every cached plan and its graphs hold the old addresses."""
@@ -354,17 +381,21 @@ class BlobCtrlEngine:
                  output_type: str = "latent", callback_on_step_end=None, trace: Optional[list] = None,
                  teacher_latents: Optional[List[torch.Tensor]] = None, fg_image: Optional[torch.Tensor] = None,
                  bg_image: Optional[torch.Tensor] = None, return_sample: bool = False, eta: float = 0.0,
-                 do_classifier_free_guidance: Optional[bool] = None, callback_self=None):
+                 do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
+                 variance_noise: Optional[torch.Tensor] = None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
         Returns the final latents [B,4,h,w] fp32 for `output_type="latent"` (pipe:1143), else the decoded, denormalised
-        images ("pt" / "np", pipe:1132-1146)."""
+        images ("pt" / "np", pipe:1132-1146).
+        eta > 0 (DDIM only): stochastic DDIM.  The variance noise of every step is drawn from `generator` exactly as the reference's
+        scheduler.step draws it (after the start latents when those are drawn here; a list = one generator per sample; None = the
+        global RNG of the engine's device), or taken from `variance_noise` [num_inference_steps, B, 4, h, w].  It is drawn in fp32 (the
+        engine keeps fp32 latents); a reference pipeline running in fp16 would draw fp16 noise."""
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 (stochastic DDIM) is not supported: the scheduler tables are the eta = 0 update")
+        stochastic = self._check_eta(float(eta))
         if output_type not in ("latent", "pt", "np"):
             raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
         if output_type != "latent" and self.vae is None:
@@ -414,13 +445,27 @@ class BlobCtrlEngine:
             [blobnet_conditioning_scale] * Bi
         if len(req_scales) != Bi:
             raise ValueError(f"blobnet_conditioning_scale: expected {Bi} values, got {len(req_scales)}")
-        P = self._plan(B, h, w, T, Dc, n, per_request)
+        if isinstance(generator, list) and len(generator) != B:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                             f" size of {B}. Make sure the batch size matches the length of the generators.")
+        if variance_noise is not None:
+            if not stochastic:
+                raise ValueError("variance_noise is only used with eta > 0")
+            if generator is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                                 " `variance_noise` stays `None`.")
+            if tuple(variance_noise.shape) != (n, B, 4, h, w):
+                raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (steps, batch, 4, h, w), got "
+                                 f"{tuple(variance_noise.shape)}")
+        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0)
+        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic)
         dev = self.device
-        sched = self._scheduler_table(n)
         self.timesteps = sched.timesteps
         if latents is None:                                                          # pipe:438-453
-            latents = torch.randn((B, 4, h, w), generator=generator, device=generator.device if generator else "cpu",
-                                  dtype=torch.float32)
+            g0 = generator[0] if isinstance(generator, list) else generator
+            latents = randn_tensor((B, 4, h, w), generator, g0.device if g0 is not None else "cpu")
+        if stochastic and variance_noise is None:                                    # scheduling_ddim.py:455-458, after the latents
+            variance_noise = self.variance_noise(n, B, h, w, generator, dev)
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         scale_rows = [[sc * k for sc in req_scales] for k in keep]                   # [step][image]
         scales = [max(abs(v) for v in row) for row in scale_rows]                    # a step is BlobNet-free iff every scale is 0
@@ -444,6 +489,8 @@ class BlobCtrlEngine:
             coef[:, 11] = float(guidance_scale)          # read by the captured cfg/scheduler kernel
             P.coef.copy_(coef)
             P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
+            if stochastic:
+                P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
             P.step_idx.zero_()
             P.hist.zero_()
         P.guidance[0] = float(guidance_scale)
@@ -507,7 +554,7 @@ class BlobCtrlEngine:
         """`denoise(...)`; a plain tensor-level edit (explicit start latents, latent output, no callbacks / traces / images) goes through
         the dispatcher as torch.ops.blobctrl.denoise (ops.py), everything else calls `denoise` directly."""
         plain = {"num_inference_steps", "guidance_scale", "latents", "blobnet_conditioning_scale", "blobnet_control_guidance_start",
-                 "blobnet_control_guidance_end"}
+                 "blobnet_control_guidance_end", "eta", "variance_noise"}
         sc = kw.get("blobnet_conditioning_scale", 1.0)
         # (ints and anything else take `denoise` directly, which raises the reference's TypeError for them)
         is_list = isinstance(sc, (list, tuple))
@@ -519,20 +566,26 @@ class BlobCtrlEngine:
                                               int(kw.get("num_inference_steps", 50)), float(kw.get("guidance_scale", 7.5)),
                                               [float(v) for v in sc] if is_list else [float(sc)],
                                               float(kw.get("blobnet_control_guidance_start", 0.0)),
-                                              float(kw.get("blobnet_control_guidance_end", 1.0)), ops.register(self), is_list)
+                                              float(kw.get("blobnet_control_guidance_end", 1.0)), ops.register(self), is_list,
+                                              float(kw.get("eta", 0.0)), kw.get("variance_noise"))
         return self.denoise(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, **kw)
 
     def compile_plan(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale=7.5, blobnet_conditioning_scale=1.0,
-                     blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0):
+                     blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None):
         """Write the launch plan of one edit configuration as a relocatable `.bcplan` file for the C plan runtime
         (include/blobctrl_hip.h: bc_plan_load / bc_plan_buffer / bc_step / bc_plan_capture_loop): segments "prologue",
         "step_active", "step_inactive"; packed weights and the scheduler / guidance tables stored with their contents; the per-edit
         inputs are the NAMED buffers latents, fg_lat, bg_lat, fg_score, bg_score (fp32), feat (fp32) / feat16 (fp16, rank-1
         collapse), ctx (fp16 [2B][T][ctx_dim] = cat(negative, positive)); the result is read from `latents`.  Returns the per-step
-        segment names (which steps run BlobNet)."""
+        segment names (which steps run BlobNet).
+        eta > 0 (DDIM): a stochastic plan with the named buffer `variance_noise` [n][B][4][h][w] fp32, saved with `variance_noise`'s
+        contents when given (else zero-filled: a C host fills it through bc_plan_buffer before each edit)."""
         n = num_inference_steps
-        P = self._plan(B, h, w, T, ctx_dim, n, False)
-        sched = self._scheduler_table(n)
+        stochastic = self._check_eta(float(eta))
+        if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
+            raise ValueError(f"variance_noise needs eta > 0 and shape {(n, B, 4, h, w)}")
+        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0)
+        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic)
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         P.t_table.copy_(sched.timesteps.to(torch.float32))
         coef = sched.table().clone()
@@ -541,12 +594,20 @@ class BlobCtrlEngine:
         P.scale_table.copy_(torch.tensor([blobnet_conditioning_scale * k for k in keep], dtype=torch.float32))
         for t in (P.t_table, P.coef, P.scale_table):                 # constants of this configuration: saved WITH their contents
             P.rec._workspace.discard(t.untyped_storage().data_ptr())
+        if stochastic:
+            key = P.variance_noise.untyped_storage().data_ptr()
+            if variance_noise is not None:
+                P.variance_noise.copy_(variance_noise.to(P.variance_noise.device, torch.float32))
+                P.rec._workspace.discard(key)
+            else:
+                P.variance_noise.zero_()
+                P.rec._workspace.add(key)
         P.rec.save(path)
         return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
 
     # convenience for bench / tests ------------------------------------------------------------------
-    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request)
+    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic)
 
 
 # ======================================================================================================================
@@ -921,7 +982,8 @@ class StableDiffusionBlobNetPipeline:
                                     blobnet_conditioning_scale=blobnet_conditioning_scale,
                                     blobnet_control_guidance_start=blobnet_control_guidance_start[0],
                                     blobnet_control_guidance_end=blobnet_control_guidance_end[0], output_type="latent",
-                                    callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg)
+                                    callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
+                                    generator=generator)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

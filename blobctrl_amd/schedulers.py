@@ -10,11 +10,14 @@ whose scalar coefficients are precomputed here per step index, uploaded once, an
     [2] use_corrector
     [3] cc_x [4] cc_m0 [5] cc_m1 [6] cc_mt                 x_c  = c3*last + c4*x0_{i-1} + c5*x0_{i-2} + c6*x0      (UniC)
     [7] cp_x [8] cp_m0 [9] cp_m1 [10] cp_eps               x'   = c7*x_c + c8*x0 + c9*x0_{i-1} + c10*eps           (UniP / DDIM)
+    [11] guidance scale (filled by the engine)
+    [12] std_dev_t                                         x'  += c12*noise[i]     (stochastic DDIM, eta > 0; 0 otherwise)
 Scalar maths follows the reference in fp32 torch CPU ops (same operation order) so the tables match it to rounding.
 
 SD-1.5 scheduler config: betas 0.00085 -> 0.012 scaled_linear, 1000 train steps, steps_offset 1,
 epsilon prediction; UniPC: solver_order 2, bh2, predict_x0, lower_order_final, linspace spacing, final sigma 0;
-DDIM: leading spacing, clip_sample False, set_alpha_to_one False, eta 0.
+DDIM: leading spacing, clip_sample False, set_alpha_to_one False; eta >= 0 (eta > 0 adds std_dev_t * variance_noise, the noise being
+drawn on the host in the reference's order: scheduling_ddim.py:438-466).
 """
 import numpy as np
 import torch
@@ -146,38 +149,74 @@ class UniPCTable(_Base):
 
 
 class DDIMTable(_Base):
-    """DDIMScheduler (eta = 0) as a coefficient table (scheduling_ddim.py:297-340, 342-468)."""
+    """DDIMScheduler as a coefficient table (scheduling_ddim.py:253-261, 297-340, 342-468); eta > 0 fills column 12 with std_dev_t."""
 
-    def set_timesteps(self, n, device=None):
+    def set_timesteps(self, n, device=None, eta=0.0):
         ratio = self.num_train // n
         ts = (np.arange(0, n) * ratio).round()[::-1].copy().astype(np.int64) + 1
         self.timesteps = torch.from_numpy(ts)
         self.num_inference_steps = n
+        self.eta = float(eta)
         coef = torch.zeros(n, 16, dtype=torch.float32)
         final_alpha = self.alphas_cumprod[0]
         for i, t in enumerate(ts.tolist()):
             prev_t = t - ratio
             a_t = self.alphas_cumprod[t]
             a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else final_alpha
+            variance = ((1 - a_prev) / (1 - a_t)) * (1 - a_t / a_prev)
+            std = eta * variance ** 0.5
             coef[i, 0] = 1.0 / a_t ** 0.5
             coef[i, 1] = (1 - a_t) ** 0.5 / a_t ** 0.5
             coef[i, 8] = a_prev ** 0.5
-            coef[i, 10] = (1 - a_prev) ** 0.5
+            coef[i, 10] = (1 - a_prev - std ** 2) ** 0.5
+            coef[i, 12] = std
+            if not torch.isfinite(coef[i]).all():
+                raise ValueError(f"eta = {eta}: DDIM step {i} (timestep {t}) has 1 - alpha_prev - std_dev_t^2 < 0, "
+                                 "no finite update (the reference would produce NaN latents)")
         self.coef = coef
         return self
 
 
-def apply_table_step(coef_row, eps, x, hist):
-    """Host (torch) evaluation of one table row - the same arithmetic `bc_cfg_scheduler_step` performs after CFG.
-    Used by the drop-in scheduler objects; `hist` = dict(m0, m1, last)."""
+def apply_table_step(coef_row, eps, x, hist, noise=None):
+    """Host (torch) evaluation of one table row - the same arithmetic `bc_cfg_scheduler_step` (and, with `noise`,
+    `bc_cfg_scheduler_step_noise`) performs after CFG.  Used by the drop-in scheduler objects; `hist` = dict(m0, m1, last)."""
     c = coef_row
     x0 = x * c[0] - eps * c[1]
     xc = x
     if c[2] != 0:
         xc = c[3] * hist["last"] + c[4] * hist["m0"] + c[5] * hist["m1"] + c[6] * x0
     xn = c[7] * xc + c[8] * x0 + c[9] * hist["m0"] + c[10] * eps
+    if noise is not None:
+        xn = xn + c[12] * noise
     hist["m1"], hist["m0"], hist["last"] = hist["m0"], x0, xc
     return xn
+
+
+def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):
+    """D/utils/torch_utils.py:38-83: a CPU generator draws on the CPU (then the tensor moves to `device`), a list of generators draws
+    one [1, ...] slice per sample (a one-element list counts as its generator), None uses the global RNG of `device`."""
+    device = torch.device(device) if device is not None else torch.device("cpu")
+    rand_device = device
+    if generator is not None:
+        gtype = generator[0].device.type if isinstance(generator, list) else generator.device.type
+        if gtype != device.type and gtype == "cpu":
+            rand_device = torch.device("cpu")
+        elif gtype != device.type:
+            raise ValueError(f"Cannot generate a {device} tensor from a generator of type {gtype}.")
+    if isinstance(generator, list) and len(generator) == 1:
+        generator = generator[0]
+    if isinstance(generator, list):
+        if len(generator) != shape[0]:
+            raise ValueError(f"a list of {len(generator)} generators for a batch of {shape[0]}")
+        one = (1,) + tuple(shape[1:])
+        return torch.cat([torch.randn(one, generator=g_, device=rand_device, dtype=dtype) for g_ in generator], 0).to(device)
+    return torch.randn(tuple(shape), generator=generator, device=rand_device, dtype=dtype).to(device)
+
+
+def draw_variance_noise(num_steps, shape, generator=None, device=None):
+    """The `variance_noise` of every step of a stochastic DDIM edit, [num_steps, *shape] fp32 on `device`: one `randn_tensor(shape,
+    generator, device)` per step, in step order - the draws `DDIMScheduler.step` makes (scheduling_ddim.py:455-458)."""
+    return torch.stack([randn_tensor(shape, generator, device) for _ in range(num_steps)], 0)
 
 
 class TableScheduler:
@@ -318,7 +357,8 @@ class UniPCMultistepScheduler(_ConfiguredScheduler):
 
 
 class DDIMScheduler(_ConfiguredScheduler):
-    """Drop-in for diffusers' DDIMScheduler with the SD-1.5 scheduler_config.json values (eta = 0)."""
+    """Drop-in for diffusers' DDIMScheduler with the SD-1.5 scheduler_config.json values; `step(..., eta=, generator=,
+    variance_noise=)` as in scheduling_ddim.py:342-468 (eta > 0: stochastic DDIM, noise drawn with the reference's randn_tensor)."""
     _kind = "ddim"
     _defaults = dict(clip_sample=False, set_alpha_to_one=False, timestep_spacing="leading", thresholding=False)
 
@@ -326,3 +366,40 @@ class DDIMScheduler(_ConfiguredScheduler):
         if cfg["clip_sample"] or cfg["set_alpha_to_one"] or cfg["timestep_spacing"] != "leading" or cfg["steps_offset"] != 1 or \
                 cfg["thresholding"]:
             raise NotImplementedError("DDIM is tabulated for clip_sample=False, set_alpha_to_one=False, leading spacing, steps_offset=1")
+
+    def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None, variance_noise=None,
+             return_dict=True):
+        """One DDIM update.  (use_clipped_model_output changes nothing without clipping or thresholding, which this configuration
+        has neither of.)  Returns `(prev_sample,)`, or an object with `.prev_sample` for return_dict=True."""
+        if eta < 0:
+            raise NotImplementedError("eta < 0 is not a DDIM variance")
+        if self._hist is None:
+            z = torch.zeros_like(sample)
+            self._hist = dict(m0=z, m1=z.clone(), last=z.clone())
+        tab = self.table_impl
+        if float(eta) != getattr(tab, "eta", 0.0):                     # (re)tabulate for this eta; raises for a non-finite row
+            tab.set_timesteps(tab.num_inference_steps, eta=float(eta))
+        noise = None
+        if eta > 0:
+            if variance_noise is not None and generator is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                                 " `variance_noise` stays `None`.")
+            noise = variance_noise if variance_noise is not None else \
+                randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        row = tab.coef[self._i].tolist()
+        out = apply_table_step(row, model_output, sample, self._hist, noise)
+        self._i += 1
+        if not return_dict:
+            return (out,)
+        return _StepOutput(out)
+
+
+class _StepOutput(tuple):
+    """`DDIMSchedulerOutput`-like: `.prev_sample`, and indexable like the tuple form."""
+
+    def __new__(cls, prev_sample):
+        return super().__new__(cls, (prev_sample,))
+
+    @property
+    def prev_sample(self):
+        return self[0]

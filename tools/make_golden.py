@@ -176,6 +176,115 @@ def golden_schedulers():
     print("schedulers: unipc50 t0..2", out["unipc_50_timesteps"][:3], "ddim50", out["ddim_50_timesteps"][:3])
 
 
+def golden_schedulers_eta():
+    """Stochastic DDIM (scheduling_ddim.py:342-468 with eta > 0): reference trajectories with an explicit `variance_noise` per step
+    (noise_i = g(200 + i)), same inputs as golden_schedulers, plus one run that draws the noise from a CPU generator."""
+    out = {}
+    for n in (5, 20, 50):
+        for eta in (0.3, 1.0):
+            sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+            sch.set_timesteps(n)
+            x = g(21, 1, 4, 8, 8)
+            xs = [x.numpy()]
+            for i, t in enumerate(sch.timesteps):
+                x = sch.step(g(100 + i, 1, 4, 8, 8), t, x, eta=eta, variance_noise=g(200 + i, 1, 4, 8, 8), return_dict=False)[0]
+                xs.append(x.numpy())
+            out[f"ddim_{n}_eta{int(round(eta * 10)):02d}_traj"] = np.stack(xs)
+    sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+    sch.set_timesteps(5)
+    gen = torch.Generator().manual_seed(77)
+    x = g(21, 1, 4, 8, 8)
+    xs = [x.numpy()]
+    for i, t in enumerate(sch.timesteps):
+        x = sch.step(g(100 + i, 1, 4, 8, 8), t, x, eta=1.0, generator=gen, return_dict=False)[0]
+        xs.append(x.numpy())
+    out["ddim_5_eta10_gen77_traj"] = np.stack(xs)
+    np.savez_compressed(os.path.join(OUT, "schedulers_eta.npz"), **out)
+    print("schedulers_eta:", sorted(out))
+
+
+class _TapNoise:
+    """Records every `randn_tensor` call DDIMScheduler.step makes (the variance noise the reference drew), in call order."""
+
+    def __init__(self):
+        import diffusers.schedulers.scheduling_ddim as m
+        self.m, self.orig, self.drawn = m, m.randn_tensor, []
+
+    def __enter__(self):
+        def tapped(*a, **k):
+            r = self.orig(*a, **k)
+            self.drawn.append(r.detach().clone())
+            return r
+        self.m.randn_tensor = tapped
+        return self
+
+    def __exit__(self, *exc):
+        self.m.randn_tensor = self.orig
+
+
+def golden_loop_eta():
+    """golden_loop's body (tiny nets, CFG 7.5, DDIM) with stochastic steps: `sch.step(eps, t, x, eta=, generator=CPU generator)`.
+    Stores the final latents, the latents entering every step (teacher-forcing inputs), the guided eps and the noise the reference
+    drew; plus `randn_tensor` with a list of three generators (one sample each), for the noise-drawing helper."""
+    from diffusers.utils.torch_utils import randn_tensor
+    unet, blob = build_tiny()
+    c = TINY
+    h = w = 8
+    B = 1
+    out = {}
+    pipe = StableDiffusionBlobNetPipeline.__new__(StableDiffusionBlobNetPipeline)
+    for steps, (gs, ge), eta, seed in ((5, (0.0, 1.0), 1.0, 1234), (6, (0.0, 0.67), 0.5, 4321)):
+        sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+        sch.set_timesteps(steps)
+        gen = torch.Generator().manual_seed(seed)
+        latents = g(31, B, 4, h, w) * sch.init_noise_sigma
+        prompt = g(32, 2 * B, 7, c["ctx"])
+        fg_lat = (g(33, 1, 4, h, w) * 0.18215 * 5).repeat(2 * B, 1, 1, 1)
+        bg_lat = (g(34, 1, 4, h, w) * 0.18215 * 5).repeat(2 * B, 1, 1, 1)
+        ell = [[40.0, 42.0], [20.0, 30.0], 25.0]
+        mean, cov = ref_inf.get_gs_from_ellipse(ell)
+        nm, nc = ref_inf.normalize_gs(mean, cov, 64, 64)
+        gs_score = splat_features(**ref_inf.get_blob_dict_from_norm_gs(nm, nc), score_size=(h, w), return_d_score=True)
+        bg_s, fg_s = gs_score.unbind(dim=1)
+        bg_s = bg_s.unsqueeze(1).repeat(2 * B, 1, 1, 1).float()
+        fg_s = fg_s.unsqueeze(1).repeat(2 * B, 1, 1, 1).float()
+        dino = g(35, 1, 1, c["feat"])
+        feats = pipe.splat_features_from_scores(fg_s, dino.repeat(2 * B, 1, 1), size=h, channels_last=False)
+        keep = [1.0 - float(i / steps < gs or (i + 1) / steps > ge) for i in range(steps)]
+        eps_trace, lat_trace = [], []
+        with _TapNoise() as tap:
+            for i, t in enumerate(sch.timesteps):
+                lat_trace.append(latents.numpy().copy())
+                lmi = sch.scale_model_input(torch.cat([latents] * 2), t)
+                bi = pipe.construct_blobnet_input(lmi, fg_s, fg_lat, feats, background=False)
+                d, m, u = blob(bi, t, conditioning_scale=1.0 * keep[i], return_dict=False)
+                ui = pipe.construct_blobnet_input(lmi, bg_s, bg_lat, background=True)
+                npred = unet(ui, t, encoder_hidden_states=prompt, down_block_add_samples=[x[..., -x.shape[-2]:] for x in d],
+                             mid_block_add_sample=m[..., -m.shape[-2]:], up_block_add_samples=[x[..., -x.shape[-2]:] for x in u],
+                             return_dict=False)[0]
+                b_, c_, h_, w_ = npred.shape
+                npred = npred[..., :h_, w_ // 2:]
+                nu, nt = npred.chunk(2)
+                npred = nu + 7.5 * (nt - nu)
+                eps_trace.append(npred.numpy())
+                latents = sch.step(npred, t, latents, eta=eta, generator=gen, return_dict=False)[0]
+        assert len(tap.drawn) == steps
+        tag = f"ddim_{steps}"
+        out[f"{tag}_final"] = latents.numpy()
+        out[f"{tag}_eps"] = np.stack(eps_trace)
+        out[f"{tag}_lat"] = np.stack(lat_trace)
+        out[f"{tag}_noise"] = torch.stack(tap.drawn).numpy()
+        out[f"{tag}_window"] = np.array([gs, ge])
+        out[f"{tag}_eta"] = np.array(eta)
+        out[f"{tag}_seed"] = np.array(seed)
+        print(f"loop_eta {tag}: eta {eta}, final std {latents.std():.4f}")
+    gens = [torch.Generator().manual_seed(s_) for s_ in (11, 12, 13)]
+    out["list3_seeds"] = np.array([11, 12, 13])
+    out["list3_noise"] = torch.stack([randn_tensor((3, 4, h, w), generator=gens, device=torch.device("cpu"), dtype=torch.float32)
+                                      for _ in range(2)]).numpy()
+    np.savez_compressed(os.path.join(OUT, "loop_tiny_eta.npz"), **out)
+
+
 # ------------------------------------------------------------------------------------------------ 4. pipeline loop
 class _FakeVaeCfg:
     scaling_factor = 0.18215
@@ -724,14 +833,11 @@ def golden_blob_edit_cv():
     print("blob_edit_cv:", names, os.path.getsize(os.path.join(OUT, "blob_edit_cv.npz")) // 1024, "KB")
 
 
-def golden_pipeline_call():
-    """The REFERENCE pipeline's own `__call__` (pipe:743-1166) end to end on tiny components: PIL images + prompt strings in, latents
-    (and one decoded image) out - tokenizer stand-in, CLIP, VAE encode (global-generator posterior samples), DINOv2 processor + model,
-    rank-1 splat, BlobNet + patched UNet loop, scheduler, VAE decode, VaeImageProcessor.postprocess."""
-    from PIL import Image
+def _tiny_pipeline_components():
+    """The reference classes of golden_pipeline_call on the tiny weights: (unet, blobnet, vae, text encoder, DINOv2 processor, DINOv2)."""
     from diffusers import AutoencoderKL
     from transformers import BitImageProcessor, CLIPTextConfig, CLIPTextModel, Dinov2Config, Dinov2Model
-    from tests.common import PIPE, FakeTokenizer, pipeline_cases, tiny_pipeline_weights
+    from tests.common import PIPE, tiny_pipeline_weights
     c = TINY
     unet5, blob = build_tiny()
     # the script's construction (inf:229-249): a 4-channel UNet whose conv_in is replaced by a 5-channel one; config.in_channels stays 4
@@ -763,6 +869,16 @@ def golden_pipeline_call():
     proc = BitImageProcessor(do_resize=True, size={"shortest_edge": 256}, resample=3, do_center_crop=True,
                              crop_size={"height": 224, "width": 224}, do_rescale=True, rescale_factor=1 / 255, do_normalize=True,
                              image_mean=[0.485, 0.456, 0.406], image_std=[0.229, 0.224, 0.225], do_convert_rgb=True)
+    return unet, blob, vae, te, proc, dino
+
+
+def golden_pipeline_call():
+    """The REFERENCE pipeline's own `__call__` (pipe:743-1166) end to end on tiny components: PIL images + prompt strings in, latents
+    (and one decoded image) out - tokenizer stand-in, CLIP, VAE encode (global-generator posterior samples), DINOv2 processor + model,
+    rank-1 splat, BlobNet + patched UNet loop, scheduler, VAE decode, VaeImageProcessor.postprocess."""
+    from PIL import Image
+    from tests.common import FakeTokenizer, pipeline_cases
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
     rng = np.random.Generator(np.random.PCG64(3))
     # smooth-ish images (random low-res blocks upsampled) so that resize filters matter but nothing saturates
     def img(h, w):
@@ -822,6 +938,53 @@ def golden_pipeline_call():
             out[f"{name}_image_np"] = np.asarray(r.images)
         print(f"pipeline __call__ {name}: latents std {out[f'{name}_latents'].std():.4f}")
     np.savez_compressed(os.path.join(OUT, "pipeline_call.npz"), **out)
+
+
+def golden_pipeline_call_eta():
+    """The reference's own `__call__` (pipe:743-1166) with DDIM, eta = 1.0 and a CPU `generator`: the generator draws the start latents
+    (pipe:438-453), then every scheduler step's variance noise (pipe:313-327, 1102).  Case = `ddim_neg2` of pipeline_call.npz (two
+    prompts, negative prompts) with its own seeds; the images and scores are those of pipeline_call.npz.  Stores the final latents,
+    the noise tapped from scheduler.step and the loop-entry tensors."""
+    from PIL import Image
+    from tests.common import FakeTokenizer, pipeline_cases
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"], seed=2024, rng_seed=21)
+    kw.pop("scheduler")
+    sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+    pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                          safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+    pipe.set_progress_bar_config(disable=True)
+    entry = {"lat": []}
+
+    def tap(fn, key):
+        def wrapped(*a, **k_):
+            r_ = fn(*a, **k_)
+            if key == "lat":
+                entry["lat"].append(r_.detach().clone())
+            else:
+                entry[key] = r_
+            return r_
+        return wrapped
+    pipe.encode_prompt = tap(pipe.encode_prompt, "prompt")
+    pipe.encode_latents = tap(pipe.encode_latents, "lat")
+    pipe.encode_image_dinov2 = tap(pipe.encode_image_dinov2, "dino")
+    seed, rng_seed = kw.pop("seed"), kw.pop("rng_seed")
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "eta": np.array(1.0)}
+    torch.manual_seed(rng_seed)
+    with _TapNoise() as noise:
+        r = pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                 height=64, width=64, eta=1.0, generator=torch.Generator().manual_seed(seed), output_type="latent", **kw)
+    assert len(noise.drawn) == kw["num_inference_steps"]
+    out["latents"] = r.images.numpy()
+    out["noise"] = torch.stack(noise.drawn).numpy()
+    pe, ne = entry["prompt"]
+    out["entry_prompt_embeds"], out["entry_negative_prompt_embeds"] = pe.numpy(), ne.numpy()
+    out["entry_fg_latents"] = entry["lat"][0][:1].numpy()
+    out["entry_bg_latents"] = entry["lat"][1][:1].numpy()
+    out["entry_dino"] = entry["dino"].numpy()
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_eta.npz"), **out)
+    print(f"pipeline __call__ eta=1: latents std {out['latents'].std():.4f}, noise {out['noise'].shape}")
 
 
 def golden_blocks():
@@ -894,6 +1057,9 @@ if __name__ == "__main__":
     golden_nets()
     golden_loop()
     golden_blocks()
+    golden_schedulers_eta()
+    golden_loop_eta()
+    golden_pipeline_call_eta()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))

@@ -7,7 +7,14 @@ compiled against host addresses and is relocatable.  Weights come from blobctrl_
     <out>/tiny_edit_io.bin            u32 count, then per record: char name[32], u64 bytes, data  (inputs named like the plan's
                                       buffers; "expected_latents" = the reference loop's final latents; "sequence" = int32 per step,
                                       1 = step_active)
+
+`--eta ETA` compiles the stochastic-DDIM edit of tests/golden/loop_tiny_eta.npz instead (5 steps, window [0, 1], ETA must be that
+run's eta): the plan then also holds the named buffer `variance_noise` [5][1][4][8][8] with the noise the reference drew embedded, and
+"expected_latents" is that run's final latents.
+
+    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA]
 """
+import argparse
 import os
 import struct
 import sys
@@ -22,18 +29,30 @@ from tests.common import TINY, g, tiny_weights  # noqa: E402
 from tests.gpu_common import tiny_trunk_configs  # noqa: E402
 
 GOLD = os.path.join(REPO, "tests", "golden")
-OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "gpurun_out", "plan_fixture")
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default=os.path.join(REPO, "build", "plan_fixture"))
+    ap.add_argument("--eta", type=float, default=0.0, help="stochastic DDIM: the eta of loop_tiny_eta.npz's 5-step run")
+    args = ap.parse_args()
+    OUT = args.out
     os.makedirs(OUT, exist_ok=True)
     z = np.load(os.path.join(GOLD, "loop_tiny.npz"))
+    extra, expected = {}, z["ddim_5_final"]
+    if args.eta:
+        ze = np.load(os.path.join(GOLD, "loop_tiny_eta.npz"))
+        if float(ze["ddim_5_eta"]) != args.eta:
+            sys.exit(f"--eta {args.eta}: the 5-step run of loop_tiny_eta.npz was drawn with eta = {float(ze['ddim_5_eta'])}")
+        extra = dict(eta=args.eta, variance_noise=torch.from_numpy(ze["ddim_5_noise"]))
+        expected = ze["ddim_5_final"]
     usd, bsd = tiny_weights()
     ucfg, bcfg = tiny_trunk_configs()
     eng = BlobCtrlEngine(usd, bsd, ucfg, bcfg, device="cpu", scheduler="ddim", compile_only=True)
     B, h, w, T, steps = 1, 8, 8, 7, 5
     seq = eng.compile_plan(os.path.join(OUT, "tiny_edit.bcplan"), B, h, w, T, TINY["ctx"], steps, guidance_scale=7.5,
-                           blobnet_conditioning_scale=1.0, blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0)
+                           blobnet_conditioning_scale=1.0, blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0,
+                           **extra)
     score = torch.from_numpy(z["gs_score"]).float()                     # [1,2,h,w] = (bg, fg)
     dino = g(35, 1, 1, TINY["feat"])
     feat16 = torch.zeros(1, 8, dtype=torch.float16)
@@ -47,7 +66,7 @@ def main():
         "fg_score": score[:, 1].contiguous().numpy(),
         "feat": dino.reshape(1, -1).numpy(),
         "feat16": feat16.numpy(),
-        "expected_latents": z["ddim_5_final"].astype(np.float32),
+        "expected_latents": expected.astype(np.float32),
         "sequence": np.array([1 if s == "step_active" else 0 for s in seq], np.int32),
     }
     with open(os.path.join(OUT, "tiny_edit_io.bin"), "wb") as f:
