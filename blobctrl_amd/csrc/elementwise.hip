@@ -138,7 +138,8 @@ __global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, long
 //  [3] cc_x (last_sample) [4] cc_m0 (prev x0) [5] cc_m1 (prev-prev x0) [6] cc_mt (this x0)      x_c = sum
 //  [7] cp_x (x_c)         [8] cp_m0 (this x0) [9] cp_m1 (prev x0)  [10] cp_eps (guided eps)     x_next = sum
 //  [11] guidance scale (used when the launch argument is negative: lets a captured graph follow per-call values)
-//  [12] std_dev_t (stochastic DDIM, eta > 0): x_next += c12 * noise[step]   (cfg_step_noise_kernel only)
+//  [12] std_dev_t (stochastic DDIM, eta > 0; SDE-DPM-Solver++): x_next += c12 * noise[step]   (cfg_step_noise_kernel only)
+//  [13] cp_m2 (prev-prev x0, third-order DPM-Solver++): x_next += c13 * x0_{i-2}               (cfg_step3_kernel only)
 __global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
                                 int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
                                 float* __restrict__ eps_out) {
@@ -206,6 +207,40 @@ __global__ void cfg_step_noise_kernel(const float* __restrict__ eps, float* __re
     m0[i] = x0;
     last[i] = xc;
     latents[i] = xn + cf[12] * noise[(size_t)step * n + i];
+}
+
+// cfg_step_kernel plus the x0_{i-2} term of third-order DPM-Solver++ (scheduling_dpmsolver_multistep.py:804-887): x_next +=
+// coef[step][13] * x0_{i-2}, read from the hist slot m1 that every step kernel already loads.  Like cfg_step_noise_kernel, a step index
+// at or past nsteps has no table row: the launch then leaves every buffer as it is.
+__global__ void cfg_step3_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
+                                 const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
+                                 int nsteps, float* __restrict__ eps_out) {
+    const int n = B * 4 * h * w;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int step = *step_idx;
+    if (i >= n || step < 0 || step >= nsteps) return;
+    const float* cf = coef + (size_t)step * 16;
+    const int xx = i % w;
+    const int yy = (i / w) % h;
+    const int c = (i / (w * h)) % 4;
+    const int b = i / (4 * w * h);
+    const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
+    const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
+    const float eu = eps[pu], ec = eps[pc];
+    const float gscale = guidance >= 0.f ? guidance : cf[11];
+    const float e = eu + gscale * (ec - eu);
+    if (eps_out) eps_out[i] = e;
+    const float x = latents[i];
+    float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
+    const float x0 = x * cf[0] - e * cf[1];
+    float xc = x;
+    const float pm0 = m0[i], pm1 = m1[i];
+    if (cf[2] != 0.f) xc = cf[3] * last[i] + cf[4] * pm0 + cf[5] * pm1 + cf[6] * x0;
+    const float xn = cf[7] * xc + cf[8] * x0 + cf[9] * pm0 + cf[10] * e;
+    m1[i] = pm0;
+    m0[i] = x0;
+    last[i] = xc;
+    latents[i] = xn + cf[13] * pm1;
 }
 
 
@@ -403,6 +438,23 @@ extern "C" int bc_cfg_scheduler_step_noise(const float* eps, float* latents, con
     int n = B * 4 * h * w;
     hipLaunchKernelGGL(cfg_step_noise_kernel, dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef, step_idx, hist,
                        guidance_scale, B, h, w, noise, nsteps, eps_out);
+    BC_CHECK_LAUNCH();
+    if (advance) {
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
+        BC_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" int bc_cfg_scheduler_step3(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
+                                      float guidance_scale, int B, int h, int w, int nsteps, float* eps_out, int advance,
+                                      bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0,
+                 "bc_cfg_scheduler_step3: bad args");
+    int n = B * 4 * h * w;
+    hipLaunchKernelGGL(cfg_step3_kernel, dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef, step_idx, hist,
+                       guidance_scale, B, h, w, nsteps, eps_out);
     BC_CHECK_LAUNCH();
     if (advance) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);

@@ -118,6 +118,9 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
         case BC_OP_CFG_SCHEDULER_STEP_NOISE:
             return bc_cfg_scheduler_step_noise(CP(float, 0), MP(float, 1), CP(float, 2), MP(int, 3), MP(float, 4), F(5), I(6), I(7), I(8),
                                                CP(float, 9), I(10), MP(float, 11), I(12), s);
+        case BC_OP_CFG_SCHEDULER_STEP3:
+            return bc_cfg_scheduler_step3(CP(float, 0), MP(float, 1), CP(float, 2), MP(int, 3), MP(float, 4), F(5), I(6), I(7), I(8),
+                                          I(9), MP(float, 10), I(11), s);
         case BC_OP_EMBED_TOKENS:
             return bc_embed_tokens(CP(long long, 0), CP(bc_half, 1), CP(float, 2), I(3), I(4), I(5), I(6), MP(bc_half, 7), s);
         case BC_OP_SOFTMAX_ROWS: return bc_softmax_rows(MP(bc_half, 0), I(1), I(2), I(3), s);

@@ -36,6 +36,7 @@ inline const char* op_signature(int op) {
         case BC_OP_TIMESTEP_EMBEDDING_TABLE: return "piiip";
         case BC_OP_CFG_SCHEDULER_STEP: return "pppppfiiipi";
         case BC_OP_CFG_SCHEDULER_STEP_NOISE: return "pppppfiiipipi";
+        case BC_OP_CFG_SCHEDULER_STEP3: return "pppppfiiiipi";
         case BC_OP_EMBED_TOKENS: return "pppiiiip";
         case BC_OP_SOFTMAX_ROWS: return "piii";
         case BC_OP_PATCHIFY: return "piiiiip";

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .engine import TrunkConfig, TrunkPlan
 from .launch import Recorder
-from .schedulers import DDIMTable, UniPCTable, draw_variance_noise, randn_tensor
+from .schedulers import DDIMTable, DPMSolverMultistepTable, UniPCTable, draw_variance_noise, randn_tensor
 from .weights import PackedTrunk, pad8
 
 
@@ -77,12 +77,16 @@ class BlobCtrlEngine:
         self.text_encoder = text_encoder                              # optional blobctrl_amd.clip_text.CLIPTextModel
 
     # ------------------------------------------------------------------------------------------------ planning
-    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False):
+    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
-        conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 - the plan owns the named buffer
-        `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are per-call
-        contents of the coefficient table and of that buffer, so one plan and its graphs serve every eta > 0 and every seed)."""
-        key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic))
+        conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
+        named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
+        per-call contents of the coefficient table and of that buffer, so one plan and its graphs serve every eta > 0 and every seed).
+        third_order: a table with third-order DPM-Solver++ rows (column 13) - the steps end in bc_cfg_scheduler_step3.  Every other
+        table (UniPC, DDIM, DPM-Solver++ of order 1 / 2) runs on the same plan: only the tables differ."""
+        if stochastic and third_order:
+            raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
+        key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -116,6 +120,7 @@ class BlobCtrlEngine:
         P.hist = rec.zeros(3, B * 4 * h * w, dtype=f32, name="hist")
         P.eps_guided = rec.zeros(B, 4, h, w, dtype=f32, name="eps_guided")
         P.stochastic = bool(stochastic)
+        P.third_order = bool(third_order)
         P.variance_noise = rec.zeros(nsteps, B, 4, h, w, dtype=f32, name="variance_noise") if stochastic else None
         P.guidance = [7.5]
 
@@ -195,6 +200,9 @@ class BlobCtrlEngine:
             if P.stochastic:
                 rec.call("bc_cfg_scheduler_step_noise", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.variance_noise,
                          nsteps, P.eps_guided, 1, kind="cfg_step")
+            elif P.third_order:
+                rec.call("bc_cfg_scheduler_step3", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, nsteps, P.eps_guided, 1,
+                         kind="cfg_step")
             else:
                 rec.call("bc_cfg_scheduler_step", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.eps_guided, 1,
                          kind="cfg_step")
@@ -238,20 +246,37 @@ class BlobCtrlEngine:
         return P
 
     def set_scheduler(self, kind, params=None):
-        """`kind` "unipc" | "ddim"; `params` = (num_train_timesteps, beta_start, beta_end) of the scheduler's configuration (the
-        drop-in scheduler objects accept non-default betas: the engine must tabulate the SAME alphas)."""
-        if kind not in ("unipc", "ddim"):
-            raise NotImplementedError(f"scheduler {kind!r} has no coefficient table (UniPC and DDIM have)")
+        """`kind` "unipc" | "ddim" | "dpmsolver"; `params` = (num_train_timesteps, beta_start, beta_end) of the scheduler's configuration
+        (the drop-in scheduler objects accept non-default betas: the engine must tabulate the SAME alphas); for "dpmsolver" a fourth entry
+        holds the DPM-Solver options as (key, value) pairs (`DPMSolverMultistepScheduler.table_params()`; missing = diffusers' defaults)."""
+        if kind not in ("unipc", "ddim", "dpmsolver"):
+            raise NotImplementedError(f"scheduler {kind!r} has no coefficient table (UniPC, DDIM and DPM-Solver have)")
         self.scheduler_kind = kind
         if params is not None:
-            self.scheduler_params = (int(params[0]), float(params[1]), float(params[2]))
+            p = (int(params[0]), float(params[1]), float(params[2]))
+            if kind == "dpmsolver" and len(params) > 3:
+                p += (tuple(sorted((str(k), v) for k, v in dict(params[3]).items())),)
+            self.scheduler_params = p
 
-    def _scheduler_table(self, n, eta=0.0):
-        """Coefficient tables depend only on (scheduler, its beta configuration, steps, DDIM eta)."""
-        key = (self.scheduler_kind, self.scheduler_params, n, float(eta))
+    def _scheduler_table(self, n, eta=0.0, timesteps=None):
+        """Coefficient tables depend only on (scheduler, its configuration, steps, DDIM eta, caller timesteps)."""
+        ts = None if timesteps is None else tuple(int(t) for t in timesteps)
+        key = (self.scheduler_kind, self.scheduler_params, n, float(eta)) + ((ts,) if ts is not None else ())
         sched = self._sched_cache.get(key)
         if sched is None:
-            nt, b0, b1 = self.scheduler_params
+            nt, b0, b1 = self.scheduler_params[:3]
+            if self.scheduler_kind == "dpmsolver":
+                opts = dict(self.scheduler_params[3]) if len(self.scheduler_params) > 3 else {}
+                sched = DPMSolverMultistepTable(num_train_timesteps=nt, beta_start=b0, beta_end=b1, **opts)
+                if ts is not None:
+                    sched.set_timesteps(timesteps=list(ts))
+                else:
+                    sched.set_timesteps(n)
+                self._sched_cache[key] = sched
+                return sched
+            if ts is not None:
+                raise NotImplementedError(f"custom `timesteps` are not tabulated for {self.scheduler_kind} (the reference's set_timesteps "
+                                          "takes none): pass num_inference_steps, or use DPMSolverMultistepScheduler")
             cls = UniPCTable if self.scheduler_kind == "unipc" else DDIMTable
             sched = cls(num_train_timesteps=nt, beta_start=b0, beta_end=b1)
             if eta:
@@ -261,8 +286,16 @@ class BlobCtrlEngine:
             self._sched_cache[key] = sched
         return sched
 
+    @staticmethod
+    def _step_form(sched, stochastic):
+        """(stochastic, third_order) of the plan a table runs on: the noise step for DDIM eta > 0 and SDE-DPM-Solver++, the
+        third-order step when a row uses column 13, the plain step otherwise."""
+        third = bool((sched.table()[:, 13] != 0).any())
+        return bool(stochastic or getattr(sched, "sde", False)), third
+
     def _check_eta(self, eta):
-        """eta > 0 is stochastic DDIM; UniPC has no eta (its step takes none, so the reference ignores it: refused here)."""
+        """eta > 0 is stochastic DDIM; UniPC and DPM-Solver have no eta (their step takes none, so the reference ignores it: refused
+        here)."""
         if eta < 0:
             raise NotImplementedError(f"eta = {eta}: a negative eta is not a DDIM variance")
         if eta != 0.0 and self.scheduler_kind != "ddim":
@@ -382,7 +415,7 @@ class BlobCtrlEngine:
                  teacher_latents: Optional[List[torch.Tensor]] = None, fg_image: Optional[torch.Tensor] = None,
                  bg_image: Optional[torch.Tensor] = None, return_sample: bool = False, eta: float = 0.0,
                  do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
-                 variance_noise: Optional[torch.Tensor] = None):
+                 variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -391,7 +424,10 @@ class BlobCtrlEngine:
         eta > 0 (DDIM only): stochastic DDIM.  The variance noise of every step is drawn from `generator` exactly as the reference's
         scheduler.step draws it (after the start latents when those are drawn here; a list = one generator per sample; None = the
         global RNG of the engine's device), or taken from `variance_noise` [num_inference_steps, B, 4, h, w].  It is drawn in fp32 (the
-        engine keeps fp32 latents); a reference pipeline running in fp16 would draw fp16 noise."""
+        engine keeps fp32 latents); a reference pipeline running in fp16 would draw fp16 noise.
+        With an SDE-DPM-Solver++ scheduler (algorithm_type "sde-dpmsolver++") every step draws its noise the same way, eta staying 0.
+        `timesteps` (DPM-Solver only): the caller's timestep schedule, as the reference's set_timesteps(timesteps=) takes it; the edit
+        then has len(timesteps) steps and `num_inference_steps` is not used."""
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
@@ -410,6 +446,8 @@ class BlobCtrlEngine:
             if bg_image is None:
                 raise ValueError("give bg_image_latents or bg_image")
             bg_image_latents = self.encode_latents(bg_image)
+        if timesteps is not None:
+            num_inference_steps = len(timesteps)
         self.check_inputs(blobnet_conditioning_scale, blobnet_control_guidance_start, blobnet_control_guidance_end,
                           num_inference_steps)
         # pipe:494-497: guidance_scale <= 1 switches classifier-free guidance OFF in the reference (prompt_embeds then holds the
@@ -448,23 +486,24 @@ class BlobCtrlEngine:
         if isinstance(generator, list) and len(generator) != B:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
                              f" size of {B}. Make sure the batch size matches the length of the generators.")
+        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
+        stochastic, third_order = self._step_form(sched, stochastic)
         if variance_noise is not None:
             if not stochastic:
-                raise ValueError("variance_noise is only used with eta > 0")
+                raise ValueError("variance_noise is only used with eta > 0 (DDIM) or an SDE-DPM-Solver++ scheduler")
             if generator is not None:
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
                                  " `variance_noise` stays `None`.")
             if tuple(variance_noise.shape) != (n, B, 4, h, w):
                 raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (steps, batch, 4, h, w), got "
                                  f"{tuple(variance_noise.shape)}")
-        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0)
-        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic)
+        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order)
         dev = self.device
         self.timesteps = sched.timesteps
         if latents is None:                                                          # pipe:438-453
             g0 = generator[0] if isinstance(generator, list) else generator
             latents = randn_tensor((B, 4, h, w), generator, g0.device if g0 is not None else "cpu")
-        if stochastic and variance_noise is None:                                    # scheduling_ddim.py:455-458, after the latents
+        if stochastic and variance_noise is None:            # scheduling_ddim.py:455-458 / dpmsolver_multistep.py:979-982, after the latents
             variance_noise = self.variance_noise(n, B, h, w, generator, dev)
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         scale_rows = [[sc * k for sc in req_scales] for k in keep]                   # [step][image]
@@ -571,7 +610,7 @@ class BlobCtrlEngine:
         return self.denoise(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, **kw)
 
     def compile_plan(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale=7.5, blobnet_conditioning_scale=1.0,
-                     blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None):
+                     blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None, timesteps=None):
         """Write the launch plan of one edit configuration as a relocatable `.bcplan` file for the C plan runtime
         (include/blobctrl_hip.h: bc_plan_load / bc_plan_buffer / bc_step / bc_plan_capture_loop): segments "prologue",
         "step_active", "step_inactive"; packed weights and the scheduler / guidance tables stored with their contents; the per-edit
@@ -579,13 +618,16 @@ class BlobCtrlEngine:
         collapse), ctx (fp16 [2B][T][ctx_dim] = cat(negative, positive)); the result is read from `latents`.  Returns the per-step
         segment names (which steps run BlobNet).
         eta > 0 (DDIM): a stochastic plan with the named buffer `variance_noise` [n][B][4][h][w] fp32, saved with `variance_noise`'s
-        contents when given (else zero-filled: a C host fills it through bc_plan_buffer before each edit)."""
-        n = num_inference_steps
+        contents when given (else zero-filled: a C host fills it through bc_plan_buffer before each edit).  An SDE-DPM-Solver++ scheduler
+        gives the same stochastic plan; a third-order DPM-Solver++ table ends its steps in bc_cfg_scheduler_step3.  `timesteps` (DPM-Solver
+        only): the caller's schedule, n = len(timesteps)."""
+        n = num_inference_steps if timesteps is None else len(timesteps)
         stochastic = self._check_eta(float(eta))
+        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
+        stochastic, third_order = self._step_form(sched, stochastic)
         if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
-            raise ValueError(f"variance_noise needs eta > 0 and shape {(n, B, 4, h, w)}")
-        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0)
-        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic)
+            raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
+        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order)
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         P.t_table.copy_(sched.timesteps.to(torch.float32))
         coef = sched.table().clone()
@@ -606,8 +648,8 @@ class BlobCtrlEngine:
         return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
 
     # convenience for bench / tests ------------------------------------------------------------------
-    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic)
+    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order)
 
 
 # ======================================================================================================================
@@ -645,7 +687,8 @@ class StableDiffusionBlobNetPipeline:
         if safety_checker is not None:
             raise NotImplementedError("the reference disables the safety checker (pipe:1133-1135); pass safety_checker=None")
         if not isinstance(scheduler, TableScheduler):
-            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler or DDIMScheduler")
+            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler or "
+                            "DPMSolverMultistepScheduler")
         self.vae, self.unet, self.blobnet, self.tokenizer, self.text_encoder = vae, unet, blobnet, tokenizer, text_encoder
         self.dinov2, self.dinov2_processor = dinov2, dinov2_processor if dinov2_processor is not None else Dinov2ImageProcessor()
         self.safety_checker = None
@@ -729,7 +772,8 @@ class StableDiffusionBlobNetPipeline:
     def scheduler(self, s):
         from .schedulers import TableScheduler
         if not isinstance(s, TableScheduler):
-            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler or DDIMScheduler")
+            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler or "
+                            "DPMSolverMultistepScheduler")
         self._scheduler = s
 
     def to(self, *a, **k):
@@ -929,7 +973,8 @@ class StableDiffusionBlobNetPipeline:
             raise NotImplementedError("`callback` is deprecated in the reference (pipe:868-875): use callback_on_step_end")
         if kwargs:
             raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")
-        if timesteps is not None:
+        if timesteps is not None and getattr(self._scheduler, "kind", None) != "dpmsolver":
+            # the reference's retrieve_timesteps (pipe:142-148) honours them only for schedulers whose set_timesteps takes them
             raise NotImplementedError("custom `timesteps` are not tabulated; pass num_inference_steps")
         if cross_attention_kwargs:
             raise NotImplementedError("cross_attention_kwargs (runtime LoRA scale) are not supported: LoRA is merged at load")
@@ -962,7 +1007,11 @@ class StableDiffusionBlobNetPipeline:
         if cfg:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds])
         # 5./6. timesteps and latents (pipe:953-968); the noise is drawn BEFORE the images are encoded, like the reference
-        self.scheduler.set_timesteps(num_inference_steps)
+        if timesteps is not None:                                    # retrieve_timesteps (pipe:142-151)
+            self.scheduler.set_timesteps(timesteps=timesteps)
+            num_inference_steps = len(self.scheduler.timesteps)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps)
         self._num_timesteps = num_inference_steps
         lat0, noise = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, height, width,
                                            prompt_embeds.dtype, self.device, generator, latents)
@@ -983,7 +1032,7 @@ class StableDiffusionBlobNetPipeline:
                                     blobnet_control_guidance_start=blobnet_control_guidance_start[0],
                                     blobnet_control_guidance_end=blobnet_control_guidance_end[0], output_type="latent",
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
-                                    generator=generator)
+                                    generator=generator, timesteps=timesteps)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

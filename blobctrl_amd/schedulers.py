@@ -11,8 +11,10 @@ whose scalar coefficients are precomputed here per step index, uploaded once, an
     [3] cc_x [4] cc_m0 [5] cc_m1 [6] cc_mt                 x_c  = c3*last + c4*x0_{i-1} + c5*x0_{i-2} + c6*x0      (UniC)
     [7] cp_x [8] cp_m0 [9] cp_m1 [10] cp_eps               x'   = c7*x_c + c8*x0 + c9*x0_{i-1} + c10*eps           (UniP / DDIM)
     [11] guidance scale (filled by the engine)
-    [12] std_dev_t                                         x'  += c12*noise[i]     (stochastic DDIM, eta > 0; 0 otherwise)
+    [12] std_dev_t                                         x'  += c12*noise[i]     (stochastic DDIM, eta > 0; SDE-DPM-Solver++; 0 otherwise)
+    [13] cp_m2                                             x'  += c13*x0_{i-2}     (third-order DPM-Solver++, `bc_cfg_scheduler_step3`)
 Scalar maths follows the reference in fp32 torch CPU ops (same operation order) so the tables match it to rounding.
+DPM-Solver++ (scheduling_dpmsolver_multistep.py) fills c0 / c1 (x0), c7 (x), c8 (x0), c9 (x0_{i-1}), c12 (SDE noise) and c13 (order 3).
 
 SD-1.5 scheduler config: betas 0.00085 -> 0.012 scaled_linear, 1000 train steps, steps_offset 1,
 epsilon prediction; UniPC: solver_order 2, bh2, predict_x0, lower_order_final, linspace spacing, final sigma 0;
@@ -177,15 +179,214 @@ class DDIMTable(_Base):
         return self
 
 
+# the DPMSolverMultistepScheduler options a coefficient table depends on (the engine keys its tables and plans on them)
+DPM_OPTIONS = dict(solver_order=2, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
+                   use_karras_sigmas=False, use_lu_lambdas=False, final_sigmas_type="zero", lambda_min_clipped=-float("inf"),
+                   timestep_spacing="linspace", steps_offset=0)
+
+
+class DPMSolverMultistepTable(_Base):
+    """DPMSolverMultistepScheduler as a coefficient table (scheduling_dpmsolver_multistep.py:306-408 timesteps / sigmas, 612-887 the
+    first-, second- and third-order updates, 963-995 the order of each step).  Data prediction only ("dpmsolver++" and its SDE form
+    "sde-dpmsolver++"): x0 = (x - sigma_s0 * eps) / alpha_s0 in c0 / c1, the update x' = c7 * x + c8 * x0 + c9 * x0_{i-1} + c13 * x0_{i-2}
+    (+ c12 * noise for the SDE).  Caller `timesteps` are taken as the reference takes them."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, **options):
+        super().__init__(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end)
+        unknown = set(options) - set(DPM_OPTIONS)
+        if unknown:
+            raise TypeError(f"unknown DPM-Solver option(s) {sorted(unknown)}")
+        o = dict(DPM_OPTIONS, **options)
+        if o["algorithm_type"] not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type {o['algorithm_type']!r} is not tabulated (dpmsolver++ and sde-dpmsolver++ are)")
+        if o["solver_type"] not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_type {o['solver_type']!r} is not tabulated (midpoint and heun are)")
+        if o["solver_order"] not in (1, 2, 3):
+            raise NotImplementedError(f"solver_order {o['solver_order']} is not tabulated (1, 2 and 3 are)")
+        if o["solver_order"] == 3 and o["algorithm_type"] == "sde-dpmsolver++":
+            raise NotImplementedError("solver_order=3 with algorithm_type 'sde-dpmsolver++': the reference's third-order update has no "
+                                      "SDE branch (scheduling_dpmsolver_multistep.py:871-886)")
+        self.options = o
+        self.sde = o["algorithm_type"] == "sde-dpmsolver++"
+        self.sigmas = None
+        self.num_inference_steps = None
+
+    # ---- scheduling_dpmsolver_multistep.py:306-408
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None):
+        o = self.options
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps`.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
+        if timesteps is not None and o["use_karras_sigmas"]:
+            raise ValueError("Cannot use `timesteps` with `config.use_karras_sigmas = True`")
+        if timesteps is not None and o["use_lu_lambdas"]:
+            raise ValueError("Cannot use `timesteps` with `config.use_lu_lambdas = True`")
+        ac = self.alphas_cumprod
+        if timesteps is not None:
+            ts = np.array(timesteps).astype(np.int64)
+        else:
+            lambda_t = torch.log(torch.sqrt(ac)) - torch.log(torch.sqrt(1 - ac))
+            clipped_idx = torch.searchsorted(torch.flip(lambda_t, [0]), o["lambda_min_clipped"])
+            last_timestep = ((self.num_train - clipped_idx).numpy()).item()
+            n = num_inference_steps
+            if o["timestep_spacing"] == "linspace":
+                ts = np.linspace(0, last_timestep - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+            elif o["timestep_spacing"] == "leading":
+                step_ratio = last_timestep // (n + 1)
+                ts = (np.arange(0, n + 1) * step_ratio).round()[::-1][:-1].copy().astype(np.int64)
+                ts += o["steps_offset"]
+            elif o["timestep_spacing"] == "trailing":
+                step_ratio = self.num_train / n
+                ts = np.arange(last_timestep, 0, -step_ratio).round().copy().astype(np.int64)
+                ts -= 1
+            else:
+                raise ValueError(f"{o['timestep_spacing']} is not supported. Please make sure to choose one of 'linspace', 'leading' or "
+                                 "'trailing'.")
+        sigmas = (((1 - ac) / ac) ** 0.5).numpy().copy()
+        log_sigmas = np.log(sigmas)
+        if o["use_karras_sigmas"]:
+            sigmas = np.flip(sigmas).copy()
+            sigmas = self._convert_to_karras(sigmas, num_inference_steps)
+            ts = np.array([self._sigma_to_t(s, log_sigmas) for s in sigmas]).round()
+        elif o["use_lu_lambdas"]:
+            lambdas = np.flip(log_sigmas.copy())
+            lambdas = self._convert_to_lu(lambdas, num_inference_steps)
+            sigmas = np.exp(lambdas)
+            ts = np.array([self._sigma_to_t(s, log_sigmas) for s in sigmas]).round()
+        else:
+            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
+        if o["final_sigmas_type"] == "sigma_min":
+            sigma_last = float(((1 - ac[0]) / ac[0]) ** 0.5)
+        elif o["final_sigmas_type"] == "zero":
+            sigma_last = 0
+        else:
+            raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {o['final_sigmas_type']}")
+        self.sigmas = torch.from_numpy(np.concatenate([sigmas, [sigma_last]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.int64)
+        self.num_inference_steps = len(ts)
+        self.coef = self._build()
+        return self
+
+    @staticmethod
+    def _sigma_to_t(sigma, log_sigmas):                                   # :445-466
+        log_sigma = np.log(np.maximum(sigma, 1e-10))
+        dists = log_sigma - log_sigmas[:, np.newaxis]
+        low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = np.clip((low - log_sigma) / (low - high), 0, 1)
+        t = (1 - w) * low_idx + w * high_idx
+        return t.reshape(sigma.shape)
+
+    @staticmethod
+    def _convert_to_karras(in_sigmas, num_inference_steps):               # :475-498 (the config has no sigma_min / sigma_max)
+        sigma_min, sigma_max = in_sigmas[-1].item(), in_sigmas[0].item()
+        rho = 7.0
+        ramp = np.linspace(0, 1, num_inference_steps)
+        min_inv_rho, max_inv_rho = sigma_min ** (1 / rho), sigma_max ** (1 / rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
+
+    @staticmethod
+    def _convert_to_lu(in_lambdas, num_inference_steps):                  # :500-511
+        lambda_min, lambda_max = in_lambdas[-1].item(), in_lambdas[0].item()
+        rho = 1.0
+        ramp = np.linspace(0, 1, num_inference_steps)
+        min_inv_rho, max_inv_rho = lambda_min ** (1 / rho), lambda_max ** (1 / rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
+
+    @staticmethod
+    def _as(sigma):                                                       # :468-472
+        alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
+        return alpha_t, sigma * alpha_t
+
+    def _lam(self, k):
+        a, s = self._as(self.sigmas[k])
+        return torch.log(a) - torch.log(s)
+
+    def step_orders(self):
+        """The solver order of every step (step, :963-995): lower_order_nums, lower_order_final, lower_order_second."""
+        o = self.options
+        N = self.num_inference_steps
+        orders, lower_order_nums = [], 0
+        for i in range(N):
+            lower_order_final = (i == N - 1) and (o["euler_at_final"] or (o["lower_order_final"] and N < 15)
+                                                  or o["final_sigmas_type"] == "zero")
+            lower_order_second = (i == N - 2) and o["lower_order_final"] and N < 15
+            if o["solver_order"] == 1 or lower_order_nums < 1 or lower_order_final:
+                orders.append(1)
+            elif o["solver_order"] == 2 or lower_order_nums < 2 or lower_order_second:
+                orders.append(2)
+            else:
+                orders.append(3)
+            if lower_order_nums < o["solver_order"]:
+                lower_order_nums += 1
+        return orders
+
+    def _build(self):
+        o = self.options
+        midpoint = o["solver_type"] == "midpoint"
+        N = self.num_inference_steps
+        coef = torch.zeros(N, 16, dtype=torch.float32)
+        for i, order in enumerate(self.step_orders()):
+            alpha_s0, sigma_s0 = self._as(self.sigmas[i])
+            coef[i, 0] = 1.0 / alpha_s0
+            coef[i, 1] = sigma_s0 / alpha_s0
+            alpha_t, sigma_t = self._as(self.sigmas[i + 1])
+            if float(sigma_t) == 0.0:
+                # final step to sigma 0 (always first order, :963-967): lambda_t = h = +inf; the first-order rows have the finite limits
+                # sigma_t / sigma_s0 (* e^-h) = 0, alpha_t (1 - e^-h) = alpha_t (1 - e^-2h) = alpha_t, sigma_t sqrt(1 - e^-2h) = 0
+                assert order == 1
+                coef[i, 8] = alpha_t
+                continue
+            lambda_t = torch.log(alpha_t) - torch.log(sigma_t)
+            lambda_s0 = torch.log(alpha_s0) - torch.log(sigma_s0)
+            h = lambda_t - lambda_s0
+            if self.sde:
+                c_x = sigma_t / sigma_s0 * torch.exp(-h)
+                a = alpha_t * (1 - torch.exp(-2.0 * h))                     # weight of D0
+                b = 0.5 * a if midpoint else alpha_t * ((1.0 - torch.exp(-2.0 * h)) / (-2.0 * h) + 1.0)   # weight of D1
+                coef[i, 12] = sigma_t * torch.sqrt(1.0 - torch.exp(-2 * h))
+            else:
+                c_x = sigma_t / sigma_s0
+                a = -(alpha_t * (torch.exp(-h) - 1.0))
+                b = -0.5 * (alpha_t * (torch.exp(-h) - 1.0)) if midpoint else alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)
+            coef[i, 7] = c_x
+            if order == 1:                                                   # :654-679
+                coef[i, 8] = a
+            elif order == 2:                                                 # :723-802: D1 = (m0 - m1) / r0
+                r0 = (lambda_s0 - self._lam(i - 1)) / h
+                w = b * (1.0 / r0)
+                coef[i, 8] = a + w
+                coef[i, 9] = -w
+            else:                                                            # :846-878 (dpmsolver++ only)
+                lambda_s1, lambda_s2 = self._lam(i - 1), self._lam(i - 2)
+                h_0, h_1 = lambda_s0 - lambda_s1, lambda_s1 - lambda_s2
+                r0, r1 = h_0 / h, h_1 / h
+                b = alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)              # x_t = c7 x + a D0 + b D1 - c D2 (whatever solver_type)
+                c = alpha_t * ((torch.exp(-h) - 1.0 + h) / h ** 2 - 0.5)
+                i0, i1 = 1.0 / r0, 1.0 / r1
+                k, q = r0 / (r0 + r1), 1.0 / (r0 + r1)
+                # D1_0 = i0 (m0 - m1), D1_1 = i1 (m1 - m2), D1 = D1_0 + k (D1_0 - D1_1), D2 = q (D1_0 - D1_1), expanded in m0, m1, m2
+                coef[i, 8] = a + b * (1 + k) * i0 - c * q * i0
+                coef[i, 9] = -b * ((1 + k) * i0 + k * i1) + c * q * (i0 + i1)
+                coef[i, 13] = b * k * i1 - c * q * i1
+        assert torch.isfinite(coef).all(), "non-finite DPM-Solver coefficient"
+        return coef
+
+
 def apply_table_step(coef_row, eps, x, hist, noise=None):
-    """Host (torch) evaluation of one table row - the same arithmetic `bc_cfg_scheduler_step` (and, with `noise`,
-    `bc_cfg_scheduler_step_noise`) performs after CFG.  Used by the drop-in scheduler objects; `hist` = dict(m0, m1, last)."""
+    """Host (torch) evaluation of one table row - the same arithmetic `bc_cfg_scheduler_step` (with `noise`,
+    `bc_cfg_scheduler_step_noise`; with a third-order row, `bc_cfg_scheduler_step3`) performs after CFG.  Used by the drop-in scheduler
+    objects; `hist` = dict(m0, m1, last)."""
     c = coef_row
     x0 = x * c[0] - eps * c[1]
     xc = x
     if c[2] != 0:
         xc = c[3] * hist["last"] + c[4] * hist["m0"] + c[5] * hist["m1"] + c[6] * x0
     xn = c[7] * xc + c[8] * x0 + c[9] * hist["m0"] + c[10] * eps
+    if c[13] != 0:
+        xn = xn + c[13] * hist["m1"]
     if noise is not None:
         xn = xn + c[12] * noise
     hist["m1"], hist["m0"], hist["last"] = hist["m0"], x0, xc
@@ -226,7 +427,8 @@ class TableScheduler:
     init_noise_sigma = 1.0
 
     def __init__(self, kind="unipc", **kw):
-        self.table_impl = UniPCTable(**kw) if kind == "unipc" else DDIMTable(**kw)
+        self.table_impl = UniPCTable(**kw) if kind == "unipc" else DPMSolverMultistepTable(**kw) if kind == "dpmsolver" else \
+            DDIMTable(**kw)
         self.kind = kind
 
     def set_timesteps(self, num_inference_steps, device=None):
@@ -335,9 +537,10 @@ def scheduler_from_config_dir(path):
     with open(os.path.join(path, "scheduler_config.json")) as f:
         cfg = json.load(f)
     name = cfg.get("_class_name", "PNDMScheduler")
-    classes = {"PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler, "DDIMScheduler": DDIMScheduler}
+    classes = {"PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler, "DDIMScheduler": DDIMScheduler,
+               "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
     if name not in classes:
-        raise NotImplementedError(f"scheduler class {name} is not available (PNDM config holder, UniPC and DDIM are)")
+        raise NotImplementedError(f"scheduler class {name} is not available (PNDM config holder, UniPC, DDIM and DPM-Solver are)")
     cls = classes[name]
     known = set(_SD15) | set(cls._defaults)
     return cls(**{k: v for k, v in cfg.items() if k in known})
@@ -403,3 +606,99 @@ class _StepOutput(tuple):
     @property
     def prev_sample(self):
         return self[0]
+
+
+class DPMSolverMultistepScheduler(_ConfiguredScheduler):
+    """Drop-in for diffusers' DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py), e.g. "DPM++ 2M Karras" as
+    `DPMSolverMultistepScheduler.from_config(pipeline.scheduler.config, use_karras_sigmas=True)`.  Tabulated for data prediction
+    ("dpmsolver++", "sde-dpmsolver++") at orders 1-3 (3 without the SDE), midpoint / heun, karras / lu / plain sigmas, the three spacings,
+    both final-sigma types and caller `timesteps`; `step(..., generator=, variance_noise=)` draws the SDE noise as :979-986 does."""
+    _kind = "dpmsolver"
+    _defaults = dict(trained_betas=None, thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0, variance_type=None,
+                     rescale_betas_zero_snr=False, **DPM_OPTIONS)
+
+    def __init__(self, **kw):
+        if kw.get("algorithm_type") == "deis":                        # the reference re-registers these two (:255-265)
+            kw["algorithm_type"] = "dpmsolver++"
+        if kw.get("solver_type") in ("logrho", "bh1", "bh2"):
+            kw["solver_type"] = "midpoint"
+        super().__init__(**kw)
+        # diffusers' `_use_default_values`: the __init__ keys the caller did not pass (an explicit None counts as passed)
+        self.config["_use_default_values"] = sorted(k for k in self.config if not k.startswith("_") and k not in kw)
+        self.table_impl = DPMSolverMultistepTable(num_train_timesteps=self.config["num_train_timesteps"],
+                                                  beta_start=self.config["beta_start"], beta_end=self.config["beta_end"],
+                                                  **{k: self.config[k] for k in DPM_OPTIONS})
+
+    def _check(self, cfg):
+        if cfg["algorithm_type"] in ("dpmsolver", "sde-dpmsolver"):
+            raise NotImplementedError(f"algorithm_type {cfg['algorithm_type']!r} (the deprecated noise-prediction form) is not "
+                                      "tabulated: use 'dpmsolver++' or 'sde-dpmsolver++'")
+        if cfg["algorithm_type"] not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type {cfg['algorithm_type']!r} is not implemented")
+        if cfg["thresholding"]:
+            raise NotImplementedError("thresholding=True (dynamic thresholding of x0) is not tabulated")
+        if cfg["variance_type"] in ("learned", "learned_range"):
+            raise NotImplementedError(f"variance_type {cfg['variance_type']!r} (a learned variance) is not supported: the UNet predicts "
+                                      "4 channels")
+        if cfg["solver_order"] == 3 and cfg["algorithm_type"] == "sde-dpmsolver++":
+            raise NotImplementedError("solver_order=3 with algorithm_type 'sde-dpmsolver++': the reference's third-order update has no "
+                                      "SDE branch")
+        if cfg["solver_order"] not in (1, 2, 3) or cfg["solver_type"] not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_order {cfg['solver_order']} / solver_type {cfg['solver_type']!r} is not tabulated")
+        if cfg["trained_betas"] is not None or cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("trained_betas / rescale_betas_zero_snr are not tabulated")
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """diffusers' ConfigMixin.from_config (configuration_utils.py:188-270, 456-549): keys the source left at their defaults are
+        dropped, this class's keys are taken, every other key is kept in `.config` as a hidden entry (`_class_name` renamed)."""
+        src = dict(config)
+        defaulted = set(src.pop("_use_default_values", ()))
+        src = {k: v for k, v in src.items() if k not in defaulted}
+        known = set(_SD15) | set(cls._defaults)
+        init = {k: v for k, v in src.items() if k in known}
+        init.update(kw)
+        s = cls(**init)
+        hidden = {k: v for k, v in src.items() if k not in init}
+        if "_class_name" in hidden:
+            hidden["_class_name"] = cls.__name__
+        s.config.update(hidden)
+        return s
+
+    def table_params(self):
+        """(num_train_timesteps, beta_start, beta_end, DPM options as sorted (key, value) pairs): what the engine tabulates."""
+        return super().table_params() + (tuple(sorted((k, self.config[k]) for k in DPM_OPTIONS)),)
+
+    @property
+    def sigmas(self):
+        return self.table_impl.sigmas
+
+    @property
+    def num_inference_steps(self):
+        return self.table_impl.num_inference_steps
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None):
+        self.table_impl.set_timesteps(num_inference_steps, timesteps=timesteps)
+        self.timesteps = self.table_impl.timesteps.to(device) if device is not None else self.table_impl.timesteps
+        self._i = 0
+        self._hist = None
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True):
+        """One DPM-Solver++ update (:920-1007).  The SDE variant draws `randn_tensor(shape, generator, device, float32)` per step unless
+        `variance_noise` is given.  Returns `(prev_sample,)` for return_dict=False, else an object with `.prev_sample`."""
+        tab = self.table_impl
+        if tab.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        sample = sample.to(torch.float32)
+        if self._hist is None:
+            z = torch.zeros_like(sample)
+            self._hist = dict(m0=z, m1=z.clone(), last=z.clone())
+        noise = None
+        if tab.sde:
+            noise = variance_noise.to(device=model_output.device, dtype=torch.float32) if variance_noise is not None else \
+                randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
+        out = apply_table_step(tab.coef[self._i].tolist(), model_output, sample, self._hist, noise).to(model_output.dtype)
+        self._i += 1
+        if not return_dict:
+            return (out,)
+        return _StepOutput(out)

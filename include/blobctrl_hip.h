@@ -323,6 +323,13 @@ int bc_cfg_scheduler_step_noise(const float* eps, float* latents, const float* c
                                 float guidance_scale, int B, int h, int w, const float* noise, int nsteps, float* eps_out,
                                 int advance, bc_stream stream);
 
+/* bc_cfg_scheduler_step for third-order DPM-Solver++ (scheduling_dpmsolver_multistep.py:804-887): the update then adds
+ * coef[*step_idx][13] * x0_{i-2}, the x0 of two steps back (hist slot m1, which every step kernel already reads).
+ *   nsteps : rows of coef.  A launch with *step_idx >= nsteps writes nothing (only `advance` still counts).
+ * The other arguments are those of bc_cfg_scheduler_step. */
+int bc_cfg_scheduler_step3(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
+                           float guidance_scale, int B, int h, int w, int nsteps, float* eps_out, int advance, bc_stream stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Row-chain: everything of a Transformer2D block that acts on token rows independently, as ONE launch per attention
  * boundary (csrc/rowchain.hip).  Replaces, for 320- and 640-channel blocks (the 64 x 128 and 32 x 64 levels of SD-1.5; C / 80 waves
@@ -449,7 +456,7 @@ enum { BC_OP_GEMM = 0, BC_OP_GN_STATS = 1, BC_OP_GN_FINALIZE = 2, BC_OP_GN_APPLY
        BC_OP_PATCHIFY = 14, BC_OP_ADD_CLS_POS = 15, BC_OP_SILU = 16, BC_OP_NCHW_TO_NHWC_F16 = 17, BC_OP_NHWC_TO_NCHW = 18,
        BC_OP_GAUSSIAN_SAMPLE = 19, BC_OP_SIGNAL = 20 /* arg: event id */, BC_OP_WAIT = 21 /* arg: event id */, BC_OP_ROWCHAIN = 22, BC_OP_ASSEMBLE_IM2COL = 23,
        BC_OP_MEMSET_ZERO = 24, BC_OP_ROWCHAIN_MIDX = 25, BC_OP_ROWCHAIN_PACK_KV = 26, BC_OP_ROWCHAIN_SUM = 27, BC_OP_CTX_FOLD = 28, BC_OP_DUP_HALVES = 29,
-       BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_COUNT = 31 };
+       BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_CFG_SCHEDULER_STEP3 = 31, BC_OP_COUNT = 32 };
 typedef struct BcPlanBuffer {
     const char* name;        /* "" for anonymous workspace; named buffers are found again with bc_plan_buffer */
     const void* address;     /* the address the launch records were built against */

@@ -204,10 +204,12 @@ def golden_schedulers_eta():
 
 
 class _TapNoise:
-    """Records every `randn_tensor` call DDIMScheduler.step makes (the variance noise the reference drew), in call order."""
+    """Records every `randn_tensor` call DDIMScheduler.step (or another scheduler module's step) makes (the variance noise the
+    reference drew), in call order."""
 
-    def __init__(self):
-        import diffusers.schedulers.scheduling_ddim as m
+    def __init__(self, module="diffusers.schedulers.scheduling_ddim"):
+        import importlib
+        m = importlib.import_module(module)
         self.m, self.orig, self.drawn = m, m.randn_tensor, []
 
     def __enter__(self):
@@ -283,6 +285,186 @@ def golden_loop_eta():
     out["list3_noise"] = torch.stack([randn_tensor((3, 4, h, w), generator=gens, device=torch.device("cpu"), dtype=torch.float32)
                                       for _ in range(2)]).numpy()
     np.savez_compressed(os.path.join(OUT, "loop_tiny_eta.npz"), **out)
+
+
+# DPM-Solver cases of schedulers_dpm.npz: name -> (DPMSolverMultistepScheduler options on top of SD_SCHED, steps, caller timesteps)
+DPM_CUSTOM_TS = [999, 850, 736, 645, 545, 455, 343, 233, 124, 24]
+DPM_CASES = {
+    "pp2_mid_lin_5": (dict(), 5, None),
+    "pp2_mid_lin_14": (dict(), 14, None),
+    "pp2_mid_lin_15": (dict(), 15, None),
+    "pp2_heun_lin_20": (dict(solver_type="heun"), 20, None),
+    "pp2_mid_karras_50": (dict(use_karras_sigmas=True), 50, None),
+    "pp2_heun_karras_14": (dict(use_karras_sigmas=True, solver_type="heun"), 14, None),
+    "pp2_mid_lu_5": (dict(use_lu_lambdas=True), 5, None),
+    "pp2_mid_leading_5": (dict(timestep_spacing="leading"), 5, None),
+    "pp2_mid_trailing_5": (dict(timestep_spacing="trailing"), 5, None),
+    "pp2_sigmamin_15": (dict(final_sigmas_type="sigma_min"), 15, None),
+    "pp2_sigmamin_euler_15": (dict(final_sigmas_type="sigma_min", euler_at_final=True), 15, None),
+    "pp2_sigmamin_5": (dict(final_sigmas_type="sigma_min"), 5, None),
+    "pp1_lin_5": (dict(solver_order=1), 5, None),
+    "pp3_lin_5": (dict(solver_order=3), 5, None),
+    "pp3_lin_14": (dict(solver_order=3), 14, None),
+    "pp3_karras_15": (dict(solver_order=3, use_karras_sigmas=True), 15, None),
+    "pp3_lu_sigmamin_5": (dict(solver_order=3, use_lu_lambdas=True, final_sigmas_type="sigma_min"), 5, None),
+    "pp2_custom_10": (dict(), None, DPM_CUSTOM_TS),
+    "pp3_custom_10": (dict(solver_order=3), None, DPM_CUSTOM_TS),
+    "sde1_lin_5": (dict(algorithm_type="sde-dpmsolver++", solver_order=1), 5, None),
+    "sde2_mid_lin_15": (dict(algorithm_type="sde-dpmsolver++"), 15, None),
+    "sde2_heun_karras_14": (dict(algorithm_type="sde-dpmsolver++", solver_type="heun", use_karras_sigmas=True), 14, None),
+    "sde2_mid_lu_5": (dict(algorithm_type="sde-dpmsolver++", use_lu_lambdas=True), 5, None),
+    "sde2_trailing_sigmamin_5": (dict(algorithm_type="sde-dpmsolver++", timestep_spacing="trailing", final_sigmas_type="sigma_min"),
+                                 5, None),
+    "sde2_custom_10": (dict(algorithm_type="sde-dpmsolver++"), None, DPM_CUSTOM_TS),
+}
+SD15_SCHEDULER_JSON = {"_class_name": "PNDMScheduler", "_diffusers_version": "0.6.0", "beta_end": 0.012, "beta_schedule": "scaled_linear",
+                       "beta_start": 0.00085, "num_train_timesteps": 1000, "set_alpha_to_one": False, "skip_prk_steps": True,
+                       "steps_offset": 1, "trained_betas": None, "clip_sample": False}
+
+
+def golden_schedulers_dpm():
+    """DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py) on golden_schedulers' inputs (8x8 latents, eps_i = g(100 + i)),
+    the SDE noise given as variance_noise = g(200 + i): timesteps, sigmas and trajectories of DPM_CASES, plus one SDE run that draws
+    from a CPU generator.  The `.config` of `from_config(<SD-1.5 scheduler_config.json>)` goes to dpm_config.json."""
+    from diffusers import DPMSolverMultistepScheduler, PNDMScheduler
+    out = {}
+    for name, (kw, n, ts) in DPM_CASES.items():
+        sch = DPMSolverMultistepScheduler(**SD_SCHED, **kw)
+        if ts is not None:
+            sch.set_timesteps(timesteps=ts)
+        else:
+            sch.set_timesteps(n)
+        sde = kw.get("algorithm_type") == "sde-dpmsolver++"
+        x = g(21, 1, 4, 8, 8)
+        xs = [x.numpy()]
+        for i, t in enumerate(sch.timesteps):
+            x = sch.step(g(100 + i, 1, 4, 8, 8), t, x, variance_noise=g(200 + i, 1, 4, 8, 8) if sde else None, return_dict=False)[0]
+            xs.append(x.numpy())
+        out[f"{name}_timesteps"] = sch.timesteps.numpy()
+        out[f"{name}_sigmas"] = sch.sigmas.numpy()
+        out[f"{name}_traj"] = np.stack(xs)
+        out[f"{name}_kw"] = np.array(json.dumps(dict(kw, timesteps=ts, n=n)))
+    sch = DPMSolverMultistepScheduler(**SD_SCHED, algorithm_type="sde-dpmsolver++")
+    sch.set_timesteps(5)
+    gen = torch.Generator().manual_seed(77)
+    x = g(21, 1, 4, 8, 8)
+    xs = [x.numpy()]
+    for i, t in enumerate(sch.timesteps):
+        x = sch.step(g(100 + i, 1, 4, 8, 8), t, x, generator=gen, return_dict=False)[0]
+        xs.append(x.numpy())
+    out["sde2_gen77_5_traj"] = np.stack(xs)
+    np.savez_compressed(os.path.join(OUT, "schedulers_dpm.npz"), **out)
+    cfg = dict(DPMSolverMultistepScheduler.from_config(SD15_SCHEDULER_JSON).config)
+    via_pndm = dict(DPMSolverMultistepScheduler.from_config(PNDMScheduler.from_config(SD15_SCHEDULER_JSON).config).config)
+    for c in (cfg, via_pndm):
+        c["_use_default_values"] = sorted(c["_use_default_values"])
+    assert cfg == via_pndm, (cfg, via_pndm)
+    with open(os.path.join(OUT, "dpm_config.json"), "w") as f:
+        json.dump({"source": SD15_SCHEDULER_JSON, "config": cfg}, f, indent=1, sort_keys=True)
+    print("schedulers_dpm:", len(DPM_CASES), "cases; config keys", sorted(cfg))
+
+
+# DPM-Solver cases of loop_tiny_dpm.npz: tag -> (options on top of SD_SCHED, steps, caller timesteps, guidance window, generator seed)
+DPM_LOOPS = {
+    "karras2m_6": (dict(use_karras_sigmas=True), 6, None, (0.0, 0.67), None),
+    "sde2m_5": (dict(algorithm_type="sde-dpmsolver++"), 5, None, (0.0, 1.0), 1234),
+    "dpm3m_6": (dict(solver_order=3), 6, None, (0.0, 1.0), None),
+    "custom2m_10": (dict(), None, DPM_CUSTOM_TS, (0.0, 0.9), None),
+}
+
+
+def golden_loop_dpm():
+    """golden_loop's body (tiny nets, CFG 7.5) with DPM-Solver++: 2M Karras, SDE 2M (CPU generator, noise tapped from step), 3M, and
+    2M on caller timesteps.  Stores the final latents, the latents entering every step and the guided eps."""
+    from diffusers import DPMSolverMultistepScheduler
+    unet, blob = build_tiny()
+    c = TINY
+    h = w = 8
+    B = 1
+    out = {}
+    pipe = StableDiffusionBlobNetPipeline.__new__(StableDiffusionBlobNetPipeline)
+    for tag, (kw, steps, ts, (gs, ge), seed) in DPM_LOOPS.items():
+        sch = DPMSolverMultistepScheduler(**SD_SCHED, **kw)
+        if ts is not None:
+            sch.set_timesteps(timesteps=ts)
+        else:
+            sch.set_timesteps(steps)
+        steps = len(sch.timesteps)
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        latents = g(31, B, 4, h, w) * sch.init_noise_sigma
+        prompt = g(32, 2 * B, 7, c["ctx"])
+        fg_lat = (g(33, 1, 4, h, w) * 0.18215 * 5).repeat(2 * B, 1, 1, 1)
+        bg_lat = (g(34, 1, 4, h, w) * 0.18215 * 5).repeat(2 * B, 1, 1, 1)
+        ell = [[40.0, 42.0], [20.0, 30.0], 25.0]
+        mean, cov = ref_inf.get_gs_from_ellipse(ell)
+        nm, nc = ref_inf.normalize_gs(mean, cov, 64, 64)
+        gs_score = splat_features(**ref_inf.get_blob_dict_from_norm_gs(nm, nc), score_size=(h, w), return_d_score=True)
+        bg_s, fg_s = gs_score.unbind(dim=1)
+        bg_s = bg_s.unsqueeze(1).repeat(2 * B, 1, 1, 1).float()
+        fg_s = fg_s.unsqueeze(1).repeat(2 * B, 1, 1, 1).float()
+        dino = g(35, 1, 1, c["feat"])
+        feats = pipe.splat_features_from_scores(fg_s, dino.repeat(2 * B, 1, 1), size=h, channels_last=False)
+        keep = [1.0 - float(i / steps < gs or (i + 1) / steps > ge) for i in range(steps)]
+        eps_trace, lat_trace = [], []
+        with _TapNoise("diffusers.schedulers.scheduling_dpmsolver_multistep") as tap:
+            for i, t in enumerate(sch.timesteps):
+                lat_trace.append(latents.numpy().copy())
+                lmi = sch.scale_model_input(torch.cat([latents] * 2), t)
+                bi = pipe.construct_blobnet_input(lmi, fg_s, fg_lat, feats, background=False)
+                d, m, u = blob(bi, t, conditioning_scale=1.0 * keep[i], return_dict=False)
+                ui = pipe.construct_blobnet_input(lmi, bg_s, bg_lat, background=True)
+                npred = unet(ui, t, encoder_hidden_states=prompt, down_block_add_samples=[x[..., -x.shape[-2]:] for x in d],
+                             mid_block_add_sample=m[..., -m.shape[-2]:], up_block_add_samples=[x[..., -x.shape[-2]:] for x in u],
+                             return_dict=False)[0]
+                b_, c_, h_, w_ = npred.shape
+                npred = npred[..., :h_, w_ // 2:]
+                nu, nt = npred.chunk(2)
+                npred = nu + 7.5 * (nt - nu)
+                eps_trace.append(npred.numpy())
+                latents = sch.step(npred, t, latents, generator=gen, return_dict=False)[0]
+        assert len(tap.drawn) == (steps if seed is not None else 0)
+        out[f"{tag}_final"] = latents.numpy()
+        out[f"{tag}_eps"] = np.stack(eps_trace)
+        out[f"{tag}_lat"] = np.stack(lat_trace)
+        out[f"{tag}_timesteps"] = sch.timesteps.numpy()
+        out[f"{tag}_window"] = np.array([gs, ge])
+        out[f"{tag}_kw"] = np.array(json.dumps(dict(kw, timesteps=ts, n=steps)))
+        if seed is not None:
+            out[f"{tag}_noise"] = torch.stack(tap.drawn).numpy()
+            out[f"{tag}_seed"] = np.array(seed)
+        print(f"loop_dpm {tag}: {steps} steps, final std {latents.std():.4f}")
+    np.savez_compressed(os.path.join(OUT, "loop_tiny_dpm.npz"), **out)
+
+
+def golden_pipeline_call_dpm():
+    """The reference's own `__call__` (pipe:743-1166) with an SDE-DPM-Solver++ 2M scheduler, caller `timesteps` (retrieve_timesteps,
+    pipe:114-155) and a CPU `generator` (start latents, then every step's noise: pipe:313-328, 1102).  Case = `ddim_neg2` of
+    pipeline_call.npz with its own seeds; the images and scores are those of pipeline_call.npz."""
+    from PIL import Image
+    from diffusers import DPMSolverMultistepScheduler
+    from tests.common import FakeTokenizer, pipeline_cases
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"], seed=2025, rng_seed=22)
+    kw.pop("scheduler"), kw.pop("num_inference_steps")
+    timesteps = [999, 750, 500, 250]
+    sch = DPMSolverMultistepScheduler.from_config(DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False).config,
+                                                  algorithm_type="sde-dpmsolver++")
+    pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                          safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+    pipe.set_progress_bar_config(disable=True)
+    seed, rng_seed = kw.pop("seed"), kw.pop("rng_seed")
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "timesteps": np.array(timesteps)}
+    torch.manual_seed(rng_seed)
+    with _TapNoise("diffusers.schedulers.scheduling_dpmsolver_multistep") as noise:
+        r = pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                 height=64, width=64, timesteps=timesteps, generator=torch.Generator().manual_seed(seed), output_type="latent", **kw)
+    assert len(noise.drawn) == len(timesteps) and pipe.num_timesteps == len(timesteps)
+    out["latents"] = r.images.numpy()
+    out["noise"] = torch.stack(noise.drawn).numpy()
+    out["scheduler_timesteps"] = sch.timesteps.numpy()
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_dpm.npz"), **out)
+    print(f"pipeline __call__ sde-dpm++ 2m on {timesteps}: latents std {out['latents'].std():.4f}, noise {out['noise'].shape}")
 
 
 # ------------------------------------------------------------------------------------------------ 4. pipeline loop
@@ -1060,6 +1242,9 @@ if __name__ == "__main__":
     golden_schedulers_eta()
     golden_loop_eta()
     golden_pipeline_call_eta()
+    golden_schedulers_dpm()
+    golden_loop_dpm()
+    golden_pipeline_call_dpm()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
