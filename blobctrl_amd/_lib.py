@@ -45,6 +45,7 @@ class BcGemm(C.Structure):
         ("ln_colsum", C.c_void_p), ("ln_eps", C.c_float),
         ("C_t", C.c_void_p), ("ldc_t", C.c_int), ("n_t0", C.c_int),
         ("w_bstride", C.c_longlong), ("vec_bstride", C.c_int), ("sm_group", C.c_int), ("sm_valid", C.c_int), ("sm_keep", C.c_int),
+        ("S", C.c_void_p), ("S2", C.c_void_p), ("lds", C.c_int), ("lds2", C.c_int), ("S1", C.c_int), ("Cs", C.c_int),
     ]
 
 
@@ -59,6 +60,9 @@ _SIGNATURES = {
     "bc_conv_halo_eligible": (C.c_int, [C.c_int] * 8),
     "bc_conv_halo_max_chunks": (C.c_int, []),
     "bc_conv_wreg_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_conv_wreg_pack_sc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_conv_wreg_sc_eligible": (C.c_int, [C.c_int] * 7),
+    "bc_conv_wreg_pack_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "bc_gemm_wreg_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bc_gemm_wreg_stream_elems": (C.c_longlong, [C.c_int, C.c_int]),
     "bc_gemm_wreg_eligible": (C.c_int, [C.c_int] * 5),

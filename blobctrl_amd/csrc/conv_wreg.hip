@@ -16,6 +16,8 @@
 //     (ky = 0..2) that read row r: 10 ds_read_b128 per kx group instead of 24, 0.4 LDS reads per MFMA;
 //   * one barrier per CHUNK: the halo images are triple-buffered; the four two-tile waves (which have matrix-pipe time to spare, and run
 //     at raised priority) issue the LDS-DMA of chunk c + 2 and run the in-place pass over chunk c + 1 while everybody multiplies chunk c.
+//   * a ResBlock's 1x1 shortcut rides in the same launch (BcGemm.S): behind the nine-tap chunks the accumulators run on over ONE-TAP chunks of
+//     the raw shortcut operand - a second, peeled loop with its own ring and halo images (see "the folded 1x1 shortcut" below).
 // Every LDS access of the loop and the whole weight ring are inline asm with hand-counted lgkmcnt / vmcnt waits: hipcc orders plain
 // LDS reads behind every LDS-DMA in flight, and with an LDS-DMA in the same loop it drains the memory counter (vmcnt(0)) at the first
 // use of any loaded register.  Two rules follow for registers the asm loads into (both learnt the hard way): they must
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
     // its first use sits, behind a dozen separate s_waitcnt - at the cold start of a launch each one a scalar-cache miss of its own in
     // front of the workgroup's first memory request (BC_WREG_STAMPS: 4.3k cycles from entry to the first request).
     asm volatile("" ::"s"(p.A), "s"(p.A2), "s"(p.W), "s"(p.Hv), "s"(p.Wv), "s"(p.Hin), "s"(p.Win), "s"(p.lda), "s"(p.lda2), "s"(p.C1), "s"(p.Cin),
-                 "s"(p.splitk), "s"(p.a_act), "s"(g.halo_tpi), "s"(g.halo_tx), "s"(g.halo_nch), "s"(g.halo_cps), "s"(g.nband), "s"(g.halo_stamps));
+                 "s"(p.splitk), "s"(p.a_act), "s"(g.halo_tpi), "s"(g.halo_tx), "s"(g.halo_nch), "s"(g.halo_nsc), "s"(g.halo_cps), "s"(g.halo_cps_sc), "s"(g.nband), "s"(g.halo_stamps));
     asm volatile("" ::"s"(g.wr_plane.mul), "s"(g.wr_plane.shift), "s"(g.wr_plane.d), "s"(g.wr_gx.mul), "s"(g.wr_gx.shift), "s"(g.wr_gx.d), "s"(g.wr_gy.mul),
                  "s"(g.wr_gy.shift), "s"(g.wr_gy.d), "s"(g.wr_tpi.mul), "s"(g.wr_tpi.shift), "s"(g.wr_tx.mul), "s"(g.wr_tx.shift), "s"(p.bias), "s"(p.rowvec),
                  "s"(p.rowvec_idx), "s"(p.rowvec_step), "s"(p.ld_rowvec), "s"(g.halo_dbg), "s"(g.div_rpb.d));
@@ -110,8 +112,19 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
     // F.interpolate(scale_factor=2.0, mode="nearest") -> conv) that is the VIRTUAL image and a halo pixel reads source pixel (y/2, x/2)
     const int H = p.Hv, W = p.Wv;
     const bool ups2 = p.Hv != p.Hin;
-    const int c_begin = split * g.halo_cps;
-    const int nch = min(g.halo_nch, c_begin + g.halo_cps) - c_begin;
+    // A split takes its share of BOTH kinds of chunk: nine-tap chunks [c_lo, c_lo + n9) of the convolution's halo_nch and one-tap chunks
+    // [sc_begin, sc_begin + nsc) of the folded 1x1 shortcut's halo_nsc (BcGemm.S) - a one-tap chunk costs about a twentieth of a nine-tap
+    // one, so only this keeps the splits as even as the unfolded launch's.  Either share may be empty (the rounding of the two shares
+    // differs).  The loop below always runs at least one nine-tap chunk: a workgroup with shortcut chunks only multiplies a ZERO image of
+    // chunk 0 first (`dummy`: its prologue - tables, finalize, barriers - is then that of chunk 0, with every address valid).
+    const int c_lo = split * g.halo_cps;
+    const int n9 = max(0, min(g.halo_nch, c_lo + g.halo_cps) - c_lo);
+    const int sc_begin = split * g.halo_cps_sc;
+    const int nsc = max(0, min(g.halo_nsc, sc_begin + g.halo_cps_sc) - sc_begin);
+    const bool dummy = n9 == 0;
+    const int c_begin = dummy ? 0 : c_lo;
+    const int nch = dummy ? 1 : n9;
+    const long long tsl = (long long)(9 * g.halo_nch + g.halo_nsc) * 512;   // halves of one tile column's stream (one K half)
 
     unsigned long long* const stamps = g.halo_stamps;        // BC_WREG_STAMPS diagnostics (null in production): waves 0 (three tiles) and 2 (staging)
     auto stamp = [&](int i) {
@@ -158,7 +171,7 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
             const int off = pixv[q] * stride + kin + csubv[q] * 8;
-            const h16* s = (valid && pixv[q] >= 0) ? src + off : zero;
+            const h16* s = (valid && !dummy && pixv[q] >= 0) ? src + off : zero;
             glds16(s, dst + q * 4096);
         }
     };
@@ -189,7 +202,7 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
             if (p.a_act == BC_ACT_SILU) v = v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
             o[j] = (h16)v;
         }
-        if (outside) outraw = (u32x4v){0u, 0u, 0u, 0u};
+        if (outside || dummy) outraw = (u32x4v){0u, 0u, 0u, 0u};
         if (store) asm volatile("ds_write_b128 %0, %1" ::"v"(sa), "v"(outraw) : "memory");
     };
     // FIRST image (prologue): every lane of the workgroup owns three 16-byte slots for the in-place pass: bytes [tid * 16 + 8192 q,
@@ -250,8 +263,8 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
         const h16* b4 = (BASE) + (((GX) * G + f) & ~3) * 512;                                                                          \
         asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(ring[(GX) * G + f]) : "v"(lane16), "s"(b4), "n"((((GX) * G + f) & 3) * 1024) : "memory"); \
     }
-        const h16* wb = reinterpret_cast<const h16*>(p.W) + ((long long)ntile * 20 + 2 * tile0 + kg * NT) * g.halo_nch * per_chunk +
-                        (long long)c_begin * NT * per_chunk;     // wave-uniform stream pointer (chunk cl)
+        const h16* const wstream = reinterpret_cast<const h16*>(p.W) + ((long long)ntile * 20 + 2 * tile0 + kg * NT) * tsl;
+        const h16* wb = wstream + (long long)c_begin * NT * per_chunk;     // wave-uniform stream pointer (chunk cl)
         // Request order = order of use: the first two halo images, ring group 0, the tables; then the rest of chunk 0's weights.  (A
         // workgroup's first requests - 48 KiB of halo rows + 144-216 KiB of weights - take ~5000 cycles at the per-CU fetch rate: the
         // first MFMA waits only for what it needs.)
@@ -575,6 +588,94 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
         }
         }
 
+        // ---- the folded 1x1 shortcut (BcGemm.S): the accumulators run on over `nsc` ONE-TAP chunks of the raw shortcut operand.  Same halo
+        // geometry and staging lanes as above (only the 8 x 16 centre pixels are read: row i + 1, x shift 1), no in-place pass, NT fragments per
+        // chunk and wave.  The nine-tap loop has drained (its last chunk is peeled: nothing in flight, every image free), so this phase starts
+        // its own pipeline, U chunks deep in both the images (NB2 = 5 of them: the affine table and the finalize scratch are dead) and the
+        // weights.  A chunk costs about what its 24 KiB of LDS-DMA cost (~1100 cycles at 22 B/clk), less than a memory round trip - hence the
+        // depth.  Issue order per wave, prologue included: D(0) L(0) .. D(U-1) L(U-1) | chunk s: D(s + U), wait L(s), multiply, L(s + U),
+        // wait D(s + 1), barrier  (D = the 6 LDS-DMA pieces of a staging wave, L = NT fragment loads).  Vector-memory operations complete in
+        // order, so a wait counts what was issued BEHIND its target: L(s): (U - 1) L + U D; D(s + 1): U L + (U - 1) D.  Nothing is conditional:
+        // behind the last chunk D reads the zero line, L re-reads the last chunk, and the rest of an unrolled round multiplies zero images.
+        stamp(14);
+        if (nsc > 0) {
+            constexpr int U = 4, NB2 = 5, D1 = STG ? 6 : 0;
+            static_assert(NB2 * HALO_BYTES <= LDS_EPI && U < NB2 && U * 3 + 6 * U < 64, "shortcut phase: images below the epilogue vectors, vmcnt range");
+            const h16* __restrict__ S1p = reinterpret_cast<const h16*>(p.S);
+            const h16* __restrict__ S2p = reinterpret_cast<const h16*>(p.S2);
+            const h16* const ws = wstream + ((long long)g.halo_nch * 9 + sc_begin) * NT * 512;
+            u32x4v sr[U * NT];
+            auto issue_s = [&](int sx, int bufi) {
+                const int k0 = (sc_begin + sx) * 64;
+                const bool second = S2p != nullptr && k0 >= p.S1;         // wave-uniform (S1 % 64 == 0)
+                const h16* src = second ? S2p : S1p;
+                const int stride = second ? p.lds2 : p.lds;
+                const int kin = second ? k0 - p.S1 : k0;
+                char* dst = smem + bufi * HALO_BYTES + (wave - 2) * 1024;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    const int off = pixv[q] * stride + kin + csubv[q] * 8;
+                    const h16* s_ = (sx < nsc && pixv[q] >= 0) ? src + off : zero;
+                    glds16(s_, dst + q * 4096);
+                }
+            };
+#define BC_WREG_LOAD_SC(J, SX)                                                                                                          \
+    {                                                                                                                                   \
+        const h16* b4 = ws + (long long)min((SX), nsc - 1) * (NT * 512);                                                                \
+        _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                                                  \
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(sr[(J) * NT + t]) : "v"(lane16), "s"(b4), "n"((t % NT) * 1024) : "memory"); \
+    }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                if (STG) issue_s(j, j);
+                BC_WREG_LOAD_SC(j, j)
+            }
+            if (STG) wait_vm_c<U * NT + 6 * (U - 1)>();              // image 0 has landed
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            int sbuf = 0;                                             // image of chunk s
+            for (int s0 = 0; s0 < nsc; s0 += U) {
+#pragma unroll
+                for (int j = 0; j < U; ++j) {
+                    const int sx = s0 + j;
+                    const int bufn = sbuf + U >= NB2 ? sbuf + U - NB2 : sbuf + U;     // image of chunk sx + U (= that of chunk sx - 1: free)
+                    if (STG) issue_s(sx + U, bufn);
+                    if (NT == 3) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(sr[j * NT]), "+v"(sr[j * NT + 1]), "+v"(sr[j * NT + NT - 1]) : "n"((U - 1) * NT + U * D1) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(sr[j * NT]), "+v"(sr[j * NT + 1]) : "n"((U - 1) * NT + U * D1) : "memory");
+                    const unsigned abase = lds0 + sbuf * HALO_BYTES + a_off[1];
+                    u32x4v a8[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a8[i]) : "v"(abase), "n"((i + 1) * HSTR * 128) : "memory");
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a8[i]) : "n"(7 - i) : "memory");
+                        __builtin_amdgcn_sched_barrier(0);
+                        const h16x8 af = __builtin_bit_cast(h16x8, a8[i]);
+#pragma unroll
+                        for (int t = 0; t < NT; ++t)
+                            acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, sr[j * NT + t]), af, acc[i][t], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    BC_WREG_LOAD_SC(j, sx + U)
+                    if (STG) wait_vm_c<U * NT + 6 * (U - 1)>();      // image of chunk sx + 1 has landed
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();                     // image of chunk sx is free; image of chunk sx + 1 is visible
+                    asm volatile("" ::: "memory");
+                    sbuf = sbuf + 1 == NB2 ? 0 : sbuf + 1;
+                }
+            }
+            // the refills and zero-line pieces of the tail: nothing may be in flight when the ring dies or the epilogue takes the LDS over
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                if (NT == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(sr[j * NT]), "+v"(sr[j * NT + 1]), "+v"(sr[j * NT + NT - 1]) :: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" : "+v"(sr[j * NT]), "+v"(sr[j * NT + 1]) :: "memory");
+            }
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+#undef BC_WREG_LOAD_SC
+        }
         __builtin_amdgcn_s_setprio(0);
         stamp(3);
         // ---- the two K halves are summed through LDS (the halo images are dead: every wave passed the last barrier).  The partner
@@ -794,30 +895,36 @@ __global__ __launch_bounds__(512) void conv_wreg_kernel(const GemmArgs g) {
     stamp(5);
 }
 
-// out[frag stream] <- w[N][9 * Cin] (k = (ky * 3 + kx) * Cin + c, the layout of every other 3x3 path): one thread per 16-byte lane slot
-__global__ void conv_wreg_pack_kernel(const h16* __restrict__ w, int N, int Cin, h16* __restrict__ out) {
-    const long long total = (long long)N * 9 * Cin / 8;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
+// out[frag stream] <- w[N][9 * Cin] (k = (ky * 3 + kx) * Cin + c, the layout of every other 3x3 path): one thread per 16-byte lane slot.
+// Cs > 0: the one-tap fragments of a folded 1x1 shortcut wsc[N][Cs] behind every wave stream, [chunk of Cs][tile][lane].
+// Source of lane slot idx of the stream (shared by the kernel and the host statement bc_conv_wreg_pack_host): element offset into w, or,
+// with `sc` set, into wsc.
+__host__ __device__ inline long long conv_wreg_pack_src(long long idx, int Cin, int Cs, bool& sc) {
     const int nchunks = Cin / 64;
-    const long long per_ntile = (long long)20 * nchunks * 9 * 64;           // lane slots per 160-column block
+    const long long per_tile_stream = (long long)(nchunks * 9 + Cs / 64) * 64;   // lane slots of one tile column and K half
+    const long long per_ntile = 20 * per_tile_stream;                        // lane slots per 160-column block
     const int ntile = (int)(idx / per_ntile);
     long long rem = idx - (long long)ntile * per_ntile;
-    // stream order inside a block: (group, K half) streams of nchunks * 9 * NT fragments, starting at (2 * tile0 + kg * NT) tile-streams
-    const long long per_tile_stream = (long long)nchunks * 9 * 64;          // lane slots of one tile column and K half
+    // stream order inside a block: (group, K half) streams of (nchunks * 9 + Cs / 64) * NT fragments, starting at (2 * tile0 + kg * NT) tile-streams
     const int ts = (int)(rem / per_tile_stream);                             // 0..19 = 2 * tile0 + kg * NT + (position inside the wave stream)
-    int grp, tile0, NT;
-    if (ts < 6) { grp = 0; tile0 = 0; NT = 3; }
-    else if (ts < 10) { grp = 1; tile0 = 3; NT = 2; }
-    else if (ts < 14) { grp = 2; tile0 = 5; NT = 2; }
-    else { grp = 3; tile0 = 7; NT = 3; }
-    (void)grp;
+    int tile0, NT;
+    if (ts < 6) { tile0 = 0; NT = 3; }
+    else if (ts < 10) { tile0 = 3; NT = 2; }
+    else if (ts < 14) { tile0 = 5; NT = 2; }
+    else { tile0 = 7; NT = 3; }
     const long long in_grp = rem - (long long)2 * tile0 * per_tile_stream;  // lane slot inside the group's two wave streams
     const long long per_wave = per_tile_stream * NT;
     const int kg = (int)(in_grp / per_wave);
     long long s = in_grp - (long long)kg * per_wave;                         // lane slot inside the wave stream
     const int lane = (int)(s & 63);
     s >>= 6;                                                                 // fragment index = ((chunk * 3 + kx) * 3 + ky) * NT + t
+    sc = s >= (long long)nchunks * 9 * NT;
+    if (sc) {                                                                // shortcut part: fragment index = chunk * NT + t
+        s -= (long long)nchunks * 9 * NT;
+        const int t = (int)(s % NT), chunk = (int)(s / NT);
+        const int n = ntile * HBN + (tile0 + t) * 16 + (lane & 15);
+        return (long long)n * Cs + chunk * 64 + kg * 32 + 8 * (lane >> 4);
+    }
     const int t = (int)(s % NT);
     s /= NT;
     const int ky = (int)(s % 3);
@@ -826,20 +933,59 @@ __global__ void conv_wreg_pack_kernel(const h16* __restrict__ w, int N, int Cin,
     const int chunk = (int)(s / 3);
     const int n = ntile * HBN + (tile0 + t) * 16 + (lane & 15);
     const long long k = (long long)(ky * 3 + kx) * Cin + chunk * 64 + kg * 32 + 8 * (lane >> 4);
-    *reinterpret_cast<uint4*>(out + idx * 8) = *reinterpret_cast<const uint4*>(w + (long long)n * 9 * Cin + k);
+    return (long long)n * 9 * Cin + k;
+}
+
+__global__ void conv_wreg_pack_kernel(const h16* __restrict__ w, int N, int Cin, const h16* __restrict__ wsc, int Cs, h16* __restrict__ out) {
+    const long long total = (long long)N * (9 * Cin + Cs) / 8;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    bool sc;
+    const long long src = conv_wreg_pack_src(idx, Cin, Cs, sc);
+    *reinterpret_cast<uint4*>(out + idx * 8) = *reinterpret_cast<const uint4*>((sc ? wsc : w) + src);
 }
 
 }  // namespace
 
-extern "C" int bc_conv_wreg_pack(const bc_half* w, int N, int Cin, bc_half* out, bc_stream stream_) {
+extern "C" int bc_conv_wreg_pack_sc(const bc_half* w, int N, int Cin, const bc_half* wsc, int Cs, bc_half* out, bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BC_CHECK_ARG(w && out && N > 0 && N % HBN == 0 && Cin > 0 && Cin % 64 == 0, "bc_conv_wreg_pack: N %% 160 == 0 and Cin %% 64 == 0 (N=%d Cin=%d)", N, Cin);
-    BC_CHECK_ARG(((uintptr_t)w % 16 == 0) && ((uintptr_t)out % 16 == 0) && w != out, "bc_conv_wreg_pack: 16-byte aligned, out of place");
-    const long long total = (long long)N * 9 * Cin / 8;
+    BC_CHECK_ARG((wsc == nullptr) == (Cs == 0) && Cs >= 0 && Cs % 64 == 0, "bc_conv_wreg_pack: shortcut weight and Cs %% 64 == 0 go together (Cs=%d)", Cs);
+    BC_CHECK_ARG(((uintptr_t)w % 16 == 0) && ((uintptr_t)wsc % 16 == 0) && ((uintptr_t)out % 16 == 0) && w != out && wsc != out,
+                 "bc_conv_wreg_pack: 16-byte aligned, out of place");
+    const long long total = (long long)N * (9 * Cin + Cs) / 8;
     hipLaunchKernelGGL(conv_wreg_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const h16*>(w), N, Cin,
-                       reinterpret_cast<h16*>(out));
+                       reinterpret_cast<const h16*>(wsc), Cs, reinterpret_cast<h16*>(out));
     BC_CHECK_LAUNCH();
     return 0;
+}
+
+// the same re-ordering of HOST arrays, on the CPU (the statement the Python packer is tested against where there is no GPU)
+extern "C" int bc_conv_wreg_pack_host(const bc_half* w, int N, int Cin, const bc_half* wsc, int Cs, bc_half* out) {
+    BC_CHECK_ARG(w && out && N > 0 && N % HBN == 0 && Cin > 0 && Cin % 64 == 0, "bc_conv_wreg_pack: N %% 160 == 0 and Cin %% 64 == 0 (N=%d Cin=%d)", N, Cin);
+    BC_CHECK_ARG((wsc == nullptr) == (Cs == 0) && Cs >= 0 && Cs % 64 == 0, "bc_conv_wreg_pack: shortcut weight and Cs %% 64 == 0 go together (Cs=%d)", Cs);
+    const long long total = (long long)N * (9 * Cin + Cs) / 8;
+    const unsigned short* w_ = reinterpret_cast<const unsigned short*>(w);
+    const unsigned short* s_ = reinterpret_cast<const unsigned short*>(wsc);
+    unsigned short* o_ = reinterpret_cast<unsigned short*>(out);
+    for (long long idx = 0; idx < total; ++idx) {
+        bool sc;
+        const long long src = conv_wreg_pack_src(idx, Cin, Cs, sc);
+        std::copy_n((sc ? s_ : w_) + src, 8, o_ + idx * 8);
+    }
+    return 0;
+}
+
+extern "C" int bc_conv_wreg_pack(const bc_half* w, int N, int Cin, bc_half* out, bc_stream stream) {
+    return bc_conv_wreg_pack_sc(w, N, Cin, nullptr, 0, out, stream);
+}
+
+int bc_conv_wreg_sc_ok(const BcGemm& p) {
+    if (!p.S || p.R || p.Cs <= 0 || p.Cs % 64 != 0 || p.Hv != p.Hin || p.Wv != p.Win) return 0;
+    if (p.S2 && (p.S1 <= 0 || p.S1 >= p.Cs || p.S1 % 64 != 0)) return 0;
+    if (p.lds < (p.S2 ? p.S1 : p.Cs) || p.lds % 8 != 0 || (uintptr_t)p.S % 16 != 0) return 0;
+    if (p.S2 && (p.lds2 < p.Cs - p.S1 || p.lds2 % 8 != 0 || (uintptr_t)p.S2 % 16 != 0)) return 0;
+    return 1;
 }
 
 int bc_conv_wreg_launch(GemmArgs& g, hipStream_t stream) {
@@ -847,16 +993,20 @@ int bc_conv_wreg_launch(GemmArgs& g, hipStream_t stream) {
     g.halo_tx = p.Wout / TW;
     g.halo_tpi = g.halo_tx * (p.Hout / TH);
     g.halo_nch = p.Cin / 64;
+    g.halo_nsc = p.S ? p.Cs / 64 : 0;                // (the folded 1x1 shortcut's one-tap chunks: every split takes its share of both kinds)
     g.halo_dbg = 0;                                  // (bit 0x100 = the round-4 in-prologue finalize: kept in the kernel for reference, not selectable)
     g.halo_stamps = nullptr;
-    int sk = std::max(1, std::min(p.splitk, g.halo_nch));
+    int sk = std::max(1, std::min(p.splitk, g.halo_nch + g.halo_nsc));
     g.halo_cps = bc_ceil_div(g.halo_nch, sk);
-    p.splitk = bc_ceil_div(g.halo_nch, g.halo_cps);
+    g.halo_cps_sc = bc_ceil_div(g.halo_nsc, sk);
+    p.splitk = std::max(bc_ceil_div(g.halo_nch, g.halo_cps), g.halo_nsc ? bc_ceil_div(g.halo_nsc, g.halo_cps_sc) : 1);
     BC_CHECK_ARG(g.halo_cps <= MAX_CH, "bc_gemm(wreg conv): %d channel chunks per split exceed %d (raise splitk)", g.halo_cps, MAX_CH);
     BC_CHECK_ARG(p.splitk == 1 || p.slab != nullptr, "bc_gemm(wreg conv): splitk=%d needs a slab", p.splitk);
     const int B = p.M / (p.Hout * p.Wout);
     BC_CHECK_ARG((long long)p.M * std::max(p.lda, p.lda2) < 2147483647LL, "bc_gemm(wreg conv): activation of %d pixels x stride %d exceeds 32-bit element offsets",
                  p.M, std::max(p.lda, p.lda2));
+    BC_CHECK_ARG(!p.S || (bc_conv_wreg_sc_ok(p) && (long long)p.M * std::max(p.lds, p.lds2) < 2147483647LL),
+                 "bc_gemm(wreg conv): folded shortcut outside the kernel's limits (Cs=%d S1=%d)", p.Cs, p.S1);
     dim3 grid(p.N / HBN, B * g.halo_tpi, p.splitk);
     g.wr_plane = make_fastdiv(grid.x * grid.y);
     g.wr_gx = make_fastdiv(grid.x);
@@ -902,6 +1052,9 @@ int bc_conv_wreg_launch(GemmArgs& g, hipStream_t stream) {
                     }
                 fprintf(stderr, "[wreg stamps] prologue detail (ticks since entry): inputs requested %.0f, ring group 0 requested %.0f, totals landed %.0f, "
                         "barrier 1 %.0f, barrier 2 %.0f, table written %.0f\n", pr[0] / n, pr[1] / n, pr[2] / n, pr[3] / n, pr[4] / n, pr[5] / n);
+                double scp = 0;                                       // the folded shortcut's phase: stamp 14 -> 3
+                for (size_t i = 0; i < n; ++i) scp += (double)(h[(i * 2 + w) * 16 + 3] - h[(i * 2 + w) * 16 + 14]);
+                if (p.S) fprintf(stderr, "[wreg stamps] folded shortcut: Cs=%d, %.0f ticks per workgroup behind the nine-tap chunks (of the loop's %.0f)\n", p.Cs, scp / n, d[2] / n);
                 fprintf(stderr, "[wreg stamps] M=%d N=%d Cin=%d sk=%d cps=%d wgs=%zu %s | avg ticks: setup+table %.0f, first halo %.0f (landing %.0f, pass %.0f, "
                         "next DMA + barrier %.0f), loop %.0f (%.0f per tap), k-half sum %.0f, stores %.0f\n", p.M, p.N, p.Cin, p.splitk, cps, n,
                         w ? "staging wave " : "3-tile wave  ", d[0] / n, d[1] / n, e[0] / n, e[1] / n, e[2] / n, d[2] / n, d[2] / n / (cps * 9), d[3] / n, d[4] / n);

@@ -417,12 +417,24 @@ extern "C" int bc_gemm_plan(int M, int N, int K, int fast, int* tile_cfg, int* s
     return 0;
 }
 
+alignas(16) static const char g_sc_aligned[16] = {0};
+
 extern "C" int bc_conv_halo_eligible(int Cin, int C1, int N, int Hin, int Win, int Hout, int Wout, int stride) {
     BcGemm p = {};
     p.a_mode = BC_A_CONV3X3; p.Cin = Cin; p.C1 = C1; p.N = N; p.Hin = p.Hv = Hin; p.Win = p.Wv = Win; p.Hout = Hout; p.Wout = Wout;
     p.stride = stride;
     p.A2 = C1 > 0 ? reinterpret_cast<const bc_half*>(&p) : nullptr;       // (only tested for non-null)
     return bc_conv_halo_ok(p);
+}
+
+extern "C" int bc_conv_wreg_sc_eligible(int Cin, int N, int H, int W, int Cs, int S1, int) {
+    BcGemm p = {};
+    p.a_mode = BC_A_CONV3X3; p.tile_cfg = BC_TILE_WREG; p.Cin = Cin; p.N = N; p.Hin = p.Hv = p.Hout = H; p.Win = p.Wv = p.Wout = W; p.stride = 1;
+    p.M = H * W;
+    p.Cs = Cs; p.S1 = S1; p.lds = S1 > 0 ? S1 : Cs; p.lds2 = Cs - S1;
+    p.S = reinterpret_cast<const bc_half*>(g_sc_aligned);                // (only tested for non-null and alignment)
+    p.S2 = S1 > 0 ? p.S : nullptr;
+    return bc_conv_halo_ok(p) && bc_conv_wreg_sc_ok(p);
 }
 
 extern "C" int bc_conv_halo_max_chunks(void) { return bc_conv_halo_max_chunks_impl(); }
@@ -543,6 +555,7 @@ extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
     }
     g.nk = bc_ceil_div(p.K, BK);
     if (halo) g.nk = p.Cin / BK;                    // split-K counts 64-channel chunks (each covers the nine taps)
+    if (wreg && p.S) g.nk += p.Cs / BK;             // ... and those of the folded 1x1 shortcut (bc_conv_wreg_launch deals both kinds out to the splits)
     if (p.splitk > g.nk) p.splitk = g.nk;
     if (p.splitk > 1) BC_CHECK_ARG(p.slab != nullptr, "bc_gemm: splitk=%d needs a slab", p.splitk);
     g.kt_per_split = bc_ceil_div(g.nk, p.splitk);
@@ -558,6 +571,13 @@ extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
         fast_ok = fast_ok && (p.Cin % BK == 0) && (!ups || (p.Hv == 2 * p.Hin && p.Wv == 2 * p.Win && p.stride == 1));
     } else if (p.A2) {
         fast_ok = fast_ok && (p.C1 % BK == 0);
+    }
+    BC_CHECK_ARG(!p.S || wreg, "bc_gemm: a folded shortcut (S) needs BC_TILE_WREG");
+    if (p.S) {
+        if (p.lds <= 0) p.lds = p.S2 ? p.S1 : p.Cs;
+        if (p.S2 && p.lds2 <= 0) p.lds2 = p.Cs - p.S1;
+        BC_CHECK_ARG(bc_conv_wreg_sc_ok(p), "bc_gemm: folded shortcut needs Cs%%64==0, S1%%64==0, pixel strides >= the channel counts and %%8==0, 16-byte "
+                                            "aligned sources, no upsample and no residual R (Cs=%d S1=%d lds=%d lds2=%d)", p.Cs, p.S1, p.lds, p.lds2);
     }
     static const bool force_generic = getenv("BC_GEMM_GENERIC") != nullptr;
     static const int force_tile = getenv("BC_GEMM_TILE") ? atoi(getenv("BC_GEMM_TILE")) : 0;

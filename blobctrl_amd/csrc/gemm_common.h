@@ -42,6 +42,7 @@ struct GemmArgs {
     int vec_transposed;  // 1: BC_OUT_F16_T with rows_per_batch % 8 == 0 and ldc % 8 == 0: 16-byte stores along the token axis
     int halo_tx, halo_tpi;   // halo conv: pixel tiles per image row / per image
     int halo_nch, halo_cps;  // halo conv: 64-channel chunks in total / per split
+    int halo_nsc, halo_cps_sc;   // conv_wreg: 64-channel chunks of the folded 1x1 shortcut (BcGemm.S) in total / per split (0: none)
     int halo_dbg;            // halo conv: BC_HALO_DBG ablation bits (diagnostics)
     int nband;               // fast GEMM: 1 = an XCD owns a band of COLUMN tiles (all row tiles): it fetches 1/8 of the weights and the
                              // whole activation - chosen when the weight matrix is the larger operand (low-resolution levels)
@@ -376,6 +377,7 @@ bool bc_gemm_probe_hit();
 int bc_conv_halo_launch(bcg::GemmArgs& g, hipStream_t stream);
 // conv_wreg.hip: the same convolution with the weights streamed into VGPRs from a packed fragment stream (BC_TILE_WREG).
 int bc_conv_wreg_launch(bcg::GemmArgs& g, hipStream_t stream);
+int bc_conv_wreg_sc_ok(const BcGemm& p);     // the folded 1x1 shortcut (BcGemm.S) of a BC_TILE_WREG convolution is within the kernel's limits
 // gemm_wreg.hip: small-M projections with the weights streamed into VGPRs (BC_TILE_GW*).
 int bc_gemm_wreg_nt(int tile_cfg);
 int bc_gemm_wreg_ok(const BcGemm& p, int tile_cfg);

@@ -65,7 +65,7 @@ const size_t kGemmPtrFields[] = {
     offsetof(BcGemm, rowvec_idx), offsetof(BcGemm, colscale), offsetof(BcGemm, alpha_dev), offsetof(BcGemm, alpha_idx),
     offsetof(BcGemm, R), offsetof(BcGemm, R2), offsetof(BcGemm, C), offsetof(BcGemm, gn_tot), offsetof(BcGemm, a_affine),
     offsetof(BcGemm, a_tot1), offsetof(BcGemm, a_tot2), offsetof(BcGemm, a_gamma), offsetof(BcGemm, a_beta),
-    offsetof(BcGemm, ln_colsum), offsetof(BcGemm, C_t)};
+    offsetof(BcGemm, ln_colsum), offsetof(BcGemm, C_t), offsetof(BcGemm, S), offsetof(BcGemm, S2)};
 
 struct Rec {
     int op = 0, sid = 0, enabled = 1;

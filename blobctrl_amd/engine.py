@@ -78,8 +78,10 @@ class TrunkPlan:
         return opt("halo") and bool(self.rec.lib.bc_conv_halo_eligible(Cin, C1, Cout, H, W, H, W, 1))
 
     def conv3x3(self, x: Act, wname, Cout, stride=1, up_to=None, rowvec=None, R=None, r2=None, out_f32=False,
-                kind="conv3x3", out=None, x2: Optional[Act] = None, affine=None, halo=False, tile_cfg=0):
-        """`halo=True`: conv_halo.hip on the channel-concat (x | x2) with `affine` = (ab tensor, activation) applied while staging."""
+                kind="conv3x3", out=None, x2: Optional[Act] = None, affine=None, halo=False, tile_cfg=0, sc=None):
+        """`halo=True`: conv_halo.hip on the channel-concat (x | x2) with `affine` = (ab tensor, activation) applied while staging.
+        `sc` = (name of a 1x1 convolution, source, second source or None): conv1x1(source | second) added to the output inside the
+        launch (conv_wreg.hip only; the caller has asked sc_fold_ok)."""
         rec, pw = self.rec, self.pw
         Hv, Wv = up_to if up_to is not None else (x.H, x.W)
         Hout, Wout = (Hv + 2 - 3) // stride + 1, (Wv + 2 - 3) // stride + 1
@@ -99,14 +101,21 @@ class TrunkPlan:
         if halo:
             wreg = opt("wreg")                                       # conv_wreg.hip (weights streamed into VGPRs) instead of conv_halo.hip
             kw.update(tile_cfg=_lib.TILE_WREG if wreg else _lib.TILE_HALO, lda=x.C)
-            if wreg:
+            if wreg and sc is None:
                 wkey = pw.wreg(wname + ".weight")
+            if sc is not None:
+                assert wreg and R is None
+                wkey, bkey = pw.wreg_sc(wname, sc[0])
+                s1, s2 = sc[1], sc[2]
+                kw.update(S=s1.t, lds=s1.C, Cs=s1.C + (s2.C if s2 is not None else 0))
+                if s2 is not None:
+                    kw.update(S2=s2.t, lds2=s2.C, S1=s1.C)
             if x2 is not None:
                 kw.update(A2=x2.t, C1=x.C, lda2=x2.C)
             if affine is not None:
                 kw.update(a_act=affine[1], **({"a_gn": affine[0]} if isinstance(affine[0], dict) else {"a_affine": affine[0]}))
         else:
-            assert x2 is None and affine is None
+            assert x2 is None and affine is None and sc is None
             # the exact 2x nearest upsample in front of a plain convolution also runs on conv_wreg.hip (source pixel = halo pixel / 2)
             ups_wreg = up_to is not None and (Hv, Wv) == (2 * x.H, 2 * x.W) and stride == 1 and Cin % 64 == 0 and Cout % 160 == 0 and \
                 Wv % 16 == 0 and Hv % 8 == 0 and opt("wreg")
@@ -118,7 +127,7 @@ class TrunkPlan:
         rec.gemm(A=x.t, W=pw.h[wkey], M=M, N=Cout, K=9 * Cin, out=out,
                  out_mode=_lib.OUT_F32 if out_f32 else _lib.OUT_F16,
                  conv=dict(Cin=Cin, Hin=x.H, Win=x.W, Hv=Hv, Wv=Wv, Hout=Hout, Wout=Wout, stride=stride),
-                 bias=pw.f[wname + ".bias"], rows_per_batch=Hout * Wout, kind=kind, want_gn=not out_f32, **kw)
+                 bias=pw.f[bkey if sc is not None else wname + ".bias"], rows_per_batch=Hout * Wout, kind=kind, want_gn=not out_f32, **kw)
         return Act(out, Cout, Hout, Wout)
 
     def g256_tile(self, M, N, K, kw):
@@ -169,7 +178,14 @@ class TrunkPlan:
             gn = dict(x1=x.t, C1=x.C, x2=x2.t if x2 is not None else None, C2=C2, B=self.B, HW=x.H * x.W, G=self.G, eps=eps,
                       gamma=pw.f[norm + ".weight"], beta=pw.f[norm + ".bias"])
             return self.conv3x3(x, wname, Cout, x2=x2, affine=(gn, _lib.ACT_SILU), halo=True, **kw)
+        assert kw.get("sc") is None
         return self.conv3x3(self.groupnorm(x, x2, norm, eps, True), wname, Cout, **kw)
+
+    def sc_fold_ok(self, Cmid, Cout, H, W, Cs, S1):
+        """conv2 of a ResBlock (Cmid -> Cout on H x W) runs on conv_wreg.hip and takes the block's 1x1 shortcut over Cs channels (split
+        S1 | Cs - S1, 0 = one source) as one-tap chunks behind its own (BcGemm.S): no conv1x1 launch, no residual read."""
+        return opt("sc_fold") and opt("wreg") and self.halo_ok(Cmid, 0, Cout, H, W) and \
+            bool(self.rec.lib.bc_conv_wreg_sc_eligible(Cmid, Cout, H, W, Cs, S1, 0))
 
     def groupnorm(self, x: Act, x2: Optional[Act], name, eps, silu):
         pw = self.pw
@@ -188,6 +204,9 @@ class TrunkPlan:
         rowvec = (self.tproj.data_ptr() + off * 2, pw.temb_total) + getattr(self, "tproj_table", ())
         h = self.gn_conv(x, skip, p + "norm1", 1e-5, p + "conv1", Cout, rowvec=rowvec)
         M = self.B * x.H * x.W
+        if (p + "conv_shortcut.weight") in pw.h and self.sc_fold_ok(Cout, Cout, x.H, x.W, Cin, x.C if skip is not None else 0):
+            return self.gn_conv(h, None, p + "norm2", 1e-5, p + "conv2", Cout, sc=(p + "conv_shortcut", x, skip), r2=r2,
+                                **({"out": out} if out is not None else {}))
         if (p + "conv_shortcut.weight") in pw.h:
             kw = {}
             if skip is not None:

@@ -380,7 +380,7 @@ class Recorder:
              alpha=1.0, alpha_dev=None, alpha_idx=None, alpha_bstride=0, R=None, ldr=0, R2=None, ldr2=0, r2_xmin=0, r2_bmod=1,
              out_w=0, splitk=None, kind="gemm", a_offset=0, w_offset=0, out_offset=0, want_gn=False, tile_cfg=0, ldw=None,
              a_affine=None, a_act=_lib.ACT_NONE, a_gn=None, ln_colsum=None, ln_eps=1e-5, C_t=None, ldc_t=0, n_t0=0,
-             w_bstride=0, vec_bstride=0, sm_group=0, sm_valid=0, sm_keep=0, gn_tot_out=None):
+             w_bstride=0, vec_bstride=0, sm_group=0, sm_valid=0, sm_keep=0, gn_tot_out=None, S=None, S2=None, lds=0, lds2=0, S1=0, Cs=0):
         """Record one bc_gemm.  `conv` = dict(Cin, Hin, Win, Hv, Wv, Hout, Wout, stride) for the 3x3 gather mode.
         Pointer offsets are in ELEMENTS of the respective tensor."""
         n_out = N // 2 if act == _lib.ACT_GEGLU else (N // sm_group * sm_keep if sm_group else N)
@@ -415,6 +415,9 @@ class Recorder:
         g.ln_colsum, g.ln_eps = ptr(ln_colsum), ln_eps
         g.C_t, g.ldc_t, g.n_t0 = ptr(C_t), ldc_t, n_t0
         g.w_bstride, g.vec_bstride, g.sm_group, g.sm_valid, g.sm_keep = w_bstride, vec_bstride, sm_group, sm_valid, sm_keep
+        if S is not None:                # 1x1 shortcut over (S | S2) folded into a BC_TILE_WREG convolution: one-tap chunks behind the nine-tap ones
+            assert tile_cfg == _lib.TILE_WREG and R is None and Cs % 64 == 0 and Cs > 0
+            g.S, g.S2, g.lds, g.lds2, g.S1, g.Cs = ptr(S), ptr(S2), lds, lds2, S1, Cs
         # mirror of the C-side fast-path eligibility (bc_gemm)
         fast = K % 64 == 0
         mode = "dense"
@@ -432,6 +435,7 @@ class Recorder:
             # LDS-resident input-halo convolution (conv_halo.hip): split-K counts 64-channel chunks; fill ~one workgroup per CU
             nch = conv["Cin"] // 64
             base = (M // 128) * (N // 160)
+            explicit_sk, sk_req = splitk, None
             if splitk is None:
                 # Workgroups a split pass aims for and the fewest 64-channel chunks per workgroup.  With conv_wreg.hip (tap loop 867
                 # instead of 1445 cycles) a workgroup's fixed costs weigh more and a pass that leaves CUs to the other trunk is worth
@@ -457,7 +461,18 @@ class Recorder:
             splitk = max(splitk, -(-nch // self.lib.bc_conv_halo_max_chunks()))     # (the workgroup's affine table lives in LDS)
             cps = -(-nch // max(1, splitk))
             cfg, sk, bm, bn = tile_cfg, -(-nch // cps), 128, 160
+            if Cs:
+                # a folded 1x1 shortcut: the K split is chosen as for the convolution alone (above) and every split takes its share of the
+                # nine-tap chunks AND of the shortcut's one-tap chunks (a twentieth of the cost each: splitting the chunk sequence by count gave
+                # one split all the convolution - [1024, 1280, 9 * 1280 + 2560] 120.9 us against 98.2 us for the two launches).  The numbers
+                # below are bc_gemm's and bc_conv_wreg_launch's own arithmetic (the slab is reserved for the resulting split count).
+                nsc = Cs // 64
+                sk_req = min(sk if explicit_sk is None else splitk, nch + nsc)      # (what bc_gemm is given: it repeats this arithmetic)
+                s2 = -(-(nch + nsc) // -(-(nch + nsc) // sk_req))
+                cps = -(-nch // s2)
+                sk = max(-(-nch // cps), -(-nsc // -(-nsc // s2)))
             fast, mode = True, "halo"
+            sc_mode = "_sc" if S is not None else ""
             if a_gn is not None:
                 # GroupNorm in front of the convolution: a_gn = dict(x1, C1, x2, C2, B, HW, G, eps, gamma, beta).  The finalize runs
                 # inside the convolution's prologue - every workgroup reads the statistics totals (six words per channel) of the groups
@@ -477,6 +492,7 @@ class Recorder:
                     a_affine = self.gn_affine(a_gn["x1"], a_gn["C1"], a_gn["x2"], a_gn["C2"], a_gn["B"], a_gn["HW"], G_, a_gn["eps"],
                                               a_gn["gamma"], a_gn["beta"])
                     g.a_affine = ptr(a_affine)
+            mode += sc_mode
         elif tile_cfg in _lib.GW_TILES:
             # small-M projection with the weights streamed into VGPRs (gemm_wreg.hip); W is the stream packed for this configuration
             assert not conv and a_affine is None and splitk in (None, 1) and rowvec is None
@@ -499,6 +515,8 @@ class Recorder:
             assert a_affine is None and (not conv or A2 is None), "fused GroupNorm prologue / two-source conv need TILE_HALO / TILE_WREG"
             cfg, sk, bm, bn = self.plan_gemm(M, N, K, fast, mode, tile_cfg, splitk)
         g.splitk = sk
+        if Cs:
+            g.splitk = sk_req
         g.tile_cfg = cfg
         if sk > 1:
             self.reserve_slab(sk * M * N)
@@ -519,7 +537,7 @@ class Recorder:
         idx = self.lib.bc_plan_add_gemm(self.plan, self.seg.id, self.sid, C.byref(g))
         if idx < 0 or idx != len(self.seg.meta):
             _lib.check(1, "bc_plan_add_gemm")
-        refs = (A, A2, W, out, bias, R, R2, rowvec, rowvec_idx, colscale, alpha_dev, alpha_idx, part, a_affine, ln_colsum, C_t)
+        refs = (A, A2, W, out, bias, R, R2, rowvec, rowvec_idx, colscale, alpha_dev, alpha_idx, part, a_affine, ln_colsum, C_t, S, S2)
         self.keep.append(refs)
         for t in refs:
             self.register(t)
@@ -542,8 +560,8 @@ class Recorder:
             rp = "gemm_kernel<" + ("256, 64, 4, 1" if bn == 64 else "128, 128, 2, 2") + ">"
         # algorithmic HBM bytes: activation (a convolution reads each input pixel once), weights and the result once
         a_elems = (M // (conv["Hout"] * conv["Wout"])) * conv["Hin"] * conv["Win"] * conv["Cin"] if conv else M * K
-        alg_bytes = 2 * (a_elems + N * K + M * n_out) + (2 * M * n_out if R is not None else 0)
-        self._push(kind, 2 * M * N * K, variant, (mode, M, N, K, sk), alg_bytes, rp)
+        alg_bytes = 2 * (a_elems + N * K + M * n_out) + (2 * M * n_out if R is not None else 0) + 2 * (M + N) * Cs
+        self._push(kind, 2 * M * N * (K + Cs), variant, (mode, M, N, K + Cs, sk), alg_bytes, rp)
         return out
 
     # ------------------------------------------------------------------ norms

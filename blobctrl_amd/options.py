@@ -30,6 +30,7 @@ TABLE = {
     "gw_ff1_g256": (True, "ff.net.0 of the 1280-channel blocks at M <= gw_maxm as LayerNorm + gemm256.hip where it has >= g256_min_tiles tiles"),
     "cfg_prefix": (True, "CFG-invariant prefix of the UNet once per image pair (0: every launch at the full CFG batch)"),
     "wreg": (True, "ResBlock convolutions on csrc/conv_wreg.hip (0: csrc/conv_halo.hip)"),
+    "sc_fold": (True, "a ResBlock's 1x1 shortcut folded into conv2's K loop on csrc/conv_wreg.hip (0: a conv1x1 launch + residual read)"),
     "halo": (True, "ResBlock convolutions with the fused GroupNorm prologue at all (0: GroupNorm pass + implicit GEMM)"),
     "gn_finalize_launch": (False, "a bc_gn_finalize launch per GroupNorm instead of the finalize in the consumer's prologue"),
     # ---- planning constants (defaults = the measured optima: DESIGN 3.6, 3.7, 6)

@@ -52,23 +52,35 @@ def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
 WREG_TILES = ((0, 3), (3, 2), (5, 2), (7, 3))      # (first column tile, tiles) of the four column groups of csrc/conv_wreg.hip
 
 
-def pack_conv_wreg(w: torch.Tensor) -> torch.Tensor:
+def pack_conv_wreg(w: torch.Tensor, wsc: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Packed 3x3 weights [N][9 * Cin] (k = (ky * 3 + kx) * Cin + c: `pack_conv3x3`) -> the per-wave fragment streams of BC_TILE_WREG
     (csrc/conv_wreg.hip, same as `bc_conv_wreg_pack`): per 160-column block, per (column group, K half of the 64-channel chunk) one
-    contiguous stream [chunk][kx][ky][tile][lane = 16 (k sub-chunk) + row][8]."""
+    contiguous stream [chunk][kx][ky][tile][lane = 16 (k sub-chunk) + row][8].
+    `wsc` [N][Cs]: the 1x1 shortcut folded into the convolution (BcGemm.S; same bytes as `bc_conv_wreg_pack_sc`) - every stream is followed
+    by the shortcut's one-tap fragments [chunk of Cs][tile][lane][8]; the result is [N][9 * Cin + Cs]."""
     N, K = w.shape
     Cin = K // 9
     assert N % 160 == 0 and Cin % 64 == 0 and K == 9 * Cin, (N, K)
     nch = Cin // 64
     # [block, tile 10, row 16, ky, kx, chunk, kg, q 4, 8]
     v = w.reshape(N // 160, 10, 16, 3, 3, nch, 2, 4, 8)
+    Cs = 0
+    if wsc is not None:
+        Cs = wsc.shape[1]
+        assert wsc.shape[0] == N and Cs % 64 == 0 and Cs > 0, tuple(wsc.shape)
+        vs = wsc.reshape(N // 160, 10, 16, Cs // 64, 2, 4, 8)        # [block, tile 10, row 16, chunk, kg, q 4, 8]
     parts = []
     for blk in range(N // 160):
         for t0, nt in WREG_TILES:
             g = v[blk, t0:t0 + nt]                                   # [t, row, ky, kx, chunk, kg, q, 8]
             g = g.permute(5, 4, 3, 2, 0, 6, 1, 7)                     # [kg, chunk, kx, ky, t, q, row, 8]
-            parts.append(g.reshape(-1))
-    return torch.cat(parts).reshape(N, K)
+            if wsc is None:
+                parts.append(g.reshape(-1))
+                continue
+            s = vs[blk, t0:t0 + nt].permute(3, 2, 0, 4, 1, 5)         # [kg, chunk, t, q, row, 8]
+            for kg in range(2):                                       # (a wave's stream: its nine-tap fragments, then its one-tap fragments)
+                parts += [g[kg].reshape(-1), s[kg].reshape(-1)]
+    return torch.cat(parts).reshape(N, K + Cs)
 
 
 def pack_matrix(w: torch.Tensor) -> torch.Tensor:
@@ -190,6 +202,15 @@ class PackedTrunk:
         if k2 not in self.h:
             self.h[k2] = pack_conv_wreg(self.h[key])
         return k2
+
+    def wreg_sc(self, conv: str, sc: str):
+        """(key of the fragment stream, key of the fp32 bias) of the convolution `conv` with the 1x1 shortcut `sc` folded in (BcGemm.S):
+        3x3 fragments followed by the shortcut's, and the sum of the two biases made in fp32."""
+        k2, kb = conv + ".weight+sc_wreg", conv + ".bias+sc"
+        if k2 not in self.h:
+            self.h[k2] = pack_conv_wreg(self.h[conv + ".weight"], self.h[sc + ".weight"])
+            self.f[kb] = (self.f[conv + ".bias"].float() + self.f[sc + ".bias"].float()).contiguous()
+        return k2, kb
 
     def __init__(self, sd: Dict[str, torch.Tensor], device, block_out_channels, layers_per_block=2):
         self.device = device

@@ -128,6 +128,14 @@ typedef struct BcGemm {
      *      group are written as fp16 probabilities, compacted: C[m][(n / 128) * sm_keep + n % 128].  The scores never exist in HBM (fp32
      *      inside the launch).  0 = none. ---- */
     int sm_group, sm_valid, sm_keep;
+    /* ---- BC_TILE_WREG only: the ResBlock's 1x1 shortcut FOLDED into the convolution (D/models/resnet.py:366-371, conv_shortcut(x) +
+     *      conv2(..)): after the nine-tap chunks of Cin the accumulators run on over the Cs RAW channels (no GroupNorm, no activation) of
+     *      the output pixel itself in S (channels k < S1, pixel stride lds) | S2 (channels k >= S1, pixel stride lds2; NULL = one source,
+     *      S1 ignored), with a one-tap weight.  W is then the stream of bc_conv_wreg_pack_sc (3x3 fragments, then the shortcut's), `bias`
+     *      the SUM of both biases, and split-K counts the (Cin + Cs) / 64 chunks of both parts.  Needs Cs % 64 == 0, S1 % 64 == 0, no
+     *      upsample (bc_conv_wreg_sc_eligible).  NULL = none. ---- */
+    const bc_half* S; const bc_half* S2;
+    int lds, lds2, S1, Cs;
 } BcGemm;
 
 int bc_gemm(const BcGemm* p, bc_stream stream);
@@ -141,7 +149,8 @@ enum { BC_TILE_AUTO = 0, BC_TILE_256x128 = 1, BC_TILE_128x128_S3 = 2, BC_TILE_12
         * chosen by BC_TILE_AUTO: callers ask for it (bc_conv_halo_eligible). */
        BC_TILE_HALO = 8,
        /* the same convolution, tile, prologue and epilogue with the weights streamed straight into VGPRs (conv_wreg.hip): `W` is the
-        * fragment stream bc_conv_wreg_pack wrote for this layer (not the row-major matrix), ldw is ignored.  Same eligibility. */
+        * fragment stream bc_conv_wreg_pack wrote for this layer (not the row-major matrix), ldw is ignored.  Same eligibility.  Takes a
+        * ResBlock's 1x1 shortcut as extra K (BcGemm.S, bc_conv_wreg_pack_sc). */
        BC_TILE_WREG = 9,
        /* small-M projections with the weights streamed straight into VGPRs (gemm_wreg.hip): dense A (one or two sources), M % 64 == 0,
         * K % 320 == 0 (C1 % 320 == 0), workgroup = 64 rows x 128 / 256 / 320 columns (N a multiple of that); `W` is the fragment stream
@@ -173,6 +182,15 @@ int bc_gemm256_eligible(int M, int N, int K, int C1, int out_mode, int rows_per_
  * streams of BC_TILE_WREG (same size, out of place): per 160-column block, per (column group 3|2|2|3 tiles, K half of the 64-channel
  * chunk) one contiguous stream [chunk][kx][ky][tile][64 lanes][8]; lane l holds w[n0 + 16 tile + (l & 15)][k0 + 8 (l >> 4) .. + 8]. */
 int bc_conv_wreg_pack(const bc_half* w, int N, int Cin, bc_half* out, bc_stream stream);
+/* The same with a ResBlock's 1x1 shortcut weight wsc[N][Cs] (Cs % 64 == 0) folded in (BcGemm.S): every (column group, K half) stream is
+ * followed by the shortcut's one-tap fragments [chunk of Cs][tile][64 lanes][8], lane l holding wsc[n0 + 16 tile + (l & 15)][64 chunk +
+ * 32 (K half) + 8 (l >> 4) .. + 8]; `out` holds N * (9 * Cin + Cs) elements.  wsc == NULL, Cs == 0: bc_conv_wreg_pack. */
+int bc_conv_wreg_pack_sc(const bc_half* w, int N, int Cin, const bc_half* wsc, int Cs, bc_half* out, bc_stream stream);
+/* ... and of HOST arrays on the CPU (no device needed): the same index map as the kernel. */
+int bc_conv_wreg_pack_host(const bc_half* w, int N, int Cin, const bc_half* wsc, int Cs, bc_half* out);
+/* 1 when the 1x1 shortcut over Cs channels (split S1 | Cs - S1; S1 = 0: one source) can be folded into the BC_TILE_WREG convolution
+ * Cin -> N on an H x W image (BcGemm.S). */
+int bc_conv_wreg_sc_eligible(int Cin, int N, int H, int W, int Cs, int S1, int reserved);
 /* 1 when a convolution can run on BC_TILE_HALO. */
 int bc_conv_halo_eligible(int Cin, int C1, int N, int Hin, int Win, int Hout, int Wout, int stride);
 /* most 64-channel chunks one workgroup of BC_TILE_HALO may take: callers keep ceil(Cin / 64 / splitk) <= this */
