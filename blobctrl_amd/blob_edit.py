@@ -225,6 +225,17 @@ def ellipse_from_mask(mask: np.ndarray) -> Ellipse:
     return fit_ellipse(convex_hull(np.stack([xs, ys], 1)))
 
 
+def blob_overlay(ellipse: Ellipse, height: int, width: int, viz_colors, device: str = "cuda:0") -> np.ndarray:
+    """app:611-650 chained: ellipse -> normalised Gaussian -> the app's `splat_features(..., viz_size=(H, W), is_viz=True,
+    only_vis=True)` call -> `* 255` -> uint8 [H, W, 3].  `viz_colors` [K, 3] is the caller's palette (row 0 background, row 1 the blob).
+    The image is packed to bytes on the GPU (bc_pack_rgb8), so 3 H W bytes cross to the host; this is the only synchronising step."""
+    import torch
+    blob = blob_dict_from_ellipse(ellipse, width, height)
+    img = splat_features(**blob, interp_size=64, viz_size=(height, width), is_viz=True, ret_layout=True, score_size=64,
+                         viz_score_fn=lambda score: score, viz_colors=viz_colors, only_vis=True, device=device)["feature_img"]
+    return torch.ops.blobctrl.pack_rgb8(img).cpu().numpy()
+
+
 def build_edit_inputs(op: str, image: np.ndarray, start_ellipse: Ellipse, target_ellipse: Ellipse = None, strength: float = 1.0,
                       device: str = "cuda:0"):
     """The three things an edit hands to the pipeline: (bg_image uint8 [H,W,3], gs_score [1,2,h,w], strength).

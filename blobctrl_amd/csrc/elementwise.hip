@@ -1,39 +1,18 @@
 // Blob maths and loop glue kernels (all HBM/latency-trivial): Gaussian-blob splat rasteriser, input assembly,
 // timestep embedding, CFG + scheduler step, layout conversion at the nn.Module boundary, DINOv2 embedding glue.
 #include "bc_common.h"
+#include "bc_splat.h"
 
 namespace {
 
-// blobctrl/utils/utils.py:145-194 for one blob per image, fp64 like the reference (numpy float64 -> torch float64).
-//   delta = (grid - mu*(W,H)) / (W,H) ; m = delta^T cov^-1 delta ; s = min(1, 2*sigmoid(-m)) ; s = 1e-6f if size < 0.5
+// blobctrl/utils/utils.py:145-194 for one blob per image (the score itself: bc_splat.h).
 //   out[0] = (1 - s) * 1 (background after alpha compositing), out[1] = s.
-struct SplatParams { double v[16 * 8]; };
 __global__ void splat_kernel(const SplatParams prm, int h, int w, double* __restrict__ out) {
     const int n = blockIdx.y;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= h * w) return;
-    const double* p = prm.v + n * 8;
-    const double xs = p[0], ys = p[1], a = p[2], b = p[3], c = p[4], d = p[5], size = p[6];
     const int gy = idx / w, gx = idx - gy * w;
-    const double dx = ((double)gx - xs * (double)w) / (double)w;      // ut:151-153
-    const double dy = ((double)gy - ys * (double)h) / (double)h;
-    // solve [[a b][c d]] z = delta  (ut:156, torch.linalg.solve = LU with partial pivoting)
-    double z0, z1;
-    if (fabs(a) >= fabs(c)) {
-        const double f = c / a;
-        const double u = d - f * b;
-        z1 = (dy - f * dx) / u;
-        z0 = (dx - b * z1) / a;
-    } else {
-        const double f = a / c;
-        const double u = b - f * d;
-        z1 = (dx - f * dy) / u;
-        z0 = (dy - d * z1) / c;
-    }
-    const double m = dx * z0 + dy * z1;
-    double s = 1.0 / (1.0 + exp(m));                                  // sigmoid(-m)  ut:162
-    s = fmin(2.0 * s, 1.0);                                           // ut:163
-    if (size < 0.5) s = (double)1e-6f;                                // ut:165-172 (float32 constant in the reference)
+    const double s = bc_splat_score(prm.v + n * 8, gx, gy, h, w);
     double* o = out + (size_t)n * 2 * h * w;
     o[idx] = (1.0 - s);                                               // ut:179-181 alpha composite with bg score 1
     o[(size_t)h * w + idx] = s;

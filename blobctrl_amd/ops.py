@@ -3,12 +3,18 @@
 BASELINE.json's north star words the boundary as "driven from Python through PyTorch-ROCm custom ops that keep the
 StableDiffusionBlobCtrlPipeline.__call__ / BlobNet / UNet-LoRA API surface".  The compute entry points of this package are the C ABI
 of libblobctrl_hip.so (include/blobctrl_hip.h) reached through ctypes; this module registers the four calls the reference makes into
-its hot path as dispatcher-visible ops OVER that same C ABI, so that `torch.profiler`, dispatch modes and fake-tensor tracing see them:
+its hot path, and the five steps of its blob visualisation / feature grid, as dispatcher-visible ops OVER that same C ABI, so that
+`torch.profiler`, dispatch modes and fake-tensor tracing see them:
 
     blobctrl::splat_scores     blobctrl/utils/utils.py:145-194             (splat_features, tuple score_size branch)
     blobctrl::blobnet_forward  blobctrl/models/blobnet.py:720-945          (BlobNetModel.forward -> down / mid / up residuals)
     blobctrl::unet_forward     D/models/unets/unet_2d_condition.py:1039-1353 (patched forward with the three residual lists)
     blobctrl::denoise          blobctrl/pipelines/pipeline_blobnet.py:1025-1123 (the whole loop: one hipGraph launch per edit)
+    blobctrl::splat_maps       blobctrl/utils/utils.py:120-135, 145-181    (raw and composed scores, channels-last)
+    blobctrl::alpha_composite  blobctrl/utils/utils.py:179-181, 205-209    (compositing of raw scores a viz_score_fn changed)
+    blobctrl::splat_from_scores blobctrl/utils/utils.py:57-77, pipeline_blobnet.py:706-721 (scores x features, resize folded in)
+    blobctrl::resize_bilinear  blobctrl/utils/utils.py:280-294             (one level of pyramid_resize)
+    blobctrl::pack_rgb8        scripts/blobctrl_app.py:647-648             (fp64 [1][3][H][W] -> uint8 [H][W][3])
 
 The nn.Module shells (modules.py), `splat.splat_features` and `BlobCtrlEngine.__call__` call THROUGH these ops.  A module / engine is
 passed as an integer handle (ops take tensors and scalars, not Python objects): `register(obj)` keeps a weak reference.  Every op has
@@ -60,6 +66,68 @@ def splat_scores(params: torch.Tensor, h: int, w: int, device_index: int) -> tor
 @splat_scores.register_fake
 def _(params, h, w, device_index):
     return torch.empty((params.shape[0], 2, h, w), dtype=torch.float64, device=_dev(device_index))
+
+
+# ------------------------------------------------------------------------------------------------------------------ blob visualisation
+@torch.library.custom_op("blobctrl::splat_maps", mutates_args=())
+def splat_maps(params: torch.Tensor, h: int, w: int, device_index: int) -> List[torch.Tensor]:
+    """params as for splat_scores -> [raw, composed], each [n][h][w][2] float64 on the GPU: raw = (1, s), composed = ((1 - s), s)."""
+    from . import splat
+    return splat._splat_maps_impl(params, h, w, _dev(device_index))
+
+
+@splat_maps.register_fake
+def _(params, h, w, device_index):
+    return [torch.empty((params.shape[0], h, w, 2), dtype=torch.float64, device=_dev(device_index)) for _ in range(2)]
+
+
+@torch.library.custom_op("blobctrl::alpha_composite", mutates_args=())
+def alpha_composite(raw: torch.Tensor) -> torch.Tensor:
+    """raw [..., K] float64 on the GPU -> composed scores of the same shape: d_i = s_i * prod_{j>i}(1 - s_j), d_{K-1} = s_{K-1}."""
+    from . import splat
+    return splat._alpha_composite_impl(raw)
+
+
+@alpha_composite.register_fake
+def _(raw):
+    return torch.empty(tuple(raw.shape), dtype=raw.dtype, device=raw.device)
+
+
+@torch.library.custom_op("blobctrl::splat_from_scores", mutates_args=())
+def splat_from_scores(scores: torch.Tensor, features: torch.Tensor, out_h: int, out_w: int, channels_last: bool) -> torch.Tensor:
+    """scores [N][H][W][M] (channels_last) or [N][M][H][W], any strides, x features [N][M][C] -> [N][C][out_h][out_w] in the scores' dtype
+    (float64 / float32); a grid other than H x W is sampled bilinearly (align_corners=False) inside the read."""
+    from . import splat
+    return splat._splat_from_scores_impl(scores, features, out_h, out_w, channels_last)
+
+
+@splat_from_scores.register_fake
+def _(scores, features, out_h, out_w, channels_last):
+    return torch.empty((scores.shape[0], features.shape[2], out_h, out_w), dtype=scores.dtype, device=scores.device)
+
+
+@torch.library.custom_op("blobctrl::resize_bilinear", mutates_args=())
+def resize_bilinear(img: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
+    """img [N][K][H][W] float64 / float32 on the GPU -> [N][K][out_h][out_w], F.interpolate(mode="bilinear", align_corners=False)."""
+    from . import splat
+    return splat._resize_bilinear_impl(img, out_h, out_w)
+
+
+@resize_bilinear.register_fake
+def _(img, out_h, out_w):
+    return torch.empty((img.shape[0], img.shape[1], out_h, out_w), dtype=img.dtype, device=img.device)
+
+
+@torch.library.custom_op("blobctrl::pack_rgb8", mutates_args=())
+def pack_rgb8(img: torch.Tensor) -> torch.Tensor:
+    """img [1][3][H][W] float64 in [0, 1] on the GPU -> [H][W][3] uint8 = truncation of img * 255."""
+    from . import splat
+    return splat._pack_rgb8_impl(img)
+
+
+@pack_rgb8.register_fake
+def _(img):
+    return torch.empty((img.shape[2], img.shape[3], 3), dtype=torch.uint8, device=img.device)
 
 
 # ------------------------------------------------------------------------------------------------------------------ blobnet_forward

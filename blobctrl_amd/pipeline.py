@@ -737,6 +737,13 @@ class StableDiffusionBlobNetPipeline:
         return cls(vae=vae, unet=unet, tokenizer=tokenizer, text_encoder=text_encoder, blobnet=blobnet, scheduler=scheduler,
                    safety_checker=None, dinov2_processor=dinov2_processor, dinov2=dinov2)
 
+    def splat_features_from_scores(self, scores: torch.Tensor, features: torch.Tensor, size: Optional[int],
+                                   channels_last: bool = True) -> torch.Tensor:
+        """pipe:706-721 as a callable (the loop itself folds its rank-1 case into bc_assemble_input): float64 / float32 scores on the
+        GPU, one bc_splat_from_scores launch."""
+        from .splat import splat_features_from_scores
+        return splat_features_from_scores(scores, features, size, channels_last=channels_last)
+
     @property
     def engine(self) -> BlobCtrlEngine:
         """The captured-plan loop engine over the CURRENT packed weights of `unet` / `blobnet`: built on first use, re-pointed (plans

@@ -292,6 +292,28 @@ int bc_attention_causal(const bc_half* Q, const bc_half* K, const bc_half* Vt, b
  * out: DEVICE double [n][2][h][w]  (channel 0 = background, 1 = foreground), computed in fp64 like the reference. */
 int bc_splat_scores(const double* params_host, int n, int h, int w, double* out, bc_stream stream);
 
+/* The same rasteriser for the visualisation / dictionary branches: blobctrl/utils/utils.py:120-135 and 145-181 (one blob per
+ * image).  Same params.  raw, composed: DEVICE double [n][h][w][2], channels-last as the reference holds them:
+ * raw = (1, s) (ut:175-176), composed = ((1 - s), s) (ut:179-181); composed equals the output of the entry point above bit for bit. */
+int bc_splat_maps(const double* params_host, int n, int h, int w, double* raw, double* composed, bc_stream stream);
+/* Alpha compositing of raw scores, blobctrl/utils/utils.py:179-181 and 205-209: raw, out DEVICE double [npix][K] (K last),
+ * out_i = raw_i * prod_{j>i}(1 - raw_j), out_{K-1} = raw_{K-1}.  Not in place. */
+int bc_alpha_composite(const double* raw, long long npix, int K, double* out, bc_stream stream);
+/* Feature splat, blobctrl/utils/utils.py:57-77 and pipeline_blobnet.py:706-721: out[n][c][y][x] = sum_m S[n][m][y][x] * F[n][m][c].
+ * S is read through its element strides s_n, s_m, s_y, s_x (channels-first or channels-last, no transposed copy) on an Hin x Win
+ * grid; when Hout x Wout differs, S is resampled inside the read as F.interpolate(mode="bilinear", align_corners=False) does:
+ * src = (dst + 0.5) * in / out - 0.5 clamped at 0, upper neighbour clamped to in - 1, positions and weights in fp64.
+ * F [N][M][C] and out [N][C][Hout][Wout] contiguous; is_f32 selects float elements for S, F and out, else double. */
+int bc_splat_from_scores(const void* S, const void* F, int N, int M, int C, int Hin, int Win, long long s_n, long long s_m,
+                         long long s_y, long long s_x, int Hout, int Wout, int is_f32, void* out, bc_stream stream);
+/* One level of pyramid_resize, blobctrl/utils/utils.py:280-294: in [planes][Hin][Win] -> out [planes][Hout][Wout] with the
+ * sampling rule above; float (is_f32) or double. */
+int bc_resize_bilinear(const void* in, long long planes, int Hin, int Win, int Hout, int Wout, int is_f32, void* out,
+                       bc_stream stream);
+/* The app's image, scripts/blobctrl_app.py:647-648: img DEVICE double [3][H][W] with values in [0, 1] -> out DEVICE
+ * unsigned char [H][W][3] = truncation of img * 255, as astype(np.uint8) does. */
+int bc_pack_rgb8(const double* img, int H, int W, unsigned char* out, bc_stream stream);
+
 /* Input assembly: pipeline_blobnet.py:724-739 (construct_blobnet_input) fused with NCHW->NHWC, fp16 cast, channel padding
  * and the rank-1 feature splat (pipeline_blobnet.py:706-721).  Writes X[Bout][h][2w][Cpad]:
  *   left half  = (img_lat[bi][4], score[bi], score*feat[bi][0..F))   right half = (latents[b % Blat][4], score, score*feat)

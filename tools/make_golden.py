@@ -121,6 +121,123 @@ def golden_splat():
     print("splat: fg.sum=%.6f fg.max=%.6f" % (s[0, 1].sum(), s[0, 1].max()))
 
 
+# ------------------------------------------------------------------------------------------------ 1b. blob visualisation
+def viz_boost(s):
+    """A viz_score_fn that is not the identity: the `s * 1.5` enlargement the reference's docstring names (ut:109), clamped."""
+    return s.mul(1.5).clamp(max=1)
+
+
+def golden_blob_viz():
+    """splat_features beyond the pipeline's branch (ut:120-241), splat_features_from_scores (ut:57-77) and pyramid_resize (ut:280-294)
+    from the real reference: the app's blob image call (app:637-650), the dictionary return, the stand-alone helpers.  The palette is
+    drawn here (numpy PCG64) and stored with the outputs: the reference's own colour table is program text and is not copied."""
+    import time
+    from blobctrl.utils import utils as ut
+    rng = np.random.Generator(np.random.PCG64(2024))
+    colors = torch.from_numpy(rng.random((29, 3), dtype=np.float32))
+    out, meta = {"viz_colors": colors.numpy()}, {}
+
+    def blob_of(ell, W, H, size=1.0):
+        mean, cov = ref_inf.get_gs_from_ellipse(ell)
+        nm, nc = ref_inf.normalize_gs(mean, cov, W, H)
+        blob = ref_inf.get_blob_dict_from_norm_gs(nm, nc)
+        blob["sizes"] = torch.tensor([[size]])
+        return blob
+
+    def app_call(blob, viz_size, fn=ut.viz_score_fn):             # app:638-646 keyword for keyword (palette apart)
+        return splat_features(**blob, interp_size=64, viz_size=viz_size, is_viz=True, ret_layout=True, score_size=64,
+                              viz_score_fn=fn, viz_colors=colors, only_vis=True)["feature_img"]
+
+    # 1. the app's call on small grids
+    demo = "/root/reference/assets/results/demo"
+    cases = []
+    for name in ("move_hat", "enlarge_deer"):                     # two demo states whose first and last ellipse differ
+        st = json.load(open(os.path.join(demo, name, "state", "state.json")))
+        for idx in (0, -1):
+            cases.append(dict(name=f"{name}[{idx}]", ellipse=st["ellipse_lists"][idx][0], W=512, H=512, viz=[40, 40], size=1.0))
+    cases.append(dict(name="nonsquare", ellipse=[[300.0, 120.0], [60.0, 150.0], 33.0], W=640, H=384, viz=[48, 80], size=1.0))
+    cases.append(dict(name="degenerate", ellipse=[[256.0, 256.0], [1e-5, 1e-5], 0.0], W=512, H=512, viz=[40, 40], size=1.0))   # app:1384
+    cases.append(dict(name="absent", ellipse=cases[0]["ellipse"], W=512, H=512, viz=[40, 40], size=0.2))
+    for i, c in enumerate(cases):
+        img = app_call(blob_of(c["ellipse"], c["W"], c["H"], c["size"]), tuple(c["viz"]))
+        assert img.dtype == torch.float64 and tuple(img.shape) == (1, 3) + tuple(c["viz"])
+        out[f"app_{i}"] = img.numpy()
+    meta["app"] = cases
+
+    # 2. one full-resolution app call as the uint8 image the app makes of it (app:647-648) + its near-integer entries
+    full = cases[1]
+    blob = blob_of(full["ellipse"], 512, 512)
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        img = app_call(blob, (512, 512))
+        hwc = img[0].permute(1, 2, 0).contiguous().cpu().numpy()
+        u8 = (hwc * 255).astype(np.uint8)
+        times.append(time.perf_counter() - t0)
+    v = hwc * 255
+    near = np.argwhere(np.abs(v - np.round(v)) < 1e-6)
+    assert len(near) <= 1e-4 * hwc.size, f"{len(near)} near-integer entries: take another palette seed"
+    out["full_u8"], out["full_near_pos"] = u8, near.astype(np.int32)
+    out["full_near_val"] = hwc[tuple(near.T)] if len(near) else np.zeros(0)
+    meta["full"] = dict(ellipse=full["ellipse"], W=512, H=512, near=int(len(near)),
+                        reference_cpu_ms_median_of_5=1e3 * float(np.median(times)), threads=torch.get_num_threads())
+
+    # 3. dictionary returns
+    feats = torch.from_numpy(rng.standard_normal((1, 2, 16)))
+    out["dict_features"] = feats.numpy()
+    ell = cases[1]["ellipse"]
+    meta["dict"] = dict(ellipse=ell, W=512, H=512, ns_ellipse=cases[4]["ellipse"], ns_W=640, ns_H=384)
+    d0 = splat_features(**blob_of(ell, 512, 512), score_size=(64, 64), interp_size=16, features=feats)
+    d1 = splat_features(**blob_of(cases[4]["ellipse"], 640, 384), score_size=(48, 80), interp_size=20, features=feats, is_viz=True,
+                        viz_size=32, viz_colors=colors)
+    for tag, d in (("d0", d0), ("d1", d1)):
+        assert d["feature_img"] is None and d["entropy_img"] is None
+        meta[tag + "_keys"] = sorted(d.keys())
+        meta[tag + "_levels"] = sorted(int(k) for k in d["scores_pyramid"])
+        for k, lvl in d["scores_pyramid"].items():
+            out[f"{tag}_pyr_{int(k)}"] = lvl.numpy()
+        for k in ("feature_grid", "raw_scores", "composed_scores"):
+            out[f"{tag}_{k}"] = d[k].numpy()
+    try:
+        splat_features(**blob_of(cases[4]["ellipse"], 640, 384), score_size=(48, 80), interp_size=16, features=feats)
+        raise AssertionError("expected KeyError")
+    except KeyError:
+        meta["keyerror"] = dict(score_size=[48, 80], interp_size=16)
+
+    # 4. int viz_size, fg / bg only, a viz_score_fn that is not the identity
+    b = blob_of(ell, 512, 512)
+    out["vis_int32"] = splat_features(**b, score_size=(64, 64), viz_size=32, is_viz=True, viz_colors=colors, only_vis=True)["feature_img"].numpy()
+    out["fg_only"] = splat_features(**b, score_size=(64, 64), return_d_score=True, only_splatting_fg=True).contiguous().numpy()
+    out["bg_only"] = splat_features(**b, score_size=(64, 64), return_d_score=True, only_splatting_bg=True).contiguous().numpy()
+    out["app_boost"] = app_call(b, (40, 40), fn=viz_boost).numpy()
+
+    # 5. the helpers stand-alone
+    S = rng.random((2, 3, 9, 14))
+    Fm = rng.standard_normal((2, 3, 5))
+    out["sfs_scores"], out["sfs_features"] = S, Fm
+    for dt in ("f64", "f32"):
+        tdt = torch.float64 if dt == "f64" else torch.float32
+        s_cf, f = torch.from_numpy(S).to(tdt), torch.from_numpy(Fm).to(tdt)
+        for cl in (0, 1):
+            sc = s_cf.permute(0, 2, 3, 1).contiguous() if cl else s_cf
+            for tag, size in (("none", None), ("7", 7), ("9x14", (9, 14))):
+                r = ut.splat_features_from_scores(sc, f, size, channels_last=bool(cl))
+                assert r.dtype == tdt
+                out[f"sfs_{dt}_cl{cl}_{tag}"] = r.numpy()
+    P = rng.random((1, 2, 48, 80))
+    out["pyr_in"] = P
+    pyr = ut.pyramid_resize(torch.from_numpy(P), 20)
+    meta["pyr_levels"] = sorted(int(k) for k in pyr)
+    for k, lvl in pyr.items():
+        if int(k) != 80:
+            out[f"pyr_{int(k)}"] = lvl.numpy()
+    out["meta"] = np.array(json.dumps(meta))
+    path = os.path.join(OUT, "blob_viz.npz")
+    np.savez_compressed(path, **out)
+    print("blob_viz: %d arrays, %.1f KB, near-integer entries of the 512^2 image: %d, reference CPU %.1f ms" %
+          (len(out), os.path.getsize(path) / 1024, len(near), meta["full"]["reference_cpu_ms_median_of_5"]))
+
+
 # ------------------------------------------------------------------------------------------------ 2. nets
 def golden_nets():
     unet, blob = build_tiny()
@@ -1234,6 +1351,7 @@ if __name__ == "__main__":
     golden_clip_text()
     golden_vae()
     golden_splat()
+    golden_blob_viz()
     golden_schedulers()
     golden_dinov2()
     golden_nets()
