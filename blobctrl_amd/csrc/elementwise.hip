@@ -111,117 +111,53 @@ __global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, long
         y[i] = (h16)bc_silu_f((float)x[i]);
 }
 
-// coef row layout (blobctrl_amd/schedulers.py): see bc_cfg_scheduler_step in the header.
-//  [0] inv_alpha_t  [1] sigma_over_alpha      x0 = x*c0 - eps*c1
-//  [2] use_corrector
-//  [3] cc_x (last_sample) [4] cc_m0 (prev x0) [5] cc_m1 (prev-prev x0) [6] cc_mt (this x0)      x_c = sum
-//  [7] cp_x (x_c)         [8] cp_m0 (this x0) [9] cp_m1 (prev x0)  [10] cp_eps (guided eps)     x_next = sum
-//  [11] guidance scale (used when the launch argument is negative: lets a captured graph follow per-call values)
-//  [12] std_dev_t (stochastic DDIM, eta > 0; SDE-DPM-Solver++): x_next += c12 * noise[step]   (cfg_step_noise_kernel only)
-//  [13] cp_m2 (prev-prev x0, third-order DPM-Solver++): x_next += c13 * x0_{i-2}               (cfg_step3_kernel only)
+// Crop (right half) + classifier-free guidance + scheduler step: ONE body behind the three bc_cfg_scheduler_step* entry points,
+// specialised at compile time.  cf = coef row *step_idx (16 floats; the full column table is at the top of blobctrl_amd/schedulers.py).
+//   NOISE: x_next += cf[12] * noise[step][i], the variance noise of stochastic DDIM (scheduling_ddim.py:438-466) and SDE-DPM-Solver++;
+//          noise fp32 [nsteps][B][4][h][w]
+//   THIRD: x_next += cf[13] * x0_{i-2}, third-order DPM-Solver++ (scheduling_dpmsolver_multistep.py:804-887), read from the hist slot
+//          m1 that every instantiation already loads
+//   GUARD: a step index outside [0, nsteps) (the capture warm-ups advance the counter) has no table row and no noise slice: the
+//          launch then leaves every buffer as it is.  The plain entry point has no nsteps in its ABI, hence no guard.
+// `noise` / `nsteps` are not read by an instantiation without NOISE / GUARD.
+template <bool NOISE, bool THIRD, bool GUARD>
 __global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
-                                int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
-                                float* __restrict__ eps_out) {
+                                const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
+                                const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
     const int n = B * 4 * h * w;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int step = *step_idx;
-    if (i < n) {
-        const float* cf = coef + (size_t)step * 16;
-        int xx = i % w;
-        int yy = (i / w) % h;
-        int c = (i / (w * h)) % 4;
-        int b = i / (4 * w * h);
-        // eps token-major [2B][h][2w][4]; right half, uncond = batch b, cond = batch B + b   (pipe:1092-1098)
-        size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-        size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-        float eu = eps[pu], ec = eps[pc];
-        const float gscale = guidance >= 0.f ? guidance : cf[11];     // < 0: read from the coefficient table (graph-replay safe)
-        float e = eu + gscale * (ec - eu);
-        if (eps_out) eps_out[i] = e;
-        float x = latents[i];
-        float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
-        float x0 = x * cf[0] - e * cf[1];
-        float xc = x;
-        float pm0 = m0[i], pm1 = m1[i];
-        if (cf[2] != 0.f) xc = cf[3] * last[i] + cf[4] * pm0 + cf[5] * pm1 + cf[6] * x0;
-        float xn = cf[7] * xc + cf[8] * x0 + cf[9] * pm0 + cf[10] * e;
-        m1[i] = pm0;
-        m0[i] = x0;
-        last[i] = xc;
-        latents[i] = xn;
-    }
+    if (i >= n) return;
+    if (GUARD && (step < 0 || step >= nsteps)) return;
+    const float* cf = coef + (size_t)step * 16;
+    const int xx = i % w;
+    const int yy = (i / w) % h;
+    const int c = (i / (w * h)) % 4;
+    const int b = i / (4 * w * h);
+    // eps token-major [2B][h][2w][4]; right half, uncond = batch b, cond = batch B + b   (pipe:1092-1098)
+    const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
+    const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
+    const float eu = eps[pu], ec = eps[pc];
+    const float gscale = guidance >= 0.f ? guidance : cf[11];     // < 0: read from the coefficient table (graph-replay safe)
+    const float e = eu + gscale * (ec - eu);
+    if (eps_out) eps_out[i] = e;
+    const float x = latents[i];
+    float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
+    const float x0 = x * cf[0] - e * cf[1];
+    float xc = x;
+    const float pm0 = m0[i], pm1 = m1[i];
+    if (cf[2] != 0.f) xc = cf[3] * last[i] + cf[4] * pm0 + cf[5] * pm1 + cf[6] * x0;
+    float xn = cf[7] * xc + cf[8] * x0 + cf[9] * pm0 + cf[10] * e;
+    m1[i] = pm0;
+    m0[i] = x0;
+    last[i] = xc;
+    // the optional terms come last, after the history stores: every instantiation is the plain step up to here
+    if (NOISE) xn = xn + cf[12] * noise[(size_t)step * n + i];
+    if (THIRD) xn = xn + cf[13] * pm1;
+    latents[i] = xn;
 }
 
 __global__ void advance_kernel(int* step_idx) { *step_idx += 1; }
-
-// cfg_step_kernel plus the variance-noise term of stochastic DDIM (scheduling_ddim.py:438-466): x_next += coef[step][12] *
-// noise[step][i], noise fp32 [nsteps][B][4][h][w].  A step index at or past nsteps (the capture warm-ups advance the counter) has no
-// table row and no noise slice: the launch then leaves every buffer as it is.
-__global__ void cfg_step_noise_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
-                                      const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
-                                      const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
-    const int n = B * 4 * h * w;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int step = *step_idx;
-    if (i >= n || step < 0 || step >= nsteps) return;
-    const float* cf = coef + (size_t)step * 16;
-    const int xx = i % w;
-    const int yy = (i / w) % h;
-    const int c = (i / (w * h)) % 4;
-    const int b = i / (4 * w * h);
-    const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    const float eu = eps[pu], ec = eps[pc];
-    const float gscale = guidance >= 0.f ? guidance : cf[11];
-    const float e = eu + gscale * (ec - eu);
-    if (eps_out) eps_out[i] = e;
-    const float x = latents[i];
-    float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
-    const float x0 = x * cf[0] - e * cf[1];
-    float xc = x;
-    const float pm0 = m0[i], pm1 = m1[i];
-    if (cf[2] != 0.f) xc = cf[3] * last[i] + cf[4] * pm0 + cf[5] * pm1 + cf[6] * x0;
-    const float xn = cf[7] * xc + cf[8] * x0 + cf[9] * pm0 + cf[10] * e;
-    m1[i] = pm0;
-    m0[i] = x0;
-    last[i] = xc;
-    latents[i] = xn + cf[12] * noise[(size_t)step * n + i];
-}
-
-// cfg_step_kernel plus the x0_{i-2} term of third-order DPM-Solver++ (scheduling_dpmsolver_multistep.py:804-887): x_next +=
-// coef[step][13] * x0_{i-2}, read from the hist slot m1 that every step kernel already loads.  Like cfg_step_noise_kernel, a step index
-// at or past nsteps has no table row: the launch then leaves every buffer as it is.
-__global__ void cfg_step3_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
-                                 const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
-                                 int nsteps, float* __restrict__ eps_out) {
-    const int n = B * 4 * h * w;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int step = *step_idx;
-    if (i >= n || step < 0 || step >= nsteps) return;
-    const float* cf = coef + (size_t)step * 16;
-    const int xx = i % w;
-    const int yy = (i / w) % h;
-    const int c = (i / (w * h)) % 4;
-    const int b = i / (4 * w * h);
-    const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    const float eu = eps[pu], ec = eps[pc];
-    const float gscale = guidance >= 0.f ? guidance : cf[11];
-    const float e = eu + gscale * (ec - eu);
-    if (eps_out) eps_out[i] = e;
-    const float x = latents[i];
-    float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
-    const float x0 = x * cf[0] - e * cf[1];
-    float xc = x;
-    const float pm0 = m0[i], pm1 = m1[i];
-    if (cf[2] != 0.f) xc = cf[3] * last[i] + cf[4] * pm0 + cf[5] * pm1 + cf[6] * x0;
-    const float xn = cf[7] * xc + cf[8] * x0 + cf[9] * pm0 + cf[10] * e;
-    m1[i] = pm0;
-    m0[i] = x0;
-    last[i] = xc;
-    latents[i] = xn + cf[13] * pm1;
-}
-
 
 __global__ void nchw_to_nhwc_kernel(const void* __restrict__ src, int src_f32, int B, int C, int HW, int Cpad,
                                     h16* __restrict__ dst) {
@@ -392,54 +328,45 @@ extern "C" int bc_silu(const bc_half* x, bc_half* y, long long n, bc_stream stre
     return 0;
 }
 
-extern "C" int bc_cfg_scheduler_step(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
-                                     float guidance_scale, int B, int h, int w, float* eps_out, int advance,
-                                     bc_stream stream_) {
+// The launcher behind the three step entry points: `name` is the entry point's own name for the error text; an entry point without
+// NOISE / GUARD passes noise = nullptr / nsteps = 0, which its instantiation never reads.
+template <bool NOISE, bool THIRD, bool GUARD>
+static int cfg_step_launch(const char* name, const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
+                           float guidance_scale, int B, int h, int w, const float* noise, int nsteps, float* eps_out, int advance,
+                           bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0, "bc_cfg_scheduler_step: bad args");
+    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && (!NOISE || noise) && (!GUARD || (h > 0 && w > 0 && nsteps > 0)),
+                 "%s: bad args", name);
     int n = B * 4 * h * w;
-    hipLaunchKernelGGL(cfg_step_kernel, dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef, step_idx, hist,
-                       guidance_scale, B, h, w, eps_out);
+    hipLaunchKernelGGL((cfg_step_kernel<NOISE, THIRD, GUARD>), dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef,
+                       step_idx, hist, guidance_scale, B, h, w, noise, nsteps, eps_out);
     BC_CHECK_LAUNCH();
     if (advance) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
         BC_CHECK_LAUNCH();
     }
     return 0;
+}
+
+extern "C" int bc_cfg_scheduler_step(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
+                                     float guidance_scale, int B, int h, int w, float* eps_out, int advance,
+                                     bc_stream stream) {
+    return cfg_step_launch<false, false, false>("bc_cfg_scheduler_step", eps, latents, coef, step_idx, hist, guidance_scale, B, h, w,
+                                                nullptr, 0, eps_out, advance, stream);
 }
 
 extern "C" int bc_cfg_scheduler_step_noise(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
                                            float guidance_scale, int B, int h, int w, const float* noise, int nsteps, float* eps_out,
-                                           int advance, bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && noise && B > 0 && h > 0 && w > 0 && nsteps > 0,
-                 "bc_cfg_scheduler_step_noise: bad args");
-    int n = B * 4 * h * w;
-    hipLaunchKernelGGL(cfg_step_noise_kernel, dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef, step_idx, hist,
-                       guidance_scale, B, h, w, noise, nsteps, eps_out);
-    BC_CHECK_LAUNCH();
-    if (advance) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
-        BC_CHECK_LAUNCH();
-    }
-    return 0;
+                                           int advance, bc_stream stream) {
+    return cfg_step_launch<true, false, true>("bc_cfg_scheduler_step_noise", eps, latents, coef, step_idx, hist, guidance_scale, B, h,
+                                              w, noise, nsteps, eps_out, advance, stream);
 }
 
 extern "C" int bc_cfg_scheduler_step3(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
                                       float guidance_scale, int B, int h, int w, int nsteps, float* eps_out, int advance,
-                                      bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0,
-                 "bc_cfg_scheduler_step3: bad args");
-    int n = B * 4 * h * w;
-    hipLaunchKernelGGL(cfg_step3_kernel, dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef, step_idx, hist,
-                       guidance_scale, B, h, w, nsteps, eps_out);
-    BC_CHECK_LAUNCH();
-    if (advance) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
-        BC_CHECK_LAUNCH();
-    }
-    return 0;
+                                      bc_stream stream) {
+    return cfg_step_launch<false, true, true>("bc_cfg_scheduler_step3", eps, latents, coef, step_idx, hist, guidance_scale, B, h, w,
+                                              nullptr, nsteps, eps_out, advance, stream);
 }
 
 extern "C" int bc_nchw_to_nhwc_f16(const void* src, int src_is_f32, int B, int C, int HW, int Cpad, bc_half* dst,

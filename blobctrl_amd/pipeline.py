@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .engine import TrunkConfig, TrunkPlan
 from .launch import Recorder
-from .schedulers import DDIMTable, DPMSolverMultistepTable, UniPCTable, draw_variance_noise, randn_tensor
+from .schedulers import draw_variance_noise, randn_tensor, table_class
 from .weights import PackedTrunk, pad8
 
 
@@ -197,15 +197,10 @@ class BlobCtrlEngine:
             else:
                 eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=True)   # (images b and b + B: the CFG pair)
             P.eps = eps
-            if P.stochastic:
-                rec.call("bc_cfg_scheduler_step_noise", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.variance_noise,
-                         nsteps, P.eps_guided, 1, kind="cfg_step")
-            elif P.third_order:
-                rec.call("bc_cfg_scheduler_step3", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, nsteps, P.eps_guided, 1,
-                         kind="cfg_step")
-            else:
-                rec.call("bc_cfg_scheduler_step", eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, P.eps_guided, 1,
-                         kind="cfg_step")
+            # the plan's step form: the entry point and what it takes between `w` and `eps_out`
+            name, extra = ("bc_cfg_scheduler_step_noise", (P.variance_noise, nsteps)) if P.stochastic else \
+                ("bc_cfg_scheduler_step3", (nsteps,)) if P.third_order else ("bc_cfg_scheduler_step", ())
+            rec.call(name, eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, *extra, P.eps_guided, 1, kind="cfg_step")
 
         # ---- step A: BlobNet + UNet
         # The BlobNet branch is recorded for the side stream: fork (side waits for the start of the step on main), every
@@ -265,21 +260,15 @@ class BlobCtrlEngine:
         sched = self._sched_cache.get(key)
         if sched is None:
             nt, b0, b1 = self.scheduler_params[:3]
-            if self.scheduler_kind == "dpmsolver":
-                opts = dict(self.scheduler_params[3]) if len(self.scheduler_params) > 3 else {}
-                sched = DPMSolverMultistepTable(num_train_timesteps=nt, beta_start=b0, beta_end=b1, **opts)
-                if ts is not None:
-                    sched.set_timesteps(timesteps=list(ts))
-                else:
-                    sched.set_timesteps(n)
-                self._sched_cache[key] = sched
-                return sched
-            if ts is not None:
+            dpm = self.scheduler_kind == "dpmsolver"
+            if ts is not None and not dpm:
                 raise NotImplementedError(f"custom `timesteps` are not tabulated for {self.scheduler_kind} (the reference's set_timesteps "
                                           "takes none): pass num_inference_steps, or use DPMSolverMultistepScheduler")
-            cls = UniPCTable if self.scheduler_kind == "unipc" else DDIMTable
-            sched = cls(num_train_timesteps=nt, beta_start=b0, beta_end=b1)
-            if eta:
+            opts = dict(self.scheduler_params[3]) if dpm and len(self.scheduler_params) > 3 else {}
+            sched = table_class(self.scheduler_kind)(num_train_timesteps=nt, beta_start=b0, beta_end=b1, **opts)
+            if ts is not None:
+                sched.set_timesteps(timesteps=list(ts))
+            elif eta and not dpm:                                     # (DPM-Solver has no eta: its table takes none)
                 sched.set_timesteps(n, eta=float(eta))
             else:
                 sched.set_timesteps(n)

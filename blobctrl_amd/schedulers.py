@@ -47,6 +47,15 @@ class _Base:
         """[num_steps, 16] float32 coefficient rows."""
         return self.coef
 
+    @staticmethod
+    def _as(sigma):                                                       # (alpha_t, sigma_t) of a sigma (dpmsolver_multistep.py:468-472)
+        alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
+        return alpha_t, sigma * alpha_t
+
+    def _lam(self, i):                                                    # lambda = log(alpha) - log(sigma) of self.sigmas[i]
+        a, s = self._as(self.sigmas[i])
+        return torch.log(a) - torch.log(s)
+
 
 class UniPCTable(_Base):
     """UniPCMultistepScheduler restated as a coefficient table (scheduling_unipc_multistep.py:282-360, 453-901)."""
@@ -64,15 +73,6 @@ class UniPCTable(_Base):
         self.num_inference_steps = n
         self.coef = self._build(n)
         return self
-
-    @staticmethod
-    def _as(sigma):
-        alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
-        return alpha_t, sigma * alpha_t
-
-    def _lam(self, i):
-        a, s = self._as(self.sigmas[i])
-        return torch.log(a) - torch.log(s)
 
     @staticmethod
     def _bh(h, rks, order):
@@ -295,15 +295,6 @@ class DPMSolverMultistepTable(_Base):
         min_inv_rho, max_inv_rho = lambda_min ** (1 / rho), lambda_max ** (1 / rho)
         return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
 
-    @staticmethod
-    def _as(sigma):                                                       # :468-472
-        alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
-        return alpha_t, sigma * alpha_t
-
-    def _lam(self, k):
-        a, s = self._as(self.sigmas[k])
-        return torch.log(a) - torch.log(s)
-
     def step_orders(self):
         """The solver order of every step (step, :963-995): lower_order_nums, lower_order_final, lower_order_second."""
         o = self.options
@@ -375,6 +366,12 @@ class DPMSolverMultistepTable(_Base):
         return coef
 
 
+def table_class(kind):
+    """Scheduler kind -> its coefficient table class, for the drop-in schedulers and the engine alike ("unipc", "dpmsolver"; every
+    other kind tabulates DDIM)."""
+    return {"unipc": UniPCTable, "dpmsolver": DPMSolverMultistepTable}.get(kind, DDIMTable)
+
+
 def apply_table_step(coef_row, eps, x, hist, noise=None):
     """Host (torch) evaluation of one table row - the same arithmetic `bc_cfg_scheduler_step` (with `noise`,
     `bc_cfg_scheduler_step_noise`; with a third-order row, `bc_cfg_scheduler_step3`) performs after CFG.  Used by the drop-in scheduler
@@ -427,27 +424,33 @@ class TableScheduler:
     init_noise_sigma = 1.0
 
     def __init__(self, kind="unipc", **kw):
-        self.table_impl = UniPCTable(**kw) if kind == "unipc" else DPMSolverMultistepTable(**kw) if kind == "dpmsolver" else \
-            DDIMTable(**kw)
+        self.table_impl = table_class(kind)(**kw)
         self.kind = kind
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        self.table_impl.set_timesteps(num_inference_steps)
+    def _set_timesteps(self, device, *table_args, **table_kw):
+        """(Re)tabulate with the table's own `set_timesteps` arguments and rewind: step 0, no history."""
+        self.table_impl.set_timesteps(*table_args, **table_kw)
         self.timesteps = self.table_impl.timesteps.to(device) if device is not None else self.table_impl.timesteps
         self._i = 0
         self._hist = None
 
+    def set_timesteps(self, num_inference_steps, device=None):
+        self._set_timesteps(device, num_inference_steps)
+
     def scale_model_input(self, sample, timestep=None):
         return sample
 
-    def step(self, model_output, timestep, sample, return_dict=False, **kw):
+    def _apply_row(self, model_output, sample, noise=None):
+        """Table row `_i` applied to (model_output, sample): creates the history on the first step, then moves on to the next row."""
         if self._hist is None:
             z = torch.zeros_like(sample)
             self._hist = dict(m0=z, m1=z.clone(), last=z.clone())
-        row = self.table_impl.coef[self._i].tolist()
-        out = apply_table_step(row, model_output, sample, self._hist)
+        out = apply_table_step(self.table_impl.coef[self._i].tolist(), model_output, sample, self._hist, noise)
         self._i += 1
-        return (out,)
+        return out
+
+    def step(self, model_output, timestep, sample, return_dict=False, **kw):
+        return (self._apply_row(model_output, sample),)
 
 
 class SchedulerConfig(dict):
@@ -469,18 +472,29 @@ class _ConfiguredScheduler(TableScheduler):
     _defaults = {}
 
     def __init__(self, **kw):
-        cfg = dict(_SD15)
-        cfg.update(self._defaults)
-        cfg.update({k: v for k, v in kw.items() if v is not None})
+        cfg = self._make_config(kw)
         if cfg["beta_schedule"] != "scaled_linear" or cfg["prediction_type"] != "epsilon":
             raise NotImplementedError("only the SD-1.5 configuration (scaled_linear betas, epsilon prediction) is tabulated")
         self._check(cfg)
         super().__init__(self._kind, num_train_timesteps=cfg["num_train_timesteps"], beta_start=cfg["beta_start"],
                          beta_end=cfg["beta_end"])
-        self.config = SchedulerConfig(cfg)
-        # like diffusers' `_use_default_values`: keys the caller did not give are NOT inherited by another class's from_config
-        self.config["_use_default_values"] = sorted(k for k in cfg if k not in kw or kw[k] is None)
+        self.config = cfg
         self.timesteps = None
+
+    @classmethod
+    def _make_config(cls, kw):
+        """`.config` of an object built with the keyword arguments `kw`: SD-1.5 values, this class's defaults, then what the caller gave."""
+        cfg = dict(_SD15)
+        cfg.update(cls._defaults)
+        cfg.update({k: v for k, v in kw.items() if v is not None})
+        # like diffusers' `_use_default_values`: keys the caller did not give are NOT inherited by another class's from_config
+        return SchedulerConfig(cfg, _use_default_values=sorted(k for k in cfg if k not in kw or kw[k] is None))
+
+    @classmethod
+    def _known(cls, src):
+        """The entries of `src` that are constructor arguments of this class."""
+        known = set(_SD15) | set(cls._defaults)
+        return {k: v for k, v in src.items() if k in known}
 
     def _check(self, cfg):
         pass
@@ -489,11 +503,10 @@ class _ConfiguredScheduler(TableScheduler):
     def from_config(cls, config, **kw):
         """Like diffusers' ConfigMixin.from_config: keys this class knows are taken from `config` (another scheduler's config is
         fine - unknown keys such as PNDM's `skip_prk_steps` are dropped), everything else keeps this class's defaults."""
-        known = set(_SD15) | set(cls._defaults)
         defaulted = set(dict(config).get("_use_default_values", ()))
         src = {k: v for k, v in dict(config).items() if k not in defaulted}
         src.update(kw)
-        return cls(**{k: v for k, v in src.items() if k in known})
+        return cls(**cls._known(src))
 
     def table_params(self):
         """(num_train_timesteps, beta_start, beta_end): what the engine builds its coefficient table from."""
@@ -515,11 +528,7 @@ class PNDMScheduler(_ConfiguredScheduler):
     _defaults = dict(skip_prk_steps=True, set_alpha_to_one=False, timestep_spacing="leading", clip_sample=False)
 
     def __init__(self, **kw):
-        cfg = dict(_SD15)
-        cfg.update(self._defaults)
-        cfg.update({k: v for k, v in kw.items() if v is not None})
-        self.config = SchedulerConfig(cfg)
-        self.config["_use_default_values"] = sorted(k for k in cfg if k not in kw or kw[k] is None)
+        self.config = self._make_config(kw)
         self.timesteps = None
         self.table_impl = None
 
@@ -541,9 +550,7 @@ def scheduler_from_config_dir(path):
                "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
     if name not in classes:
         raise NotImplementedError(f"scheduler class {name} is not available (PNDM config holder, UniPC, DDIM and DPM-Solver are)")
-    cls = classes[name]
-    known = set(_SD15) | set(cls._defaults)
-    return cls(**{k: v for k, v in cfg.items() if k in known})
+    return classes[name](**classes[name]._known(cfg))
 
 
 class UniPCMultistepScheduler(_ConfiguredScheduler):
@@ -576,9 +583,6 @@ class DDIMScheduler(_ConfiguredScheduler):
         has neither of.)  Returns `(prev_sample,)`, or an object with `.prev_sample` for return_dict=True."""
         if eta < 0:
             raise NotImplementedError("eta < 0 is not a DDIM variance")
-        if self._hist is None:
-            z = torch.zeros_like(sample)
-            self._hist = dict(m0=z, m1=z.clone(), last=z.clone())
         tab = self.table_impl
         if float(eta) != getattr(tab, "eta", 0.0):                     # (re)tabulate for this eta; raises for a non-finite row
             tab.set_timesteps(tab.num_inference_steps, eta=float(eta))
@@ -589,12 +593,8 @@ class DDIMScheduler(_ConfiguredScheduler):
                                  " `variance_noise` stays `None`.")
             noise = variance_noise if variance_noise is not None else \
                 randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
-        row = tab.coef[self._i].tolist()
-        out = apply_table_step(row, model_output, sample, self._hist, noise)
-        self._i += 1
-        if not return_dict:
-            return (out,)
-        return _StepOutput(out)
+        out = self._apply_row(model_output, sample, noise)
+        return _StepOutput(out) if return_dict else (out,)
 
 
 class _StepOutput(tuple):
@@ -655,8 +655,7 @@ class DPMSolverMultistepScheduler(_ConfiguredScheduler):
         src = dict(config)
         defaulted = set(src.pop("_use_default_values", ()))
         src = {k: v for k, v in src.items() if k not in defaulted}
-        known = set(_SD15) | set(cls._defaults)
-        init = {k: v for k, v in src.items() if k in known}
+        init = cls._known(src)
         init.update(kw)
         s = cls(**init)
         hidden = {k: v for k, v in src.items() if k not in init}
@@ -678,10 +677,7 @@ class DPMSolverMultistepScheduler(_ConfiguredScheduler):
         return self.table_impl.num_inference_steps
 
     def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None):
-        self.table_impl.set_timesteps(num_inference_steps, timesteps=timesteps)
-        self.timesteps = self.table_impl.timesteps.to(device) if device is not None else self.table_impl.timesteps
-        self._i = 0
-        self._hist = None
+        self._set_timesteps(device, num_inference_steps, timesteps=timesteps)
 
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True):
         """One DPM-Solver++ update (:920-1007).  The SDE variant draws `randn_tensor(shape, generator, device, float32)` per step unless
@@ -689,16 +685,9 @@ class DPMSolverMultistepScheduler(_ConfiguredScheduler):
         tab = self.table_impl
         if tab.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        sample = sample.to(torch.float32)
-        if self._hist is None:
-            z = torch.zeros_like(sample)
-            self._hist = dict(m0=z, m1=z.clone(), last=z.clone())
         noise = None
         if tab.sde:
             noise = variance_noise.to(device=model_output.device, dtype=torch.float32) if variance_noise is not None else \
                 randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
-        out = apply_table_step(tab.coef[self._i].tolist(), model_output, sample, self._hist, noise).to(model_output.dtype)
-        self._i += 1
-        if not return_dict:
-            return (out,)
-        return _StepOutput(out)
+        out = self._apply_row(model_output, sample.to(torch.float32), noise).to(model_output.dtype)
+        return _StepOutput(out) if return_dict else (out,)

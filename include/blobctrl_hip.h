@@ -345,11 +345,11 @@ int bc_silu(const bc_half* x, bc_half* y, long long n, bc_stream stream);
  * combinations with per-step host-precomputed coefficients).
  *   eps      : UNet output, fp32 token-major [2B][h][2w][4]  (uncond batch first, then cond)
  *   latents  : fp32 [B][4][h][w] NCHW, updated in place
- *   coef     : device table [nsteps][16] (layout in blobctrl_amd/schedulers.py), row = *step_idx
+ *   coef     : device table [nsteps][16] (column layout: the table at the top of blobctrl_amd/schedulers.py), row = *step_idx
  *   hist     : fp32 [3][B*4*h*w] scheduler history (x0_prev, x0_prevprev, last_sample)
  *   eps_out  : optional fp32 [B][4][h][w] guided epsilon (for parity tracing) or NULL
  * guidance_scale < 0 => the scale is read from coef[*step_idx][11] (a captured graph then follows per-call values).
- * Increments *step_idx when advance != 0. */
+ * Increments *step_idx when advance != 0.  The two variants below are the same launch with one more term each. */
 int bc_cfg_scheduler_step(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
                           float guidance_scale, int B, int h, int w, float* eps_out, int advance, bc_stream stream);
 
@@ -364,8 +364,8 @@ int bc_cfg_scheduler_step_noise(const float* eps, float* latents, const float* c
                                 int advance, bc_stream stream);
 
 /* bc_cfg_scheduler_step for third-order DPM-Solver++ (scheduling_dpmsolver_multistep.py:804-887): the update then adds
- * coef[*step_idx][13] * x0_{i-2}, the x0 of two steps back (hist slot m1, which every step kernel already reads).
- *   nsteps : rows of coef.  A launch with *step_idx >= nsteps writes nothing (only `advance` still counts).
+ * coef[*step_idx][13] * x0_{i-2}, the x0 of two steps back (hist slot m1, which every step already reads).
+ *   nsteps : rows of coef, with the out-of-table rule of bc_cfg_scheduler_step_noise.
  * The other arguments are those of bc_cfg_scheduler_step. */
 int bc_cfg_scheduler_step3(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
                            float guidance_scale, int B, int h, int w, int nsteps, float* eps_out, int advance, bc_stream stream);

@@ -1,4 +1,8 @@
 """Shared helpers for the test-suite: tiny configs (must mirror tools/make_golden.py) and seeded inputs."""
+import os
+import struct
+import subprocess
+
 import numpy as np
 import torch
 
@@ -273,3 +277,51 @@ def write_model_tree(root, lora=True):
 def set_plan(monkeypatch, **kv):
     """BC_PLAN for the plans recorded from here on (blobctrl_amd/options.py): planner options as key=value pairs, bools as 0 / 1."""
     monkeypatch.setenv("BC_PLAN", ",".join(f"{k}={int(v)}" for k, v in kv.items()))
+
+
+# ------------------------------------------------------------------------------------------------ compiled plans (.bcplan files)
+def build_plan_dump(workdir):
+    """Compile tests/c/plan_dump.cpp into `workdir`; returns dump(path) -> (bufs, segs) of a `.bcplan` file: bufs = {index: (name,
+    bytes)}, segs = {segment name: [(op, stream id, [argument, ...]), ...]}, pointer arguments spelled 'p<buffer index>+<offset>'."""
+    exe = os.path.join(str(workdir), "plan_dump")
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "c", "plan_dump.cpp")
+    cc = subprocess.run(["g++", "-std=c++17", "-O1", src, "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr[-3000:]
+
+    def dump(path):
+        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        bufs, segs, cur = {}, {}, None
+        for line in r.stdout.splitlines():
+            f = line.split()
+            if f[0] == "buf":
+                bufs[int(f[1])] = (f[2], int(f[3]))
+            elif f[0] == "seg":
+                cur = segs.setdefault(f[1], [])
+            else:
+                cur.append((int(f[1]), int(f[2]), f[3:]))
+        return bufs, segs
+    return dump
+
+
+def plan_named(bufs, arg):
+    """'p<index>+<offset>' -> (buffer name, offset)."""
+    i, off = arg[1:].split("+")
+    return bufs[int(i)][0], int(off)
+
+
+def plan_stored(path):
+    """name -> bytes of the buffers a `.bcplan` file stores with their contents."""
+    raw = open(path, "rb").read()
+    o, nb = 16, struct.unpack_from("<I", raw, 12)[0]
+    data = {}
+    for _ in range(nb):
+        ln = struct.unpack_from("<I", raw, o)[0]
+        name = raw[o + 4:o + 4 + ln].decode()
+        o += 4 + ln
+        nbytes, has = struct.unpack_from("<QI", raw, o)
+        o += 12
+        if has:
+            data[name] = raw[o:o + nbytes]
+            o += nbytes
+    return data

@@ -2,13 +2,12 @@
 (tests/golden/schedulers_eta.npz), the noise-drawing helper against the noise the reference drew (loop_tiny_eta.npz,
 pipeline_call_eta.npz), and what a compiled stochastic plan launches (read back through the host-side `.bcplan` parser)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from tests.common import TINY, g, tiny_weights
+from tests.common import TINY, build_plan_dump, g, plan_named as _named, plan_stored, tiny_weights
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(REPO, "tests", "golden")
@@ -137,25 +136,7 @@ def test_noise_helper_draws_exactly_what_the_reference_drew():
 # ------------------------------------------------------------------------------------------------------------ compiled plans
 @pytest.fixture(scope="module")
 def plan_dump(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dump") / "plan_dump")
-    cc = subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(REPO, "tests", "c", "plan_dump.cpp"), "-o", exe],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-
-    def dump(path):
-        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        bufs, segs, cur = {}, {}, None
-        for line in r.stdout.splitlines():
-            f = line.split()
-            if f[0] == "buf":
-                bufs[int(f[1])] = (f[2], int(f[3]))
-            elif f[0] == "seg":
-                cur = segs.setdefault(f[1], [])
-            else:
-                cur.append((int(f[1]), int(f[2]), f[3:]))
-        return bufs, segs
-    return dump
+    return build_plan_dump(tmp_path_factory.mktemp("dump"))
 
 
 @pytest.fixture(scope="module")
@@ -165,12 +146,6 @@ def ddim_engine():
     usd, bsd = tiny_weights()
     ucfg, bcfg = tiny_trunk_configs()
     return BlobCtrlEngine(usd, bsd, ucfg, bcfg, device="cpu", scheduler="ddim", compile_only=True)
-
-
-def _named(bufs, arg):
-    """'p<index>+<offset>' -> (buffer name, offset)."""
-    i, off = arg[1:].split("+")
-    return bufs[int(i)][0], int(off)
 
 
 def test_compiled_plans_launch_the_noise_step_only_when_stochastic(ddim_engine, plan_dump, tmp_path):
@@ -205,19 +180,7 @@ def test_compiled_plans_launch_the_noise_step_only_when_stochastic(ddim_engine, 
         assert a[5:9] == ["-1", "1", "8", "8"] and a[10] == str(n) and a[12] == "1"
         assert len(segs1[name]) == len(segs[name])                      # the same launch list otherwise
     # the noise is stored WITH its contents (a C host can run the edit as is, or refill the named buffer)
-    import struct
-    raw = open(sto, "rb").read()
-    o, nb = 16, struct.unpack_from("<I", raw, 12)[0]
-    data = {}
-    for _ in range(nb):
-        ln = struct.unpack_from("<I", raw, o)[0]
-        name = raw[o + 4:o + 4 + ln].decode()
-        o += 4 + ln
-        nbytes, has = struct.unpack_from("<QI", raw, o)
-        o += 12
-        if has:
-            data[name] = raw[o:o + nbytes]
-            o += nbytes
+    data = plan_stored(sto)
     assert np.array_equal(np.frombuffer(data["variance_noise"], np.float32), noise.numpy().reshape(-1))
     coef = np.frombuffer(data["coef"], np.float32).reshape(n, 16)
     from blobctrl_amd.schedulers import DDIMTable

@@ -6,7 +6,6 @@ per-request batch with one generator per request, and the noise indexing of the 
 Bars (fixed before measuring, those of tests/test_parity_gpu.py::test_denoise_loop_matches_reference and tests/test_pipeline_call_gpu.py):
 tiny loop and loop-from-entry-tensors max-abs / scale < 1e-2 and PSNR > 40 dB; end-to-end __call__ < 3e-2 and > 36 dB; kernel
 max-abs <= 1e-6 of max |ref|; full-size step arithmetic max-abs <= 1e-5 of max |x|."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -16,7 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests.common import PIPE, TINY, FakeTokenizer, g, pipeline_cases, psnr, tiny_cfgs, tiny_pipeline_weights, tiny_weights  # noqa: E402
-from tests.gpu_common import make_pipeline, tiny_trunk_configs  # noqa: E402
+from tests.gpu_common import launch_step, make_pipeline, tiny_trunk_configs  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -59,7 +58,6 @@ def test_noise_step_kernel_matches_its_table_row(B):
     coef = coef.to(dev)
     eps = g(1, 2 * B, h, 2 * w, 4).to(dev)
     noise = g(2, nsteps, B, 4, h, w).to(dev)
-    stream = torch.cuda.current_stream().cuda_stream
 
     def run(step, guidance, advance=1):
         x = g(3 + step, B, 4, h, w).to(dev)
@@ -67,9 +65,8 @@ def test_noise_step_kernel_matches_its_table_row(B):
         eps_out = torch.full((B, 4, h, w), 123.0, device=dev)
         idx = torch.tensor([step], dtype=torch.int32, device=dev)
         x_in, hist_in = x.clone(), hist.clone()
-        _lib.check(lib.bc_cfg_scheduler_step_noise(eps.data_ptr(), x.data_ptr(), coef.data_ptr(), idx.data_ptr(), hist.data_ptr(),
-                                                   guidance, B, h, w, noise.data_ptr(), nsteps, eps_out.data_ptr(), advance,
-                                                   C.c_void_p(stream)), "bc_cfg_scheduler_step_noise")
+        _lib.check(launch_step(lib, "noise", eps, x, coef, idx, hist, guidance, B, h, w, eps_out, advance, noise=noise, nsteps=nsteps),
+                   "bc_cfg_scheduler_step_noise")
         torch.cuda.synchronize()
         assert int(idx.item()) == step + advance
         return x_in, hist_in, x, hist, eps_out

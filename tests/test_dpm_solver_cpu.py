@@ -3,14 +3,12 @@ DPMSolverMultistepScheduler (tests/golden/schedulers_dpm.npz, dpm_config.json), 
 pipeline_call_dpm.npz), and what compiled DPM plans launch (read back through the host-side `.bcplan` parser)."""
 import json
 import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from tests.common import TINY, g, tiny_weights
+from tests.common import TINY, build_plan_dump, g, plan_named as _named, plan_stored as _stored, tiny_weights
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(REPO, "tests", "golden")
@@ -209,47 +207,7 @@ def test_scheduler_config_dir_and_engine_tables():
 # ------------------------------------------------------------------------------------------------------------ compiled plans
 @pytest.fixture(scope="module")
 def plan_dump(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dump") / "plan_dump")
-    cc = subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(REPO, "tests", "c", "plan_dump.cpp"), "-o", exe],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-
-    def dump(path):
-        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        bufs, segs, cur = {}, {}, None
-        for line in r.stdout.splitlines():
-            f = line.split()
-            if f[0] == "buf":
-                bufs[int(f[1])] = (f[2], int(f[3]))
-            elif f[0] == "seg":
-                cur = segs.setdefault(f[1], [])
-            else:
-                cur.append((int(f[1]), int(f[2]), f[3:]))
-        return bufs, segs
-    return dump
-
-
-def _stored(path):
-    """name -> bytes of the buffers a `.bcplan` file stores with their contents."""
-    raw = open(path, "rb").read()
-    o, nb = 16, struct.unpack_from("<I", raw, 12)[0]
-    data = {}
-    for _ in range(nb):
-        ln = struct.unpack_from("<I", raw, o)[0]
-        name = raw[o + 4:o + 4 + ln].decode()
-        o += 4 + ln
-        nbytes, has = struct.unpack_from("<QI", raw, o)
-        o += 12
-        if has:
-            data[name] = raw[o:o + nbytes]
-            o += nbytes
-    return data
-
-
-def _named(bufs, arg):
-    i, off = arg[1:].split("+")
-    return bufs[int(i)][0], int(off)
+    return build_plan_dump(tmp_path_factory.mktemp("dump"))
 
 
 def test_compiled_dpm_plans(plan_dump, tmp_path):

@@ -3,10 +3,9 @@ tables, the tiny-net loop against the REFERENCE's own DPM-Solver loops (tests/go
 `__call__(timesteps=[...], generator=)` with an SDE-DPM-Solver++ scheduler (pipeline_call_dpm.npz), and the plan / graph cache when the
 scheduler changes between UniPC and DPM-Solver++ 2M.
 
-Bars (fixed before measuring, those of tests/test_kernels_gpu.py:516-544 and tests/test_ddim_eta_gpu.py:129-225): kernel max-abs <= 1e-6
+Bars (fixed before measuring, those of tests/test_kernels_gpu.py:516-544 and tests/test_ddim_eta_gpu.py:126-222): kernel max-abs <= 1e-6
 of max |ref| against an fp64 host evaluation; tiny loop (teacher-forced guided eps and free-running final latents) max-abs / scale
 < 1e-2 and PSNR > 40 dB; end-to-end __call__ < 3e-2 and > 36 dB."""
-import ctypes as C
 import json
 import os
 
@@ -17,7 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests.common import PIPE, TINY, FakeTokenizer, g, pipeline_cases, psnr, tiny_pipeline_weights, tiny_weights  # noqa: E402
-from tests.gpu_common import make_pipeline, tiny_trunk_configs  # noqa: E402
+from tests.gpu_common import launch_step, make_pipeline, tiny_trunk_configs  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 SD = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", num_train_timesteps=1000, steps_offset=1)
@@ -70,23 +69,13 @@ def test_step_kernels_on_dpm_tables(B, form):
     coef[:, 11] = 7.5
     coef = coef.to(dev)
     noise = torch.stack([g(200 + i, 1, 4, h, w).repeat(B, 1, 1, 1) for i in range(nsteps)]).to(dev)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     x = torch.from_numpy(ref[0]).repeat(B, 1, 1, 1).to(dev).contiguous()
     hist = torch.zeros(3, n, device=dev)
     idx = torch.zeros(1, dtype=torch.int32, device=dev)
     eps_out = torch.zeros(B, 4, h, w, device=dev)
 
     def launch(eps, guidance=-1.0, advance=1):
-        if form == "step":
-            rc = lib.bc_cfg_scheduler_step(eps.data_ptr(), x.data_ptr(), coef.data_ptr(), idx.data_ptr(), hist.data_ptr(), guidance,
-                                           B, h, w, eps_out.data_ptr(), advance, stream)
-        elif form == "noise":
-            rc = lib.bc_cfg_scheduler_step_noise(eps.data_ptr(), x.data_ptr(), coef.data_ptr(), idx.data_ptr(), hist.data_ptr(),
-                                                 guidance, B, h, w, noise.data_ptr(), nsteps, eps_out.data_ptr(), advance, stream)
-        else:
-            rc = lib.bc_cfg_scheduler_step3(eps.data_ptr(), x.data_ptr(), coef.data_ptr(), idx.data_ptr(), hist.data_ptr(), guidance,
-                                            B, h, w, nsteps, eps_out.data_ptr(), advance, stream)
-        _lib.check(rc, form)
+        _lib.check(launch_step(lib, form, eps, x, coef, idx, hist, guidance, B, h, w, eps_out, advance, noise=noise, nsteps=nsteps), form)
         torch.cuda.synchronize()
 
     worst = 0.0

@@ -516,6 +516,7 @@ def test_timestep_embedding(rec):
 def test_cfg_scheduler_step_matches_reference_trajectory(rec, golden_dir, kind, n):
     from blobctrl_amd.schedulers import DDIMTable, UniPCTable
     from oracle.schedulers import DDIMOracle, UniPCOracle
+    from tests.gpu_common import launch_step
     B, hh, ww = 1, 8, 8
     tab = (UniPCTable() if kind == "unipc" else DDIMTable()).set_timesteps(n)
     orc = UniPCOracle() if kind == "unipc" else DDIMOracle()
@@ -534,8 +535,7 @@ def test_cfg_scheduler_step_matches_reference_trajectory(rec, golden_dir, kind, 
         full[B:, :, ww:, :] = ec.permute(0, 2, 3, 1)
         full[:, :, :ww, :] = 123.0                                    # left half must be ignored (pipe:1092-1093)
         fd = full.cuda()
-        rc = lib.bc_cfg_scheduler_step(fd.data_ptr(), lat.data_ptr(), coef.data_ptr(), idx.data_ptr(), hist.data_ptr(), 7.5,
-                                       B, hh, ww, eg.data_ptr(), 1, torch.cuda.current_stream().cuda_stream)
+        rc = launch_step(lib, "step", fd, lat, coef, idx, hist, 7.5, B, hh, ww, eg, 1)
         assert rc == 0
         e = eu + 7.5 * (ec - eu)
         x = orc.step(e, x)
