@@ -214,9 +214,10 @@ class TrunkPlan:
             gw = self.gw_tile(M, Cout, Cin, x.C if skip is not None else 0) if Cout >= 1280 else 0
             if gw:                                        # low-resolution levels: weights streamed into VGPRs (gemm_wreg.hip)
                 w, _, b = pw.gw(p + "conv_shortcut.weight", gw, bias=p + "conv_shortcut.bias")
-                out = self.rec.empty(M, Cout)
-                self.rec.gemm(A=x.t, W=w, M=M, N=Cout, K=Cin, out=out, bias=b, tile_cfg=gw, kind="conv1x1", **kw)
-                sc = Act(out, Cout, x.H, x.W)
+                # (a name of its own: `out` is the caller's buffer for conv2, which must not write over the residual it reads)
+                sc_t = self.rec.empty(M, Cout)
+                self.rec.gemm(A=x.t, W=w, M=M, N=Cout, K=Cin, out=sc_t, bias=b, tile_cfg=gw, kind="conv1x1", **kw)
+                sc = Act(sc_t, Cout, x.H, x.W)
             else:
                 sc = Act(self.dense(x.t, M, Cin, p + "conv_shortcut", Cout, kind="conv1x1", **kw), Cout, x.H, x.W)
         else:

@@ -412,6 +412,17 @@ class Recorder:
         g.out_mode = out_mode
         g.C = out.data_ptr() + out_offset * out.element_size()
         g.ldc = ldc if ldc is not None else (n_t0 if C_t is not None else n_out)
+        # an epilogue reads R / R2 / S rows while other workgroups (split-K reducers, neighbouring tiles of a convolution's shortcut taps)
+        # already write theirs: an output over one of them computes garbage silently, so it is refused here
+        es = out.element_size()
+        c_hi = g.C + (((M - 1) * g.ldc + n_out) * es if out_mode != _lib.OUT_F16_T else out.numel() * es - out_offset * es)
+        for nm, t, ld, width in (("R", R, ldr, n_out), ("R2", R2, ldr2, n_out), ("S", S, lds, S1 or Cs), ("S2", S2, lds2, Cs - S1)):
+            if t is None:
+                continue
+            lo = t if isinstance(t, int) else t.data_ptr()
+            hi = lo + (((M - 1) * ld + width) * 2 if isinstance(t, int) or nm != "R2" else t.numel() * t.element_size())
+            if lo < c_hi and g.C < hi:
+                raise _lib.BlobCtrlHipError(f"bc_gemm({kind}): the output [{g.C:#x}, {c_hi:#x}) overlaps {nm} [{lo:#x}, {hi:#x})")
         g.ln_colsum, g.ln_eps = ptr(ln_colsum), ln_eps
         g.C_t, g.ldc_t, g.n_t0 = ptr(C_t), ldc_t, n_t0
         g.w_bstride, g.vec_bstride, g.sm_group, g.sm_valid, g.sm_keep = w_bstride, vec_bstride, sm_group, sm_valid, sm_keep

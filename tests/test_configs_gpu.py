@@ -123,6 +123,24 @@ def test_batch8_samples_equal_batch1_full_size(full_pipe):
         assert e < 3e-2 and psnr(out8[b:b + 1], single) > 40.0, f"sample {b}: rel {e:.3e} psnr {psnr(out8[b:b + 1], single):.1f}"
 
 
+@pytest.mark.parametrize("batch", [3, 5, 6, 7])
+def test_odd_request_batches_equal_batch1_full_size(full_pipe, batch):
+    """Request batches between the ones the other tests run (1, 2, 4, 8) at 512^2: BlobNet at B = 3, 5, 6, 7 and the UNet at twice that cross
+    gn_pass_min_requests, ctx_fold_maxb, gw_maxm and the row-block thresholds at other levels than batch 8 does.  One denoise step of EVERY
+    request inside the batch against the same request alone, at the bars of test_batch8_samples_equal_batch1_full_size."""
+    inp, score = _inputs(512, batch)
+    out = _run(full_pipe, inp, score, 1, guidance_scale=7.5)
+    assert out.shape == (batch, 4, 64, 64) and np.isfinite(out).all()
+    for b in range(batch):
+        one = dict(inp)
+        one["latents"] = inp["latents"][b:b + 1]
+        one["prompt"] = torch.cat([inp["prompt"][b:b + 1], inp["prompt"][batch + b:batch + b + 1]])
+        single = _run(full_pipe, one, score, 1, guidance_scale=7.5)
+        e, p = _rel(out[b:b + 1], single), psnr(out[b:b + 1], single)
+        print(f"request batch {batch}, request {b}: one step vs the request alone rel {e:.3e}, PSNR {p:.1f} dB")
+        assert e < 3e-2 and p > 40.0, f"batch {batch} request {b}: rel {e:.3e} psnr {p:.1f}"
+
+
 def test_plan_cache_is_bounded():
     """Plans (static buffers + captured graphs) are cached per (batch, canvas, steps); the cache evicts least-recently-used plans."""
     usd, bsd = tiny_weights()

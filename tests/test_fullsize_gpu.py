@@ -55,6 +55,64 @@ def test_full_size_blobnet_and_unet_step(full):
     assert err < 1e-2 and psnr(eps, ref) > 40.0
 
 
+def _step_vs_oracle(full, h, w, requests, tag):
+    """One BlobNet forward at batch `requests` and one UNet forward at the CFG batch 2 x requests (with the ORACLE's residuals: isolates the
+    UNet) on an h x w canvas through the modules, against oracle.nets: all 28 BlobNet residuals and the UNet's eps at the BASELINE.json bar."""
+    import os
+    from blobctrl_amd.modules import BlobNetModel, UNet2DConditionModel
+    from oracle.nets import blobnet_forward, unet_forward
+    torch.set_num_threads(min(32, len(os.sched_getaffinity(0))))
+    n = requests
+    t = torch.tensor(601)
+    xb = torch.cat([g(11, n, 4, h, w), g(12, n, 1, h, w).abs().clamp(max=1), g(13, n, 1024, h, w) * 0.3], 1)
+    blobnet = BlobNetModel(full["bsd"], full["bcfg"])
+    down, mid, up = blobnet(xb.cuda(), t, conditioning_scale=1.0, return_dict=False)
+    rd, rm, ru = blobnet_forward(full["bsd"], full["obcfg"], xb, t, 1.0)
+    assert len(down) + 1 + len(up) == len(rd) + 1 + len(ru) == 28
+    worst, worst_db = 0.0, 1e9
+    for a, b in list(zip(down, rd)) + [(mid, rm)] + list(zip(up, ru)):
+        a, b = a.float().cpu().numpy(), b.numpy()
+        assert a.shape == b.shape
+        worst = max(worst, np.abs(a - b).max() / max(np.abs(b).max(), 1e-6))
+        worst_db = min(worst_db, psnr(a, b))
+    del blobnet
+    xu = g(14, 2 * n, 5, h, w)
+    ehs = g(15, 2 * n, 77, 768)
+    sq = lambda r: r[..., -r.shape[-2]:].contiguous()          # (the slice the pipeline passes: the right-hand H columns of the canvas)
+    rd2 = [sq(r).repeat(2, 1, 1, 1) for r in rd]
+    rm2 = sq(rm).repeat(2, 1, 1, 1)
+    ru2 = [sq(r).repeat(2, 1, 1, 1) for r in ru]
+    ref = unet_forward(full["usd"], full["oucfg"], xu, t, ehs, rd2, rm2, ru2).numpy()
+    unet = UNet2DConditionModel(full["usd"], full["ucfg"])
+    eps = unet(xu.cuda(), t, encoder_hidden_states=ehs.cuda(), down_block_add_samples=[r.cuda() for r in rd2],
+               mid_block_add_sample=rm2.cuda(), up_block_add_samples=[r.cuda() for r in ru2], return_dict=False)[0]
+    eps = eps.float().cpu().numpy()
+    err = np.abs(eps - ref).max() / np.abs(ref).max()
+    print(f"full-size step {tag}: UNet eps max-abs/scale {err:.3e}, PSNR {psnr(eps, ref):.1f} dB; BlobNet residuals worst {worst:.3e}, {worst_db:.1f} dB")
+    assert worst < 1e-2 and worst_db > 40.0, f"{tag}: BlobNet residuals max-abs/scale {worst:.3e}, PSNR {worst_db:.1f} dB"
+    assert err < 1e-2 and psnr(eps, ref) > 40.0, f"{tag}: UNet eps {err:.3e} / {psnr(eps, ref):.1f} dB"
+
+
+def test_full_size_step_576x448(full):
+    """A 576 x 448 edit: canvas 72 x 112 (9 x 7 convolution tiles), then 36 x 56, 18 x 28 and 9 x 14 - maps on which every fused family is
+    ineligible and the fallback launch list runs at 640 and 1280 channels.  The oracle costs what the 512 x 512 step above costs (the same
+    pixel count to 2 %)."""
+    _step_vs_oracle(full, 72, 112, 1, "576x448")
+
+
+def test_full_size_step_520x520(full):
+    """A 520 x 520 edit: canvas 65 x 130, then 33 x 65, 17 x 33 and 9 x 17 - odd maps at every level, explicit-size upsamples and skips at
+    full width.  The oracle costs what the 512 x 512 step above costs."""
+    _step_vs_oracle(full, 65, 130, 1, "520x520")
+
+
+def test_full_size_step_512x512_request_batch_3(full):
+    """512 x 512 at request batch 3: BlobNet at B = 3, the UNet at B = 6 - an odd batch between the sizes the other tests run (1, 2, 4, 8).
+    The oracle runs three BlobNet and six UNet images: about five times the cost of the one-minute 512 x 512 case above on a host where that
+    one takes its minute (measured on one 32-thread box: 20 s against 9 s)."""
+    _step_vs_oracle(full, 64, 128, 3, "512x512 x3")
+
+
 def test_full_size_two_step_loop_vs_oracle(full):
     """The north-star bar at the benchmark's own size: final latents of a (2-step, DDIM, CFG 7.5) 512x512 edit through the
     hipGraph-replayed engine vs the CPU oracle loop on the same seeded weights and inputs: PSNR >= 40 dB, max-abs <= 1e-2 of the
