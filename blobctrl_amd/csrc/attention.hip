@@ -389,16 +389,18 @@ int launch_attn_nw(const h16* Q, const h16* K, const h16* Vt, h16* O, int B, int
     return 0;
 }
 
-template <int D>
-int launch_attn(const h16* Q, const h16* K, const h16* Vt, h16* O, int B, int heads, int Nq, int Nkv, int ldq, int ldk,
-                int ldvt, int ldo, long long qbs, long long kbs, long long vbs, long long obs, float scale,
-                int causal, hipStream_t stream) {
+// The build of a launch: NW * 10 + WPE (waves per workgroup, minimum waves per SIMD the register allocation allows) from the shape
+// alone.  Host arithmetic without a device: launch_attn dispatches on it and bc_attention_build reports it, so a test can assert
+// which instantiation a shape runs.  BC_ATTN_NO8 is read at every call (a process can run both d = 40 builds on one shape): the
+// loop's launches are replayed from captured graphs, so the getenv is off the replay path; under BC_NO_GRAPHS it is one more
+// environment lookup per d = 40 launch, expected to be negligible next to the launch itself (not measured).
+int attn_build(int d, int B, int heads, int Nq, int Nkv, int causal) {
     // Measured on MI355X: splitting short sequences over more, smaller workgroups (NW = 2 / 1) is SLOWER (every workgroup
     // re-stages the whole K / V with fewer threads: D=160, N=512: 18 vs 35 TFLOP/s), so the 4-wave form is always used.
     // A second query block per wave (template parameter QB = 2: K / V fragments read once for 64 queries) was measured slower
     // than QB = 1 at every shape of the loop once the tiles arrive by LDS-DMA (d=40 N=8192: 556 vs 613 TFLOP/s; it costs
     // occupancy), so only QB = 1 is instantiated.
-    if constexpr (D == 40) {
+    if (d == 40) {
         // Round 2 (tools/attn_probe.py, L0 shape B=2 / 768^2 batch 4, TFLOP/s): 4 waves x 1 query block 633 / 775; 4 x 2 blocks
         // (each K / V^T fragment feeds two MFMAs: half the LDS reads) 634 / 793; 8 waves x 1 block (the tile is staged once for 256
         // queries) 659 / 804; 8 x 2 660 / 737.  Halving the LDS traffic buys nothing - the kernel is VALU-issue-bound - so the
@@ -406,23 +408,44 @@ int launch_attn(const h16* Q, const h16* K, const h16* Vt, h16* O, int B, int he
         const long long wgs8 = (long long)bc_ceil_div(Nq, QW * 8) * heads * B;
         // Round 3: from ONE 8-wave workgroup per CU (was two): BlobNet's batch-1 self-attention at the 64 x 128 level (256 such
         // workgroups) then stages every K / V^T tile once per 256 queries too - step 10.59 -> 10.49 ms (same box, two rounds).
-        static const bool no8 = getenv("BC_ATTN_NO8") != nullptr;      // (the 4-wave form for every grid: tests run both on one shape)
-        if (wgs8 >= 256 && Nkv >= 1024 && !causal && !no8)
-            return launch_attn_nw<D, 8, 1, 4>(Q, K, Vt, O, B, heads, Nq, Nkv, ldq, ldk, ldvt, ldo, qbs, kbs, vbs, obs, scale, causal, stream);
+        if (wgs8 >= 256 && Nkv >= 1024 && !causal && getenv("BC_ATTN_NO8") == nullptr)     // (BC_ATTN_NO8: the 4-wave form for every grid)
+            return 84;
     }
-    if constexpr (D == 80) {
+    if (d == 80) {
         // Round 5: the 8-wave form at the 32 x 64 level too (2048 keys; the UNet's launch = 128 workgroups: a K / V^T tile staged once for 256
         // queries, two waves per SIMD on half the CUs instead of one wave per SIMD on all of them - their MFMA and softmax phases
         // interleave, and the other queue has the other CUs): six interleaved same-box pairs, ms per step, 4-wave vs 8-wave: 9.122 / 9.071,
         // 9.086 / 9.082, 9.094 / 9.076, 9.084 / 9.068, 8.937 / 8.887, 8.907 / 8.904.
-        if (Nkv >= 1024 && !causal && Nq % (QW * 8) == 0)
+        if (Nkv >= 1024 && !causal && Nq % (QW * 8) == 0) return 81;
+    }
+    if (d <= 40) {
+        // enough workgroups for 4 per CU and a long key loop: take the 128-VGPR build (4 waves per SIMD)
+        const long long wgs = (long long)bc_ceil_div(Nq, QW * 4) * heads * B;
+        if (wgs >= 4 * 256 && Nkv >= 1024 && !causal) return 44;
+    }
+    return 41;
+}
+
+template <int D>
+int launch_attn(const h16* Q, const h16* K, const h16* Vt, h16* O, int B, int heads, int Nq, int Nkv, int ldq, int ldk,
+                int ldvt, int ldo, long long qbs, long long kbs, long long vbs, long long obs, float scale,
+                int causal, hipStream_t stream) {
+    const int build = attn_build(D, B, heads, Nq, Nkv, causal);
+    if constexpr (D == 40) {
+        if (build == 84)
+            return launch_attn_nw<D, 8, 1, 4>(Q, K, Vt, O, B, heads, Nq, Nkv, ldq, ldk, ldvt, ldo, qbs, kbs, vbs, obs, scale, causal, stream);
+    }
+    if constexpr (D == 80) {
+        if (build == 81)
             return launch_attn_nw<D, 8, 1>(Q, K, Vt, O, B, heads, Nq, Nkv, ldq, ldk, ldvt, ldo, qbs, kbs, vbs, obs, scale, causal, stream);
     }
     if constexpr (D <= 40) {
-        // enough workgroups for 4 per CU and a long key loop: take the 128-VGPR build (4 waves per SIMD)
-        const long long wgs = (long long)bc_ceil_div(Nq, QW * 4) * heads * B;
-        if (wgs >= 4 * 256 && Nkv >= 1024 && !causal)
+        if (build == 44)
             return launch_attn_nw<D, 4, 1, 4>(Q, K, Vt, O, B, heads, Nq, Nkv, ldq, ldk, ldvt, ldo, qbs, kbs, vbs, obs, scale, causal, stream);
+    }
+    if (build != 41) {                                     // (a build attn_build names must have its launch above)
+        bc_set_error("bc_attention: no launch for build %d at head_dim %d", build, D);
+        return 1;
     }
     return launch_attn_nw<D, 4, 1>(Q, K, Vt, O, B, heads, Nq, Nkv, ldq, ldk, ldvt, ldo, qbs, kbs, vbs, obs, scale, causal, stream);
 }
@@ -476,4 +499,13 @@ extern "C" int bc_attention_causal(const bc_half* Q, const bc_half* K, const bc_
                                    bc_stream stream) {
     return attention_impl(Q, K, Vt, O, B, heads, d, Nq, Nkv, ldq, ldk, ldvt, ldo, q_bstride, k_bstride, vt_bstride, o_bstride,
                           scale, 1, stream);
+}
+
+extern "C" int bc_attention_build(int d, int B, int heads, int Nq, int Nkv, int causal) {
+    switch (d) {
+        case 8: case 16: case 32: case 40: case 64: case 80: case 160:
+            return attn_build(d, B, heads, Nq, Nkv, causal);
+        default:
+            return -1;
+    }
 }

@@ -283,6 +283,10 @@ int bc_attention_causal(const bc_half* Q, const bc_half* K, const bc_half* Vt, b
                         int ldq, int ldk, int ldvt, int ldo,
                         long long q_bstride, long long k_bstride, long long vt_bstride, long long o_bstride,
                         float scale, bc_stream stream);
+/* Which instantiation bc_attention (causal = 0) / bc_attention_causal (causal = 1) launches for a shape: NW * 10 + WPE = 41, 44, 81 or
+ * 84 (NW waves per workgroup = 32 NW queries; WPE = 4 is the 128-VGPR build), negative for a head_dim that is not instantiated.  Host
+ * arithmetic only (no device); reads BC_ATTN_NO8 (d = 40: never the 8-wave form) at every call, like the launcher. */
+int bc_attention_build(int d, int B, int heads, int Nq, int Nkv, int causal);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Blob maths and loop glue

@@ -411,9 +411,13 @@ def test_attention_large_ragged_uses_128_vgpr_build(rec, eight_waves, monkeypatc
     """B=2, 8 heads, d=40, 8450 tokens (a 65 x 130 canvas): the grid is large enough for the 128-VGPR (4 waves per SIMD) builds -
     the 8-wave workgroup (256 queries) the loop uses, and the 4-wave one (BC_ATTN_NO8) - and 8450 % 64 != 0 sends the last key tile
     through the masked tail (the path where those builds keep their few register spills); 8450 % 256 != 0 leaves a ragged query block."""
-    if not eight_waves:
+    from blobctrl_amd import _lib
+    if eight_waves:
+        monkeypatch.delenv("BC_ATTN_NO8", raising=False)
+    else:
         monkeypatch.setenv("BC_ATTN_NO8", "1")
     B, heads, d, N = 2, 8, 40, 8450
+    assert _lib.load().bc_attention_build(d, B, heads, N, N, 0) == (84 if eight_waves else 44)      # (the switch is read at every launch)
     Cc = heads * d
     q, k, v = (g(s_, B, N, Cc).half().cuda() for s_ in (1, 2, 3))
     ldvt = (N + 63) // 64 * 64
