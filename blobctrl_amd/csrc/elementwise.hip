@@ -18,11 +18,25 @@ __global__ void splat_kernel(const SplatParams prm, int h, int w, double* __rest
     o[(size_t)h * w + idx] = s;
 }
 
+// The divisor of the noisy latents in a SCALED assembly (pipe:1032 `scheduler.scale_model_input`, the sigma-space schedulers):
+// column 14 of coefficient row *step_idx, sqrt(sigma_t^2 + 1).  A step index outside [0, nsteps) (the capture warm-ups advance the
+// counter) has no table row: the divisor is then 1 and x / 1 = x, the unscaled kernel's output bit for bit.
+__device__ __forceinline__ float input_divisor(const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps) {
+    const int step = *step_idx;
+    return (step >= 0 && step < nsteps) ? coef[(size_t)step * 16 + 14] : 1.f;
+}
+
 // pipeline_blobnet.py:724-739 + :706-721.  X[b][y][x][c], x in [0, 2w): left = clean image latents, right = noisy latents.
+//   SCALED: the noisy latents (right half, channels 0-3) are divided by input_divisor() in fp32 before the fp16 conversion, as the
+//           reference divides `latent_model_input`; the clean latents, the score and the feature channels are what they are without
+//           it.  `coef` / `step_idx` / `nsteps` are not read by the instantiation without SCALED.
+template <bool SCALED>
 __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
                                 const float* __restrict__ score, const float* __restrict__ feat, int Bimg, int F, int Bout,
-                                int h, int w, int Cpad, int dup_score, h16* __restrict__ X) {
+                                int h, int w, int Cpad, int dup_score, const float* __restrict__ coef,
+                                const int* __restrict__ step_idx, int nsteps, h16* __restrict__ X) {
     const long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
+    const float div = SCALED ? input_divisor(coef, step_idx, nsteps) : 1.f;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
         const int nch = Cpad / 8;
@@ -43,6 +57,7 @@ __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, con
             float v = 0.f;
             if (c < 4) {
                 v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + y) * w + xs] : img_lat[(((size_t)bi * 4 + c) * h + y) * w + xs];
+                if (SCALED && right) v = v / div;
             } else if (c == 4) {
                 v = sc;
             } else if (c < 5 + F) {
@@ -59,11 +74,14 @@ __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, con
 // The same input (8 channels: 4 latents, score, [score], 0, 0) written as the 3x3 im2col operand of conv_in: row = canvas pixel,
 // k = tap * 8 + channel for the nine taps (zero outside the h x 2w canvas = the convolution's padding), zero-filled up to 128, so that
 // conv_in (K = 72: outside the LDS-DMA GEMM's K % 64 == 0 fast path, 41 us per launch on the register-staged kernel) runs as a dense
-// K = 128 GEMM.  One thread per (pixel, 16-byte chunk).
+// K = 128 GEMM.  One thread per (pixel, 16-byte chunk).  SCALED as in assemble_kernel: the noisy latents of every tap are divided.
+template <bool SCALED>
 __global__ void assemble_im2col_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
                                        const float* __restrict__ score, int Bimg, int Bout, int h, int w, int dup_score,
+                                       const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps,
                                        h16* __restrict__ X) {
     const long long total = (long long)Bout * h * 2 * w * 16;
+    const float div = SCALED ? input_divisor(coef, step_idx, nsteps) : 1.f;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const int chunk = (int)(idx & 15);
         const long long pix = idx >> 4;
@@ -80,9 +98,12 @@ __global__ void assemble_im2col_kernel(const float* __restrict__ latents, int Bl
                 const float sc = score[((size_t)bi * h + yy) * w + xs];
                 h16* o = reinterpret_cast<h16*>(&raw);
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    o[c] = (h16)(right ? latents[(((size_t)(b % Blat) * 4 + c) * h + yy) * w + xs]
-                                       : img_lat[(((size_t)bi * 4 + c) * h + yy) * w + xs]);
+                for (int c = 0; c < 4; ++c) {
+                    float v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + yy) * w + xs]
+                                    : img_lat[(((size_t)bi * 4 + c) * h + yy) * w + xs];
+                    if (SCALED && right) v = v / div;
+                    o[c] = (h16)v;
+                }
                 o[4] = (h16)sc;
                 o[5] = dup_score ? (h16)sc : (h16)0.f;
             }
@@ -273,29 +294,63 @@ extern "C" int bc_splat_scores(const double* params_host, int n, int h, int w, d
     return 0;
 }
 
-extern "C" int bc_assemble_input(const float* latents, int Blat, const float* img_lat, const float* score,
-                                 const float* feat, int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score,
-                                 bc_half* X, bc_stream stream_) {
+// The launchers behind the assembly entry points (`name` = the entry point's own name for the error text); an unscaled entry point
+// passes coef = step_idx = nullptr / nsteps = 0, which its instantiation never reads.
+template <bool SCALED>
+static int assemble_launch(const char* name, const float* latents, int Blat, const float* img_lat, const float* score, const float* feat,
+                           int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score, const float* coef, const int* step_idx,
+                           int nsteps, bc_half* X, bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!feat) F = 0;
-    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0, "bc_assemble_input: bad args");
-    BC_CHECK_ARG(Cpad % 8 == 0 && Cpad >= 5 + F, "bc_assemble_input: Cpad=%d must be a multiple of 8 and >= %d", Cpad, 5 + F);
+    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 &&
+                 (!SCALED || (coef && step_idx && nsteps > 0 && h > 0 && w > 0)), "%s: bad args", name);
+    BC_CHECK_ARG(Cpad % 8 == 0 && Cpad >= 5 + F, "%s: Cpad=%d must be a multiple of 8 and >= %d", name, Cpad, 5 + F);
     long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
-    hipLaunchKernelGGL(assemble_kernel, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, feat,
-                       Bimg, F, Bout, h, w, Cpad, dup_score, reinterpret_cast<h16*>(X));
+    hipLaunchKernelGGL(assemble_kernel<SCALED>, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, feat,
+                       Bimg, F, Bout, h, w, Cpad, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
     BC_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int bc_assemble_input_im2col(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg, int Bout,
-                                        int h, int w, int dup_score, bc_half* X, bc_stream stream_) {
+template <bool SCALED>
+static int assemble_im2col_launch(const char* name, const float* latents, int Blat, const float* img_lat, const float* score, int Bimg,
+                                  int Bout, int h, int w, int dup_score, const float* coef, const int* step_idx, int nsteps, bc_half* X,
+                                  bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0, "bc_assemble_input_im2col: bad args");
+    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 &&
+                 (!SCALED || (coef && step_idx && nsteps > 0 && h > 0 && w > 0)), "%s: bad args", name);
     long long total = (long long)Bout * h * 2 * w * 16;
-    hipLaunchKernelGGL(assemble_im2col_kernel, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, Bimg, Bout,
-                       h, w, dup_score, reinterpret_cast<h16*>(X));
+    hipLaunchKernelGGL(assemble_im2col_kernel<SCALED>, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, Bimg,
+                       Bout, h, w, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
     BC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int bc_assemble_input(const float* latents, int Blat, const float* img_lat, const float* score,
+                                 const float* feat, int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score,
+                                 bc_half* X, bc_stream stream) {
+    return assemble_launch<false>("bc_assemble_input", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad, dup_score, nullptr,
+                                  nullptr, 0, X, stream);
+}
+
+extern "C" int bc_assemble_input_scaled(const float* latents, int Blat, const float* img_lat, const float* score,
+                                        const float* feat, int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score,
+                                        const float* coef, const int* step_idx, int nsteps, bc_half* X, bc_stream stream) {
+    return assemble_launch<true>("bc_assemble_input_scaled", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad, dup_score,
+                                 coef, step_idx, nsteps, X, stream);
+}
+
+extern "C" int bc_assemble_input_im2col(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg, int Bout,
+                                        int h, int w, int dup_score, bc_half* X, bc_stream stream) {
+    return assemble_im2col_launch<false>("bc_assemble_input_im2col", latents, Blat, img_lat, score, Bimg, Bout, h, w, dup_score, nullptr,
+                                         nullptr, 0, X, stream);
+}
+
+extern "C" int bc_assemble_input_im2col_scaled(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg,
+                                               int Bout, int h, int w, int dup_score, const float* coef, const int* step_idx, int nsteps,
+                                               bc_half* X, bc_stream stream) {
+    return assemble_im2col_launch<true>("bc_assemble_input_im2col_scaled", latents, Blat, img_lat, score, Bimg, Bout, h, w, dup_score,
+                                        coef, step_idx, nsteps, X, stream);
 }
 
 extern "C" int bc_timestep_embedding(const float* t_table, const int* t_idx, float t_value, int rows, int dim,

@@ -132,6 +132,12 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
         case BC_OP_GAUSSIAN_SAMPLE: return bc_gaussian_sample(CP(bc_half, 0), CP(float, 1), I(2), I(3), I(4), F(5), MP(float, 6), s);
         case BC_OP_ASSEMBLE_IM2COL:
             return bc_assemble_input_im2col(CP(float, 0), I(1), CP(float, 2), CP(float, 3), I(4), I(5), I(6), I(7), I(8), MP(bc_half, 9), s);
+        case BC_OP_ASSEMBLE_INPUT_SCALED:
+            return bc_assemble_input_scaled(CP(float, 0), I(1), CP(float, 2), CP(float, 3), CP(float, 4), I(5), I(6), I(7), I(8), I(9), I(10),
+                                            I(11), CP(float, 12), CP(int, 13), I(14), MP(bc_half, 15), s);
+        case BC_OP_ASSEMBLE_IM2COL_SCALED:
+            return bc_assemble_input_im2col_scaled(CP(float, 0), I(1), CP(float, 2), CP(float, 3), I(4), I(5), I(6), I(7), I(8), CP(float, 9),
+                                                   CP(int, 10), I(11), MP(bc_half, 12), s);
         case BC_OP_ROWCHAIN:
             return bc_rowchain(I(0), I(1), I(2), I(3), CP(bc_half, 4), CP(float, 5), CP(unsigned long long, 6), CP(float, 7), CP(float, 8), I(9),
                                F(10), CP(bc_half, 11), CP(bc_half, 12), CP(bc_half, 13), I(14), I(15), I(16), CP(bc_half, 17), CP(float, 18),
@@ -447,7 +453,10 @@ extern "C" int bc_plan_save(BcPlan* pl, const char* path, const BcPlanBuffer* bu
     FILE* f = fopen(path, "wb");
     BC_CHECK_ARG(f != nullptr, "bc_plan_save: cannot open %s", path);
     Writer w{f};
-    w.u32(kMagic); w.u32(kVersion); w.u32((uint32_t)sizeof(BcGemm)); w.u32((uint32_t)nbufs);
+    uint32_t version = op_min_version(BC_OP_GEMM);    // the lowest version that has every recorded op
+    for (Seg& sg : pl->segs)
+        for (Rec& r : sg.recs) version = std::max(version, op_min_version(r.op));
+    w.u32(kMagic); w.u32(version); w.u32((uint32_t)sizeof(BcGemm)); w.u32((uint32_t)nbufs);
     for (int i = 0; i < nbufs; ++i) {
         w.str(tb[i].name);
         w.u64(tb[i].bytes);

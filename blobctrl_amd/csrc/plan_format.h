@@ -16,9 +16,12 @@ namespace bcplan {
 
 constexpr int kMaxStreams = 8;
 const uint32_t kMagic = 0x4E4C5042u;   // "BPLN"
-const uint32_t kVersion = 5;           // 2: BcGemm grew ln_colsum / C_t, GroupNorm statistics totals; 3: + BC_OP_ROWCHAIN_MIDX / _PACK_KV (round 4);
+const uint32_t kVersion = 6;           // 2: BcGemm grew ln_colsum / C_t, GroupNorm statistics totals; 3: + BC_OP_ROWCHAIN_MIDX / _PACK_KV (round 4);
                                        // 4: + BC_OP_ROWCHAIN_SUM, BC_CHAIN_OUT_FFP; 5: BcGemm grew w_bstride / vec_bstride / sm_group / sm_valid,
-                                       //    + BC_OP_CTX_FOLD (round 5)
+                                       //    + BC_OP_CTX_FOLD (round 5); 6: + BC_OP_ASSEMBLE_INPUT_SCALED / _IM2COL_SCALED
+// A file is written with the LOWEST version that describes it (op_min_version below): a plan without a version-6 op stays a version-5
+// file, byte for byte what the previous library wrote and still readable by it.
+inline uint32_t op_min_version(int op) { return op == BC_OP_ASSEMBLE_INPUT_SCALED || op == BC_OP_ASSEMBLE_IM2COL_SCALED ? 6u : 5u; }
 const uint32_t kOldestReadable = 5;    // (the records hold BcGemm by value: a file of another layout is refused by the size check below anyway)
 
 // argument kinds of the recordable entry points (stream argument excluded): p = device pointer, i = int, f = float, l = long long
@@ -55,6 +58,8 @@ inline const char* op_signature(int op) {
         case BC_OP_ROWCHAIN_SUM: return "iiipippp";
         case BC_OP_CTX_FOLD: return "pipiiiiifppppppp";
         case BC_OP_DUP_HALVES: return "plplplplplpl";
+        case BC_OP_ASSEMBLE_INPUT_SCALED: return "pipppiiiiiiippip";
+        case BC_OP_ASSEMBLE_IM2COL_SCALED: return "pippiiiiippip";
         default: return nullptr;
     }
 }
@@ -115,7 +120,8 @@ inline std::string parse_plan(FILE* f, PlanImage& img, const std::function<uint6
     rewind(f);
     constexpr uint64_t kMaxArena = 1ull << 40;       // 1 TiB: far above any real plan, far below overflow of the running sum
     if (rd.u32() != kMagic) return "not a plan file";
-    { const uint32_t v = rd.u32(); if (v < kOldestReadable || v > kVersion) return "unsupported plan version"; }
+    const uint32_t version = rd.u32();
+    if (version < kOldestReadable || version > kVersion) return "unsupported plan version";
     if (rd.u32() != sizeof(BcGemm)) return "BcGemm layout differs from this library build";
     const uint32_t nb = rd.u32();
     if (!rd.ok || nb > (1u << 20)) return "corrupt header";
@@ -178,7 +184,7 @@ inline std::string parse_plan(FILE* f, PlanImage& img, const std::function<uint6
         for (Rec& r : sg.recs) {
             const uint32_t op = rd.u32(), sid = rd.u32(), enabled = rd.u32();
             if (!rd.ok || sid >= (uint32_t)kMaxStreams) return "stream id out of range";
-            if (op != (uint32_t)BC_OP_GEMM && !op_signature((int)op)) return "unknown op code";
+            if (op != (uint32_t)BC_OP_GEMM && (!op_signature((int)op) || op_min_version((int)op) > version)) return "unknown op code";
             r.op = (int)op; r.sid = (int)sid; r.enabled = enabled ? 1 : 0;
             if (r.op == BC_OP_GEMM) {
                 rd.raw(&r.g, sizeof(r.g));

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .engine import TrunkConfig, TrunkPlan
 from .launch import Recorder
-from .schedulers import draw_variance_noise, randn_tensor, table_class
+from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, table_class
 from .weights import PackedTrunk, pad8
 
 
@@ -77,16 +77,20 @@ class BlobCtrlEngine:
         self.text_encoder = text_encoder                              # optional blobctrl_amd.clip_text.CLIPTextModel
 
     # ------------------------------------------------------------------------------------------------ planning
-    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False):
+    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
         per-call contents of the coefficient table and of that buffer, so one plan and its graphs serve every eta > 0 and every seed).
         third_order: a table with third-order DPM-Solver++ rows (column 13) - the steps end in bc_cfg_scheduler_step3.  Every other
-        table (UniPC, DDIM, DPM-Solver++ of order 1 / 2) runs on the same plan: only the tables differ."""
+        table (UniPC, DDIM, DPM-Solver++ of order 1 / 2) runs on the same plan: only the tables differ.
+        scaled: a table that scales the model input (Euler, Euler-ancestral, Heun: `scheduler.scale_model_input`, pipe:1032) - the BlobNet
+        and UNet inputs are assembled by the `_scaled` entry points, which divide the noisy latents by column 14 of the current row.  A
+        plan of its own (and with it graphs of its own): no other table ever replays these launches."""
         if stochastic and third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
-        key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ())
+        key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
+            (("scaled",) if scaled else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -121,6 +125,7 @@ class BlobCtrlEngine:
         P.eps_guided = rec.zeros(B, 4, h, w, dtype=f32, name="eps_guided")
         P.stochastic = bool(stochastic)
         P.third_order = bool(third_order)
+        P.scaled = bool(scaled)
         P.variance_noise = rec.zeros(nsteps, B, 4, h, w, dtype=f32, name="variance_noise") if stochastic else None
         P.guidance = [7.5]
 
@@ -174,13 +179,18 @@ class BlobCtrlEngine:
             hp.tproj, hp.tproj_table = half_time.tproj, half_time.tproj_table
             return hp
 
+        # the input assembly of a net: the entry point's `_scaled` form, with (coef, step_idx, nsteps) in front of the output, when the
+        # table scales the model input
+        divisor = (P.coef.data_ptr(), P.step_idx.data_ptr(), nsteps) if P.scaled else ()
+        suffix = "_scaled" if P.scaled else ""
+
         def record_unet(plan, residuals):
             if P.unet_im2col:
-                rec.call("bc_assemble_input_im2col", P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), Bi, 2 * B, h, w,
-                         0, P.unet_in.data_ptr(), kind="assemble")
+                rec.call("bc_assemble_input_im2col" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), Bi, 2 * B,
+                         h, w, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
             else:
-                rec.call("bc_assemble_input", P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), None, Bi, 0,
-                         2 * B, h, w, unet_cin, 0, P.unet_in.data_ptr(), kind="assemble")
+                rec.call("bc_assemble_input" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), None, Bi, 0,
+                         2 * B, h, w, unet_cin, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
             if temb_per_step:
                 plan.record_time(P.t_table, P.step_idx)
             if split_cfg:
@@ -211,11 +221,11 @@ class BlobCtrlEngine:
         rec.sid = 1
         rec.wait(fork)
         if P.blob_im2col:
-            rec.call("bc_assemble_input_im2col", P.latents.data_ptr(), B, P.fg_lat.data_ptr(), P.fg_score.data_ptr(), Bi, B, h, w, 1,
-                     P.blob_in.data_ptr(), kind="assemble")
+            rec.call("bc_assemble_input_im2col" + suffix, P.latents.data_ptr(), B, P.fg_lat.data_ptr(), P.fg_score.data_ptr(), Bi, B, h, w,
+                     1, *divisor, P.blob_in.data_ptr(), kind="assemble")
         else:
-            rec.call("bc_assemble_input", P.latents.data_ptr(), B, P.fg_lat.data_ptr(), P.fg_score.data_ptr(),
-                     P.feat.data_ptr() if F > 0 else None, Bi, F, B, h, w, blob_cin, 0, P.blob_in.data_ptr(), kind="assemble")
+            rec.call("bc_assemble_input" + suffix, P.latents.data_ptr(), B, P.fg_lat.data_ptr(), P.fg_score.data_ptr(),
+                     P.feat.data_ptr() if F > 0 else None, Bi, F, B, h, w, blob_cin, 0, *divisor, P.blob_in.data_ptr(), kind="assemble")
         if temb_per_step:
             blob.record_time(P.t_table, P.step_idx)
         residuals = blob.record_forward(P.blob_in, None, zero_scale=(1.0, P.scale_table, P.step_idx, B if per_request else 0),
@@ -241,34 +251,37 @@ class BlobCtrlEngine:
         return P
 
     def set_scheduler(self, kind, params=None):
-        """`kind` "unipc" | "ddim" | "dpmsolver"; `params` = (num_train_timesteps, beta_start, beta_end) of the scheduler's configuration
-        (the drop-in scheduler objects accept non-default betas: the engine must tabulate the SAME alphas); for "dpmsolver" a fourth entry
-        holds the DPM-Solver options as (key, value) pairs (`DPMSolverMultistepScheduler.table_params()`; missing = diffusers' defaults)."""
-        if kind not in ("unipc", "ddim", "dpmsolver"):
-            raise NotImplementedError(f"scheduler {kind!r} has no coefficient table (UniPC, DDIM and DPM-Solver have)")
+        """`kind` "unipc" | "ddim" | "dpmsolver" | "euler" | "euler_ancestral" | "heun"; `params` = (num_train_timesteps, beta_start,
+        beta_end) of the scheduler's configuration (the drop-in scheduler objects accept non-default betas: the engine must tabulate the
+        SAME alphas); for "dpmsolver" and the three sigma-space kinds a fourth entry holds the table's options as (key, value) pairs (the
+        scheduler object's `table_params()`; missing = diffusers' defaults)."""
+        if kind not in ("unipc", "ddim") + OPTION_KINDS:
+            raise NotImplementedError(f"scheduler {kind!r} has no coefficient table (UniPC, DDIM, DPM-Solver, Euler, Euler-ancestral and "
+                                      "Heun have)")
         self.scheduler_kind = kind
         if params is not None:
             p = (int(params[0]), float(params[1]), float(params[2]))
-            if kind == "dpmsolver" and len(params) > 3:
+            if kind in OPTION_KINDS and len(params) > 3:
                 p += (tuple(sorted((str(k), v) for k, v in dict(params[3]).items())),)
             self.scheduler_params = p
 
     def _scheduler_table(self, n, eta=0.0, timesteps=None):
         """Coefficient tables depend only on (scheduler, its configuration, steps, DDIM eta, caller timesteps)."""
-        ts = None if timesteps is None else tuple(int(t) for t in timesteps)
+        euler = self.scheduler_kind == "euler"                         # (its timesteps are float32 in the reference: nothing rounds them)
+        ts = None if timesteps is None else tuple(float(t) if euler else int(t) for t in timesteps)
         key = (self.scheduler_kind, self.scheduler_params, n, float(eta)) + ((ts,) if ts is not None else ())
         sched = self._sched_cache.get(key)
         if sched is None:
             nt, b0, b1 = self.scheduler_params[:3]
-            dpm = self.scheduler_kind == "dpmsolver"
-            if ts is not None and not dpm:
-                raise NotImplementedError(f"custom `timesteps` are not tabulated for {self.scheduler_kind} (the reference's set_timesteps "
-                                          "takes none): pass num_inference_steps, or use DPMSolverMultistepScheduler")
-            opts = dict(self.scheduler_params[3]) if dpm and len(self.scheduler_params) > 3 else {}
+            has_options = self.scheduler_kind in OPTION_KINDS             # (none of these kinds has an eta: their tables take none)
+            if ts is not None and self.scheduler_kind not in ("dpmsolver", "euler"):
+                raise NotImplementedError(f"custom `timesteps` are not tabulated for {self.scheduler_kind}: pass num_inference_steps, or "
+                                          "use DPMSolverMultistepScheduler / EulerDiscreteScheduler")
+            opts = dict(self.scheduler_params[3]) if has_options and len(self.scheduler_params) > 3 else {}
             sched = table_class(self.scheduler_kind)(num_train_timesteps=nt, beta_start=b0, beta_end=b1, **opts)
             if ts is not None:
                 sched.set_timesteps(timesteps=list(ts))
-            elif eta and not dpm:                                     # (DPM-Solver has no eta: its table takes none)
+            elif eta and not has_options:                                     # (DPM-Solver has no eta: its table takes none)
                 sched.set_timesteps(n, eta=float(eta))
             else:
                 sched.set_timesteps(n)
@@ -277,8 +290,8 @@ class BlobCtrlEngine:
 
     @staticmethod
     def _step_form(sched, stochastic):
-        """(stochastic, third_order) of the plan a table runs on: the noise step for DDIM eta > 0 and SDE-DPM-Solver++, the
-        third-order step when a row uses column 13, the plain step otherwise."""
+        """(stochastic, third_order) of the plan a table runs on: the noise step for DDIM eta > 0, SDE-DPM-Solver++ and Euler-ancestral,
+        the third-order step when a row uses column 13, the plain step otherwise."""
         third = bool((sched.table()[:, 13] != 0).any())
         return bool(stochastic or getattr(sched, "sde", False)), third
 
@@ -414,9 +427,13 @@ class BlobCtrlEngine:
         scheduler.step draws it (after the start latents when those are drawn here; a list = one generator per sample; None = the
         global RNG of the engine's device), or taken from `variance_noise` [num_inference_steps, B, 4, h, w].  It is drawn in fp32 (the
         engine keeps fp32 latents); a reference pipeline running in fp16 would draw fp16 noise.
-        With an SDE-DPM-Solver++ scheduler (algorithm_type "sde-dpmsolver++") every step draws its noise the same way, eta staying 0.
-        `timesteps` (DPM-Solver only): the caller's timestep schedule, as the reference's set_timesteps(timesteps=) takes it; the edit
-        then has len(timesteps) steps and `num_inference_steps` is not used."""
+        With an SDE-DPM-Solver++ scheduler (algorithm_type "sde-dpmsolver++") or the Euler-ancestral scheduler every step draws its noise
+        the same way, eta staying 0.
+        `timesteps` (DPM-Solver and Euler only): the caller's timestep schedule, as the reference's set_timesteps(timesteps=) takes it; the
+        edit then has len(timesteps) steps and `num_inference_steps` is not used.
+        With a sigma-space scheduler (Euler, Euler-ancestral, Heun) the start latents are multiplied by the table's init_noise_sigma and
+        the latents a callback / `teacher_latents` / `trace` see stay in the scheduler's sigma space, as in the reference; only what the
+        networks read is divided by sqrt(sigma^2 + 1).  Heun runs 2 * num_inference_steps - 1 network evaluations (`self.timesteps`)."""
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
@@ -476,17 +493,18 @@ class BlobCtrlEngine:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
                              f" size of {B}. Make sure the batch size matches the length of the generators.")
         sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
+        n = len(sched.timesteps)                             # network evaluations (Heun: 2 * num_inference_steps - 1, pipe:1025 loops over them)
         stochastic, third_order = self._step_form(sched, stochastic)
         if variance_noise is not None:
             if not stochastic:
-                raise ValueError("variance_noise is only used with eta > 0 (DDIM) or an SDE-DPM-Solver++ scheduler")
+                raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++ or an Euler-ancestral scheduler")
             if generator is not None:
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
                                  " `variance_noise` stays `None`.")
             if tuple(variance_noise.shape) != (n, B, 4, h, w):
                 raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (steps, batch, 4, h, w), got "
                                  f"{tuple(variance_noise.shape)}")
-        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order)
+        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order, sched.scales_input)
         dev = self.device
         self.timesteps = sched.timesteps
         if latents is None:                                                          # pipe:438-453
@@ -559,7 +577,7 @@ class BlobCtrlEngine:
                 trace.append((P.eps_guided.clone(), P.latents.clone()))
             if callback_on_step_end is not None:
                 self.stream.synchronize()
-                ret = callback_on_step_end(callback_self or self, i, int(sched.timesteps[i]), {"latents": P.latents})
+                ret = callback_on_step_end(callback_self or self, i, sched.timesteps[i].item(), {"latents": P.latents})
                 if isinstance(ret, dict) and ret.get("latents") is not None and ret["latents"] is not P.latents:
                     with torch.cuda.stream(self.stream):                         # pipe:1112 `latents = callback_outputs.pop(...)`
                         P.latents.copy_(ret["latents"].to(dev, torch.float32))
@@ -608,15 +626,17 @@ class BlobCtrlEngine:
         segment names (which steps run BlobNet).
         eta > 0 (DDIM): a stochastic plan with the named buffer `variance_noise` [n][B][4][h][w] fp32, saved with `variance_noise`'s
         contents when given (else zero-filled: a C host fills it through bc_plan_buffer before each edit).  An SDE-DPM-Solver++ scheduler
-        gives the same stochastic plan; a third-order DPM-Solver++ table ends its steps in bc_cfg_scheduler_step3.  `timesteps` (DPM-Solver
-        only): the caller's schedule, n = len(timesteps)."""
+        or the Euler-ancestral scheduler gives the same stochastic plan; a third-order DPM-Solver++ table ends its steps in
+        bc_cfg_scheduler_step3; a sigma-space table (Euler, Euler-ancestral, Heun) assembles its inputs with the `_scaled` entry points.
+        `timesteps` (DPM-Solver and Euler only): the caller's schedule, n = len(timesteps).  Heun: 2 * num_inference_steps - 1 steps."""
         n = num_inference_steps if timesteps is None else len(timesteps)
         stochastic = self._check_eta(float(eta))
         sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
+        n = len(sched.timesteps)
         stochastic, third_order = self._step_form(sched, stochastic)
         if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
             raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
-        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order)
+        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order, sched.scales_input)
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         P.t_table.copy_(sched.timesteps.to(torch.float32))
         coef = sched.table().clone()
@@ -637,8 +657,8 @@ class BlobCtrlEngine:
         return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
 
     # convenience for bench / tests ------------------------------------------------------------------
-    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order)
+    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled)
 
 
 # ======================================================================================================================
@@ -663,7 +683,8 @@ class StableDiffusionBlobNetPipeline:
 
     Components (pipe:206-243): `vae` = blobctrl_amd.vae.AutoencoderKL, `unet` / `blobnet` = blobctrl_amd.modules shells (any LoRA is
     merged when the UNet is packed), `tokenizer` = any callable with the CLIPTokenizer call contract (host side), `text_encoder` =
-    blobctrl_amd.clip_text.CLIPTextModel, `scheduler` = blobctrl_amd.schedulers.UniPCMultistepScheduler | DDIMScheduler,
+    blobctrl_amd.clip_text.CLIPTextModel, `scheduler` = blobctrl_amd.schedulers.UniPCMultistepScheduler | DDIMScheduler | DPMSolverMultistepScheduler | EulerDiscreteScheduler |
+    EulerAncestralDiscreteScheduler | HeunDiscreteScheduler,
     `dinov2_processor` = image_processor.Dinov2ImageProcessor (or the HF processor), `dinov2` = blobctrl_amd.dinov2.Dinov2Model.
     The denoise loop itself is the captured-plan engine (BlobCtrlEngine): the module shells are not called per step."""
 
@@ -676,8 +697,8 @@ class StableDiffusionBlobNetPipeline:
         if safety_checker is not None:
             raise NotImplementedError("the reference disables the safety checker (pipe:1133-1135); pass safety_checker=None")
         if not isinstance(scheduler, TableScheduler):
-            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler or "
-                            "DPMSolverMultistepScheduler")
+            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler, "
+                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler or HeunDiscreteScheduler")
         self.vae, self.unet, self.blobnet, self.tokenizer, self.text_encoder = vae, unet, blobnet, tokenizer, text_encoder
         self.dinov2, self.dinov2_processor = dinov2, dinov2_processor if dinov2_processor is not None else Dinov2ImageProcessor()
         self.safety_checker = None
@@ -768,8 +789,8 @@ class StableDiffusionBlobNetPipeline:
     def scheduler(self, s):
         from .schedulers import TableScheduler
         if not isinstance(s, TableScheduler):
-            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler or "
-                            "DPMSolverMultistepScheduler")
+            raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler, "
+                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler or HeunDiscreteScheduler")
         self._scheduler = s
 
     def to(self, *a, **k):
@@ -969,7 +990,7 @@ class StableDiffusionBlobNetPipeline:
             raise NotImplementedError("`callback` is deprecated in the reference (pipe:868-875): use callback_on_step_end")
         if kwargs:
             raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")
-        if timesteps is not None and getattr(self._scheduler, "kind", None) != "dpmsolver":
+        if timesteps is not None and getattr(self._scheduler, "kind", None) not in ("dpmsolver", "euler"):
             # the reference's retrieve_timesteps (pipe:142-148) honours them only for schedulers whose set_timesteps takes them
             raise NotImplementedError("custom `timesteps` are not tabulated; pass num_inference_steps")
         if cross_attention_kwargs:
@@ -1008,7 +1029,7 @@ class StableDiffusionBlobNetPipeline:
             num_inference_steps = len(self.scheduler.timesteps)
         else:
             self.scheduler.set_timesteps(num_inference_steps)
-        self._num_timesteps = num_inference_steps
+        self._num_timesteps = len(self.scheduler.timesteps)          # pipe:954 (Heun: 2 * num_inference_steps - 1)
         lat0, noise = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, height, width,
                                            prompt_embeds.dtype, self.device, generator, latents)
         # 7. image latents (pipe:970-971): fg first, then bg - the order in which the reference consumes the global generator

@@ -13,8 +13,16 @@ whose scalar coefficients are precomputed here per step index, uploaded once, an
     [11] guidance scale (filled by the engine)
     [12] std_dev_t                                         x'  += c12*noise[i]     (stochastic DDIM, eta > 0; SDE-DPM-Solver++; 0 otherwise)
     [13] cp_m2                                             x'  += c13*x0_{i-2}     (third-order DPM-Solver++, `bc_cfg_scheduler_step3`)
+    [14] input divisor sqrt(sigma_t^2 + 1)                 the networks read x / c14 (`scale_model_input`; the sigma-space schedulers Euler,
+                                                           Euler-ancestral and Heun: `bc_assemble_input_scaled`, `bc_assemble_input_im2col_scaled`).
+                                                           0 in every other table: UniPC, DDIM and DPM-Solver++ do not scale their input and
+                                                           never reach a kernel that reads the column
+    [15] unused
 Scalar maths follows the reference in fp32 torch CPU ops (same operation order) so the tables match it to rounding.
 DPM-Solver++ (scheduling_dpmsolver_multistep.py) fills c0 / c1 (x0), c7 (x), c8 (x0), c9 (x0_{i-1}), c12 (SDE noise) and c13 (order 3).
+The sigma-space (k-diffusion) schedulers work on x = x0 + sigma * eps: an Euler step x' = x + (sigma_next - sigma) * eps is c0 = 1,
+c1 = sigma, c7 = 1, c10 = sigma_next - sigma; Euler-ancestral steps down to sigma_down and adds c12 = sigma_up times the step's noise; Heun's
+second stage reads the first stage's x (`last`) and x0 (`m0`) through the corrector columns c2 - c4.
 
 SD-1.5 scheduler config: betas 0.00085 -> 0.012 scaled_linear, 1000 train steps, steps_offset 1,
 epsilon prediction; UniPC: solver_order 2, bh2, predict_x0, lower_order_final, linspace spacing, final sigma 0;
@@ -33,6 +41,7 @@ def _alphas_cumprod(num_train, beta_start, beta_end):
 class _Base:
     order = 1
     init_noise_sigma = 1.0
+    scales_input = False                                                  # True: the networks read x / c14 (the sigma-space tables)
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012):
         self.num_train = num_train_timesteps
@@ -366,10 +375,204 @@ class DPMSolverMultistepTable(_Base):
         return coef
 
 
+
+# ---- the sigma-space (k-diffusion) schedulers: EulerDiscrete, EulerAncestralDiscrete, HeunDiscrete --------------------------------------
+# the options a table depends on (the engine keys its tables and plans on them), with the reference's defaults
+EULER_OPTIONS = dict(interpolation_type="linear", use_karras_sigmas=False, timestep_spacing="linspace", timestep_type="discrete",
+                     steps_offset=0, final_sigmas_type="zero")
+EULER_ANCESTRAL_OPTIONS = dict(timestep_spacing="linspace", steps_offset=0)
+HEUN_OPTIONS = dict(use_karras_sigmas=False, timestep_spacing="linspace", steps_offset=0)
+
+
+class _SigmaTable(_Base):
+    """What the three sigma-space tables share: the spaced (float32, possibly fractional) timesteps, the interpolated sigmas,
+    `init_noise_sigma` and the Euler row.  `scales_input`: the networks read x / sqrt(sigma^2 + 1), column 14."""
+    scales_input = True
+    _option_defaults = {}
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, **options):
+        super().__init__(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end)
+        unknown = set(options) - set(self._option_defaults)
+        if unknown:
+            raise TypeError(f"unknown {type(self).__name__} option(s) {sorted(unknown)}")
+        self.options = dict(self._option_defaults, **options)
+        self.sigmas = None
+        self.num_inference_steps = None
+
+    def _train_sigmas(self):
+        return (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy().copy()
+
+    def _spaced(self, n):                                                 # scheduling_euler_discrete.py:357-381 (the same in all three)
+        o = self.options
+        if o["timestep_spacing"] == "linspace":
+            return np.linspace(0, self.num_train - 1, n, dtype=np.float32)[::-1].copy()
+        if o["timestep_spacing"] == "leading":
+            step_ratio = self.num_train // n
+            ts = (np.arange(0, n) * step_ratio).round()[::-1].copy().astype(np.float32)
+            ts += o["steps_offset"]
+            return ts
+        if o["timestep_spacing"] == "trailing":
+            step_ratio = self.num_train / n
+            ts = np.arange(self.num_train, 0, -step_ratio).round().copy().astype(np.float32)
+            ts -= 1
+            return ts
+        raise ValueError(f"{o['timestep_spacing']} is not supported. Please make sure to choose one of 'linspace', 'leading' or "
+                         "'trailing'.")
+
+    def _karras(self, sigmas, log_sigmas, n):                             # :395-397: fractional timesteps, not rounded
+        sigmas = DPMSolverMultistepTable._convert_to_karras(sigmas, n)
+        return sigmas, np.array([DPMSolverMultistepTable._sigma_to_t(s, log_sigmas) for s in sigmas])
+
+    @property
+    def init_noise_sigma(self):                                           # :244-250: of the CURRENT sigmas, so read it after set_timesteps
+        sig = self.sigmas if self.sigmas is not None else torch.from_numpy(self._train_sigmas())
+        max_sigma = sig.max()
+        if self.options["timestep_spacing"] in ("linspace", "trailing"):
+            return float(max_sigma)
+        return float((max_sigma ** 2 + 1) ** 0.5)
+
+    @staticmethod
+    def _euler_row(row, sigma, target, up=None):
+        """x0 = x - sigma * eps; x' = x + (target - sigma) * eps (+ up * noise); the networks read x / sqrt(sigma^2 + 1)."""
+        row[0] = 1.0
+        row[1] = sigma
+        row[7] = 1.0
+        row[10] = target - sigma
+        row[14] = (sigma ** 2 + 1) ** 0.5
+        if up is not None:
+            row[12] = up
+
+
+class EulerDiscreteTable(_SigmaTable):
+    """EulerDiscreteScheduler as a coefficient table (scheduling_euler_discrete.py:301-420 timesteps / sigmas, 493-599 the step with
+    s_churn = 0, i.e. gamma = 0 and sigma_hat = sigma).  Caller `timesteps` are taken as the reference takes them."""
+    _option_defaults = EULER_OPTIONS
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        o = self.options
+        if o["interpolation_type"] == "log_linear":
+            raise NotImplementedError("interpolation_type 'log_linear' is not tabulated ('linear' is)")
+        if o["timestep_type"] != "discrete":
+            raise NotImplementedError(f"timestep_type {o['timestep_type']!r} is not tabulated ('discrete' is)")
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
+        o = self.options
+        if sigmas is not None:
+            raise NotImplementedError("custom `sigmas` are not tabulated: pass num_inference_steps or `timesteps`")
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps` or `sigmas.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `timesteps` or `sigmas`.")
+        if timesteps is not None and o["use_karras_sigmas"]:
+            raise ValueError("Cannot set `timesteps` with `config.use_karras_sigmas = True`.")
+        n = num_inference_steps if num_inference_steps is not None else len(timesteps)
+        ts = np.array(timesteps).astype(np.float32) if timesteps is not None else self._spaced(n)
+        sig = self._train_sigmas()
+        log_sigmas = np.log(sig)
+        if o["interpolation_type"] != "linear":
+            raise ValueError(f"{o['interpolation_type']} is not implemented. Please specify interpolation_type to either 'linear' or "
+                             "'log_linear'")
+        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        if o["use_karras_sigmas"]:
+            sig, ts = self._karras(sig, log_sigmas, n)
+        if o["final_sigmas_type"] == "sigma_min":
+            sigma_last = ((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5
+        elif o["final_sigmas_type"] == "zero":
+            sigma_last = 0
+        else:
+            raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {o['final_sigmas_type']}")
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [sigma_last]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(ts.astype(np.float32))
+        self.num_inference_steps = n
+        coef = torch.zeros(n, 16, dtype=torch.float32)
+        for i in range(n):
+            self._euler_row(coef[i], self.sigmas[i], self.sigmas[i + 1])
+        assert torch.isfinite(coef).all(), "non-finite Euler coefficient"
+        self.coef = coef
+        return self
+
+
+class EulerAncestralTable(_SigmaTable):
+    """EulerAncestralDiscreteScheduler as a coefficient table (scheduling_euler_ancestral_discrete.py:277-320, 345-440): an Euler step down
+    to sigma_down, then sigma_up times the step's noise in column 12 - the steps end in bc_cfg_scheduler_step_noise.  The reference's
+    set_timesteps takes no caller `timesteps`."""
+    _option_defaults = EULER_ANCESTRAL_OPTIONS
+    sde = True                                                            # a noise term in every step (the engine's stochastic plan)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        n = num_inference_steps
+        ts = self._spaced(n)
+        sig = self._train_sigmas()
+        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(ts)
+        self.num_inference_steps = n
+        coef = torch.zeros(n, 16, dtype=torch.float32)
+        for i in range(n):
+            sigma_from, sigma_to = self.sigmas[i], self.sigmas[i + 1]
+            sigma_up = (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5
+            sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+            self._euler_row(coef[i], sigma_from, sigma_down, up=sigma_up)
+        assert torch.isfinite(coef).all(), "non-finite Euler-ancestral coefficient"
+        self.coef = coef
+        return self
+
+
+class HeunTable(_SigmaTable):
+    """HeunDiscreteScheduler as a coefficient table (scheduling_heun_discrete.py:225-305, 370-467).  `timesteps` / `sigmas` are the
+    reference's interleaved ones: n inference steps are 2n - 1 network evaluations = rows.  A first-stage row is the Euler row to
+    sigma_next (c2 = 0, so the step kernel leaves last = x, m0 = x0); the second-stage row, on the first stage's result, is
+        x' = last + dt / 2 * ((last - m0) / sigma + eps),   dt = sigma_next - sigma,
+    i.e. c2 = 1, c3 = 1 + dt / (2 sigma), c4 = -dt / (2 sigma), c7 = 1, c10 = dt / 2, with x0 and the input divisor at sigma_next.
+    The last evaluation (sigma_next = 0) is a lone first stage, as in the reference."""
+    order = 2
+    _option_defaults = HEUN_OPTIONS
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        n = num_inference_steps
+        ts = self._spaced(n)
+        sig = self._train_sigmas()
+        log_sigmas = np.log(sig)
+        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        if self.options["use_karras_sigmas"]:
+            sig, ts = self._karras(sig, log_sigmas, n)
+        s = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        t = torch.from_numpy(ts)
+        self.sigmas = torch.cat([s[:1], s[1:-1].repeat_interleave(2), s[-1:]])
+        self.timesteps = torch.cat([t[:1], t[1:].repeat_interleave(2)])
+        self.num_inference_steps = n
+        coef = torch.zeros(2 * n - 1, 16, dtype=torch.float32)
+        for k in range(n):
+            sigma, sigma_next = s[k], s[k + 1]
+            self._euler_row(coef[2 * k], sigma, sigma_next)
+            if k == n - 1:
+                break
+            row = coef[2 * k + 1]
+            dt = sigma_next - sigma
+            w = dt / (2 * sigma)
+            row[0] = 1.0
+            row[1] = sigma_next
+            row[2] = 1.0
+            row[3] = 1 + w
+            row[4] = -w
+            row[7] = 1.0
+            row[10] = dt / 2
+            row[14] = (sigma_next ** 2 + 1) ** 0.5
+        assert torch.isfinite(coef).all(), "non-finite Heun coefficient"
+        self.coef = coef
+        return self
+
+
+# scheduler kinds whose table takes options as a fourth `table_params()` entry
+OPTION_KINDS = ("dpmsolver", "euler", "euler_ancestral", "heun")
+
+
 def table_class(kind):
-    """Scheduler kind -> its coefficient table class, for the drop-in schedulers and the engine alike ("unipc", "dpmsolver"; every
-    other kind tabulates DDIM)."""
-    return {"unipc": UniPCTable, "dpmsolver": DPMSolverMultistepTable}.get(kind, DDIMTable)
+    """Scheduler kind -> its coefficient table class, for the drop-in schedulers and the engine alike ("unipc", "dpmsolver", "euler",
+    "euler_ancestral", "heun"; every other kind tabulates DDIM)."""
+    return {"unipc": UniPCTable, "dpmsolver": DPMSolverMultistepTable, "euler": EulerDiscreteTable,
+            "euler_ancestral": EulerAncestralTable, "heun": HeunTable}.get(kind, DDIMTable)
 
 
 def apply_table_step(coef_row, eps, x, hist, noise=None):
@@ -438,7 +641,11 @@ class TableScheduler:
         self._set_timesteps(device, num_inference_steps)
 
     def scale_model_input(self, sample, timestep=None):
-        return sample
+        """pipe:1032.  Identity for UniPC, DDIM and DPM-Solver++; a sigma-space table divides by column 14 of the current row,
+        sqrt(sigma^2 + 1), as its reference does (scheduling_euler_discrete.py:277-299)."""
+        if not self.table_impl.scales_input:
+            return sample
+        return sample / self.table_impl.coef[self._i, 14].to(sample.device)
 
     def _apply_row(self, model_output, sample, noise=None):
         """Table row `_i` applied to (model_output, sample): creates the history on the first step, then moves on to the next row."""
@@ -540,16 +747,19 @@ class PNDMScheduler(_ConfiguredScheduler):
 
 
 def scheduler_from_config_dir(path):
-    """`<model>/scheduler/scheduler_config.json` -> the scheduler object its `_class_name` names (PNDM / UniPC / DDIM)."""
+    """`<model>/scheduler/scheduler_config.json` -> the scheduler object its `_class_name` names (PNDM / UniPC / DDIM / DPM-Solver /
+    Euler / Euler-ancestral / Heun)."""
     import json
     import os
     with open(os.path.join(path, "scheduler_config.json")) as f:
         cfg = json.load(f)
     name = cfg.get("_class_name", "PNDMScheduler")
     classes = {"PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler, "DDIMScheduler": DDIMScheduler,
-               "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
+               "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler, "EulerDiscreteScheduler": EulerDiscreteScheduler,
+               "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler, "HeunDiscreteScheduler": HeunDiscreteScheduler}
     if name not in classes:
-        raise NotImplementedError(f"scheduler class {name} is not available (PNDM config holder, UniPC, DDIM and DPM-Solver are)")
+        raise NotImplementedError(f"scheduler class {name} is not available (PNDM config holder, UniPC, DDIM, DPM-Solver, Euler, "
+                                  "Euler-ancestral and Heun are)")
     return classes[name](**classes[name]._known(cfg))
 
 
@@ -608,6 +818,20 @@ class _StepOutput(tuple):
         return self[0]
 
 
+def _from_config_with_hidden(cls, config, kw):
+    src = dict(config)
+    defaulted = set(src.pop("_use_default_values", ()))
+    src = {k: v for k, v in src.items() if k not in defaulted}
+    init = cls._known(src)
+    init.update(kw)
+    s = cls(**init)
+    hidden = {k: v for k, v in src.items() if k not in init}
+    if "_class_name" in hidden:
+        hidden["_class_name"] = cls.__name__
+    s.config.update(hidden)
+    return s
+
+
 class DPMSolverMultistepScheduler(_ConfiguredScheduler):
     """Drop-in for diffusers' DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py), e.g. "DPM++ 2M Karras" as
     `DPMSolverMultistepScheduler.from_config(pipeline.scheduler.config, use_karras_sigmas=True)`.  Tabulated for data prediction
@@ -652,17 +876,7 @@ class DPMSolverMultistepScheduler(_ConfiguredScheduler):
     def from_config(cls, config, **kw):
         """diffusers' ConfigMixin.from_config (configuration_utils.py:188-270, 456-549): keys the source left at their defaults are
         dropped, this class's keys are taken, every other key is kept in `.config` as a hidden entry (`_class_name` renamed)."""
-        src = dict(config)
-        defaulted = set(src.pop("_use_default_values", ()))
-        src = {k: v for k, v in src.items() if k not in defaulted}
-        init = cls._known(src)
-        init.update(kw)
-        s = cls(**init)
-        hidden = {k: v for k, v in src.items() if k not in init}
-        if "_class_name" in hidden:
-            hidden["_class_name"] = cls.__name__
-        s.config.update(hidden)
-        return s
+        return _from_config_with_hidden(cls, config, kw)
 
     def table_params(self):
         """(num_train_timesteps, beta_start, beta_end, DPM options as sorted (key, value) pairs): what the engine tabulates."""
@@ -691,3 +905,136 @@ class DPMSolverMultistepScheduler(_ConfiguredScheduler):
                 randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
         out = self._apply_row(model_output, sample.to(torch.float32), noise).to(model_output.dtype)
         return _StepOutput(out) if return_dict else (out,)
+
+
+class _SigmaScheduler(_ConfiguredScheduler):
+    """What the drop-ins for the sigma-space schedulers share: the reference's `__init__` keys in `.config`, `from_config` with hidden
+    entries, the table built from `_options`, `sigmas` / `init_noise_sigma` of the table, and `scale_model_input` dividing by
+    sqrt(sigma^2 + 1) of the current step (TableScheduler)."""
+    _options = {}
+
+    def __init__(self, **kw):
+        cfg = self._make_config(kw)
+        name = type(self).__name__
+        if cfg["beta_schedule"] != "scaled_linear":
+            raise NotImplementedError(f"{name}: beta_schedule {cfg['beta_schedule']!r} is not tabulated ('scaled_linear' is)")
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"{name}: prediction_type {cfg['prediction_type']!r} is not tabulated ('epsilon' is)")
+        if cfg["trained_betas"] is not None:
+            raise NotImplementedError(f"{name}: trained_betas are not tabulated")
+        self._check(cfg)
+        # diffusers' `_use_default_values`: the __init__ keys the caller did not pass (an explicit None counts as passed)
+        cfg["_use_default_values"] = sorted(k for k in cfg if not k.startswith("_") and k not in kw)
+        self.config = cfg
+        self.timesteps = None
+        self.table_impl = table_class(self._kind)(num_train_timesteps=cfg["num_train_timesteps"], beta_start=cfg["beta_start"],
+                                                  beta_end=cfg["beta_end"], **{k: cfg[k] for k in self._options})
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """diffusers' ConfigMixin.from_config, as DPMSolverMultistepScheduler.from_config above (a PNDM, UniPC or DPM config is fine)."""
+        return _from_config_with_hidden(cls, config, kw)
+
+    def table_params(self):
+        """(num_train_timesteps, beta_start, beta_end, table options as sorted (key, value) pairs): what the engine tabulates."""
+        return super().table_params() + (tuple(sorted((k, self.config[k]) for k in self._options)),)
+
+    @property
+    def order(self):
+        return self.table_impl.order
+
+    @property
+    def sigmas(self):
+        return self.table_impl.sigmas
+
+    @property
+    def num_inference_steps(self):
+        return self.table_impl.num_inference_steps
+
+    @property
+    def init_noise_sigma(self):
+        return self.table_impl.init_noise_sigma
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self._set_timesteps(device, num_inference_steps)
+
+    def _step(self, model_output, sample, noise, return_dict):
+        if self.table_impl.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        out = self._apply_row(model_output, sample.to(torch.float32), noise).to(model_output.dtype)
+        return _StepOutput(out) if return_dict else (out,)
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """Drop-in for diffusers' EulerDiscreteScheduler ("Euler"; `EulerDiscreteScheduler.from_config(pipeline.scheduler.config)`).  Tabulated
+    for epsilon prediction with linear sigma interpolation, discrete timesteps, the three spacings (`linspace` gives fractional timesteps),
+    Karras sigmas, both final-sigma types and caller `timesteps`; s_churn (and with it s_tmin / s_tmax / s_noise) is not."""
+    _kind = "euler"
+    _options = EULER_OPTIONS
+    _defaults = dict(trained_betas=None, sigma_min=None, sigma_max=None, rescale_betas_zero_snr=False, **EULER_OPTIONS)
+
+    def _check(self, cfg):
+        if cfg["interpolation_type"] == "log_linear":
+            raise NotImplementedError("interpolation_type 'log_linear' is not tabulated ('linear' is)")
+        if cfg["timestep_type"] != "discrete":
+            raise NotImplementedError(f"timestep_type {cfg['timestep_type']!r} is not tabulated ('discrete' is)")
+        if cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("rescale_betas_zero_snr=True is not tabulated")
+        if cfg["sigma_min"] is not None or cfg["sigma_max"] is not None:
+            raise NotImplementedError("sigma_min / sigma_max (the Karras range) are not tabulated: the range of the schedule is used")
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
+        self._set_timesteps(device, num_inference_steps, timesteps=timesteps, sigmas=sigmas)
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
+             return_dict=True):
+        """One Euler update (:493-599) with gamma = 0.  Returns `(prev_sample,)`, or an object with `.prev_sample` for return_dict=True."""
+        if s_churn != 0:
+            raise NotImplementedError("s_churn != 0 (stochastic churn) is not tabulated")
+        if generator is not None:                                         # the reference draws (and discards) one noise tensor per step (:558)
+            randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        return self._step(model_output, sample, None, return_dict)
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """Drop-in for diffusers' EulerAncestralDiscreteScheduler ("Euler a"): `step(..., generator=)` draws the step's noise as :427 does;
+    `variance_noise=` gives it instead, as this package's DDIM and SDE-DPM-Solver++ steps take it."""
+    _kind = "euler_ancestral"
+    _options = EULER_ANCESTRAL_OPTIONS
+    _defaults = dict(trained_betas=None, rescale_betas_zero_snr=False, **EULER_ANCESTRAL_OPTIONS)
+
+    def _check(self, cfg):
+        if cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("rescale_betas_zero_snr=True is not tabulated")
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None):
+        if variance_noise is not None and generator is not None:
+            raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                             " `variance_noise` stays `None`.")
+        noise = variance_noise.to(device=model_output.device, dtype=torch.float32) if variance_noise is not None else \
+            randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        return self._step(model_output, sample, noise, return_dict)
+
+
+class HeunDiscreteScheduler(_SigmaScheduler):
+    """Drop-in for diffusers' HeunDiscreteScheduler ("Heun"): n inference steps are 2n - 1 entries of `timesteps` (order = 2), the
+    pipeline's loop runs over all of them.  Tabulated for the three spacings and Karras sigmas."""
+    _kind = "heun"
+    _options = HEUN_OPTIONS
+    _defaults = dict(trained_betas=None, clip_sample=False, clip_sample_range=1.0, **HEUN_OPTIONS)
+
+    def _check(self, cfg):
+        if cfg["clip_sample"]:
+            raise NotImplementedError("clip_sample=True (clipping of x0) is not tabulated")
+
+    def set_timesteps(self, num_inference_steps=None, device=None, num_train_timesteps=None, timesteps=None):
+        if timesteps is not None:
+            raise NotImplementedError("custom `timesteps` are not tabulated for Heun: pass num_inference_steps")
+        if num_train_timesteps is not None and num_train_timesteps != self.config["num_train_timesteps"]:
+            raise NotImplementedError("num_train_timesteps other than the configuration's is not tabulated")
+        if num_inference_steps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `custom_timesteps`.")
+        self._set_timesteps(device, num_inference_steps)
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        return self._step(model_output, sample, None, return_dict)

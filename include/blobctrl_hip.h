@@ -332,6 +332,20 @@ int bc_assemble_input(const float* latents, int Blat, const float* img_lat, cons
  * conv_in (pipe:724-739 -> unet_2d_condition.py:1166 / blobnet.py:812) is a dense K = 128 GEMM on the LDS-DMA fast path. */
 int bc_assemble_input_im2col(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg, int Bout,
                              int h, int w, int dup_score, bc_half* X, bc_stream stream);
+/* The two assemblies for a scheduler that scales its model input (pipe:1032 `scheduler.scale_model_input`: Euler, Euler-ancestral,
+ * Heun).  The noisy latents - the right half of the canvas, channels 0-3 - are divided in fp32 by coef[*step_idx * 16 + 14]
+ * (= sqrt(sigma_t^2 + 1), column 14 of the scheduler table) before the fp16 conversion.  The clean image latents of the left half, the
+ * score channel and the feature channels are NOT scaled: the reference scales `latent_model_input` only, not what
+ * construct_blobnet_input concatenates to it.
+ *   coef     : fp32 [nsteps][16] scheduler table (device), step_idx : device int, both read at launch time (graph-replay safe)
+ *   nsteps   : rows of coef; a step index outside [0, nsteps) reads no row and the output is that of the unscaled entry point
+ * The other arguments are those of bc_assemble_input / bc_assemble_input_im2col. */
+int bc_assemble_input_scaled(const float* latents, int Blat, const float* img_lat, const float* score, const float* feat,
+                             int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score, const float* coef, const int* step_idx,
+                             int nsteps, bc_half* X, bc_stream stream);
+int bc_assemble_input_im2col_scaled(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg, int Bout,
+                                    int h, int w, int dup_score, const float* coef, const int* step_idx, int nsteps, bc_half* X,
+                                    bc_stream stream);
 
 /* Sinusoidal timestep embedding (embeddings.py:27-78, flip_sin_to_cos=True, shift 0) for `rows` identical rows.
  * t = t_table[*t_idx] when t_table != NULL else t_value.  out [rows][dim] fp16. */
@@ -500,7 +514,8 @@ enum { BC_OP_GEMM = 0, BC_OP_GN_STATS = 1, BC_OP_GN_FINALIZE = 2, BC_OP_GN_APPLY
        BC_OP_PATCHIFY = 14, BC_OP_ADD_CLS_POS = 15, BC_OP_SILU = 16, BC_OP_NCHW_TO_NHWC_F16 = 17, BC_OP_NHWC_TO_NCHW = 18,
        BC_OP_GAUSSIAN_SAMPLE = 19, BC_OP_SIGNAL = 20 /* arg: event id */, BC_OP_WAIT = 21 /* arg: event id */, BC_OP_ROWCHAIN = 22, BC_OP_ASSEMBLE_IM2COL = 23,
        BC_OP_MEMSET_ZERO = 24, BC_OP_ROWCHAIN_MIDX = 25, BC_OP_ROWCHAIN_PACK_KV = 26, BC_OP_ROWCHAIN_SUM = 27, BC_OP_CTX_FOLD = 28, BC_OP_DUP_HALVES = 29,
-       BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_CFG_SCHEDULER_STEP3 = 31, BC_OP_COUNT = 32 };
+       BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_CFG_SCHEDULER_STEP3 = 31, BC_OP_ASSEMBLE_INPUT_SCALED = 32,
+       BC_OP_ASSEMBLE_IM2COL_SCALED = 33, BC_OP_COUNT = 34 };
 typedef struct BcPlanBuffer {
     const char* name;        /* "" for anonymous workspace; named buffers are found again with bc_plan_buffer */
     const void* address;     /* the address the launch records were built against */

@@ -584,6 +584,227 @@ def golden_pipeline_call_dpm():
     print(f"pipeline __call__ sde-dpm++ 2m on {timesteps}: latents std {out['latents'].std():.4f}, noise {out['noise'].shape}")
 
 
+# ------------------------------------------------------------------------------------------------ Euler / Euler-ancestral / Heun
+class _GiveNoise:
+    """Makes every `randn_tensor` call of a scheduler module return the next tensor of `noises` (EulerAncestralDiscreteScheduler.step has
+    no variance_noise argument: this is how a trajectory with GIVEN noise is run through the reference)."""
+
+    def __init__(self, module, noises):
+        import importlib
+        m = importlib.import_module(module)
+        self.m, self.orig, self.noises = m, m.randn_tensor, list(noises)
+
+    def __enter__(self):
+        self.m.randn_tensor = lambda *a, **k: self.noises.pop(0)
+        return self
+
+    def __exit__(self, *exc):
+        self.m.randn_tensor = self.orig
+
+
+EULER_A_MODULE = "diffusers.schedulers.scheduling_euler_ancestral_discrete"
+EULER_CUSTOM_TS = [999, 850, 736, 645, 545, 455, 343, 233, 124, 24]
+# cases of schedulers_euler.npz: name -> (scheduler class key, options on top of SD_SCHED, steps, caller timesteps)
+EULER_CASES = {
+    "euler_leading_5": ("euler", dict(timestep_spacing="leading"), 5, None),
+    "euler_leading_20": ("euler", dict(timestep_spacing="leading"), 20, None),
+    "euler_leading_50": ("euler", dict(timestep_spacing="leading"), 50, None),
+    "euler_linspace_15": ("euler", dict(), 15, None),
+    "euler_trailing_karras_10": ("euler", dict(timestep_spacing="trailing", use_karras_sigmas=True), 10, None),
+    "euler_sigmamin_8": ("euler", dict(final_sigmas_type="sigma_min"), 8, None),
+    "euler_custom_10": ("euler", dict(), None, EULER_CUSTOM_TS),
+    "eulera_noise_15": ("euler_ancestral", dict(), 15, None),
+    "eulera_leading_noise_5": ("euler_ancestral", dict(timestep_spacing="leading"), 5, None),
+    "heun_10": ("heun", dict(), 10, None),
+    "heun_karras_6": ("heun", dict(use_karras_sigmas=True), 6, None),
+    "heun_leading_5": ("heun", dict(timestep_spacing="leading"), 5, None),
+}
+
+
+def _euler_class(key):
+    from diffusers import EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler
+    return {"euler": EulerDiscreteScheduler, "euler_ancestral": EulerAncestralDiscreteScheduler, "heun": HeunDiscreteScheduler}[key]
+
+
+def golden_schedulers_euler():
+    """EulerDiscreteScheduler, EulerAncestralDiscreteScheduler and HeunDiscreteScheduler on golden_schedulers' inputs (8x8 latents
+    x = g(21) * init_noise_sigma, eps_i = g(100 + i)), the ancestral noise GIVEN as g(200 + i): timesteps, sigmas, init_noise_sigma, the
+    per-step scale_model_input of the fixed tensor g(22) and the trajectories of EULER_CASES, plus one ancestral run that draws from a
+    CPU generator.  The `.config` of `from_config(<SD-1.5 scheduler_config.json>)` of the three classes goes to euler_config.json."""
+    from diffusers import PNDMScheduler
+    out = {}
+
+    def run(sch, n, ts, step_kw):
+        sch.set_timesteps(timesteps=ts) if ts is not None else sch.set_timesteps(n)
+        fixed = g(22, 1, 4, 8, 8)
+        x = g(21, 1, 4, 8, 8) * sch.init_noise_sigma
+        xs, scaled = [x.numpy()], []
+        for i, t in enumerate(sch.timesteps):
+            scaled.append(sch.scale_model_input(fixed, t).numpy())
+            x = sch.step(g(100 + i, 1, 4, 8, 8), t, x, return_dict=False, **step_kw)[0]
+            xs.append(x.numpy())
+        return np.stack(xs), np.stack(scaled)
+
+    for name, (cls, kw, n, ts) in EULER_CASES.items():
+        sch = _euler_class(cls)(**SD_SCHED, **kw)
+        with _GiveNoise(EULER_A_MODULE, [g(200 + i, 1, 4, 8, 8) for i in range(200)]):
+            traj, scaled = run(sch, n, ts, {})
+        out[f"{name}_timesteps"] = sch.timesteps.numpy()
+        out[f"{name}_sigmas"] = sch.sigmas.numpy()
+        out[f"{name}_init_noise_sigma"] = np.array(float(sch.init_noise_sigma))
+        out[f"{name}_scaled"] = scaled
+        out[f"{name}_traj"] = traj
+        out[f"{name}_kw"] = np.array(json.dumps(dict(kw, cls=cls, timesteps=ts, n=n)))
+        assert sch.sigmas.dtype == torch.float32, name               # (timesteps: float32, float64 for Heun with Karras sigmas)
+    sch = _euler_class("euler_ancestral")(**SD_SCHED)                 # the generator case: the same set of arrays (it has no `_kw` entry:
+    name = "eulera_gen77_5"                                           # its noise is not the g(200 + i) of the cases above)
+    out[f"{name}_traj"], out[f"{name}_scaled"] = run(sch, 5, None, dict(generator=torch.Generator().manual_seed(77)))
+    out[f"{name}_timesteps"] = sch.timesteps.numpy()
+    out[f"{name}_sigmas"] = sch.sigmas.numpy()
+    out[f"{name}_init_noise_sigma"] = np.array(float(sch.init_noise_sigma))
+    # the float32 log-sigmas the Karras timesteps above were interpolated in (scheduling_euler_discrete.py:383-384), as THIS machine's numpy
+    # computes them: numpy's float32 log differs in the last bit between CPUs, and with it the fractional Karras timesteps
+    ac = sch.alphas_cumprod
+    out["train_log_sigmas"] = np.log(np.array(((1 - ac) / ac) ** 0.5))
+    np.savez_compressed(os.path.join(OUT, "schedulers_euler.npz"), **out)
+    cfgs = {}
+    for cls in ("euler", "euler_ancestral", "heun"):
+        C = _euler_class(cls)
+        cfg = dict(C.from_config(SD15_SCHEDULER_JSON).config)
+        via_pndm = dict(C.from_config(PNDMScheduler.from_config(SD15_SCHEDULER_JSON).config).config)
+        for c in (cfg, via_pndm):
+            c["_use_default_values"] = sorted(c["_use_default_values"])
+        assert cfg == via_pndm, (cfg, via_pndm)
+        cfgs[cls] = cfg
+    with open(os.path.join(OUT, "euler_config.json"), "w") as f:
+        json.dump(dict(cfgs, source=SD15_SCHEDULER_JSON), f, indent=1, sort_keys=True)
+    print("schedulers_euler:", len(EULER_CASES), "cases; euler config keys", sorted(cfgs["euler"]))
+
+
+# cases of loop_tiny_euler.npz: tag -> (class key, options on top of SD_SCHED, steps, caller timesteps, guidance window, generator seed)
+EULER_LOOPS = {
+    "euler_leading_6": ("euler", dict(timestep_spacing="leading"), 6, None, (0.0, 1.0), None),
+    "euler_linspace_5": ("euler", dict(), 5, None, (0.0, 1.0), None),
+    "euler_karras_6": ("euler", dict(use_karras_sigmas=True), 6, None, (0.0, 0.67), None),
+    "eulera_5": ("euler_ancestral", dict(), 5, None, (0.0, 1.0), 1234),
+    "heun_4": ("heun", dict(), 4, None, (0.0, 1.0), None),
+    "euler_custom_8": ("euler", dict(), None, [999, 850, 700, 550, 400, 250, 120, 20], (0.0, 0.9), None),
+}
+
+
+def golden_loop_euler(dtype=torch.float32, save=True):
+    """golden_loop's body (tiny nets, CFG 7.5) with the sigma-space schedulers: the latents start at g(31) * init_noise_sigma, every
+    step's model input goes through scheduler.scale_model_input (pipe:1032).  Euler (leading, linspace = fractional timesteps, Karras,
+    caller timesteps), Euler-ancestral (CPU generator, noise tapped from step) and Heun (2n - 1 evaluations).  Stores the final latents,
+    the latents entering every step and the guided eps.  `dtype=torch.float64, save=False` returns the same loop in float64 (the
+    reference's own fp32-versus-fp64 spread)."""
+    unet, blob = build_tiny()
+    unet, blob = unet.to(dtype), blob.to(dtype)
+    c = TINY
+    h = w = 8
+    B = 1
+    out = {}
+    pipe = StableDiffusionBlobNetPipeline.__new__(StableDiffusionBlobNetPipeline)
+    for tag, (cls, kw, steps, ts, (gs, ge), seed) in EULER_LOOPS.items():
+        sch = _euler_class(cls)(**SD_SCHED, **kw)
+        if ts is not None:
+            sch.set_timesteps(timesteps=ts)
+        else:
+            sch.set_timesteps(steps)
+        evals = len(sch.timesteps)
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        latents = (g(31, B, 4, h, w) * sch.init_noise_sigma).to(dtype)
+        prompt = g(32, 2 * B, 7, c["ctx"]).to(dtype)
+        fg_lat = (g(33, 1, 4, h, w) * 0.18215 * 5).repeat(2 * B, 1, 1, 1).to(dtype)
+        bg_lat = (g(34, 1, 4, h, w) * 0.18215 * 5).repeat(2 * B, 1, 1, 1).to(dtype)
+        ell = [[40.0, 42.0], [20.0, 30.0], 25.0]
+        mean, cov = ref_inf.get_gs_from_ellipse(ell)
+        nm, nc = ref_inf.normalize_gs(mean, cov, 64, 64)
+        gs_score = splat_features(**ref_inf.get_blob_dict_from_norm_gs(nm, nc), score_size=(h, w), return_d_score=True)
+        bg_s, fg_s = gs_score.unbind(dim=1)
+        bg_s = bg_s.unsqueeze(1).repeat(2 * B, 1, 1, 1).to(dtype)
+        fg_s = fg_s.unsqueeze(1).repeat(2 * B, 1, 1, 1).to(dtype)
+        dino = g(35, 1, 1, c["feat"]).to(dtype)
+        feats = pipe.splat_features_from_scores(fg_s, dino.repeat(2 * B, 1, 1), size=h, channels_last=False)
+        keep = [1.0 - float(i / evals < gs or (i + 1) / evals > ge) for i in range(evals)]          # pipe:1006-1012: over len(timesteps)
+        eps_trace, lat_trace = [], []
+        with _TapNoise(EULER_A_MODULE) as tap:
+            for i, t in enumerate(sch.timesteps):
+                lat_trace.append(latents.numpy().copy())
+                lmi = sch.scale_model_input(torch.cat([latents] * 2), t)
+                bi = pipe.construct_blobnet_input(lmi, fg_s, fg_lat, feats, background=False)
+                d, m, u = blob(bi, t, conditioning_scale=1.0 * keep[i], return_dict=False)
+                ui = pipe.construct_blobnet_input(lmi, bg_s, bg_lat, background=True)
+                npred = unet(ui, t, encoder_hidden_states=prompt, down_block_add_samples=[x[..., -x.shape[-2]:] for x in d],
+                             mid_block_add_sample=m[..., -m.shape[-2]:], up_block_add_samples=[x[..., -x.shape[-2]:] for x in u],
+                             return_dict=False)[0]
+                b_, c_, h_, w_ = npred.shape
+                npred = npred[..., :h_, w_ // 2:]
+                nu, nt = npred.chunk(2)
+                npred = nu + 7.5 * (nt - nu)
+                eps_trace.append(npred.numpy())
+                step_kw = dict(generator=gen) if cls == "euler_ancestral" else {}
+                latents = sch.step(npred, t, latents, return_dict=False, **step_kw)[0].to(dtype)
+        assert len(tap.drawn) == (evals if seed is not None else 0)
+        out[f"{tag}_final"] = latents.numpy()
+        out[f"{tag}_eps"] = np.stack(eps_trace)
+        out[f"{tag}_lat"] = np.stack(lat_trace)
+        out[f"{tag}_timesteps"] = sch.timesteps.numpy()
+        out[f"{tag}_window"] = np.array([gs, ge])
+        out[f"{tag}_kw"] = np.array(json.dumps(dict(kw, cls=cls, timesteps=ts, n=steps)))
+        if seed is not None:
+            out[f"{tag}_noise"] = torch.stack(tap.drawn).numpy()
+            out[f"{tag}_seed"] = np.array(seed)
+        print(f"loop_euler {tag} ({dtype}): {evals} evaluations, final std {latents.std():.4f}")
+    if save:
+        np.savez_compressed(os.path.join(OUT, "loop_tiny_euler.npz"), **out)
+    return out
+
+
+def euler_loop_spread():
+    """The reference's own fp32-versus-fp64 spread of golden_loop_euler's final latents (max-abs / scale), printed per case."""
+    a, b = golden_loop_euler(save=False), golden_loop_euler(torch.float64, save=False)
+    for tag in EULER_LOOPS:
+        x, y = a[f"{tag}_final"].astype(np.float64), b[f"{tag}_final"].astype(np.float64)
+        print(f"{tag}: reference fp32 vs fp64 final latents max-abs/scale {np.abs(x - y).max() / np.abs(y).max():.3e}")
+
+
+def golden_pipeline_call_euler():
+    """The reference's own `__call__` (pipe:743-1166) with `EulerDiscreteScheduler.from_config(pipeline.scheduler.config)` (linspace:
+    fractional timesteps) and with EulerAncestralDiscreteScheduler (leading spacing) and a CPU `generator` (start latents, then every step's
+    noise).  Case = `ddim_neg2` of pipeline_call.npz with its own seeds; the images and scores are those of pipeline_call.npz."""
+    from PIL import Image
+    from diffusers import EulerAncestralDiscreteScheduler, EulerDiscreteScheduler
+    from tests.common import FakeTokenizer, pipeline_cases
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"], seed=2026, rng_seed=23)
+    kw.pop("scheduler")
+    seed, rng_seed = kw.pop("seed"), kw.pop("rng_seed")
+    kw["num_inference_steps"] = 5
+    src = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+    pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=src,
+                                          safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+    pipe.set_progress_bar_config(disable=True)
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(kw["num_inference_steps"])}
+    call = lambda: pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                        height=64, width=64, generator=torch.Generator().manual_seed(seed), output_type="latent", **kw)
+    pipe.scheduler = EulerDiscreteScheduler.from_config(src.config)
+    torch.manual_seed(rng_seed)
+    out["euler_latents"] = call().images.numpy()
+    out["euler_timesteps"] = pipe.scheduler.timesteps.numpy()
+    pipe.scheduler = EulerAncestralDiscreteScheduler.from_config(src.config, timestep_spacing="leading")
+    torch.manual_seed(rng_seed)
+    with _TapNoise(EULER_A_MODULE) as noise:
+        out["eulera_latents"] = call().images.numpy()
+    assert len(noise.drawn) == kw["num_inference_steps"]
+    out["eulera_noise"] = torch.stack(noise.drawn).numpy()
+    out["eulera_timesteps"] = pipe.scheduler.timesteps.numpy()
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_euler.npz"), **out)
+    print(f"pipeline __call__ euler {out['euler_timesteps']}: latents std {out['euler_latents'].std():.4f}; euler a "
+          f"{out['eulera_timesteps']}: std {out['eulera_latents'].std():.4f}, noise {out['eulera_noise'].shape}")
+
+
 # ------------------------------------------------------------------------------------------------ 4. pipeline loop
 class _FakeVaeCfg:
     scaling_factor = 0.18215
@@ -1363,6 +1584,9 @@ if __name__ == "__main__":
     golden_schedulers_dpm()
     golden_loop_dpm()
     golden_pipeline_call_dpm()
+    golden_schedulers_euler()
+    golden_loop_euler()
+    golden_pipeline_call_euler()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))

@@ -12,7 +12,11 @@ compiled against host addresses and is relocatable.  Weights come from blobctrl_
 run's eta): the plan then also holds the named buffer `variance_noise` [5][1][4][8][8] with the noise the reference drew embedded, and
 "expected_latents" is that run's final latents.
 
-    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA]
+`--euler TAG` compiles a case of tests/golden/loop_tiny_euler.npz instead (e.g. euler_leading_6: the Euler scheduler, whose plan
+assembles its inputs with the `_scaled` entry points): "latents" is then the start noise times the table's init_noise_sigma, and
+"expected_latents" that run's final latents - or the contents of `--expected FILE.npy` (e.g. what the in-process engine computed).
+
+    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG [--expected FILE.npy]]
 """
 import argparse
 import os
@@ -35,11 +39,30 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out", nargs="?", default=os.path.join(REPO, "build", "plan_fixture"))
     ap.add_argument("--eta", type=float, default=0.0, help="stochastic DDIM: the eta of loop_tiny_eta.npz's 5-step run")
+    ap.add_argument("--euler", default=None, help="a case of loop_tiny_euler.npz (Euler / Euler-ancestral / Heun)")
+    ap.add_argument("--expected", default=None, help=".npy file with the expected final latents (default: the reference loop's)")
     args = ap.parse_args()
     OUT = args.out
     os.makedirs(OUT, exist_ok=True)
     z = np.load(os.path.join(GOLD, "loop_tiny.npz"))
     extra, expected = {}, z["ddim_5_final"]
+    sigma0, steps, window, sched = 1.0, 5, (0.0, 1.0), None
+    if args.euler:
+        import json
+        from blobctrl_amd import schedulers
+        ze = np.load(os.path.join(GOLD, "loop_tiny_euler.npz"))
+        kw = json.loads(str(ze[f"{args.euler}_kw"]))
+        cls, steps, ts = kw.pop("cls"), kw.pop("n"), kw.pop("timesteps")
+        sched = {"euler": schedulers.EulerDiscreteScheduler, "euler_ancestral": schedulers.EulerAncestralDiscreteScheduler,
+                 "heun": schedulers.HeunDiscreteScheduler}[cls](steps_offset=1, **kw)
+        sched.set_timesteps(timesteps=ts) if ts is not None else sched.set_timesteps(steps)
+        sigma0, window, expected = sched.init_noise_sigma, tuple(float(v) for v in ze[f"{args.euler}_window"]), ze[f"{args.euler}_final"]
+        if ts is not None:
+            extra = dict(timesteps=ts)
+        if f"{args.euler}_noise" in ze.files:
+            extra["variance_noise"] = torch.from_numpy(ze[f"{args.euler}_noise"])
+    if args.expected:
+        expected = np.load(args.expected)
     if args.eta:
         ze = np.load(os.path.join(GOLD, "loop_tiny_eta.npz"))
         if float(ze["ddim_5_eta"]) != args.eta:
@@ -49,16 +72,18 @@ def main():
     usd, bsd = tiny_weights()
     ucfg, bcfg = tiny_trunk_configs()
     eng = BlobCtrlEngine(usd, bsd, ucfg, bcfg, device="cpu", scheduler="ddim", compile_only=True)
-    B, h, w, T, steps = 1, 8, 8, 7, 5
+    if sched is not None:
+        eng.set_scheduler(sched.kind, sched.table_params())
+    B, h, w, T = 1, 8, 8, 7
     seq = eng.compile_plan(os.path.join(OUT, "tiny_edit.bcplan"), B, h, w, T, TINY["ctx"], steps, guidance_scale=7.5,
-                           blobnet_conditioning_scale=1.0, blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0,
+                           blobnet_conditioning_scale=1.0, blobnet_control_guidance_start=window[0], blobnet_control_guidance_end=window[1],
                            **extra)
     score = torch.from_numpy(z["gs_score"]).float()                     # [1,2,h,w] = (bg, fg)
     dino = g(35, 1, 1, TINY["feat"])
     feat16 = torch.zeros(1, 8, dtype=torch.float16)
     feat16[:, : TINY["feat"]] = dino.reshape(1, -1).half()
     recs = {
-        "latents": g(31, B, 4, h, w).numpy(),                              # x init_noise_sigma (= 1 for DDIM)
+        "latents": (g(31, B, 4, h, w) * sigma0).numpy(),                   # x init_noise_sigma (= 1 for DDIM)
         "ctx": g(32, 2 * B, T, TINY["ctx"]).half().numpy(),
         "fg_lat": (g(33, 1, 4, h, w) * 0.18215 * 5).numpy(),
         "bg_lat": (g(34, 1, 4, h, w) * 0.18215 * 5).numpy(),
