@@ -194,7 +194,10 @@ def load_unet(path: str, extra_in_channels: int = 1, lora_path: Optional[str] = 
     tc = TrunkConfig(in_channels=sd["conv_in.weight"].shape[1], block_out_channels=boc,
                      num_heads=heads if isinstance(heads, int) else heads[0], norm_num_groups=cfg.get("norm_num_groups", 32),
                      cross_attention_dim=cfg.get("cross_attention_dim", 768), out_channels=sd["conv_out.weight"].shape[0],
-                     is_blobnet=False)
+                     is_blobnet=False, time_cond_proj_dim=cfg.get("time_cond_proj_dim"))
+    if (tc.time_cond_proj_dim is not None) != ("time_embedding.cond_proj.weight" in sd):
+        raise ValueError(f"config.json says time_cond_proj_dim = {tc.time_cond_proj_dim}, the checkpoint "
+                         f"{'has no' if tc.time_cond_proj_dim is not None else 'has a'} time_embedding.cond_proj.weight")
     return sd, tc
 
 

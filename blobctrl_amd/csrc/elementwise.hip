@@ -114,17 +114,39 @@ __global__ void assemble_im2col_kernel(const float* __restrict__ latents, int Bl
 
 // embeddings.py:27-78: [cos(t*f_k) | sin(t*f_k)], f_k = exp(-ln(10000) * k / half)
 // rows_per_step > 0: row r belongs to step r / rows_per_step of the table (all steps of an edit at once)
-__global__ void temb_kernel(const float* __restrict__ t_table, const int* __restrict__ t_idx, float t_value, int rows,
-                            int dim, int rows_per_step, h16* __restrict__ out) {
+//   COND: `cond` fp32 [cond_rows][dim] = cond_proj(timestep_cond) of a UNet with time_cond_proj_dim (embeddings.py:559, 578: added to the
+//         sinusoid before linear_1); row r takes cond row r % cond_rows.  The sinusoid and the sum are formed in fp64 and rounded to
+//         fp16 ONCE: the output is the fp16 nearest to the exact sum (an fp32 sinusoid at t ~ 1000 is off by up to 1e-4, a quarter of
+//         an fp16 step; the launch is a few thousand elements once per edit).  `cond` / `cond_rows` are not read by the instantiation
+//         without COND, which is the fp32 kernel it always was.
+template <bool COND>
+__device__ __forceinline__ void temb_body(const float* __restrict__ t_table, const int* __restrict__ t_idx, float t_value, int rows,
+                                          int dim, int rows_per_step, const float* __restrict__ cond, int cond_rows,
+                                          h16* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * dim) return;
     const int r = i / dim, c = i - r * dim;
     const int halfd = dim / 2;
     const float t = rows_per_step > 0 ? t_table[r / rows_per_step] : (t_table ? t_table[t_idx ? *t_idx : 0] : t_value);
     const int k = c < halfd ? c : c - halfd;
+    if (COND) {
+        const double a = (double)t * exp(-9.210340371976184 * (double)k / (double)halfd);
+        out[i] = (h16)((c < halfd ? cos(a) : sin(a)) + (double)cond[(size_t)(r % cond_rows) * dim + c]);
+        return;
+    }
     const float freq = expf(-9.210340371976184f * (float)k / (float)halfd);
     const float a = t * freq;
     out[i] = (h16)(c < halfd ? cosf(a) : sinf(a));
+}
+
+__global__ void temb_kernel(const float* __restrict__ t_table, const int* __restrict__ t_idx, float t_value, int rows,
+                            int dim, int rows_per_step, h16* __restrict__ out) {
+    temb_body<false>(t_table, t_idx, t_value, rows, dim, rows_per_step, nullptr, 1, out);
+}
+
+__global__ void temb_cond_kernel(const float* __restrict__ t_table, const int* __restrict__ t_idx, float t_value, int rows,
+                                 int dim, int rows_per_step, const float* __restrict__ cond, int cond_rows, h16* __restrict__ out) {
+    temb_body<true>(t_table, t_idx, t_value, rows, dim, rows_per_step, cond, cond_rows, out);
 }
 
 __global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, long long n) {
@@ -140,11 +162,13 @@ __global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, long
 //          m1 that every instantiation already loads
 //   GUARD: a step index outside [0, nsteps) (the capture warm-ups advance the counter) has no table row and no noise slice: the
 //          launch then leaves every buffer as it is.  The plain entry point has no nsteps in its ABI, hence no guard.
+//   SINGLE: a guidance-free (single-pass) plan: eps holds B images, not 2B, and e is the right half of image b as it is - no second
+//          read, no guidance arithmetic, `guidance` and column 11 are not read (pipe:1031, 1095: do_classifier_free_guidance False).
 // `noise` / `nsteps` are not read by an instantiation without NOISE / GUARD.
-template <bool NOISE, bool THIRD, bool GUARD>
-__global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
-                                const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
-                                const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
+template <bool SINGLE, bool NOISE, bool THIRD, bool GUARD>
+__device__ __forceinline__ void cfg_step_body(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
+                                              const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h,
+                                              int w, const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
     const int n = B * 4 * h * w;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int step = *step_idx;
@@ -157,10 +181,15 @@ __global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict
     const int b = i / (4 * w * h);
     // eps token-major [2B][h][2w][4]; right half, uncond = batch b, cond = batch B + b   (pipe:1092-1098)
     const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    const float eu = eps[pu], ec = eps[pc];
-    const float gscale = guidance >= 0.f ? guidance : cf[11];     // < 0: read from the coefficient table (graph-replay safe)
-    const float e = eu + gscale * (ec - eu);
+    float e;
+    if (SINGLE) {
+        e = eps[pu];                                              // eps token-major [B][h][2w][4]
+    } else {
+        const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
+        const float eu = eps[pu], ec = eps[pc];
+        const float gscale = guidance >= 0.f ? guidance : cf[11];     // < 0: read from the coefficient table (graph-replay safe)
+        e = eu + gscale * (ec - eu);
+    }
     if (eps_out) eps_out[i] = e;
     const float x = latents[i];
     float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
@@ -176,6 +205,21 @@ __global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict
     if (NOISE) xn = xn + cf[12] * noise[(size_t)step * n + i];
     if (THIRD) xn = xn + cf[13] * pm1;
     latents[i] = xn;
+}
+
+template <bool NOISE, bool THIRD, bool GUARD>
+__global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
+                                const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
+                                const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
+    cfg_step_body<false, NOISE, THIRD, GUARD>(eps, latents, coef, step_idx, hist, guidance, B, h, w, noise, nsteps, eps_out);
+}
+
+// The step of a single-pass plan: always guarded (its ABI has nsteps).
+template <bool NOISE, bool THIRD>
+__global__ void step_single_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
+                                   const int* __restrict__ step_idx, float* __restrict__ hist, int B, int h, int w,
+                                   const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
+    cfg_step_body<true, NOISE, THIRD, true>(eps, latents, coef, step_idx, hist, 0.f, B, h, w, noise, nsteps, eps_out);
 }
 
 __global__ void advance_kernel(int* step_idx) { *step_idx += 1; }
@@ -374,6 +418,29 @@ extern "C" int bc_timestep_embedding_table(const float* t_table, int nsteps, int
     return 0;
 }
 
+// The `_cond` forms of the two entry points above: cond fp32 [cond_rows][dim] is added to the sinusoid in fp32 (temb_cond_kernel).
+extern "C" int bc_timestep_embedding_cond(const float* t_table, const int* t_idx, float t_value, int rows, int dim, const float* cond,
+                                          bc_half* out, bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(out && cond && rows > 0 && dim > 0 && dim % 2 == 0, "bc_timestep_embedding_cond: bad args");
+    hipLaunchKernelGGL(temb_cond_kernel, dim3(bc_ceil_div(rows * dim, 256)), dim3(256), 0, stream, t_table, t_idx, t_value, rows,
+                       dim, 0, cond, rows, reinterpret_cast<h16*>(out));
+    BC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bc_timestep_embedding_table_cond(const float* t_table, int nsteps, int rows_per_step, int dim, const float* cond,
+                                                bc_half* out, bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(t_table && cond && out && nsteps > 0 && rows_per_step > 0 && dim > 0 && dim % 2 == 0,
+                 "bc_timestep_embedding_table_cond: bad args");
+    const int rows = nsteps * rows_per_step;
+    hipLaunchKernelGGL(temb_cond_kernel, dim3(bc_ceil_div(rows * dim, 256)), dim3(256), 0, stream, t_table, nullptr, 0.f, rows, dim,
+                       rows_per_step, cond, rows_per_step, reinterpret_cast<h16*>(out));
+    BC_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int bc_silu(const bc_half* x, bc_half* y, long long n, bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BC_CHECK_ARG(x && y && n > 0, "bc_silu: bad args");
@@ -422,6 +489,31 @@ extern "C" int bc_cfg_scheduler_step3(const float* eps, float* latents, const fl
                                       bc_stream stream) {
     return cfg_step_launch<false, true, true>("bc_cfg_scheduler_step3", eps, latents, coef, step_idx, hist, guidance_scale, B, h, w,
                                               nullptr, nsteps, eps_out, advance, stream);
+}
+
+// The step of a guidance-free (single-pass) plan: eps [B][h][2w][4], e = its right half.  noise != NULL adds cf[12] * noise[step],
+// third != 0 adds cf[13] * x0_{i-2}; a step index outside [0, nsteps) leaves every buffer as it is.
+extern "C" int bc_scheduler_step_single(const float* eps, float* latents, const float* coef, int* step_idx, float* hist, int B, int h,
+                                        int w, const float* noise, int nsteps, int third, float* eps_out, int advance,
+                                        bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0, "bc_scheduler_step_single: bad args");
+    const int n = B * 4 * h * w;
+    const dim3 grid(bc_ceil_div(n, 256)), block(256);
+    if (noise && third)
+        hipLaunchKernelGGL((step_single_kernel<true, true>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
+    else if (noise)
+        hipLaunchKernelGGL((step_single_kernel<true, false>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
+    else if (third)
+        hipLaunchKernelGGL((step_single_kernel<false, true>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
+    else
+        hipLaunchKernelGGL((step_single_kernel<false, false>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
+    BC_CHECK_LAUNCH();
+    if (advance) {
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
+        BC_CHECK_LAUNCH();
+    }
+    return 0;
 }
 
 extern "C" int bc_nchw_to_nhwc_f16(const void* src, int src_is_f32, int B, int C, int HW, int Cpad, bc_half* dst,

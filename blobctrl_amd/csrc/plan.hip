@@ -138,6 +138,13 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
         case BC_OP_ASSEMBLE_IM2COL_SCALED:
             return bc_assemble_input_im2col_scaled(CP(float, 0), I(1), CP(float, 2), CP(float, 3), I(4), I(5), I(6), I(7), I(8), CP(float, 9),
                                                    CP(int, 10), I(11), MP(bc_half, 12), s);
+        case BC_OP_SCHEDULER_STEP_SINGLE:
+            return bc_scheduler_step_single(CP(float, 0), MP(float, 1), CP(float, 2), MP(int, 3), MP(float, 4), I(5), I(6), I(7), CP(float, 8),
+                                            I(9), I(10), MP(float, 11), I(12), s);
+        case BC_OP_TIMESTEP_EMBEDDING_TABLE_COND:
+            return bc_timestep_embedding_table_cond(CP(float, 0), I(1), I(2), I(3), CP(float, 4), MP(bc_half, 5), s);
+        case BC_OP_TIMESTEP_EMBEDDING_COND:
+            return bc_timestep_embedding_cond(CP(float, 0), CP(int, 1), F(2), I(3), I(4), CP(float, 5), MP(bc_half, 6), s);
         case BC_OP_ROWCHAIN:
             return bc_rowchain(I(0), I(1), I(2), I(3), CP(bc_half, 4), CP(float, 5), CP(unsigned long long, 6), CP(float, 7), CP(float, 8), I(9),
                                F(10), CP(bc_half, 11), CP(bc_half, 12), CP(bc_half, 13), I(14), I(15), I(16), CP(bc_half, 17), CP(float, 18),

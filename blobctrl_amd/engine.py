@@ -32,6 +32,7 @@ class TrunkConfig:
     cross_attention_dim: Optional[int] = 768
     out_channels: int = 4
     is_blobnet: bool = False
+    time_cond_proj_dim: Optional[int] = None      # a distilled LCM UNet: time_embedding.cond_proj over the guidance-scale embedding
 
 
 class Act:
@@ -572,28 +573,49 @@ class TrunkPlan:
         self.rec.gemm(A=fm, W=feat16, M=fm.shape[0], N=1, K=fm.shape[1], out=w8, ldc=8, out_offset=5, kind="collapse")
 
     # ------------------------------------------------------------------------------------------- time embedding
-    def record_time(self, t_table, t_idx, t_value=0.0):
-        """embeddings.py:27-78, 576-588 and the 22 `time_emb_proj(silu(emb))` of resnet.py:343-350 as three GEMMs."""
+    def record_cond_proj(self, cond):
+        """`cond_proj(timestep_cond)` of a UNet with time_cond_proj_dim (embeddings.py:559, 578; no bias): cond fp16 [B][pad8(dim)] -> fp32
+        [B][c0] through the dense path, for the `_cond` time-embedding entry points to add to the sinusoid in fp32."""
+        B, c0 = self.B, self.cfg.block_out_channels[0]
+        if "time_embedding.cond_proj.weight" not in self.pw.h:
+            raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
+        out = self.rec.empty(B, c0, dtype=torch.float32)
+        return self.dense(cond, B, cond.shape[-1], None, c0, bias=False, wkey="time_embedding.cond_proj.weight", out=out,
+                          out_mode=_lib.OUT_F32, kind="temb")
+
+    def record_time(self, t_table, t_idx, t_value=0.0, cond=None):
+        """embeddings.py:27-78, 576-588 and the 22 `time_emb_proj(silu(emb))` of resnet.py:343-350 as three GEMMs.  `cond` (fp16
+        [B][pad8(time_cond_proj_dim)], the guidance-scale embedding): cond_proj(cond) is added to the sinusoid before linear_1."""
         rec, pw, B = self.rec, self.pw, self.B
         c0 = self.cfg.block_out_channels[0]
         te = c0 * 4
         sin = rec.empty(B, c0)
-        rec.call("bc_timestep_embedding", _ptr(t_table), _ptr(t_idx), float(t_value), B, c0, sin.data_ptr(),
-                 kind="temb", keep=(t_table, t_idx, sin))
+        if cond is not None:
+            proj = self.record_cond_proj(cond)
+            rec.call("bc_timestep_embedding_cond", _ptr(t_table), _ptr(t_idx), float(t_value), B, c0, proj.data_ptr(), sin.data_ptr(),
+                     kind="temb", keep=(t_table, t_idx, proj, sin))
+        else:
+            rec.call("bc_timestep_embedding", _ptr(t_table), _ptr(t_idx), float(t_value), B, c0, sin.data_ptr(),
+                     kind="temb", keep=(t_table, t_idx, sin))
         h = self.dense(sin, B, c0, "time_embedding.linear_1", te, act=_lib.ACT_SILU, kind="temb")
         h = self.dense(h, B, te, "time_embedding.linear_2", te, act=_lib.ACT_SILU, kind="temb")   # silu(emb)
         self.tproj = self.dense(h, B, te, "temb_all", pw.temb_total, kind="temb")
 
-    def record_time_table(self, t_table, nsteps, t_idx):
+    def record_time_table(self, t_table, nsteps, t_idx, cond=None):
         """The same three GEMMs over ALL steps of an edit at once (prologue): tproj [nsteps * B][temb_total]; the ResBlock
         epilogues then pick the block of the current step through the device step counter (BcGemm.rowvec_idx), and no
-        time-embedding launch is left in the step."""
+        time-embedding launch is left in the step.  `cond` as in record_time: row r of the table takes cond_proj(cond)[r % B]."""
         rec, pw, B = self.rec, self.pw, self.B
         c0 = self.cfg.block_out_channels[0]
         te = c0 * 4
         rows = nsteps * B
         sin = rec.empty(rows, c0)
-        rec.call("bc_timestep_embedding_table", _ptr(t_table), nsteps, B, c0, sin.data_ptr(), kind="temb", keep=(t_table, sin))
+        if cond is not None:
+            proj = self.record_cond_proj(cond)
+            rec.call("bc_timestep_embedding_table_cond", _ptr(t_table), nsteps, B, c0, proj.data_ptr(), sin.data_ptr(), kind="temb",
+                     keep=(t_table, proj, sin))
+        else:
+            rec.call("bc_timestep_embedding_table", _ptr(t_table), nsteps, B, c0, sin.data_ptr(), kind="temb", keep=(t_table, sin))
         h = self.dense(sin, rows, c0, "time_embedding.linear_1", te, act=_lib.ACT_SILU, kind="temb")
         h = self.dense(h, rows, te, "time_embedding.linear_2", te, act=_lib.ACT_SILU, kind="temb")
         self.tproj = self.dense(h, rows, te, "temb_all", pw.temb_total, kind="temb")

@@ -68,7 +68,7 @@ class _TrunkModule(torch.nn.Module):
             in_channels=latent if config.is_blobnet or config.in_channels in (latent, latent + 1) else config.in_channels,
             conv_in_channels=config.in_channels, out_channels=config.out_channels, block_out_channels=tuple(config.block_out_channels),
             layers_per_block=config.layers_per_block, attention_head_dim=config.num_heads, norm_num_groups=config.norm_num_groups,
-            cross_attention_dim=config.cross_attention_dim, time_cond_proj_dim=None, sample_size=64,
+            cross_attention_dim=config.cross_attention_dim, time_cond_proj_dim=config.time_cond_proj_dim, sample_size=64,
             conditioning_channels=(config.in_channels - latent) if config.is_blobnet else None)
 
     # ---- weights: packed lazily from the host state dict + the active LoRA adapters
@@ -318,8 +318,10 @@ class UNet2DConditionModel(_TrunkModule):
                 up.append((rev[i],) + sizes[nb - 2 - i])
         return down, mid, up
 
-    def _plan(self, B, H, W, T, Dc, with_res):
-        key = (B, H, W, T, Dc, with_res)
+    def _plan(self, B, H, W, T, Dc, with_res, cond=False):
+        """`cond`: the plan takes a `timestep_cond` (fp16 [B][pad8(time_cond_proj_dim)]) and adds cond_proj of it to the sinusoid; a
+        plan of its own, so that calls without one keep the launches they always recorded."""
+        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ())
         if key not in self._plans:
             rec = Recorder(self.device)
             P = type("Plan", (), {})()
@@ -338,7 +340,11 @@ class UNet2DConditionModel(_TrunkModule):
             P.seg = rec.begin("unet")
             plan = TrunkPlan(rec, self.weights, self.trunk_config, B, H, W)
             plan.record_context(P.ctx, T)
-            plan.record_time(P.t, P.idx)
+            if cond:
+                P.cond = rec.zeros(B, pad8(self.trunk_config.time_cond_proj_dim))
+                plan.record_time(P.t, P.idx, cond=P.cond)
+            else:
+                plan.record_time(P.t, P.idx)
             P.eps = plan.record_forward(P.x_in, residuals)
             self._plans[key] = P
         return self._plans[key]
@@ -361,23 +367,36 @@ class UNet2DConditionModel(_TrunkModule):
             raise ValueError(f"expected {self.trunk_config.in_channels} input channels, got {C}")
         is_blobnet = (down_block_add_samples is not None and mid_block_add_sample is not None
                       and up_block_add_samples is not None)                        # unet_2d_condition.py:1200
-        # through the dispatcher (torch.ops.blobctrl.unet_forward, ops.py)
+        # unet_2d_condition.py:1152 -> embeddings.py:576-579: a UNet with time_cond_proj_dim adds cond_proj(timestep_cond) to the sinusoid;
+        # without a timestep_cond it runs without the add, as the reference does
+        dim = self.trunk_config.time_cond_proj_dim
+        if timestep_cond is not None:
+            if dim is None:
+                raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
+            if tuple(timestep_cond.shape) != (B, dim):
+                raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
+        # through the dispatcher (torch.ops.blobctrl.unet_forward, ops.py); `timestep_cond` is the op's optional trailing argument
         from . import ops
+        extra = () if timestep_cond is None else (timestep_cond,)
         eps = torch.ops.blobctrl.unet_forward(sample, float(timestep), encoder_hidden_states,
                                               list(down_block_add_samples) if is_blobnet else [], mid_block_add_sample if is_blobnet else None,
-                                              list(up_block_add_samples) if is_blobnet else [], ops.register(self))
+                                              list(up_block_add_samples) if is_blobnet else [], ops.register(self), *extra)
         if is_blobnet:                                   # the reference consumes the two lists with pop(0) (:1217, 1230, 1313)
             del down_block_add_samples[:]
             del up_block_add_samples[:]
         dt = sample.dtype if sample.dtype in (torch.float16, torch.float32) else torch.float32
         return (eps.to(dt),)
 
-    def _forward_impl(self, sample, timestep, encoder_hidden_states, down_block_add_samples, mid_block_add_sample, up_block_add_samples):
+    def _forward_impl(self, sample, timestep, encoder_hidden_states, down_block_add_samples, mid_block_add_sample, up_block_add_samples,
+                      timestep_cond=None):
         """Body of torch.ops.blobctrl.unet_forward: eps [B][4][H][W] fp32."""
         B, C, H, W = sample.shape
         is_blobnet = mid_block_add_sample is not None
         T, Dc = encoder_hidden_states.shape[1:]
-        P = self._plan(B, H, W, T, Dc, is_blobnet)
+        P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None)
+        if timestep_cond is not None:
+            P.cond.zero_()
+            P.cond[:, : timestep_cond.shape[1]].copy_(timestep_cond.to(self.device, torch.float16))
         P.x_in.copy_(self._to_nhwc(P.rec, sample, P.x_in.shape[-1]))
         P.ctx.copy_(encoder_hidden_states.to(self.device, torch.float16))
         P.t.fill_(float(timestep))

@@ -173,15 +173,18 @@ def _(sample, timestep, conditioning_scale, handle):
 # ------------------------------------------------------------------------------------------------------------------ unet_forward
 @torch.library.custom_op("blobctrl::unet_forward", mutates_args=())
 def unet_forward(sample: torch.Tensor, timestep: float, encoder_hidden_states: torch.Tensor, down_add: List[torch.Tensor],
-                 mid_add: Optional[torch.Tensor], up_add: List[torch.Tensor], handle: int) -> torch.Tensor:
-    """The patched UNet2DConditionModel.forward; empty lists / None = no BlobNet residuals.  Returns eps [B][4][H][W] fp32."""
+                 mid_add: Optional[torch.Tensor], up_add: List[torch.Tensor], handle: int,
+                 timestep_cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The patched UNet2DConditionModel.forward; empty lists / None = no BlobNet residuals.  Returns eps [B][4][H][W] fp32.
+    `timestep_cond` [B][time_cond_proj_dim] (a UNet with time_embedding.cond_proj): the guidance-scale embedding."""
     with_res = mid_add is not None
+    extra = {} if timestep_cond is None else dict(timestep_cond=timestep_cond)
     return _get(handle)._forward_impl(sample, timestep, encoder_hidden_states, list(down_add) if with_res else None, mid_add,
-                                      list(up_add) if with_res else None)
+                                      list(up_add) if with_res else None, **extra)
 
 
 @unet_forward.register_fake
-def _(sample, timestep, encoder_hidden_states, down_add, mid_add, up_add, handle):
+def _(sample, timestep, encoder_hidden_states, down_add, mid_add, up_add, handle, timestep_cond=None):
     m = _get(handle)
     B, _, H, W = sample.shape
     return torch.empty((B, m.trunk_config.out_channels, H, W), dtype=torch.float32, device=m.device)

@@ -28,6 +28,22 @@ from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, table_c
 from .weights import PackedTrunk, pad8
 
 
+def get_guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The `timestep_cond` of a distilled LCM UNet (pipe:456-483): w = guidance_scale - 1, one entry per sample -> [len(w), embedding_dim],
+    columns [sin(a_k) | cos(a_k) | 0 if embedding_dim is odd], a_k = 1000 w * exp(-ln(1e4) k / (half - 1)), half = embedding_dim // 2.
+    Host work in fp32 torch with the reference's operation order, so the values are the reference's bit for bit."""
+    if w.dim() != 1:
+        raise ValueError("w must be one-dimensional (one guidance weight per sample)")
+    half = embedding_dim // 2
+    rate = torch.log(torch.tensor(10000.0)) / (half - 1)
+    freq = torch.exp(torch.arange(half, dtype=dtype) * -rate)
+    angle = (w * 1000.0).to(dtype)[:, None] * freq[None, :]
+    out = torch.zeros(w.shape[0], embedding_dim, dtype=angle.dtype)
+    out[:, :half] = torch.sin(angle)
+    out[:, half:2 * half] = torch.cos(angle)
+    return out
+
+
 def blobnet_keep(num_steps, start, end):
     """pipe:1006-1012."""
     return [1.0 - float(i / num_steps < start or (i + 1) / num_steps > end) for i in range(num_steps)]
@@ -77,7 +93,7 @@ class BlobCtrlEngine:
         self.text_encoder = text_encoder                              # optional blobctrl_amd.clip_text.CLIPTextModel
 
     # ------------------------------------------------------------------------------------------------ planning
-    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False):
+    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
@@ -86,11 +102,14 @@ class BlobCtrlEngine:
         table (UniPC, DDIM, DPM-Solver++ of order 1 / 2) runs on the same plan: only the tables differ.
         scaled: a table that scales the model input (Euler, Euler-ancestral, Heun: `scheduler.scale_model_input`, pipe:1032) - the BlobNet
         and UNet inputs are assembled by the `_scaled` entry points, which divide the noisy latents by column 14 of the current row.  A
-        plan of its own (and with it graphs of its own): no other table ever replays these launches."""
+        plan of its own (and with it graphs of its own): no other table ever replays these launches.
+        single: a guidance-free (single-pass) plan, pipe:1031 / 1095 with do_classifier_free_guidance False: `ctx` holds the B positive
+        prompts, the UNet runs once per request at batch B (no CFG pair, so no CFG-prefix sharing and no BC_SPLIT_CFG) and the step ends
+        in bc_scheduler_step_single, which takes the right half of image b as eps.  BlobNet is what it is in every plan: batch B."""
         if stochastic and third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
         key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
-            (("scaled",) if scaled else ())
+            (("scaled",) if scaled else ()) + (("single",) if single else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -116,7 +135,13 @@ class BlobCtrlEngine:
         P.fg_score = rec.zeros(Bi, h, w, dtype=f32, name="fg_score")
         P.bg_score = rec.zeros(Bi, h, w, dtype=f32, name="bg_score")
         P.feat = rec.zeros(Bi, max(F, 1), dtype=f32, name="feat")
-        P.ctx = rec.zeros(2 * B, T, ctx_dim, name="ctx")
+        Bu = B if single else 2 * B                          # images the UNet runs: the CFG pair of every sample, or the sample alone
+        P.single = bool(single)
+        P.ctx = rec.zeros(Bu, T, ctx_dim, name="ctx")
+        # a UNet with time_cond_proj_dim (a distilled LCM UNet): the guidance-scale embedding of every UNet image, replay-time data like
+        # the guidance scale itself - zero when the caller gives none (cond_proj has no bias: the add is then + 0)
+        cond_dim = self.unet_cfg.time_cond_proj_dim
+        P.timestep_cond = rec.zeros(Bu, pad8(cond_dim), name="timestep_cond") if cond_dim is not None else None
         P.step_idx = rec.zeros(1, dtype=torch.int32, name="step_idx")
         P.t_table = rec.zeros(nsteps, dtype=f32, name="t_table")
         P.coef = rec.zeros(nsteps, 16, dtype=f32, name="coef")
@@ -141,11 +166,11 @@ class BlobCtrlEngine:
         P.blob_im2col = P.collapse
         P.feat16 = rec.zeros(Bi, pad8(max(F, 1)), name="feat16")
         P.blob_in = rec.zeros(B, H * W, 128 if P.blob_im2col else blob_cin)
-        P.unet_in = rec.zeros(2 * B, H * W, 128 if P.unet_im2col else unet_cin)
+        P.unet_in = rec.zeros(Bu, H * W, 128 if P.unet_im2col else unet_cin)
 
         # ---- prologue: prompt K/V
         P.prologue = rec.begin("prologue")
-        unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, 2 * B, H, W)
+        unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_a.record_context(P.ctx, T)
         blob = TrunkPlan(rec, self.blob_w, self.blob_cfg, B, H, W)
         if P.collapse:
@@ -153,11 +178,11 @@ class BlobCtrlEngine:
         # time-embedding path of every step, once per edit (read in the step through the device step counter)
         temb_per_step = False                                # (the per-edit table replaced the four launches per net inside every step)
         if not temb_per_step:
-            unet_a.record_time_table(P.t_table, nsteps, P.step_idx)
-            blob.record_time_table(P.t_table, nsteps, P.step_idx)
+            unet_a.record_time_table(P.t_table, nsteps, P.step_idx, **({} if P.timestep_cond is None else dict(cond=P.timestep_cond)))
+            blob.record_time_table(P.t_table, nsteps, P.step_idx)          # (BlobNet never has a cond_proj: pipe:1063 passes no timestep_cond)
 
         # CFG halves on two streams (opt-in, BC_SPLIT_CFG=1; single edits only - larger batches fill the GPU with the batch-2B UNet)
-        split_cfg = B == 1 and self.two_streams and not temb_per_step and bool(os.environ.get("BC_SPLIT_CFG"))
+        split_cfg = B == 1 and self.two_streams and not temb_per_step and bool(os.environ.get("BC_SPLIT_CFG")) and not single
         P.split_cfg = split_cfg
         if split_cfg:
             # the uncond / cond halves of the UNet batch as two batch-B plans on their own streams (ids 0 and 2): more concurrent
@@ -166,7 +191,7 @@ class BlobCtrlEngine:
             #  Not the default: it trades per-kernel efficiency - every self-attention then runs at batch 1, the 64x64-tile GEMM
             #  becomes the largest kernel of the step - for concurrency, a gain inside the box-to-box spread)
             half_time = TrunkPlan(rec, self.unet_w, self.unet_cfg, B, H, W)
-            half_time.record_time_table(P.t_table, nsteps, P.step_idx)
+            half_time.record_time_table(P.t_table, nsteps, P.step_idx, **({} if P.timestep_cond is None else dict(cond=P.timestep_cond[:B])))
             P.eps_all = rec.zeros(2 * B, H * W, self.unet_cfg.out_channels, dtype=f32)
 
         def half_plan(b0):
@@ -186,11 +211,11 @@ class BlobCtrlEngine:
 
         def record_unet(plan, residuals):
             if P.unet_im2col:
-                rec.call("bc_assemble_input_im2col" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), Bi, 2 * B,
+                rec.call("bc_assemble_input_im2col" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), Bi, Bu,
                          h, w, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
             else:
                 rec.call("bc_assemble_input" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), None, Bi, 0,
-                         2 * B, h, w, unet_cin, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
+                         Bu, h, w, unet_cin, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
             if temb_per_step:
                 plan.record_time(P.t_table, P.step_idx)
             if split_cfg:
@@ -205,8 +230,12 @@ class BlobCtrlEngine:
                 rec.wait(joined)
                 eps = P.eps_all
             else:
-                eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=True)   # (images b and b + B: the CFG pair)
+                eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=not single)   # (images b and b + B: the CFG pair)
             P.eps = eps
+            if single:                                            # one entry point, every step form: noise (or NULL), nsteps, third
+                rec.call("bc_scheduler_step_single", eps, P.latents, P.coef, P.step_idx, P.hist, B, h, w, P.variance_noise, nsteps,
+                         int(P.third_order), P.eps_guided, 1, kind="cfg_step")
+                return
             # the plan's step form: the entry point and what it takes between `w` and `eps_out`
             name, extra = ("bc_cfg_scheduler_step_noise", (P.variance_noise, nsteps)) if P.stochastic else \
                 ("bc_cfg_scheduler_step3", (nsteps,)) if P.third_order else ("bc_cfg_scheduler_step", ())
@@ -237,7 +266,7 @@ class BlobCtrlEngine:
 
         # ---- step I: UNet only (cond_scale == 0: BlobNet output is multiplied by 0, bn:936-938)
         P.step_inactive = rec.begin("step_inactive")
-        unet_i = TrunkPlan(rec, self.unet_w, self.unet_cfg, 2 * B, H, W)
+        unet_i = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_i.ctx_kv, unet_i.ctx_kvs, unet_i.ctx_folded = unet_a.ctx_kv, getattr(unet_a, "ctx_kvs", {}), getattr(unet_a, "ctx_folded", {})
         if not temb_per_step:
             unet_i.tproj, unet_i.tproj_table = unet_a.tproj, unet_a.tproj_table
@@ -251,13 +280,13 @@ class BlobCtrlEngine:
         return P
 
     def set_scheduler(self, kind, params=None):
-        """`kind` "unipc" | "ddim" | "dpmsolver" | "euler" | "euler_ancestral" | "heun"; `params` = (num_train_timesteps, beta_start,
+        """`kind` "unipc" | "ddim" | "dpmsolver" | "euler" | "euler_ancestral" | "heun" | "lcm"; `params` = (num_train_timesteps, beta_start,
         beta_end) of the scheduler's configuration (the drop-in scheduler objects accept non-default betas: the engine must tabulate the
         SAME alphas); for "dpmsolver" and the three sigma-space kinds a fourth entry holds the table's options as (key, value) pairs (the
         scheduler object's `table_params()`; missing = diffusers' defaults)."""
         if kind not in ("unipc", "ddim") + OPTION_KINDS:
-            raise NotImplementedError(f"scheduler {kind!r} has no coefficient table (UniPC, DDIM, DPM-Solver, Euler, Euler-ancestral and "
-                                      "Heun have)")
+            raise NotImplementedError(f"scheduler {kind!r} has no coefficient table (UniPC, DDIM, DPM-Solver, Euler, Euler-ancestral, "
+                                      "Heun and LCM have)")
         self.scheduler_kind = kind
         if params is not None:
             p = (int(params[0]), float(params[1]), float(params[2]))
@@ -274,9 +303,9 @@ class BlobCtrlEngine:
         if sched is None:
             nt, b0, b1 = self.scheduler_params[:3]
             has_options = self.scheduler_kind in OPTION_KINDS             # (none of these kinds has an eta: their tables take none)
-            if ts is not None and self.scheduler_kind not in ("dpmsolver", "euler"):
+            if ts is not None and self.scheduler_kind not in ("dpmsolver", "euler", "lcm"):
                 raise NotImplementedError(f"custom `timesteps` are not tabulated for {self.scheduler_kind}: pass num_inference_steps, or "
-                                          "use DPMSolverMultistepScheduler / EulerDiscreteScheduler")
+                                          "use DPMSolverMultistepScheduler / EulerDiscreteScheduler / LCMScheduler")
             opts = dict(self.scheduler_params[3]) if has_options and len(self.scheduler_params) > 3 else {}
             sched = table_class(self.scheduler_kind)(num_train_timesteps=nt, beta_start=b0, beta_end=b1, **opts)
             if ts is not None:
@@ -287,6 +316,17 @@ class BlobCtrlEngine:
                 sched.set_timesteps(n)
             self._sched_cache[key] = sched
         return sched
+
+    def _single_pass(self, single_pass, guidance_off):
+        """Whether an edit runs on a single-pass plan (the UNet once per request): the caller's `single_pass`, or by default exactly
+        when guidance is off and the scheduler is LCM or the UNet is a distilled one (time_cond_proj_dim) - every other call keeps the plan it
+        always had."""
+        if single_pass is None:
+            return bool(guidance_off and (self.scheduler_kind == "lcm" or self.unet_cfg.time_cond_proj_dim is not None))
+        if single_pass and not guidance_off:
+            raise ValueError("single_pass=True needs guidance off (guidance_scale <= 1 or do_classifier_free_guidance=False): "
+                             "classifier-free guidance reads two UNet outputs per sample")
+        return bool(single_pass)
 
     @staticmethod
     def _step_form(sched, stochastic):
@@ -306,11 +346,11 @@ class BlobCtrlEngine:
         return eta > 0
 
     @staticmethod
-    def variance_noise(num_steps, batch, h, w, generator=None, device="cuda"):
+    def variance_noise(num_steps, batch, h, w, generator=None, device="cuda", draws=None):
         """The per-step `variance_noise` of a stochastic DDIM edit, [num_steps, batch, 4, h, w] fp32: drawn as DDIMScheduler.step draws
         it (one randn_tensor per step, in step order; a CPU generator on the CPU, a list of generators one sample each, None = the global
-        RNG of `device`)."""
-        return draw_variance_noise(num_steps, (batch, 4, h, w), generator, device)
+        RNG of `device`).  `draws` (an LCM table's): the steps that draw at all - LCMScheduler's last step does not, its slice is zero."""
+        return draw_variance_noise(num_steps, (batch, 4, h, w), generator, device, draws)
 
     def set_weights(self, unet_w=None, blob_w=None):
         """New packed weights (LoRA loaded / unloaded, conv_in edited): every cached plan and its graphs hold the old addresses."""
@@ -417,7 +457,8 @@ class BlobCtrlEngine:
                  teacher_latents: Optional[List[torch.Tensor]] = None, fg_image: Optional[torch.Tensor] = None,
                  bg_image: Optional[torch.Tensor] = None, return_sample: bool = False, eta: float = 0.0,
                  do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
-                 variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None):
+                 variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None,
+                 single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -428,12 +469,20 @@ class BlobCtrlEngine:
         global RNG of the engine's device), or taken from `variance_noise` [num_inference_steps, B, 4, h, w].  It is drawn in fp32 (the
         engine keeps fp32 latents); a reference pipeline running in fp16 would draw fp16 noise.
         With an SDE-DPM-Solver++ scheduler (algorithm_type "sde-dpmsolver++") or the Euler-ancestral scheduler every step draws its noise
-        the same way, eta staying 0.
-        `timesteps` (DPM-Solver and Euler only): the caller's timestep schedule, as the reference's set_timesteps(timesteps=) takes it; the
+        the same way, eta staying 0.  The LCM scheduler draws for every step but the last (scheduling_lcm.py:578): the last slice of the
+        plan's `variance_noise` is zero, and the last slice of a caller-given `variance_noise` is ignored (its coefficient is 0).
+        `timesteps` (DPM-Solver, Euler and LCM only): the caller's timestep schedule, as the reference's set_timesteps(timesteps=) takes it; the
         edit then has len(timesteps) steps and `num_inference_steps` is not used.
         With a sigma-space scheduler (Euler, Euler-ancestral, Heun) the start latents are multiplied by the table's init_noise_sigma and
         the latents a callback / `teacher_latents` / `trace` see stay in the scheduler's sigma space, as in the reference; only what the
-        networks read is divided by sqrt(sigma^2 + 1).  Heun runs 2 * num_inference_steps - 1 network evaluations (`self.timesteps`)."""
+        networks read is divided by sqrt(sigma^2 + 1).  Heun runs 2 * num_inference_steps - 1 network evaluations (`self.timesteps`).
+        `single_pass`: with guidance off (guidance_scale <= 1 or do_classifier_free_guidance=False) the reference runs the UNet once per
+        request (pipe:1031).  True = do the same: a single-pass plan, the UNet at batch B on the positive prompts only.  False = the
+        duplicated plan (both CFG halves hold the positive prompt, effective scale 1).  None = single-pass exactly when guidance is off
+        and the scheduler is LCM or the UNet has time_cond_proj_dim; True with guidance on is an error.
+        `timestep_cond` [B, time_cond_proj_dim] (a UNet with time_embedding.cond_proj only): `get_guidance_scale_embedding(guidance_scale
+        - 1, dim)` of every sample (pipe:987-993); it is per-edit data of the plan, so another scale replays the same graph.  None: the
+        UNet runs without the add."""
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
@@ -462,20 +511,27 @@ class BlobCtrlEngine:
         # `do_classifier_free_guidance=False` (what the reference derives from guidance_scale <= 1) says explicitly that prompt_embeds
         # holds the positive prompts only; without the flag the layout is inferred from `latents` and refused when ambiguous.
         if do_classifier_free_guidance is None:
-            do_classifier_free_guidance = guidance_scale > 1.0
+            do_classifier_free_guidance = guidance_scale > 1.0 and self.unet_cfg.time_cond_proj_dim is None      # (pipe:497)
             if not do_classifier_free_guidance:
                 if latents is None:
                     raise ValueError("guidance_scale <= 1 without `latents`: pass do_classifier_free_guidance=False (prompt_embeds = "
                                      "positive prompts only) or =True (negative and positive halves) - the layout cannot be inferred")
                 do_classifier_free_guidance = prompt_embeds.shape[0] != latents.shape[0]
-        if not do_classifier_free_guidance:
+        guidance_off = guidance_scale <= 1.0 or not do_classifier_free_guidance
+        single = self._single_pass(single_pass, guidance_off)
+        if not do_classifier_free_guidance and not single:
             prompt_embeds = torch.cat([prompt_embeds, prompt_embeds], 0)
-        if guidance_scale <= 1.0 or not do_classifier_free_guidance:
+        if guidance_off:
             guidance_scale = 1.0
         B2, T, Dc = prompt_embeds.shape
-        if B2 % 2:
-            raise ValueError("prompt_embeds must hold the negative and positive halves (classifier-free guidance)")
-        B = B2 // 2
+        if single and not do_classifier_free_guidance:
+            B = B2                                                   # the positive prompts only, as the reference holds them
+        else:
+            if B2 % 2:
+                raise ValueError("prompt_embeds must hold the negative and positive halves (classifier-free guidance)")
+            B = B2 // 2
+            if single:
+                prompt_embeds = prompt_embeds[B:]                    # (both halves given, scale <= 1: eps is the positive half's)
         h, w = fg_image_latents.shape[-2:]
         n = num_inference_steps
         per_request = fg_image_latents.dim() == 4 and fg_image_latents.shape[0] > 1
@@ -495,23 +551,30 @@ class BlobCtrlEngine:
         sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
         n = len(sched.timesteps)                             # network evaluations (Heun: 2 * num_inference_steps - 1, pipe:1025 loops over them)
         stochastic, third_order = self._step_form(sched, stochastic)
+        if timestep_cond is not None:
+            dim = self.unet_cfg.time_cond_proj_dim
+            if dim is None:
+                raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
+            if tuple(timestep_cond.shape) != (B, dim):
+                raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
         if variance_noise is not None:
             if not stochastic:
-                raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++ or an Euler-ancestral scheduler")
+                raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++, an Euler-ancestral or an LCM "
+                                 "scheduler")
             if generator is not None:
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
                                  " `variance_noise` stays `None`.")
             if tuple(variance_noise.shape) != (n, B, 4, h, w):
                 raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (steps, batch, 4, h, w), got "
                                  f"{tuple(variance_noise.shape)}")
-        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order, sched.scales_input)
+        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order, sched.scales_input, single)
         dev = self.device
         self.timesteps = sched.timesteps
         if latents is None:                                                          # pipe:438-453
             g0 = generator[0] if isinstance(generator, list) else generator
             latents = randn_tensor((B, 4, h, w), generator, g0.device if g0 is not None else "cpu")
         if stochastic and variance_noise is None:            # scheduling_ddim.py:455-458 / dpmsolver_multistep.py:979-982, after the latents
-            variance_noise = self.variance_noise(n, B, h, w, generator, dev)
+            variance_noise = self.variance_noise(n, B, h, w, generator, dev, getattr(sched, "draws", None))
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         scale_rows = [[sc * k for sc in req_scales] for k in keep]                   # [step][image]
         scales = [max(abs(v) for v in row) for row in scale_rows]                    # a step is BlobNet-free iff every scale is 0
@@ -530,6 +593,11 @@ class BlobCtrlEngine:
                 if P.collapse:
                     P.feat16[:, : self.feat_dim].copy_(P.feat)
             P.ctx.copy_(prompt_embeds.to(dev, torch.float16))
+            if P.timestep_cond is not None:
+                P.timestep_cond.zero_()
+                if timestep_cond is not None:                # (both CFG halves of a sample take the sample's embedding)
+                    tc = timestep_cond.to(dev, torch.float16)
+                    P.timestep_cond[:, : tc.shape[1]].copy_(tc if P.single else torch.cat([tc, tc], 0))
             P.t_table.copy_(sched.timesteps.to(torch.float32))
             coef = sched.table().clone()
             coef[:, 11] = float(guidance_scale)          # read by the captured cfg/scheduler kernel
@@ -617,7 +685,8 @@ class BlobCtrlEngine:
         return self.denoise(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, **kw)
 
     def compile_plan(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale=7.5, blobnet_conditioning_scale=1.0,
-                     blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None, timesteps=None):
+                     blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None, timesteps=None,
+                     single_pass=None):
         """Write the launch plan of one edit configuration as a relocatable `.bcplan` file for the C plan runtime
         (include/blobctrl_hip.h: bc_plan_load / bc_plan_buffer / bc_step / bc_plan_capture_loop): segments "prologue",
         "step_active", "step_inactive"; packed weights and the scheduler / guidance tables stored with their contents; the per-edit
@@ -628,7 +697,12 @@ class BlobCtrlEngine:
         contents when given (else zero-filled: a C host fills it through bc_plan_buffer before each edit).  An SDE-DPM-Solver++ scheduler
         or the Euler-ancestral scheduler gives the same stochastic plan; a third-order DPM-Solver++ table ends its steps in
         bc_cfg_scheduler_step3; a sigma-space table (Euler, Euler-ancestral, Heun) assembles its inputs with the `_scaled` entry points.
-        `timesteps` (DPM-Solver and Euler only): the caller's schedule, n = len(timesteps).  Heun: 2 * num_inference_steps - 1 steps."""
+        `timesteps` (DPM-Solver, Euler and LCM only): the caller's schedule, n = len(timesteps).  Heun: 2 * num_inference_steps - 1 steps.
+        `single_pass` as in `denoise` (guidance is off for guidance_scale <= 1, and always for a UNet with time_cond_proj_dim): a
+        single-pass plan's `ctx` is [B][T][ctx_dim], the positive prompts, and its steps end in bc_scheduler_step_single.  A UNet with
+        time_cond_proj_dim adds the named buffer `timestep_cond` (fp16 [B or 2B][pad8(dim)], zero-filled: the host writes the
+        guidance-scale embedding of every UNet image into it before an edit)."""
+        single = self._single_pass(single_pass, guidance_scale <= 1.0 or self.unet_cfg.time_cond_proj_dim is not None)   # (pipe:497)
         n = num_inference_steps if timesteps is None else len(timesteps)
         stochastic = self._check_eta(float(eta))
         sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
@@ -636,7 +710,7 @@ class BlobCtrlEngine:
         stochastic, third_order = self._step_form(sched, stochastic)
         if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
             raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
-        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order, sched.scales_input)
+        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order, sched.scales_input, single)
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         P.t_table.copy_(sched.timesteps.to(torch.float32))
         coef = sched.table().clone()
@@ -657,8 +731,8 @@ class BlobCtrlEngine:
         return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
 
     # convenience for bench / tests ------------------------------------------------------------------
-    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled)
+    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single)
 
 
 # ======================================================================================================================
@@ -684,7 +758,7 @@ class StableDiffusionBlobNetPipeline:
     Components (pipe:206-243): `vae` = blobctrl_amd.vae.AutoencoderKL, `unet` / `blobnet` = blobctrl_amd.modules shells (any LoRA is
     merged when the UNet is packed), `tokenizer` = any callable with the CLIPTokenizer call contract (host side), `text_encoder` =
     blobctrl_amd.clip_text.CLIPTextModel, `scheduler` = blobctrl_amd.schedulers.UniPCMultistepScheduler | DDIMScheduler | DPMSolverMultistepScheduler | EulerDiscreteScheduler |
-    EulerAncestralDiscreteScheduler | HeunDiscreteScheduler,
+    EulerAncestralDiscreteScheduler | HeunDiscreteScheduler | LCMScheduler,
     `dinov2_processor` = image_processor.Dinov2ImageProcessor (or the HF processor), `dinov2` = blobctrl_amd.dinov2.Dinov2Model.
     The denoise loop itself is the captured-plan engine (BlobCtrlEngine): the module shells are not called per step."""
 
@@ -698,7 +772,8 @@ class StableDiffusionBlobNetPipeline:
             raise NotImplementedError("the reference disables the safety checker (pipe:1133-1135); pass safety_checker=None")
         if not isinstance(scheduler, TableScheduler):
             raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler, "
-                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler or HeunDiscreteScheduler")
+                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, HeunDiscreteScheduler "
+                            "or LCMScheduler")
         self.vae, self.unet, self.blobnet, self.tokenizer, self.text_encoder = vae, unet, blobnet, tokenizer, text_encoder
         self.dinov2, self.dinov2_processor = dinov2, dinov2_processor if dinov2_processor is not None else Dinov2ImageProcessor()
         self.safety_checker = None
@@ -790,7 +865,8 @@ class StableDiffusionBlobNetPipeline:
         from .schedulers import TableScheduler
         if not isinstance(s, TableScheduler):
             raise TypeError("scheduler must be blobctrl_amd.schedulers.UniPCMultistepScheduler, DDIMScheduler, "
-                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler or HeunDiscreteScheduler")
+                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, HeunDiscreteScheduler "
+                            "or LCMScheduler")
         self._scheduler = s
 
     def to(self, *a, **k):
@@ -990,7 +1066,7 @@ class StableDiffusionBlobNetPipeline:
             raise NotImplementedError("`callback` is deprecated in the reference (pipe:868-875): use callback_on_step_end")
         if kwargs:
             raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")
-        if timesteps is not None and getattr(self._scheduler, "kind", None) not in ("dpmsolver", "euler"):
+        if timesteps is not None and getattr(self._scheduler, "kind", None) not in ("dpmsolver", "euler", "lcm"):
             # the reference's retrieve_timesteps (pipe:142-148) honours them only for schedulers whose set_timesteps takes them
             raise NotImplementedError("custom `timesteps` are not tabulated; pass num_inference_steps")
         if cross_attention_kwargs:
@@ -1038,6 +1114,11 @@ class StableDiffusionBlobNetPipeline:
         # 9. DINOv2 feature of the foreground (pipe:982)
         dino = self.encode_image_dinov2(fg_image)
         # 12. loop (pipe:1025-1123) on the captured plans
+        # 6.5 the guidance-scale embedding of a UNet with time_cond_proj_dim (pipe:987-993)
+        timestep_cond = None
+        if self.unet.config.time_cond_proj_dim is not None:
+            w = torch.full((batch_size * num_images_per_prompt,), self.guidance_scale - 1, dtype=torch.float32)
+            timestep_cond = get_guidance_scale_embedding(w, self.unet.config.time_cond_proj_dim)
         cb = None
         if callback_on_step_end is not None:
             def cb(_engine, i, t, kw):
@@ -1049,7 +1130,7 @@ class StableDiffusionBlobNetPipeline:
                                     blobnet_control_guidance_start=blobnet_control_guidance_start[0],
                                     blobnet_control_guidance_end=blobnet_control_guidance_end[0], output_type="latent",
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
-                                    generator=generator, timesteps=timesteps)
+                                    generator=generator, timesteps=timesteps, timestep_cond=timestep_cond)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

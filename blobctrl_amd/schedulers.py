@@ -23,6 +23,9 @@ DPM-Solver++ (scheduling_dpmsolver_multistep.py) fills c0 / c1 (x0), c7 (x), c8 
 The sigma-space (k-diffusion) schedulers work on x = x0 + sigma * eps: an Euler step x' = x + (sigma_next - sigma) * eps is c0 = 1,
 c1 = sigma, c7 = 1, c10 = sigma_next - sigma; Euler-ancestral steps down to sigma_down and adds c12 = sigma_up times the step's noise; Heun's
 second stage reads the first stage's x (`last`) and x0 (`m0`) through the corrector columns c2 - c4.
+LCMScheduler (scheduling_lcm.py:498-592) is linear too: denoised = c_out * x0 + c_skip * x, x' = sqrt(abar_prev) * denoised +
+sqrt(1 - abar_prev) * noise, i.e. c0 = 1/sqrt(abar_t), c1 = sqrt(1 - abar_t)/sqrt(abar_t), c7 = sqrt(abar_prev) * c_skip,
+c8 = sqrt(abar_prev) * c_out, c12 = sqrt(1 - abar_prev); the last step returns `denoised` itself: c7 = c_skip, c8 = c_out, c12 = 0.
 
 SD-1.5 scheduler config: betas 0.00085 -> 0.012 scaled_linear, 1000 train steps, steps_offset 1,
 epsilon prediction; UniPC: solver_order 2, bh2, predict_x0, lower_order_final, linspace spacing, final sigma 0;
@@ -564,15 +567,109 @@ class HeunTable(_SigmaTable):
         return self
 
 
+# ---- LCMScheduler (latent-consistency models: LCM-LoRA or a distilled LCM UNet, 1-8 steps) ----------------------------------------------
+# the options a table depends on (the engine keys its tables and plans on them), with the reference's defaults (scheduling_lcm.py:196-215)
+LCM_OPTIONS = dict(original_inference_steps=50, timestep_scaling=10.0, set_alpha_to_one=True)
+
+
+class LCMTable(_Base):
+    """LCMScheduler as a coefficient table (scheduling_lcm.py:349-488 the skipping timestep schedule, 490-496 the boundary-condition
+    scalings, 498-592 the step).  Every step but the last adds sqrt(1 - abar_prev) times the step's noise (column 12), so the steps end in
+    bc_cfg_scheduler_step_noise; the last step's row has c12 = 0 and its noise slice is never drawn (`draws`).  On the last step the
+    reference takes prev_timestep = timestep, so `final_alpha_cumprod` (set_alpha_to_one) is never read: the option is kept for the key
+    only.  Caller `timesteps` and `strength` are taken as the reference takes them."""
+    sde = True                                                            # a noise term in the steps (the engine's stochastic plan)
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, **options):
+        super().__init__(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end)
+        unknown = set(options) - set(LCM_OPTIONS)
+        if unknown:
+            raise TypeError(f"unknown LCMTable option(s) {sorted(unknown)}")
+        self.options = dict(LCM_OPTIONS, **options)
+        self.num_inference_steps = None
+        self.draws = None
+
+    def set_timesteps(self, num_inference_steps=None, device=None, original_inference_steps=None, timesteps=None, strength=1.0):
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `custom_timesteps`.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
+        original_steps = original_inference_steps if original_inference_steps is not None else self.options["original_inference_steps"]
+        if original_steps > self.num_train:
+            raise ValueError(f"`original_steps`: {original_steps} cannot be larger than `self.config.train_timesteps`: {self.num_train} as "
+                             f"the unet model trained with this scheduler can only handle maximal {self.num_train} timesteps.")
+        k = self.num_train // original_steps                              # the skipping step of the distillation schedule
+        origin = np.asarray(list(range(1, int(original_steps * strength) + 1))) * k - 1
+        if timesteps is not None:
+            timesteps = [int(t) for t in timesteps]
+            for i in range(1, len(timesteps)):
+                if timesteps[i] >= timesteps[i - 1]:
+                    raise ValueError("`custom_timesteps` must be in descending order.")
+            if timesteps[0] >= self.num_train:
+                raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {self.num_train}.")
+            ts = np.array(timesteps, dtype=np.int64)
+            self.num_inference_steps = len(ts)
+            init_timestep = min(int(self.num_inference_steps * strength), self.num_inference_steps)
+            # the reference leaves num_inference_steps at the FULL length here (its TODO at :452), so with strength < 1 no step index
+            # ever reaches num_inference_steps - 1: the last row then draws noise too and, with prev_t = t, re-noises to its own level
+            ts = ts[max(self.num_inference_steps - init_timestep, 0):]
+        else:
+            n = num_inference_steps
+            if n > self.num_train:
+                raise ValueError(f"`num_inference_steps`: {n} cannot be larger than `self.config.train_timesteps`: {self.num_train} as "
+                                 f"the unet model trained with this scheduler can only handle maximal {self.num_train} timesteps.")
+            skipping_step = len(origin) // n
+            if skipping_step < 1:
+                raise ValueError(f"The combination of `original_steps x strength`: {original_steps} x {strength} is smaller than "
+                                 f"`num_inference_steps`: {n}. Make sure to either reduce `num_inference_steps` to a value smaller than "
+                                 f"{int(original_steps * strength)} or increase `strength` to a value higher than "
+                                 f"{float(n / original_steps)}.")
+            self.num_inference_steps = n
+            if n > original_steps:
+                raise ValueError(f"`num_inference_steps`: {n} cannot be larger than `original_inference_steps`: {original_steps} because "
+                                 "the final timestep schedule will be a subset of the `original_inference_steps`-sized initial timestep "
+                                 "schedule.")
+            origin = origin[::-1].copy()
+            idx = np.floor(np.linspace(0, len(origin), num=n, endpoint=False)).astype(np.int64)
+            ts = origin[idx]
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.int64)
+        self.coef = self._build()
+        return self
+
+    def _build(self):
+        ts, ac = self.timesteps, self.alphas_cumprod
+        N = len(ts)
+        coef = torch.zeros(N, 16, dtype=torch.float32)
+        self.c_skip, self.c_out, self.draws = [], [], []
+        for i in range(N):
+            t = ts[i]
+            prev_t = ts[i + 1] if i + 1 < N else t                         # :535-539
+            a_t, a_prev = ac[t], ac[prev_t]
+            scaled_t = t * self.options["timestep_scaling"]                # :490-496, sigma_data = 0.5
+            c_skip = 0.5 ** 2 / (scaled_t ** 2 + 0.5 ** 2)
+            c_out = scaled_t / (scaled_t ** 2 + 0.5 ** 2) ** 0.5
+            coef[i, 0] = 1.0 / a_t.sqrt()
+            coef[i, 1] = (1 - a_t).sqrt() / a_t.sqrt()
+            noisy = i != self.num_inference_steps - 1                      # :578
+            coef[i, 7] = a_prev.sqrt() * c_skip if noisy else c_skip
+            coef[i, 8] = a_prev.sqrt() * c_out if noisy else c_out
+            coef[i, 12] = (1 - a_prev).sqrt() if noisy else 0.0
+            self.c_skip.append(float(c_skip))
+            self.c_out.append(float(c_out))
+            self.draws.append(bool(noisy))
+        assert torch.isfinite(coef).all(), "non-finite LCM coefficient"
+        return coef
+
+
 # scheduler kinds whose table takes options as a fourth `table_params()` entry
-OPTION_KINDS = ("dpmsolver", "euler", "euler_ancestral", "heun")
+OPTION_KINDS = ("dpmsolver", "euler", "euler_ancestral", "heun", "lcm")
 
 
 def table_class(kind):
     """Scheduler kind -> its coefficient table class, for the drop-in schedulers and the engine alike ("unipc", "dpmsolver", "euler",
-    "euler_ancestral", "heun"; every other kind tabulates DDIM)."""
+    "euler_ancestral", "heun", "lcm"; every other kind tabulates DDIM)."""
     return {"unipc": UniPCTable, "dpmsolver": DPMSolverMultistepTable, "euler": EulerDiscreteTable,
-            "euler_ancestral": EulerAncestralTable, "heun": HeunTable}.get(kind, DDIMTable)
+            "euler_ancestral": EulerAncestralTable, "heun": HeunTable, "lcm": LCMTable}.get(kind, DDIMTable)
 
 
 def apply_table_step(coef_row, eps, x, hist, noise=None):
@@ -614,10 +711,16 @@ def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):
     return torch.randn(tuple(shape), generator=generator, device=rand_device, dtype=dtype).to(device)
 
 
-def draw_variance_noise(num_steps, shape, generator=None, device=None):
+def draw_variance_noise(num_steps, shape, generator=None, device=None, draws=None):
     """The `variance_noise` of every step of a stochastic DDIM edit, [num_steps, *shape] fp32 on `device`: one `randn_tensor(shape,
-    generator, device)` per step, in step order - the draws `DDIMScheduler.step` makes (scheduling_ddim.py:455-458)."""
-    return torch.stack([randn_tensor(shape, generator, device) for _ in range(num_steps)], 0)
+    generator, device)` per step, in step order - the draws `DDIMScheduler.step` makes (scheduling_ddim.py:455-458).
+    `draws` (one bool per step, an LCM table's): a step that draws nothing (LCMScheduler's last, scheduling_lcm.py:578) gets a zero
+    slice and leaves the generator where it is."""
+    if draws is None:
+        return torch.stack([randn_tensor(shape, generator, device) for _ in range(num_steps)], 0)
+    assert len(draws) == num_steps
+    return torch.stack([randn_tensor(shape, generator, device) if d else torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+                        for d in draws], 0)
 
 
 class TableScheduler:
@@ -748,7 +851,7 @@ class PNDMScheduler(_ConfiguredScheduler):
 
 def scheduler_from_config_dir(path):
     """`<model>/scheduler/scheduler_config.json` -> the scheduler object its `_class_name` names (PNDM / UniPC / DDIM / DPM-Solver /
-    Euler / Euler-ancestral / Heun)."""
+    Euler / Euler-ancestral / Heun / LCM)."""
     import json
     import os
     with open(os.path.join(path, "scheduler_config.json")) as f:
@@ -756,10 +859,11 @@ def scheduler_from_config_dir(path):
     name = cfg.get("_class_name", "PNDMScheduler")
     classes = {"PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler, "DDIMScheduler": DDIMScheduler,
                "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler, "EulerDiscreteScheduler": EulerDiscreteScheduler,
-               "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler, "HeunDiscreteScheduler": HeunDiscreteScheduler}
+               "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler, "HeunDiscreteScheduler": HeunDiscreteScheduler,
+               "LCMScheduler": LCMScheduler}
     if name not in classes:
         raise NotImplementedError(f"scheduler class {name} is not available (PNDM config holder, UniPC, DDIM, DPM-Solver, Euler, "
-                                  "Euler-ancestral and Heun are)")
+                                  "Euler-ancestral and Heun are, and LCM)")
     return classes[name](**classes[name]._known(cfg))
 
 
@@ -907,10 +1011,9 @@ class DPMSolverMultistepScheduler(_ConfiguredScheduler):
         return _StepOutput(out) if return_dict else (out,)
 
 
-class _SigmaScheduler(_ConfiguredScheduler):
-    """What the drop-ins for the sigma-space schedulers share: the reference's `__init__` keys in `.config`, `from_config` with hidden
-    entries, the table built from `_options`, `sigmas` / `init_noise_sigma` of the table, and `scale_model_input` dividing by
-    sqrt(sigma^2 + 1) of the current step (TableScheduler)."""
+class _OptionScheduler(_ConfiguredScheduler):
+    """What the drop-ins whose table takes options share: the reference's `__init__` keys in `.config`, `from_config` with hidden
+    entries, the table built from `_options`, and the step on the current row."""
     _options = {}
 
     def __init__(self, **kw):
@@ -944,16 +1047,8 @@ class _SigmaScheduler(_ConfiguredScheduler):
         return self.table_impl.order
 
     @property
-    def sigmas(self):
-        return self.table_impl.sigmas
-
-    @property
     def num_inference_steps(self):
         return self.table_impl.num_inference_steps
-
-    @property
-    def init_noise_sigma(self):
-        return self.table_impl.init_noise_sigma
 
     def set_timesteps(self, num_inference_steps, device=None):
         self._set_timesteps(device, num_inference_steps)
@@ -963,6 +1058,19 @@ class _SigmaScheduler(_ConfiguredScheduler):
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         out = self._apply_row(model_output, sample.to(torch.float32), noise).to(model_output.dtype)
         return _StepOutput(out) if return_dict else (out,)
+
+
+class _SigmaScheduler(_OptionScheduler):
+    """The drop-ins for the sigma-space schedulers: `sigmas` / `init_noise_sigma` of the table, and `scale_model_input` dividing by
+    sqrt(sigma^2 + 1) of the current step (TableScheduler)."""
+
+    @property
+    def sigmas(self):
+        return self.table_impl.sigmas
+
+    @property
+    def init_noise_sigma(self):
+        return self.table_impl.init_noise_sigma
 
 
 class EulerDiscreteScheduler(_SigmaScheduler):
@@ -1038,3 +1146,61 @@ class HeunDiscreteScheduler(_SigmaScheduler):
 
     def step(self, model_output, timestep, sample, return_dict=True):
         return self._step(model_output, sample, None, return_dict)
+
+
+class LCMScheduler(_OptionScheduler):
+    """Drop-in for diffusers' LCMScheduler (latent-consistency sampling in 1-8 steps, `LCMScheduler.from_config(pipeline.scheduler.config)`
+    with LCM-LoRA merged or a distilled LCM UNet).  Tabulated for epsilon prediction on scaled_linear betas: `original_inference_steps`
+    (config or `set_timesteps` argument), `timestep_scaling`, caller `timesteps` and `strength`; thresholding and clipping of x0 are not.
+    `step(..., generator=)` draws the noise of every step but the last as :578-582 does and returns `(prev_sample, denoised)`;
+    `variance_noise=` gives the noise instead, as this package's other stochastic steps take it."""
+    _kind = "lcm"
+    _options = LCM_OPTIONS
+    _defaults = dict(trained_betas=None, clip_sample=False, clip_sample_range=1.0, steps_offset=0, thresholding=False,
+                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0, timestep_spacing="leading", rescale_betas_zero_snr=False,
+                     **LCM_OPTIONS)
+
+    def _check(self, cfg):
+        if cfg["thresholding"]:
+            raise NotImplementedError("thresholding=True (dynamic thresholding of x0) is not tabulated")
+        if cfg["clip_sample"]:
+            raise NotImplementedError("clip_sample=True (clipping of x0) is not tabulated")
+        if cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("rescale_betas_zero_snr=True is not tabulated")
+
+    def set_timesteps(self, num_inference_steps=None, device=None, original_inference_steps=None, timesteps=None, strength=1.0):
+        self._set_timesteps(device, num_inference_steps, original_inference_steps=original_inference_steps, timesteps=timesteps,
+                            strength=strength)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None):
+        tab = self.table_impl
+        if tab.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if variance_noise is not None and generator is not None:
+            raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                             " `variance_noise` stays `None`.")
+        i = self._i
+        noise = None
+        if tab.draws[i]:
+            noise = variance_noise.to(device=model_output.device, dtype=torch.float32) if variance_noise is not None else \
+                randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        x = sample.to(torch.float32)
+        denoised = tab.c_out[i] * (x * float(tab.coef[i, 0]) - model_output * float(tab.coef[i, 1])) + tab.c_skip[i] * x
+        prev = self._apply_row(model_output, x, noise).to(model_output.dtype)
+        denoised = denoised.to(model_output.dtype)
+        return _LCMStepOutput(prev, denoised) if return_dict else (prev, denoised)
+
+
+class _LCMStepOutput(tuple):
+    """`LCMSchedulerOutput`-like: `.prev_sample`, `.denoised`, and indexable like the tuple form."""
+
+    def __new__(cls, prev_sample, denoised):
+        return super().__new__(cls, (prev_sample, denoised))
+
+    @property
+    def prev_sample(self):
+        return self[0]
+
+    @property
+    def denoised(self):
+        return self[1]

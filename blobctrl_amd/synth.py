@@ -63,15 +63,18 @@ def _transformer(shapes, p, c, ctx_dim):
 
 def trunk_param_shapes(in_channels: int, block_out_channels: Tuple[int, ...], layers_per_block: int,
                        cross_attention_dim: Optional[int], out_channels: Optional[int],
-                       blobnet: bool) -> "OrderedDict[str, tuple]":
+                       blobnet: bool, time_cond_proj_dim: Optional[int] = None) -> "OrderedDict[str, tuple]":
     """Parameter names/shapes of the SD-1.5-topology trunk.  `blobnet=True` drops conv_norm_out/conv_out and
-    attn2/norm2 (cross_attention_dim=None) and appends the 12 + 1 + 15 zero-convs (bn:336-349, 383-399, 480-491)."""
+    attn2/norm2 (cross_attention_dim=None) and appends the 12 + 1 + 15 zero-convs (bn:336-349, 383-399, 480-491).
+    `time_cond_proj_dim` (a distilled LCM UNet): adds time_embedding.cond_proj.weight, no bias (embeddings.py:559)."""
     s: "OrderedDict[str, tuple]" = OrderedDict()
     boc = tuple(block_out_channels)
     nb = len(boc)
     temb = boc[0] * 4
     s["conv_in.weight"] = (boc[0], in_channels, 3, 3)
     s["conv_in.bias"] = (boc[0],)
+    if time_cond_proj_dim is not None:
+        s["time_embedding.cond_proj.weight"] = (boc[0], time_cond_proj_dim)
     s["time_embedding.linear_1.weight"] = (temb, boc[0])
     s["time_embedding.linear_1.bias"] = (temb,)
     s["time_embedding.linear_2.weight"] = (temb, temb)

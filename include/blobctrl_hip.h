@@ -354,6 +354,14 @@ int bc_timestep_embedding(const float* t_table, const int* t_idx, float t_value,
 /* The same for EVERY step of an edit at once: out [nsteps * rows_per_step][dim], row r uses t_table[r / rows_per_step].  With
  * BcGemm.rowvec_idx the whole time-embedding path (embeddings.py:27-78, 576-588, resnet.py:343-350) then runs once per edit. */
 int bc_timestep_embedding_table(const float* t_table, int nsteps, int rows_per_step, int dim, bc_half* out, bc_stream stream);
+/* The two entry points above for a UNet with `time_cond_proj_dim` (a distilled LCM UNet: embeddings.py:559, 578
+ * `sample = sample + cond_proj(condition)` in front of linear_1).  cond fp32 [rows][dim] (per-step form) / [rows_per_step][dim] (table
+ * form: row r of the output takes cond row r % rows_per_step) = cond_proj(timestep_cond), is added to the sinusoid; sinusoid and sum
+ * are formed in fp64 and rounded to fp16 once. */
+int bc_timestep_embedding_cond(const float* t_table, const int* t_idx, float t_value, int rows, int dim, const float* cond,
+                               bc_half* out, bc_stream stream);
+int bc_timestep_embedding_table_cond(const float* t_table, int nsteps, int rows_per_step, int dim, const float* cond, bc_half* out,
+                                     bc_stream stream);
 
 /* SiLU elementwise on fp16 (resnet.py:345 nonlinearity(temb)). */
 int bc_silu(const bc_half* x, bc_half* y, long long n, bc_stream stream);
@@ -387,6 +395,13 @@ int bc_cfg_scheduler_step_noise(const float* eps, float* latents, const float* c
  * The other arguments are those of bc_cfg_scheduler_step. */
 int bc_cfg_scheduler_step3(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
                            float guidance_scale, int B, int h, int w, int nsteps, float* eps_out, int advance, bc_stream stream);
+/* The step of a guidance-free (single-pass) plan (pipe:1031, 1095 with do_classifier_free_guidance False: the UNet ran once per request
+ * at batch B).  eps fp32 token-major [B][h][2w][4]: e = the right half of image b as it is - no second read, no guidance arithmetic,
+ * column 11 is not read.  The scheduler row is applied as in bc_cfg_scheduler_step; noise != NULL (fp32 [nsteps][B][4][h][w]) adds
+ * coef[12] * noise[step] as bc_cfg_scheduler_step_noise does, third != 0 adds coef[13] * x0_{i-2} as bc_cfg_scheduler_step3 does.
+ * A step index outside [0, nsteps) leaves every buffer as it is.  eps_out (optional) receives e. */
+int bc_scheduler_step_single(const float* eps, float* latents, const float* coef, int* step_idx, float* hist, int B, int h, int w,
+                             const float* noise, int nsteps, int third, float* eps_out, int advance, bc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Row-chain: everything of a Transformer2D block that acts on token rows independently, as ONE launch per attention
@@ -515,7 +530,8 @@ enum { BC_OP_GEMM = 0, BC_OP_GN_STATS = 1, BC_OP_GN_FINALIZE = 2, BC_OP_GN_APPLY
        BC_OP_GAUSSIAN_SAMPLE = 19, BC_OP_SIGNAL = 20 /* arg: event id */, BC_OP_WAIT = 21 /* arg: event id */, BC_OP_ROWCHAIN = 22, BC_OP_ASSEMBLE_IM2COL = 23,
        BC_OP_MEMSET_ZERO = 24, BC_OP_ROWCHAIN_MIDX = 25, BC_OP_ROWCHAIN_PACK_KV = 26, BC_OP_ROWCHAIN_SUM = 27, BC_OP_CTX_FOLD = 28, BC_OP_DUP_HALVES = 29,
        BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_CFG_SCHEDULER_STEP3 = 31, BC_OP_ASSEMBLE_INPUT_SCALED = 32,
-       BC_OP_ASSEMBLE_IM2COL_SCALED = 33, BC_OP_COUNT = 34 };
+       BC_OP_ASSEMBLE_IM2COL_SCALED = 33, BC_OP_SCHEDULER_STEP_SINGLE = 34, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND = 35,
+       BC_OP_TIMESTEP_EMBEDDING_COND = 36, BC_OP_COUNT = 37 };
 typedef struct BcPlanBuffer {
     const char* name;        /* "" for anonymous workspace; named buffers are found again with bc_plan_buffer */
     const void* address;     /* the address the launch records were built against */

@@ -53,17 +53,20 @@ SD_SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear
                 steps_offset=1)
 
 
-def build_tiny():
+def build_tiny(time_cond_proj_dim=None):
+    """`time_cond_proj_dim`: the UNet of a distilled LCM model (time_embedding.cond_proj over the guidance-scale embedding)."""
     c = TINY
     unet = UNet2DConditionModel(in_channels=5, out_channels=4, block_out_channels=c["boc"], norm_num_groups=c["groups"],
-                                attention_head_dim=c["heads"], cross_attention_dim=c["ctx"], layers_per_block=2)
+                                attention_head_dim=c["heads"], cross_attention_dim=c["ctx"], layers_per_block=2,
+                                time_cond_proj_dim=time_cond_proj_dim)
     # NB: the reference script leaves unet.config.in_channels = 4 (inf:233-249); only conv_in has 5 inputs.
     blob = BlobNetModel(in_channels=4, conditioning_channels=1 + c["feat"], block_out_channels=c["boc"],
                         norm_num_groups=c["groups"], attention_head_dim=c["heads"], cross_attention_dim=None,
                         layers_per_block=2)
-    us = synth.trunk_param_shapes(5, c["boc"], 2, c["ctx"], 4, blobnet=False)
+    us = synth.trunk_param_shapes(5, c["boc"], 2, c["ctx"], 4, blobnet=False, time_cond_proj_dim=time_cond_proj_dim)
     bs = synth.trunk_param_shapes(4 + 1 + c["feat"], c["boc"], 2, None, None, blobnet=True)
     assert set(us.keys()) == set(unet.state_dict().keys()), "UNet schema mismatch"
+    assert all(tuple(v.shape) == tuple(us[k]) for k, v in unet.state_dict().items()), "UNet shape mismatch"
     assert set(bs.keys()) == set(blob.state_dict().keys()), "BlobNet schema mismatch"
     unet.load_state_dict(synth.synth_state_dict(us, c["seed"]), strict=True)
     blob.load_state_dict(synth.synth_state_dict(bs, c["seed"] + 1), strict=True)
@@ -805,6 +808,268 @@ def golden_pipeline_call_euler():
           f"{out['eulera_timesteps']}: std {out['eulera_latents'].std():.4f}, noise {out['eulera_noise'].shape}")
 
 
+# ------------------------------------------------------------------------------------------------ LCM (few-step latent-consistency edits)
+LCM_MODULE = "diffusers.schedulers.scheduling_lcm"
+LCM_CUSTOM_TS = [939, 601, 320, 19]
+# cases of schedulers_lcm.npz: name -> (LCMScheduler options on top of SD_SCHED, set_timesteps keyword arguments)
+LCM_CASES = {
+    "lcm_1": (dict(), dict(num_inference_steps=1)),
+    "lcm_2": (dict(), dict(num_inference_steps=2)),
+    "lcm_4": (dict(), dict(num_inference_steps=4)),
+    "lcm_8": (dict(), dict(num_inference_steps=8)),
+    "lcm_50": (dict(), dict(num_inference_steps=50)),
+    "lcm_orig30_6": (dict(original_inference_steps=30), dict(num_inference_steps=6)),
+    "lcm_orig30_arg_6": (dict(), dict(num_inference_steps=6, original_inference_steps=30)),
+    "lcm_scaling5_4": (dict(timestep_scaling=5.0), dict(num_inference_steps=4)),
+    "lcm_custom_4": (dict(), dict(timesteps=LCM_CUSTOM_TS)),
+    "lcm_strength_3": (dict(), dict(num_inference_steps=3, strength=0.5)),
+    # caller timesteps cut by strength: the class keeps num_inference_steps = 4, so the last of the two steps draws noise as well
+    "lcm_custom_strength_2": (dict(), dict(timesteps=LCM_CUSTOM_TS, strength=0.5)),
+}
+
+
+def golden_schedulers_lcm():
+    """LCMScheduler (scheduling_lcm.py) on golden_schedulers' inputs (8x8 latents x = g(21), eps_i = g(100 + i)), the noise GIVEN as
+    g(200 + i): timesteps, the trajectories and the `denoised` outputs of LCM_CASES, the number of noise tensors each run asked for, plus
+    one run that draws from a CPU generator.  The `.config` of `from_config(<SD-1.5 scheduler_config.json>)` goes to lcm_config.json."""
+    from diffusers import LCMScheduler, PNDMScheduler
+    out = {}
+
+    def run(sch, set_kw, step_kw):
+        sch.set_timesteps(**set_kw)
+        x = g(21, 1, 4, 8, 8) * sch.init_noise_sigma
+        xs, den = [x.numpy()], []
+        for i, t in enumerate(sch.timesteps):
+            x, d = sch.step(g(100 + i, 1, 4, 8, 8), t, x, return_dict=False, **step_kw)
+            xs.append(x.numpy())
+            den.append(d.numpy())
+        return np.stack(xs), np.stack(den)
+
+    for name, (kw, set_kw) in LCM_CASES.items():
+        sch = LCMScheduler(**SD_SCHED, set_alpha_to_one=False, **kw)
+        noises = [g(200 + i, 1, 4, 8, 8) for i in range(200)]
+        with _GiveNoise(LCM_MODULE, noises) as give:
+            out[f"{name}_traj"], out[f"{name}_denoised"] = run(sch, set_kw, {})
+        out[f"{name}_timesteps"] = sch.timesteps.numpy()
+        out[f"{name}_draws"] = np.array(200 - len(give.noises))
+        out[f"{name}_kw"] = np.array(json.dumps(dict(options=kw, set_timesteps=set_kw)))
+        assert int(out[f"{name}_draws"]) == len(sch.timesteps) - (0 if name == "lcm_custom_strength_2" else 1), name
+    sch = LCMScheduler(**SD_SCHED, set_alpha_to_one=False)
+    with _TapNoise(LCM_MODULE) as tap:
+        out["lcm_gen77_4_traj"], out["lcm_gen77_4_denoised"] = run(sch, dict(num_inference_steps=4),
+                                                                   dict(generator=torch.Generator().manual_seed(77)))
+    out["lcm_gen77_4_timesteps"] = sch.timesteps.numpy()
+    out["lcm_gen77_4_noise"] = torch.stack(tap.drawn).numpy()
+    assert len(tap.drawn) == 3
+    np.savez_compressed(os.path.join(OUT, "schedulers_lcm.npz"), **out)
+    cfg = dict(LCMScheduler.from_config(SD15_SCHEDULER_JSON).config)
+    via_pndm = dict(LCMScheduler.from_config(PNDMScheduler.from_config(SD15_SCHEDULER_JSON).config).config)
+    via_ddim = dict(LCMScheduler.from_config(DDIMScheduler.from_config(SD15_SCHEDULER_JSON).config).config)
+    for c in (cfg, via_pndm, via_ddim):
+        c["_use_default_values"] = sorted(c["_use_default_values"])
+    assert cfg == via_pndm, (cfg, via_pndm)
+    for k in ("original_inference_steps", "timestep_scaling", "timestep_spacing", "steps_offset", "set_alpha_to_one", "clip_sample"):
+        assert cfg[k] == via_ddim[k], k
+    with open(os.path.join(OUT, "lcm_config.json"), "w") as f:
+        json.dump(dict(lcm=cfg, source=SD15_SCHEDULER_JSON), f, indent=1, sort_keys=True)
+    print("schedulers_lcm:", len(LCM_CASES), "cases; config", cfg)
+
+
+# cases of loop_tiny_lcm.npz: tag -> (scheduler class key, set_timesteps keyword arguments, guidance scale, BlobNet window, generator seed)
+LCM_LOOPS = {
+    "lcm_cfg_4": ("lcm", dict(num_inference_steps=4), 7.5, (0.0, 1.0), 1234),
+    "lcm_nocfg_4": ("lcm", dict(num_inference_steps=4), 1.0, (0.0, 0.5), 1234),
+    "ddim_single_5": ("ddim", dict(num_inference_steps=5), 1.0, (0.0, 1.0), None),
+    "unipc_single_5": ("unipc", dict(num_inference_steps=5), 1.0, (0.0, 0.6), None),
+    # the UNet of a distilled LCM model (time_cond_proj_dim = 8): guidance 7.5 goes in as timestep_cond, no CFG (pipe:497)
+    "lcm_wcond_4": ("lcm", dict(num_inference_steps=4), 7.5, (0.0, 0.5), 1234),
+    "lcm_wcond_custom_3": ("lcm", dict(timesteps=[939, 601, 19]), 3.0, (0.0, 1.0), 4321),
+}
+LCM_WCOND_DIM = 8
+
+
+def golden_loop_lcm(dtype=torch.float32, save=True, given_noise=None):
+    """golden_loop's body (tiny nets) under LCMScheduler with classifier-free guidance (7.5) and without (1.0: as pipe:1031 the
+    reference then runs the networks at batch B on the positive prompt only - the second half of g(32) - and uses the UNet output as it
+    is), and the same guidance-free loop under DDIM and UniPC.  A CPU generator gives the LCM noise (tapped).  Stores the final latents,
+    the latents entering every step and the (guided) eps.  `dtype=torch.float64, save=False` returns the same loops in float64; `given_noise` (an earlier result of this
+    function) then hands every step the noise THAT run drew - a float64 generator draw is another sample, not another rounding."""
+    from diffusers import LCMScheduler
+    plain_unet, blob = build_tiny()
+    cond_unet, _ = build_tiny(LCM_WCOND_DIM)
+    plain_unet, cond_unet, blob = plain_unet.to(dtype), cond_unet.to(dtype), blob.to(dtype)
+    c = TINY
+    h = w = 8
+    out = {}
+    pipe = StableDiffusionBlobNetPipeline.__new__(StableDiffusionBlobNetPipeline)
+    for tag, (cls, set_kw, guidance, (gs, ge), seed) in LCM_LOOPS.items():
+        wcond = "wcond" in tag
+        unet = cond_unet if wcond else plain_unet
+        B = 2 if tag == "lcm_wcond_custom_3" else 1
+        sch = {"lcm": lambda: LCMScheduler.from_config(SD15_SCHEDULER_JSON), "unipc": lambda: UniPCMultistepScheduler(**SD_SCHED),
+               "ddim": lambda: DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)}[cls]()
+        sch.set_timesteps(**set_kw)
+        steps = len(sch.timesteps)
+        cfg = guidance > 1.0 and not wcond                                   # pipe:497
+        R = 2 * B if cfg else B                                              # rows the networks see
+        tcond = None
+        if wcond:                                                            # pipe:987-993
+            tcond = StableDiffusionBlobNetPipeline.get_guidance_scale_embedding(
+                pipe, torch.tensor(guidance - 1).repeat(B), embedding_dim=LCM_WCOND_DIM).to(dtype)
+            out[f"{tag}_timestep_cond"] = tcond.numpy()
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        latents = (g(31, B, 4, h, w) * sch.init_noise_sigma).to(dtype)
+        prompt = g(32, 2 * B, 7, c["ctx"]).to(dtype)
+        if not cfg:
+            prompt = prompt[B:]
+        fg_lat = (g(33, 1, 4, h, w) * 0.18215 * 5).repeat(R, 1, 1, 1).to(dtype)
+        bg_lat = (g(34, 1, 4, h, w) * 0.18215 * 5).repeat(R, 1, 1, 1).to(dtype)
+        ell = [[40.0, 42.0], [20.0, 30.0], 25.0]
+        mean, cov = ref_inf.get_gs_from_ellipse(ell)
+        nm, nc = ref_inf.normalize_gs(mean, cov, 64, 64)
+        gs_score = splat_features(**ref_inf.get_blob_dict_from_norm_gs(nm, nc), score_size=(h, w), return_d_score=True)
+        bg_s, fg_s = gs_score.unbind(dim=1)
+        bg_s = bg_s.unsqueeze(1).repeat(R, 1, 1, 1).to(dtype)
+        fg_s = fg_s.unsqueeze(1).repeat(R, 1, 1, 1).to(dtype)
+        dino = g(35, 1, 1, c["feat"]).to(dtype)
+        feats = pipe.splat_features_from_scores(fg_s, dino.repeat(R, 1, 1), size=h, channels_last=False)
+        keep = [1.0 - float(i / steps < gs or (i + 1) / steps > ge) for i in range(steps)]
+        eps_trace, lat_trace = [], []
+        give = given_noise is not None and f"{tag}_noise" in given_noise
+        ctx = _GiveNoise(LCM_MODULE, [torch.from_numpy(v).to(dtype) for v in given_noise[f"{tag}_noise"]]) if give else _TapNoise(LCM_MODULE)
+        with ctx as tap:
+            for i, t in enumerate(sch.timesteps):
+                lat_trace.append(latents.numpy().copy())
+                lmi = sch.scale_model_input(torch.cat([latents] * 2) if cfg else latents, t)       # pipe:1031-1032
+                bi = pipe.construct_blobnet_input(lmi, fg_s, fg_lat, feats, background=False)
+                d, m, u = blob(bi, t, conditioning_scale=1.0 * keep[i], return_dict=False)
+                ui = pipe.construct_blobnet_input(lmi, bg_s, bg_lat, background=True)
+                npred = unet(ui, t, encoder_hidden_states=prompt, timestep_cond=tcond,
+                             down_block_add_samples=[x[..., -x.shape[-2]:] for x in d],
+                             mid_block_add_sample=m[..., -m.shape[-2]:], up_block_add_samples=[x[..., -x.shape[-2]:] for x in u],
+                             return_dict=False)[0]
+                b_, c_, h_, w_ = npred.shape
+                npred = npred[..., :h_, w_ // 2:]
+                if cfg:                                                                             # pipe:1095-1098
+                    nu, nt = npred.chunk(2)
+                    npred = nu + guidance * (nt - nu)
+                eps_trace.append(npred.numpy())
+                step_kw = dict(generator=gen) if cls == "lcm" else {}
+                latents = sch.step(npred, t, latents, return_dict=False, **step_kw)[0].to(dtype)
+        if give:
+            assert not tap.noises
+            tap.drawn = [torch.from_numpy(v) for v in given_noise[f"{tag}_noise"]]
+        assert len(tap.drawn) == (steps - 1 if cls == "lcm" else 0)
+        out[f"{tag}_final"] = latents.numpy()
+        out[f"{tag}_eps"] = np.stack(eps_trace)
+        out[f"{tag}_lat"] = np.stack(lat_trace)
+        out[f"{tag}_timesteps"] = sch.timesteps.numpy()
+        out[f"{tag}_window"] = np.array([gs, ge])
+        out[f"{tag}_kw"] = np.array(json.dumps(dict(cls=cls, set_timesteps=set_kw, guidance_scale=guidance, batch=B,
+                                                    time_cond_proj_dim=LCM_WCOND_DIM if wcond else None)))
+        if cls == "lcm":
+            out[f"{tag}_noise"] = torch.stack(tap.drawn).numpy()
+            out[f"{tag}_seed"] = np.array(seed)
+        print(f"loop_lcm {tag} ({dtype}): {steps} steps, batch {R}, final std {latents.std():.4f}")
+    if save:
+        np.savez_compressed(os.path.join(OUT, "loop_tiny_lcm.npz"), **out)
+    return out
+
+
+def golden_unet_timecond():
+    """The tiny UNet with time_cond_proj_dim = 8 (time_embedding.cond_proj.weight [16, 8], no bias) on golden_nets' "wide" inputs: its
+    forward with a `timestep_cond` (the guidance-scale embeddings of 7.5 and 3.0, one per image, so that a wrong row shows), and without
+    one (embeddings.py:576-579: no add).  Plus `get_guidance_scale_embedding` (pipe:456-483) itself for dims 8, 7 and 256 and the scales
+    1.0, 3.0 and 7.5."""
+    unet, blob = build_tiny(LCM_WCOND_DIM)
+    assert tuple(unet.state_dict()["time_embedding.cond_proj.weight"].shape) == (TINY["boc"][0], LCM_WCOND_DIM)
+    assert "time_embedding.cond_proj.bias" not in unet.state_dict()
+    c = TINY
+    pipe = StableDiffusionBlobNetPipeline.__new__(StableDiffusionBlobNetPipeline)
+    emb = lambda scales, dim: StableDiffusionBlobNetPipeline.get_guidance_scale_embedding(
+        pipe, torch.tensor([s_ - 1 for s_ in scales], dtype=torch.float32), embedding_dim=dim)
+    out = {"scales": np.array([1.0, 3.0, 7.5])}
+    for dim in (8, 7, 256):
+        out[f"embedding_{dim}"] = emb([1.0, 3.0, 7.5], dim).numpy()
+        one = torch.cat([StableDiffusionBlobNetPipeline.get_guidance_scale_embedding(pipe, torch.tensor(s_ - 1).repeat(1), embedding_dim=dim)
+                         for s_ in (1.0, 3.0, 7.5)])                       # as pipe:990 builds it: torch.tensor(guidance_scale - 1).repeat(B)
+        assert torch.equal(one, torch.from_numpy(out[f"embedding_{dim}"])), dim
+    B, (h, w) = 2, (8, 16)
+    x_b = g(11, B, 4 + 1 + c["feat"], h, w)
+    t = torch.tensor(981)
+    down, mid, up = blob(x_b, t, conditioning_scale=0.8, return_dict=False)
+    x_u, ehs = g(12, B, 5, h, w), g(13, B, 7, c["ctx"])
+    sq = (lambda r: r[..., -r.shape[-2]:])
+    tcond = emb([7.5, 3.0], LCM_WCOND_DIM)
+    res = lambda: dict(down_block_add_samples=[sq(r).clone() for r in down], mid_block_add_sample=sq(mid).clone(),
+                       up_block_add_samples=[sq(r).clone() for r in up])
+    out.update(blob_in=x_b.numpy(), unet_in=x_u.numpy(), ehs=ehs.numpy(), timestep=np.array(981), timestep_cond=tcond.numpy(),
+               eps=unet(x_u, t, encoder_hidden_states=ehs, timestep_cond=tcond, return_dict=False, **res())[0].numpy(),
+               eps_plain=unet(x_u, t, encoder_hidden_states=ehs, timestep_cond=tcond, return_dict=False)[0].numpy(),
+               eps_nocond=unet(x_u, t, encoder_hidden_states=ehs, return_dict=False, **res())[0].numpy())
+    for i, r in enumerate(down):
+        out[f"down_{i}"] = sq(r).numpy()
+    out["mid"] = sq(mid).numpy()
+    for i, r in enumerate(up):
+        out[f"up_{i}"] = sq(r).numpy()
+    np.savez_compressed(os.path.join(OUT, "unet_tiny_timecond.npz"), **out)
+    print("unet_timecond: eps std %.4f, cond delta %.4f" % (out["eps"].std(), np.abs(out["eps"] - out["eps_nocond"]).max()))
+
+
+def lcm_loop_spread():
+    """The reference's own fp32-versus-fp64 spread of golden_loop_lcm's final latents (max-abs / scale), printed per case."""
+    a = golden_loop_lcm(save=False)
+    b = golden_loop_lcm(torch.float64, save=False, given_noise=a)
+    for tag in LCM_LOOPS:
+        x, y = a[f"{tag}_final"].astype(np.float64), b[f"{tag}_final"].astype(np.float64)
+        print(f"{tag}: reference fp32 vs fp64 final latents max-abs/scale {np.abs(x - y).max() / np.abs(y).max():.3e}")
+
+
+def golden_pipeline_call_lcm():
+    """The reference's own `__call__` (pipe:743-1166) with `LCMScheduler.from_config(pipeline.scheduler.config)` on the plain tiny
+    components, 4 steps and a CPU `generator` (start latents, then the noise of three steps), with classifier-free guidance (7.5) and
+    without (1.0: prompt_embeds holds the positive prompts only, the networks run at batch B); and on the components of a distilled LCM
+    model (UNet with time_cond_proj_dim = 8) at guidance 7.5, which goes in as timestep_cond (pipe:987-993) with CFG off (pipe:497).
+    Case = `ddim_neg2` of pipeline_call.npz
+    with its own seeds; the images and scores are those of pipeline_call.npz."""
+    from PIL import Image
+    from diffusers import LCMScheduler
+    from tests.common import FakeTokenizer, pipeline_cases
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    cond_unet = _tiny_pipeline_components(LCM_WCOND_DIM)[0]
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"], seed=2027, rng_seed=29)
+    for k in ("scheduler", "guidance_scale"):
+        kw.pop(k, None)
+    seed, rng_seed = kw.pop("seed"), kw.pop("rng_seed")
+    kw["num_inference_steps"] = 4
+    src = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+    pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=src,
+                                          safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+    pipe.set_progress_bar_config(disable=True)
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(kw["num_inference_steps"])}
+    for tag, guidance in (("cfg", 7.5), ("nocfg", 1.0), ("wcond", 7.5)):
+        if tag == "wcond":
+            pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=cond_unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob,
+                                                  scheduler=src, safety_checker=None, dinov2_processor=proc, dinov2=dino,
+                                                  requires_safety_checker=False)
+            pipe.set_progress_bar_config(disable=True)
+            assert pipe.unet.config.time_cond_proj_dim == LCM_WCOND_DIM
+        pipe.scheduler = LCMScheduler.from_config(src.config)
+        torch.manual_seed(rng_seed)
+        with _TapNoise(LCM_MODULE) as noise:
+            r = pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                     height=64, width=64, generator=torch.Generator().manual_seed(seed), output_type="latent", guidance_scale=guidance, **kw)
+        assert len(noise.drawn) == kw["num_inference_steps"] - 1 and pipe.do_classifier_free_guidance == (tag == "cfg")
+        out[f"{tag}_latents"] = r.images.numpy()
+        out[f"{tag}_noise"] = torch.stack(noise.drawn).numpy()
+        out[f"{tag}_timesteps"] = pipe.scheduler.timesteps.numpy()
+        out[f"{tag}_guidance_scale"] = np.array(guidance)
+        print(f"pipeline __call__ lcm {tag} on {out[f'{tag}_timesteps']}: latents std {out[f'{tag}_latents'].std():.4f}, noise "
+              f"{out[f'{tag}_noise'].shape}")
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_lcm.npz"), **out)
+
+
 # ------------------------------------------------------------------------------------------------ 4. pipeline loop
 class _FakeVaeCfg:
     scaling_factor = 0.18215
@@ -1353,16 +1618,17 @@ def golden_blob_edit_cv():
     print("blob_edit_cv:", names, os.path.getsize(os.path.join(OUT, "blob_edit_cv.npz")) // 1024, "KB")
 
 
-def _tiny_pipeline_components():
+def _tiny_pipeline_components(time_cond_proj_dim=None):
     """The reference classes of golden_pipeline_call on the tiny weights: (unet, blobnet, vae, text encoder, DINOv2 processor, DINOv2)."""
     from diffusers import AutoencoderKL
     from transformers import BitImageProcessor, CLIPTextConfig, CLIPTextModel, Dinov2Config, Dinov2Model
     from tests.common import PIPE, tiny_pipeline_weights
     c = TINY
-    unet5, blob = build_tiny()
+    unet5, blob = build_tiny(time_cond_proj_dim)
     # the script's construction (inf:229-249): a 4-channel UNet whose conv_in is replaced by a 5-channel one; config.in_channels stays 4
     unet = UNet2DConditionModel(in_channels=4, out_channels=4, block_out_channels=c["boc"], norm_num_groups=c["groups"],
-                                attention_head_dim=c["heads"], cross_attention_dim=c["ctx"], layers_per_block=2)
+                                attention_head_dim=c["heads"], cross_attention_dim=c["ctx"], layers_per_block=2,
+                                time_cond_proj_dim=time_cond_proj_dim)
     unet.conv_in = torch.nn.Conv2d(5, unet.conv_in.out_channels, kernel_size=3, stride=1, padding=1)
     unet.load_state_dict(unet5.state_dict(), strict=True)
     unet.eval()
@@ -1587,6 +1853,10 @@ if __name__ == "__main__":
     golden_schedulers_euler()
     golden_loop_euler()
     golden_pipeline_call_euler()
+    golden_schedulers_lcm()
+    golden_loop_lcm()
+    golden_unet_timecond()
+    golden_pipeline_call_lcm()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))

@@ -16,7 +16,10 @@ run's eta): the plan then also holds the named buffer `variance_noise` [5][1][4]
 assembles its inputs with the `_scaled` entry points): "latents" is then the start noise times the table's init_noise_sigma, and
 "expected_latents" that run's final latents - or the contents of `--expected FILE.npy` (e.g. what the in-process engine computed).
 
-    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG [--expected FILE.npy]]
+`--lcm TAG` compiles a case of tests/golden/loop_tiny_lcm.npz (e.g. lcm_nocfg_4: the LCM scheduler with guidance off, a single-pass plan
+whose `ctx` holds the positive prompt only and whose steps end in bc_scheduler_step_single; the noise the reference drew is embedded).
+
+    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG | --lcm TAG [--expected FILE.npy]]
 """
 import argparse
 import os
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("out", nargs="?", default=os.path.join(REPO, "build", "plan_fixture"))
     ap.add_argument("--eta", type=float, default=0.0, help="stochastic DDIM: the eta of loop_tiny_eta.npz's 5-step run")
     ap.add_argument("--euler", default=None, help="a case of loop_tiny_euler.npz (Euler / Euler-ancestral / Heun)")
+    ap.add_argument("--lcm", default=None, help="a case of loop_tiny_lcm.npz (LCM with or without guidance, single-pass DDIM / UniPC)")
     ap.add_argument("--expected", default=None, help=".npy file with the expected final latents (default: the reference loop's)")
     args = ap.parse_args()
     OUT = args.out
@@ -61,6 +65,23 @@ def main():
             extra = dict(timesteps=ts)
         if f"{args.euler}_noise" in ze.files:
             extra["variance_noise"] = torch.from_numpy(ze[f"{args.euler}_noise"])
+    guidance, positive_only = 7.5, False
+    if args.lcm:
+        import json
+        from blobctrl_amd import schedulers
+        zl = np.load(os.path.join(GOLD, "loop_tiny_lcm.npz"))
+        kw = json.loads(str(zl[f"{args.lcm}_kw"]))
+        src = schedulers.DDIMScheduler().config
+        sched = {"lcm": schedulers.LCMScheduler, "ddim": schedulers.DDIMScheduler, "unipc": schedulers.UniPCMultistepScheduler}[kw["cls"]].from_config(src)
+        sched.set_timesteps(**kw["set_timesteps"])
+        steps, guidance = len(sched.timesteps), float(kw["guidance_scale"])
+        window, expected = tuple(float(v) for v in zl[f"{args.lcm}_window"]), zl[f"{args.lcm}_final"]
+        positive_only = guidance <= 1.0
+        if positive_only:
+            extra["single_pass"] = True
+        if f"{args.lcm}_noise" in zl.files:                                # n - 1 draws; the last step's slice is never read
+            noise = torch.from_numpy(zl[f"{args.lcm}_noise"])
+            extra["variance_noise"] = torch.cat([noise, torch.zeros_like(noise[:1])], 0)
     if args.expected:
         expected = np.load(args.expected)
     if args.eta:
@@ -75,7 +96,7 @@ def main():
     if sched is not None:
         eng.set_scheduler(sched.kind, sched.table_params())
     B, h, w, T = 1, 8, 8, 7
-    seq = eng.compile_plan(os.path.join(OUT, "tiny_edit.bcplan"), B, h, w, T, TINY["ctx"], steps, guidance_scale=7.5,
+    seq = eng.compile_plan(os.path.join(OUT, "tiny_edit.bcplan"), B, h, w, T, TINY["ctx"], steps, guidance_scale=guidance,
                            blobnet_conditioning_scale=1.0, blobnet_control_guidance_start=window[0], blobnet_control_guidance_end=window[1],
                            **extra)
     score = torch.from_numpy(z["gs_score"]).float()                     # [1,2,h,w] = (bg, fg)
@@ -84,7 +105,7 @@ def main():
     feat16[:, : TINY["feat"]] = dino.reshape(1, -1).half()
     recs = {
         "latents": (g(31, B, 4, h, w) * sigma0).numpy(),                   # x init_noise_sigma (= 1 for DDIM)
-        "ctx": g(32, 2 * B, T, TINY["ctx"]).half().numpy(),
+        "ctx": g(32, 2 * B, T, TINY["ctx"])[B if positive_only else 0:].half().numpy(),     # a single-pass plan: the positive prompt only
         "fg_lat": (g(33, 1, 4, h, w) * 0.18215 * 5).numpy(),
         "bg_lat": (g(34, 1, 4, h, w) * 0.18215 * 5).numpy(),
         "bg_score": score[:, 0].contiguous().numpy(),
