@@ -75,6 +75,8 @@ _SIGNATURES = {
                                     C.c_void_p]),
     "bc_memset_zero": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     "bc_dup_halves": (C.c_int, [C.c_void_p, C.c_longlong] * 6 + [C.c_void_p]),
+    "bc_freeu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "bc_gn_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                               C.c_void_p, C.c_void_p]),
     "bc_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -180,7 +182,7 @@ OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused":
        "bc_rowchain_midx": 25, "bc_rowchain_pack_kv": 26, "bc_rowchain_sum": 27, "bc_ctx_fold": 28, "bc_dup_halves": 29,
        "bc_cfg_scheduler_step_noise": 30, "bc_cfg_scheduler_step3": 31,
        "bc_assemble_input_scaled": 32, "bc_assemble_input_im2col_scaled": 33, "bc_scheduler_step_single": 34,
-       "bc_timestep_embedding_table_cond": 35, "bc_timestep_embedding_cond": 36}
+       "bc_timestep_embedding_table_cond": 35, "bc_timestep_embedding_cond": 36, "bc_freeu": 37}
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)

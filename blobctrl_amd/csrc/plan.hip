@@ -145,6 +145,9 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
             return bc_timestep_embedding_table_cond(CP(float, 0), I(1), I(2), I(3), CP(float, 4), MP(bc_half, 5), s);
         case BC_OP_TIMESTEP_EMBEDDING_COND:
             return bc_timestep_embedding_cond(CP(float, 0), CP(int, 1), F(2), I(3), I(4), CP(float, 5), MP(bc_half, 6), s);
+        case BC_OP_FREEU:
+            return bc_freeu(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), CP(float, 6), I(7), CP(float, 8), MP(bc_half, 9),
+                            MP(bc_half, 10), MP(unsigned long long, 11), MP(unsigned long long, 12), s);
         case BC_OP_ROWCHAIN:
             return bc_rowchain(I(0), I(1), I(2), I(3), CP(bc_half, 4), CP(float, 5), CP(unsigned long long, 6), CP(float, 7), CP(float, 8), I(9),
                                F(10), CP(bc_half, 11), CP(bc_half, 12), CP(bc_half, 13), I(14), I(15), I(16), CP(bc_half, 17), CP(float, 18),

@@ -19,11 +19,13 @@ const uint32_t kMagic = 0x4E4C5042u;   // "BPLN"
 const uint32_t kVersion = 7;           // 2: BcGemm grew ln_colsum / C_t, GroupNorm statistics totals; 3: + BC_OP_ROWCHAIN_MIDX / _PACK_KV (round 4);
                                        // 4: + BC_OP_ROWCHAIN_SUM, BC_CHAIN_OUT_FFP; 5: BcGemm grew w_bstride / vec_bstride / sm_group / sm_valid,
                                        //    + BC_OP_CTX_FOLD (round 5); 6: + BC_OP_ASSEMBLE_INPUT_SCALED / _IM2COL_SCALED;
-                                       // 7: + BC_OP_SCHEDULER_STEP_SINGLE, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND / _COND
+                                       // 7: + BC_OP_SCHEDULER_STEP_SINGLE, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND / _COND, BC_OP_FREEU
 // A file is written with the LOWEST version that describes it (op_min_version below): a plan without a version-6 op stays a version-5
 // file, byte for byte what the previous library wrote and still readable by it.
 inline uint32_t op_min_version(int op) {
-    if (op == BC_OP_SCHEDULER_STEP_SINGLE || op == BC_OP_TIMESTEP_EMBEDDING_TABLE_COND || op == BC_OP_TIMESTEP_EMBEDDING_COND) return 7u;
+    // (BC_OP_FREEU joined version 7 without a new version number: a reader built before it refuses the record as an unknown op code)
+    if (op == BC_OP_SCHEDULER_STEP_SINGLE || op == BC_OP_TIMESTEP_EMBEDDING_TABLE_COND || op == BC_OP_TIMESTEP_EMBEDDING_COND ||
+        op == BC_OP_FREEU) return 7u;
     return op == BC_OP_ASSEMBLE_INPUT_SCALED || op == BC_OP_ASSEMBLE_IM2COL_SCALED ? 6u : 5u;
 }
 const uint32_t kOldestReadable = 5;    // (the records hold BcGemm by value: a file of another layout is refused by the size check below anyway)
@@ -67,6 +69,7 @@ inline const char* op_signature(int op) {
         case BC_OP_SCHEDULER_STEP_SINGLE: return "pppppiiipiipi";
         case BC_OP_TIMESTEP_EMBEDDING_TABLE_COND: return "piiipp";
         case BC_OP_TIMESTEP_EMBEDDING_COND: return "ppfiipp";
+        case BC_OP_FREEU: return "pipiiipippppp";
         default: return nullptr;
     }
 }

@@ -5,6 +5,7 @@ Host-side mirror of (paths relative to the reference root, D/ = diffusers/src/di
   * blobctrl/models/blobnet.py:720-945             BlobNetModel.forward
   * D/models/unets/unet_2d_blocks.py:1241-1323, 1378-1433, 860-899, 2514-2624, 2677-2765 (patched blocks)
   * D/models/resnet.py:320-373, transformers/transformer_2d.py:479-527, attention.py:421-541
+  * D/utils/torch_utils.py:93-148                      apply_freeu / fourier_filter (FreeU, up_blocks.0 and up_blocks.1 of the UNet: bc_freeu)
 re-expressed as a flat list of C-ABI launches over NHWC fp16 buffers (see launch.Recorder).  Fusions relative to
 the reference op list: channel-concat folded into the GroupNorm / shortcut loaders, nearest-upsample folded into the
 following conv's gather, bias / time-embedding / residual / BlobNet right-half add / conditioning scale / GEGLU folded
@@ -54,6 +55,31 @@ class Residuals:
     events: Optional[dict] = None        # data_ptr -> event signalled by the producer (two-stream execution)
 
 
+def freeu_enabled(freeu) -> bool:
+    """`is_freeu_enabled` of the patched up blocks (unet_2d_blocks.py:2535-2540): a truthiness test on all four of (s1, s2, b1, b2) - any
+    0.0 or None silently runs the plain network."""
+    return freeu is not None and len(freeu) == 4 and all(bool(v) for v in freeu)
+
+
+def freeu_frequencies(H: int, W: int):
+    """The frequency indices (ky, kx) that fourier_filter(threshold=1) scales (torch_utils.py:93-120): the fft-shifted box rows
+    [H // 2 - 1, H // 2 + 1) are the frequencies {H - 1, 0} - a SET, one index when H = 1 - and likewise the columns."""
+    ky, kx = sorted({0, (H - 1) % H}), sorted({0, (W - 1) % W})
+    return [(a, b) for a in ky for b in kx]
+
+
+def freeu_basis(H: int, W: int) -> torch.Tensor:
+    """(cos theta_k, sin theta_k) of every token p = y W + x for the frequencies of freeu_frequencies, theta_k = 2 pi (ky y / H + kx x / W):
+    float64 [H * W][4][2], zero rows for unused pairs.  The angle is reduced in integers first, so every entry is exact to fp64 rounding."""
+    out = torch.zeros(H * W, 4, 2, dtype=torch.float64)
+    y = torch.arange(H, dtype=torch.int64).repeat_interleave(W)
+    x = torch.arange(W, dtype=torch.int64).repeat(H)
+    for k, (ky, kx) in enumerate(freeu_frequencies(H, W)):
+        turn = ((ky * y * W + kx * x * H) % (H * W)).to(torch.float64) / (H * W)          # theta / 2 pi in [0, 1)
+        out[:, k, 0], out[:, k, 1] = torch.cos(2 * torch.pi * turn), torch.sin(2 * torch.pi * turn)
+    return out
+
+
 class TrunkPlan:
     """Records one forward of a trunk into the recorder's current segment."""
 
@@ -61,6 +87,7 @@ class TrunkPlan:
         self.rec, self.pw, self.cfg, self.B, self.H, self.W = rec, pw, cfg, B, H, W
         self.G = cfg.norm_num_groups
         self.heads = cfg.num_heads
+        self.freeu_params = None          # UNet with FreeU on: the plan's fp32 (s1, s2, b1, b2) buffer, read by bc_freeu on the device
 
     # ------------------------------------------------------------------------------------------- helpers
     def _r2(self, res_t, H, W):
@@ -194,6 +221,18 @@ class TrunkPlan:
         out = self.rec.groupnorm(x.t, x.C, x2.t if x2 is not None else None, C2, self.B, x.H * x.W, self.G, eps,
                                  pw.f[name + ".weight"], pw.f[name + ".bias"], silu)
         return Act(out, x.C + C2, x.H, x.W)
+
+    def freeu(self, h: Act, sk: Act, stage: int):
+        """apply_freeu (torch_utils.py:123-148) on (hidden, skip) of up_blocks.`stage` in front of their concat: one bc_freeu launch into
+        two new buffers, which carry their GroupNorm statistics totals with them."""
+        assert (h.H, h.W) == (sk.H, sk.W)
+        rec = self.rec
+        cache = rec.__dict__.setdefault("_freeu_basis", {})
+        if (h.H, h.W) not in cache:       # a constant of the plan (saved with its contents), tabulated in fp64
+            cache[(h.H, h.W)] = rec.register(freeu_basis(h.H, h.W).to(torch.float32).to(rec.device))
+            rec.keep.append(cache[(h.H, h.W)])
+        ht, st = rec.freeu(h.t, h.C, sk.t, sk.C, self.B, h.H, h.W, self.freeu_params, stage, cache[(h.H, h.W)])
+        return Act(ht, h.C, h.H, h.W), Act(st, sk.C, sk.H, sk.W)
 
     # ------------------------------------------------------------------------------------------- blocks
     def resnet(self, p, x: Act, skip: Optional[Act], Cout, r2=None, out=None):
@@ -785,6 +824,8 @@ class TrunkPlan:
             for j in range(n_res):
                 r = pop(res_u)
                 sk = res.pop()
+                if self.freeu_params is not None and not cfg.is_blobnet and i < 2:
+                    h, sk = self.freeu(h, sk, stage=i)         # (unet_2d_blocks.py:2543-2557, 2703-2717: at every resnet of the stage)
                 h = self.resnet(f"up_blocks.{i}.resnets.{j}.", h, sk, rev[i], r2=None if has_attn else r)
                 pre = None
                 if has_attn:

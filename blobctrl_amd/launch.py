@@ -362,6 +362,24 @@ class Recorder:
         total = sum(b for _, b in items)
         self._op("bc_dup_halves", tuple(args), "dup_halves", variant="dup_halves_kernel", shape=("dup_halves", total), bytes_=2 * total)
 
+    def freeu(self, hidden, C_h, skip, C_s, B, H, W, params, stage, basis):
+        """bc_freeu (include/blobctrl_hip.h) in front of a channel concat: returns (hidden_out, skip_out), new buffers.  `params` = the
+        plan's fp32 (s1, s2, b1, b2) buffer, `basis` = the [H * W][4][2] fp32 table of engine.freeu_basis on this device.  The launch
+        emits the GroupNorm statistics of both outputs as per-channel totals: what reads them next finds its statistics here."""
+        HW = H * W
+        h_out, s_out = self.empty(B, HW, C_h), self.empty(B, HW, C_s)
+        tot_h, tot_s = self.new_tot(B, C_h), self.new_tot(B, C_s)
+        refs = (hidden, skip, params, basis, h_out, s_out, tot_h, tot_s)
+        self.keep.append(refs)
+        for t in refs:
+            self.register(t)
+        self._op("bc_freeu", (hidden, C_h, skip, C_s, B, HW, params, stage, basis, h_out, s_out, tot_h, tot_s), "freeu",
+                 variant="freeu_kernel", shape=("freeu", B, HW, C_h, C_s, stage), bytes_=2 * 2 * B * HW * (C_h + C_s))
+        for out, tot in ((h_out, tot_h), (s_out, tot_s)):
+            self.tots[out.data_ptr()] = tot
+            self.tots_per_channel.add(id(tot))
+        return h_out, s_out
+
     # ------------------------------------------------------------------ GEMM family
     def plan_gemm(self, M, N, K, fast, mode, tile_cfg=0, splitk=None):
         """(tile_cfg, splitk, bm, bn) for a GEMM: tuning table first, then the library's cost model (bc_gemm_plan)."""

@@ -15,7 +15,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import Residuals, TrunkConfig, TrunkPlan
+from .engine import Residuals, TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder, run_graphed
 from .weights import PackedTrunk, merge_lora, pad8
 
@@ -249,6 +249,7 @@ class UNet2DConditionModel(_TrunkModule):
     def __init__(self, state_dict, config: TrunkConfig, device="cuda:0", lazy: bool = False):
         assert not config.is_blobnet
         super().__init__(state_dict, config, device, lazy)
+        self.__dict__["freeu"] = None          # (s1, s2, b1, b2) after enable_freeu
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, extra_in_channels=0, lora_path=None, lora_scale=1.0, device="cuda:0", **_ignored):
@@ -260,6 +261,17 @@ class UNet2DConditionModel(_TrunkModule):
         from .checkpoint import load_unet
         sd, cfg = load_unet(os.path.join(path, subfolder) if subfolder else path, extra_in_channels, lora_path, lora_scale)
         return cls(sd, cfg, device, lazy=True)
+
+    # ---- FreeU (unet_2d_condition.py:839-870): the reference sets s1 / s2 / b1 / b2 on every up block; here the four values are module
+    # state that the plans read (this module's own, and the loop engine's through the pipeline)
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """Enables the FreeU mechanism (https://arxiv.org/abs/2309.11497) in up_blocks.0 (s1, b1) and up_blocks.1 (s2, b2).  As in the
+        reference, a value of 0.0 or None among the four leaves the plain network running."""
+        self.__dict__["freeu"] = (s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        """Disables the FreeU mechanism."""
+        self.__dict__["freeu"] = None
 
     # ---- `unet.conv_in` as the script uses it (inf:233-249): reads .weight / .bias / .out_channels, assigns a wider Conv2d
     @property
@@ -318,10 +330,11 @@ class UNet2DConditionModel(_TrunkModule):
                 up.append((rev[i],) + sizes[nb - 2 - i])
         return down, mid, up
 
-    def _plan(self, B, H, W, T, Dc, with_res, cond=False):
+    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False):
         """`cond`: the plan takes a `timestep_cond` (fp16 [B][pad8(time_cond_proj_dim)]) and adds cond_proj of it to the sinusoid; a
-        plan of its own, so that calls without one keep the launches they always recorded."""
-        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ())
+        plan of its own, so that calls without one keep the launches they always recorded.  `freeu`: likewise a plan of its own, with
+        bc_freeu in up_blocks.0 / up_blocks.1 reading (s1, s2, b1, b2) from the plan buffer P.freeu."""
+        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ()) + (("freeu",) if freeu else ())
         if key not in self._plans:
             rec = Recorder(self.device)
             P = type("Plan", (), {})()
@@ -339,6 +352,8 @@ class UNet2DConditionModel(_TrunkModule):
             P.residuals = residuals
             P.seg = rec.begin("unet")
             plan = TrunkPlan(rec, self.weights, self.trunk_config, B, H, W)
+            if freeu:
+                P.freeu = plan.freeu_params = rec.zeros(4, dtype=torch.float32)
             plan.record_context(P.ctx, T)
             if cond:
                 P.cond = rec.zeros(B, pad8(self.trunk_config.time_cond_proj_dim))
@@ -393,7 +408,10 @@ class UNet2DConditionModel(_TrunkModule):
         B, C, H, W = sample.shape
         is_blobnet = mid_block_add_sample is not None
         T, Dc = encoder_hidden_states.shape[1:]
-        P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None)
+        freeu = self.__dict__.get("freeu")
+        P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None, freeu=freeu_enabled(freeu))
+        if freeu_enabled(freeu):
+            P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
         if timestep_cond is not None:
             P.cond.zero_()
             P.cond[:, : timestep_cond.shape[1]].copy_(timestep_cond.to(self.device, torch.float16))

@@ -3,13 +3,14 @@
 BASELINE.json's north star words the boundary as "driven from Python through PyTorch-ROCm custom ops that keep the
 StableDiffusionBlobCtrlPipeline.__call__ / BlobNet / UNet-LoRA API surface".  The compute entry points of this package are the C ABI
 of libblobctrl_hip.so (include/blobctrl_hip.h) reached through ctypes; this module registers the four calls the reference makes into
-its hot path, and the five steps of its blob visualisation / feature grid, as dispatcher-visible ops OVER that same C ABI, so that
+its hot path, FreeU, and the five steps of its blob visualisation / feature grid, as dispatcher-visible ops OVER that same C ABI, so that
 `torch.profiler`, dispatch modes and fake-tensor tracing see them:
 
     blobctrl::splat_scores     blobctrl/utils/utils.py:145-194             (splat_features, tuple score_size branch)
     blobctrl::blobnet_forward  blobctrl/models/blobnet.py:720-945          (BlobNetModel.forward -> down / mid / up residuals)
     blobctrl::unet_forward     D/models/unets/unet_2d_condition.py:1039-1353 (patched forward with the three residual lists)
     blobctrl::denoise          blobctrl/pipelines/pipeline_blobnet.py:1025-1123 (the whole loop: one hipGraph launch per edit)
+    blobctrl::freeu            D/utils/torch_utils.py:93-148                (apply_freeu on (hidden, skip) in front of an up-block concat)
     blobctrl::splat_maps       blobctrl/utils/utils.py:120-135, 145-181    (raw and composed scores, channels-last)
     blobctrl::alpha_composite  blobctrl/utils/utils.py:179-181, 205-209    (compositing of raw scores a viz_score_fn changed)
     blobctrl::splat_from_scores blobctrl/utils/utils.py:57-77, pipeline_blobnet.py:706-721 (scores x features, resize folded in)
@@ -214,3 +215,43 @@ def _(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, l
       conditioning_scales, guidance_start, guidance_end, handle, scales_are_per_request=False, eta=0.0, variance_noise=None):
     eng = _get(handle)
     return torch.empty(tuple(latents.shape), dtype=torch.float32, device=eng.device)
+
+
+# ------------------------------------------------------------------------------------------------------------------ freeu
+def freeu_launch(hidden: torch.Tensor, skip: torch.Tensor, params: torch.Tensor, stage: int):
+    """One bc_freeu launch on the current stream: (hidden_out, skip_out, tot_h, tot_s) - the two outputs and their GroupNorm statistics
+    totals [B][C][GN_TOT_WORDS] (int64, per channel).  hidden [B][H][W][C_h], skip [B][H][W][C_s] fp16 channels-last on the GPU, params
+    fp32 (s1, s2, b1, b2) on the GPU."""
+    from . import _lib
+    from .engine import freeu_basis
+    lib = _lib.load()
+    if hidden.dim() != 4 or skip.dim() != 4 or hidden.shape[:3] != skip.shape[:3]:
+        raise ValueError("freeu: hidden [B][H][W][C_h] and skip [B][H][W][C_s] must share batch, height and width")
+    if hidden.dtype != torch.float16 or skip.dtype != torch.float16 or params.dtype != torch.float32 or params.numel() != 4:
+        raise ValueError("freeu: hidden and skip are fp16, params is fp32 (s1, s2, b1, b2)")
+    if hidden.device.type != "cuda" or skip.device != hidden.device or params.device != hidden.device:
+        raise _lib.BlobCtrlHipError("freeu runs on MI355X only (all tensors on one cuda device); there is no CPU fallback")
+    B, H, W, C_h = hidden.shape
+    C_s = skip.shape[3]
+    hidden, skip, params = hidden.contiguous(), skip.contiguous(), params.contiguous()
+    basis = freeu_basis(H, W).to(torch.float32).to(hidden.device)
+    h_out, s_out = torch.empty_like(hidden), torch.empty_like(skip)
+    tot_h = torch.zeros(B, C_h, _lib.GN_TOT_WORDS, dtype=torch.int64, device=hidden.device)
+    tot_s = torch.zeros(B, C_s, _lib.GN_TOT_WORDS, dtype=torch.int64, device=hidden.device)
+    _lib.check(lib.bc_freeu(hidden.data_ptr(), C_h, skip.data_ptr(), C_s, B, H * W, params.data_ptr(), int(stage), basis.data_ptr(),
+                            h_out.data_ptr(), s_out.data_ptr(), tot_h.data_ptr(), tot_s.data_ptr(),
+                            torch.cuda.current_stream(hidden.device).cuda_stream), "bc_freeu")
+    return h_out, s_out, tot_h, tot_s
+
+
+@torch.library.custom_op("blobctrl::freeu", mutates_args=())
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, params: torch.Tensor, stage: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """apply_freeu(stage, hidden, skip, s1=, s2=, b1=, b2=) on channels-last fp16 tensors [B][H][W][C]; `params` = fp32 (s1, s2, b1, b2)
+    on the GPU, `stage` 0 | 1 = the up block's resolution_idx.  Returns new (hidden, skip); the inputs are not modified."""
+    return freeu_launch(hidden, skip, params, stage)[:2]
+
+
+@freeu.register_fake
+def _(hidden, skip, params, stage):
+    return (torch.empty(tuple(hidden.shape), dtype=hidden.dtype, device=hidden.device),
+            torch.empty(tuple(skip.shape), dtype=skip.dtype, device=skip.device))

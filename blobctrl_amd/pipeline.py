@@ -22,7 +22,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import _lib
-from .engine import TrunkConfig, TrunkPlan
+from .engine import TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder
 from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, table_class
 from .weights import PackedTrunk, pad8
@@ -93,7 +93,8 @@ class BlobCtrlEngine:
         self.text_encoder = text_encoder                              # optional blobctrl_amd.clip_text.CLIPTextModel
 
     # ------------------------------------------------------------------------------------------------ planning
-    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False):
+    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
+              freeu=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
@@ -105,11 +106,14 @@ class BlobCtrlEngine:
         plan of its own (and with it graphs of its own): no other table ever replays these launches.
         single: a guidance-free (single-pass) plan, pipe:1031 / 1095 with do_classifier_free_guidance False: `ctx` holds the B positive
         prompts, the UNet runs once per request at batch B (no CFG pair, so no CFG-prefix sharing and no BC_SPLIT_CFG) and the step ends
-        in bc_scheduler_step_single, which takes the right half of image b as eps.  BlobNet is what it is in every plan: batch B."""
+        in bc_scheduler_step_single, which takes the right half of image b as eps.  BlobNet is what it is in every plan: batch B.
+        freeu: FreeU is on (UNet2DConditionModel.enable_freeu) - every UNet forward runs bc_freeu in front of the six channel concats of
+        up_blocks.0 / up_blocks.1, reading (s1, s2, b1, b2) from the named buffer `freeu` (fp32 [4], refilled per edit: one plan and its
+        graphs serve every setting).  A plan of its own; BlobNet's up blocks never run it."""
         if stochastic and third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
         key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
-            (("scaled",) if scaled else ()) + (("single",) if single else ())
+            (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -153,6 +157,7 @@ class BlobCtrlEngine:
         P.scaled = bool(scaled)
         P.variance_noise = rec.zeros(nsteps, B, 4, h, w, dtype=f32, name="variance_noise") if stochastic else None
         P.guidance = [7.5]
+        P.freeu = rec.zeros(4, dtype=f32, name="freeu") if freeu else None
 
         # rank-1 collapse of the BlobNet feature channels (per-edit weight; round 6: per-IMAGE weights for a batch of independent requests -
         # conv_in then runs as one launch per image, engine.record_collapse)
@@ -171,6 +176,7 @@ class BlobCtrlEngine:
         # ---- prologue: prompt K/V
         P.prologue = rec.begin("prologue")
         unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
+        unet_a.freeu_params = P.freeu
         unet_a.record_context(P.ctx, T)
         blob = TrunkPlan(rec, self.blob_w, self.blob_cfg, B, H, W)
         if P.collapse:
@@ -196,6 +202,7 @@ class BlobCtrlEngine:
 
         def half_plan(b0):
             hp = TrunkPlan(rec, self.unet_w, self.unet_cfg, B, H, W)
+            hp.freeu_params = P.freeu
             hp.ctx_kv = {bp: (ck[b0 * T:(b0 + B) * T], cvt[b0:b0 + B], T_, ld) for bp, (ck, cvt, T_, ld) in unet_a.ctx_kv.items()}
             # (the K / V^T fragment streams of CHAIN_MIDX are laid out per image too: without the slice both halves fell back to the
             #  unfused MID + attention launches)
@@ -267,6 +274,7 @@ class BlobCtrlEngine:
         # ---- step I: UNet only (cond_scale == 0: BlobNet output is multiplied by 0, bn:936-938)
         P.step_inactive = rec.begin("step_inactive")
         unet_i = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
+        unet_i.freeu_params = P.freeu
         unet_i.ctx_kv, unet_i.ctx_kvs, unet_i.ctx_folded = unet_a.ctx_kv, getattr(unet_a, "ctx_kvs", {}), getattr(unet_a, "ctx_folded", {})
         if not temb_per_step:
             unet_i.tproj, unet_i.tproj_table = unet_a.tproj, unet_a.tproj_table
@@ -458,7 +466,7 @@ class BlobCtrlEngine:
                  bg_image: Optional[torch.Tensor] = None, return_sample: bool = False, eta: float = 0.0,
                  do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
                  variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None,
-                 single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None):
+                 single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None, freeu=None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -482,7 +490,10 @@ class BlobCtrlEngine:
         and the scheduler is LCM or the UNet has time_cond_proj_dim; True with guidance on is an error.
         `timestep_cond` [B, time_cond_proj_dim] (a UNet with time_embedding.cond_proj only): `get_guidance_scale_embedding(guidance_scale
         - 1, dim)` of every sample (pipe:987-993); it is per-edit data of the plan, so another scale replays the same graph.  None: the
-        UNet runs without the add."""
+        UNet runs without the add.
+        `freeu` = (s1, s2, b1, b2) or None: FreeU (UNet2DConditionModel.enable_freeu) in up_blocks.0 / up_blocks.1 of the UNet.  As in the
+        reference any value of 0.0 or None among the four runs the plain network - the plan every other call uses.  The values are
+        per-edit data of the FreeU plan: other values replay the same graph."""
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
@@ -567,7 +578,8 @@ class BlobCtrlEngine:
             if tuple(variance_noise.shape) != (n, B, 4, h, w):
                 raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (steps, batch, 4, h, w), got "
                                  f"{tuple(variance_noise.shape)}")
-        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order, sched.scales_input, single)
+        freeu_on = freeu_enabled(freeu)
+        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order, sched.scales_input, single, freeu_on)
         dev = self.device
         self.timesteps = sched.timesteps
         if latents is None:                                                          # pipe:438-453
@@ -605,6 +617,8 @@ class BlobCtrlEngine:
             P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
             if stochastic:
                 P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
+            if freeu_on:
+                P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
             P.step_idx.zero_()
             P.hist.zero_()
         P.guidance[0] = float(guidance_scale)
@@ -686,7 +700,7 @@ class BlobCtrlEngine:
 
     def compile_plan(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale=7.5, blobnet_conditioning_scale=1.0,
                      blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None, timesteps=None,
-                     single_pass=None):
+                     single_pass=None, freeu=None):
         """Write the launch plan of one edit configuration as a relocatable `.bcplan` file for the C plan runtime
         (include/blobctrl_hip.h: bc_plan_load / bc_plan_buffer / bc_step / bc_plan_capture_loop): segments "prologue",
         "step_active", "step_inactive"; packed weights and the scheduler / guidance tables stored with their contents; the per-edit
@@ -701,7 +715,9 @@ class BlobCtrlEngine:
         `single_pass` as in `denoise` (guidance is off for guidance_scale <= 1, and always for a UNet with time_cond_proj_dim): a
         single-pass plan's `ctx` is [B][T][ctx_dim], the positive prompts, and its steps end in bc_scheduler_step_single.  A UNet with
         time_cond_proj_dim adds the named buffer `timestep_cond` (fp16 [B or 2B][pad8(dim)], zero-filled: the host writes the
-        guidance-scale embedding of every UNet image into it before an edit)."""
+        guidance-scale embedding of every UNet image into it before an edit).
+        `freeu` = (s1, s2, b1, b2) as in `denoise`: a FreeU plan holds six BC_OP_FREEU launches per UNet forward, their basis tables, and
+        the named buffer `freeu` (fp32 [4]) saved with these values; a host writes other values into it before an edit."""
         single = self._single_pass(single_pass, guidance_scale <= 1.0 or self.unet_cfg.time_cond_proj_dim is not None)   # (pipe:497)
         n = num_inference_steps if timesteps is None else len(timesteps)
         stochastic = self._check_eta(float(eta))
@@ -710,14 +726,17 @@ class BlobCtrlEngine:
         stochastic, third_order = self._step_form(sched, stochastic)
         if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
             raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
-        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order, sched.scales_input, single)
+        freeu_on = freeu_enabled(freeu)
+        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order, sched.scales_input, single, freeu_on)
+        if freeu_on:
+            P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
         keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
         P.t_table.copy_(sched.timesteps.to(torch.float32))
         coef = sched.table().clone()
         coef[:, 11] = float(guidance_scale)
         P.coef.copy_(coef)
         P.scale_table.copy_(torch.tensor([blobnet_conditioning_scale * k for k in keep], dtype=torch.float32))
-        for t in (P.t_table, P.coef, P.scale_table):                 # constants of this configuration: saved WITH their contents
+        for t in (P.t_table, P.coef, P.scale_table) + ((P.freeu,) if freeu_on else ()):     # constants of this configuration: saved WITH their contents
             P.rec._workspace.discard(t.untyped_storage().data_ptr())
         if stochastic:
             key = P.variance_noise.untyped_storage().data_ptr()
@@ -731,8 +750,9 @@ class BlobCtrlEngine:
         return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
 
     # convenience for bench / tests ------------------------------------------------------------------
-    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single)
+    def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
+                 freeu=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu)
 
 
 # ======================================================================================================================
@@ -902,6 +922,18 @@ class StableDiffusionBlobNetPipeline:
 
     def unload_lora_weights(self):
         self.unet.unload_lora()
+
+    # ---- FreeU (D/pipelines/pipeline_utils.py:1905-1929, StableDiffusionMixin): forwarded to the UNet; the loop engine reads the state there
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """Enables the FreeU mechanism (https://arxiv.org/abs/2309.11497): s1 / s2 attenuate the skip features of stage 1 / 2, b1 / b2
+        amplify the backbone features."""
+        if not hasattr(self, "unet") or self.unet is None:
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        """Disables the FreeU mechanism if enabled."""
+        self.unet.disable_freeu()
 
     def get_active_adapters(self):
         return [n for n, a in self.unet._adapters.items() if a["active"]]
@@ -1130,7 +1162,8 @@ class StableDiffusionBlobNetPipeline:
                                     blobnet_control_guidance_start=blobnet_control_guidance_start[0],
                                     blobnet_control_guidance_end=blobnet_control_guidance_end[0], output_type="latent",
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
-                                    generator=generator, timesteps=timesteps, timestep_cond=timestep_cond)
+                                    generator=generator, timesteps=timesteps, timestep_cond=timestep_cond,
+                                    freeu=getattr(self.unet, "freeu", None))
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

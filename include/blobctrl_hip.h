@@ -243,6 +243,22 @@ int bc_memset_zero(void* ptr, long long bytes, bc_stream stream);
 int bc_dup_halves(void* p0, long long bytes0, void* p1, long long bytes1, void* p2, long long bytes2, void* p3, long long bytes3,
                   void* p4, long long bytes4, void* p5, long long bytes5, bc_stream stream);
 
+/* FreeU (https://arxiv.org/abs/2309.11497) in front of the channel concat of up_blocks.0 / up_blocks.1, both halves in one launch.
+ * Replaces apply_freeu (D/utils/torch_utils.py:123-148, fourier_filter :93-120) as the patched up blocks call it in front of
+ * torch.cat([hidden_states, res_hidden_states]) (D/models/unets/unet_2d_blocks.py:2535-2557, 2695-2717):
+ *   hidden_out[:, :, c] = hidden[:, :, c] * b   for c < C_h / 2 (one fp16 rounding), a bit-for-bit copy for the other channels
+ *   skip_out = fourier_filter(skip, threshold=1, scale=s) in closed form: out = x + (s - 1) / HW * sum_k (A_k cos_k + S_k sin_k),
+ *              A_k = sum x cos_k, S_k = sum x sin_k over the tokens of one (image, channel) map, fp32
+ * with s = params[stage], b = params[2 + stage]: `params` = fp32 (s1, s2, b1, b2) in DEVICE memory, read by the kernel, so one recorded
+ * launch serves every setting.  hidden [B][HW][C_h], skip [B][HW][C_s] fp16 (widths % 8 == 0), outputs are buffers of their own.
+ * `basis` [HW][4][2] fp32 = (cos theta_k, sin theta_k) of token p = y W + x, theta_k = 2 pi (ky y / H + kx x / W), for the deduplicated
+ * frequency list ky in {0, H - 1} x kx in {0, W - 1}, zero rows for unused pairs; tabulated in fp64 on the host (engine.freeu_basis).
+ * tot_h [B][C_h][BC_GN_TOT_WORDS], tot_s [B][C_s][..]: the GroupNorm statistics of the STORED outputs are added as per-channel totals
+ * (one slot per channel whatever the width, like bc_gn_stats; the tables must be zero before the launch). */
+int bc_freeu(const bc_half* hidden, int C_h, const bc_half* skip, int C_s, int B, int HW, const float* params, int stage,
+             const float* basis, bc_half* hidden_out, bc_half* skip_out, unsigned long long* tot_h, unsigned long long* tot_s,
+             bc_stream stream);
+
 /* Row softmax in place on fp16 [rows][cols] (fp32 maths): the single-head, head_dim-512 attention of the VAE mid block is run
  * as GEMM (QK^T) -> softmax -> GEMM (PV)  (attention_processor.py:2216 with heads = 1). */
 int bc_softmax_rows(bc_half* x, int rows, int cols, int ld, bc_stream stream);
@@ -531,7 +547,7 @@ enum { BC_OP_GEMM = 0, BC_OP_GN_STATS = 1, BC_OP_GN_FINALIZE = 2, BC_OP_GN_APPLY
        BC_OP_MEMSET_ZERO = 24, BC_OP_ROWCHAIN_MIDX = 25, BC_OP_ROWCHAIN_PACK_KV = 26, BC_OP_ROWCHAIN_SUM = 27, BC_OP_CTX_FOLD = 28, BC_OP_DUP_HALVES = 29,
        BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_CFG_SCHEDULER_STEP3 = 31, BC_OP_ASSEMBLE_INPUT_SCALED = 32,
        BC_OP_ASSEMBLE_IM2COL_SCALED = 33, BC_OP_SCHEDULER_STEP_SINGLE = 34, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND = 35,
-       BC_OP_TIMESTEP_EMBEDDING_COND = 36, BC_OP_COUNT = 37 };
+       BC_OP_TIMESTEP_EMBEDDING_COND = 36, BC_OP_FREEU = 37, BC_OP_COUNT = 38 };
 typedef struct BcPlanBuffer {
     const char* name;        /* "" for anonymous workspace; named buffers are found again with bc_plan_buffer */
     const void* address;     /* the address the launch records were built against */

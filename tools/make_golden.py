@@ -1070,6 +1070,139 @@ def golden_pipeline_call_lcm():
     np.savez_compressed(os.path.join(OUT, "pipeline_call_lcm.npz"), **out)
 
 
+# ------------------------------------------------------------------------------------------------ FreeU
+FREEU = (0.9, 0.2, 1.5, 1.6)                 # (s1, s2, b1, b2)
+FREEU_FILTER_ONLY = (0.9, 0.2, 1.0, 1.0)     # b = 1: only the Fourier filter acts (a scale-only implementation equals eps_off here)
+FREEU_BAR = 1e-2                             # the GPU tests' bar (max-abs / scale); the variants must lie >= 10 x that apart
+FREEU_GEOMETRIES = {"wide16": (2, 16, 32), "wide12": (2, 12, 24), "square16": (1, 16, 16)}      # UNet canvas (B, H, W)
+FREEU_RES_SCALE = 0.1
+
+
+def _freeu_residual_shapes(H, W):
+    """(channels, h, w) of the 12 down, the mid and the 15 up residuals of the tiny UNet on an H x W canvas (the right-hand square
+    slices the pipeline passes, pipe:1085-1087)."""
+    boc = TINY["boc"]
+    sizes, h, w = [], H, W
+    for i in range(len(boc)):
+        sizes.append((h, w))
+        if i < len(boc) - 1:
+            h, w = (h + 1) // 2, (w + 1) // 2
+    down = [(boc[0],) + sizes[0]]
+    for i in range(len(boc)):
+        down += [(boc[i],) + sizes[i]] * 2
+        if i < len(boc) - 1:
+            down.append((boc[i],) + sizes[i + 1])
+    rev, up = list(reversed(boc)), []
+    for i in range(len(boc)):
+        up += [(rev[i],) + sizes[len(boc) - 1 - i]] * 3
+        if i < len(boc) - 1:
+            up.append((rev[i],) + sizes[len(boc) - 2 - i])
+    sq = lambda s: (s[0], s[1], min(s[1], s[2]))
+    return [sq(s) for s in down], sq((boc[-1],) + sizes[-1]), [sq(s) for s in up]
+
+
+def freeu_residuals(seed, B, H, W):
+    """The residual tensors of a FreeU case: seeded normal draws times FREEU_RES_SCALE (tests/test_freeu_gpu.py regenerates them from the
+    stored seed - 28 tensors per geometry are not stored)."""
+    down, mid, up = _freeu_residual_shapes(H, W)
+    mk = lambda i, s: g(seed + i, B, *s) * FREEU_RES_SCALE
+    return [mk(i, s) for i, s in enumerate(down)], mk(100, mid), [mk(200 + i, s) for i, s in enumerate(up)]
+
+
+def golden_freeu():
+    """The tiny UNet of build_tiny() with the reference's `enable_freeu` (unet_2d_condition.py:839-861 -> apply_freeu, torch_utils.py:
+    93-148), laid out like unet_tiny_timecond.npz: a 16 x 32 canvas (FreeU sites 2 x 4 and 4 x 8), a 12 x 24 canvas (2 x 3 and 3 x 6: odd
+    and non-power-of-two sizes, where the reference's filter runs in fp32) and a square 16 x 16 one (2 x 2 and 4 x 4), each with residuals
+    added as BlobNet's are (seeded stand-ins, freeu_residuals) and with (s1, s2, b1, b2) = FREEU; plus `eps_off` (FreeU disabled) and
+    `eps_filter_only` (FREEU_FILTER_ONLY).  Asserts that both variants lie at least 10 x the GPU bar away from eps_off."""
+    unet, _ = build_tiny()
+    c = TINY
+    out = {"freeu": np.array(FREEU), "freeu_filter_only": np.array(FREEU_FILTER_ONLY), "timestep": np.array(981),
+           "res_scale": np.array(FREEU_RES_SCALE)}
+    t = torch.tensor(981)
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    for n, (name, (B, H, W)) in enumerate(FREEU_GEOMETRIES.items()):
+        seed = 1000 * (n + 1)
+        x_u, ehs = g(seed + 500, B, 5, H, W), g(seed + 501, B, 7, c["ctx"])
+        down, mid, up = freeu_residuals(seed, B, H, W)
+        res = lambda: dict(down_block_add_samples=[r.clone() for r in down], mid_block_add_sample=mid.clone(),
+                           up_block_add_samples=[r.clone() for r in up])
+        run = lambda: unet(x_u, t, encoder_hidden_states=ehs, return_dict=False, **res())[0].numpy()
+        unet.disable_freeu()
+        eps_off = run()
+        unet.enable_freeu(*FREEU)
+        eps = run()
+        unet.enable_freeu(*FREEU_FILTER_ONLY)
+        eps_filter = run()
+        unet.disable_freeu()
+        assert np.array_equal(run(), eps_off)
+        out.update({f"{name}_unet_in": x_u.numpy(), f"{name}_ehs": ehs.numpy(), f"{name}_res_seed": np.array(seed),
+                    f"{name}_eps": eps, f"{name}_eps_off": eps_off, f"{name}_eps_filter_only": eps_filter})
+        r1, r2 = rel(eps, eps_off), rel(eps_filter, eps_off)
+        print(f"freeu {name} ({B} x {H} x {W}): eps vs eps_off {r1:.3f} = {r1 / FREEU_BAR:.0f} x the bar, filter only vs eps_off {r2:.3f} = "
+              f"{r2 / FREEU_BAR:.0f} x the bar, eps std {eps.std():.4f}")
+        assert r1 >= 10 * FREEU_BAR and r2 >= 10 * FREEU_BAR, (name, r1, r2)
+    np.savez_compressed(os.path.join(OUT, "unet_tiny_freeu.npz"), **out)
+    print("unet_tiny_freeu.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "unet_tiny_freeu.npz")) / 1024))
+
+
+def golden_pipeline_call_freeu():
+    """The reference's own `__call__` (pipe:743-1166) after `pipe.enable_freeu(*FREEU)` (pipeline_utils.py:1905-1925): DDIM, 3 steps, the
+    case `ddim_neg2` of pipeline_call.npz with its own seeds, images and scores those of pipeline_call.npz.  Stores the final latents
+    with FreeU on, with other values (`latents_other`) and with FreeU disabled again (`latents_off`), and the loop-entry tensors."""
+    from PIL import Image
+    from tests.common import FakeTokenizer, pipeline_cases
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"], seed=2031, rng_seed=37)
+    kw.pop("scheduler")
+    kw["num_inference_steps"] = 3
+    sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+    pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                          safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+    pipe.set_progress_bar_config(disable=True)
+    entry = {"lat": []}
+
+    def tap(fn, key):
+        def wrapped(*a, **k_):
+            r_ = fn(*a, **k_)
+            if key == "lat":
+                entry["lat"].append(r_.detach().clone())
+            else:
+                entry[key] = r_
+            return r_
+        return wrapped
+    pipe.encode_prompt = tap(pipe.encode_prompt, "prompt")
+    pipe.encode_latents = tap(pipe.encode_latents, "lat")
+    pipe.encode_image_dinov2 = tap(pipe.encode_image_dinov2, "dino")
+    seed, rng_seed = kw.pop("seed"), kw.pop("rng_seed")
+    other = (0.6, 0.4, 1.2, 1.4)
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(kw["num_inference_steps"]),
+           "freeu": np.array(FREEU), "freeu_other": np.array(other)}
+
+    def call():
+        torch.manual_seed(rng_seed)
+        return pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                    height=64, width=64, generator=torch.Generator().manual_seed(seed), output_type="latent", **kw).images.numpy()
+    pipe.enable_freeu(*FREEU)
+    out["latents"] = call()
+    pe, ne = entry["prompt"]
+    out["entry_prompt_embeds"], out["entry_negative_prompt_embeds"] = pe.numpy(), ne.numpy()
+    out["entry_fg_latents"] = entry["lat"][0][:1].numpy()
+    out["entry_bg_latents"] = entry["lat"][1][:1].numpy()
+    out["entry_dino"] = entry["dino"].numpy()
+    pipe.enable_freeu(*other)
+    out["latents_other"] = call()
+    pipe.disable_freeu()
+    out["latents_off"] = call()
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    print("pipeline __call__ freeu: latents std %.4f; vs off %.3f, other vs on %.3f (max-abs / scale)" %
+          (out["latents"].std(), rel(out["latents"], out["latents_off"]), rel(out["latents_other"], out["latents"])))
+    assert rel(out["latents"], out["latents_off"]) >= 10 * FREEU_BAR and rel(out["latents_other"], out["latents"]) >= 10 * FREEU_BAR
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_freeu.npz"), **out)
+    print("pipeline_call_freeu.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "pipeline_call_freeu.npz")) / 1024))
+
+
 # ------------------------------------------------------------------------------------------------ 4. pipeline loop
 class _FakeVaeCfg:
     scaling_factor = 0.18215
@@ -1857,6 +1990,8 @@ if __name__ == "__main__":
     golden_loop_lcm()
     golden_unet_timecond()
     golden_pipeline_call_lcm()
+    golden_freeu()
+    golden_pipeline_call_freeu()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
