@@ -468,6 +468,9 @@ extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
         BC_CHECK_ARG(p.Hout == (p.Hv + pads - 3) / p.stride + 1 && p.Wout == (p.Wv + pads - 3) / p.stride + 1,
                      "bc_gemm: conv output size %dx%d inconsistent with input %dx%d stride %d", p.Hout, p.Wout, p.Hv, p.Wv, p.stride);
         BC_CHECK_ARG(p.A2 == nullptr || p.tile_cfg == BC_TILE_HALO || p.tile_cfg == BC_TILE_WREG, "bc_gemm: conv mode takes a single source (except BC_TILE_HALO / BC_TILE_WREG)");
+        // (the gather kernels address pixel * Cin: only the LDS-resident halo convolutions take a pixel stride of their own)
+        BC_CHECK_ARG(p.lda == 0 || p.lda == p.Cin || p.tile_cfg == BC_TILE_HALO || p.tile_cfg == BC_TILE_WREG,
+                     "bc_gemm: conv mode reads packed pixels (lda=%d, Cin=%d): a wider pixel stride needs BC_TILE_HALO / BC_TILE_WREG", p.lda, p.Cin);
         p.rows_per_batch = p.Hout * p.Wout;
         if (p.out_w <= 0) p.out_w = p.Wout;
         g.fast_k = (p.Cin % BK == 0);
@@ -596,6 +599,8 @@ extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
                      (!p.R || (p.ldr % 8 == 0 && aligned16(p.R))) && (!p.R2 || (p.ldr2 % 8 == 0 && aligned16(p.R2)));
     g.vec_transposed = p.out_mode == BC_OUT_F16_T && p.rows_per_batch % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) &&
                        p.act == BC_ACT_NONE && !p.rowvec && !p.colscale && !p.R && !p.R2;
+    // (conv_halo.hip / conv_wreg.hip store an unsplit launch with the 8-column epilogue, 16-byte loads and stores, whatever the output's layout)
+    BC_CHECK_ARG(!halo || g.vec_epilogue, "bc_gemm: BC_TILE_HALO / BC_TILE_WREG need an fp16 row-major output, 16-byte aligned C / R / R2 and widths %% 8 == 0");
     if (p.gn_tot) {
         // (a workgroup's rows must belong to one image: its statistics go to that image's totals)
         const int slab_rows = p.splitk > 1 ? SK_ROWS : g.bm;

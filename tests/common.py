@@ -16,6 +16,20 @@ def g(seed, *shape):
     return torch.from_numpy(np.random.Generator(np.random.PCG64(seed)).standard_normal(shape).astype(np.float32))
 
 
+def close(a, b, rtol=2e-3, atol=None, what=""):
+    """Every element of `a` within atol + rtol |b| of the reference `b` (atol defaults to 2e-3 of the reference's scale).  An output that is
+    not finite where the reference is finite fails whatever the bars: NaN compares false against any bar."""
+    a = a.detach().float().cpu()
+    b = b.detach().float().cpu()
+    if atol is None:
+        atol = 2e-3 * max(1.0, float(b.abs().max()))
+    err = (a - b).abs()
+    bad = err > atol + rtol * b.abs()
+    nonfinite = ~torch.isfinite(a) & torch.isfinite(b)
+    assert not nonfinite.any(), f"{what}: {int(nonfinite.sum())}/{a.numel()} non-finite where the reference is finite"
+    assert not bad.any(), f"{what}: {int(bad.sum())}/{bad.numel()} off, max err {float(err.max()):.4e} (atol {atol:.2e})"
+
+
 def tiny_cfgs():
     c = TINY
     ucfg = NetConfig(in_channels=5, out_channels=4, block_out_channels=c["boc"], num_heads=c["heads"],

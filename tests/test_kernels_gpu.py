@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from tests.common import g  # noqa: E402
+from tests.common import close, g  # noqa: E402,F401  (close: re-exported, tests/test_conv_halo_gpu.py imports it from here)
 
 
 @pytest.fixture(scope="module")
@@ -34,16 +34,6 @@ def run(rec, fn):
 
 def h(x):
     return x.half().cuda()
-
-
-def close(a, b, rtol=2e-3, atol=None, what=""):
-    a = a.detach().float().cpu()
-    b = b.detach().float().cpu()
-    if atol is None:
-        atol = 2e-3 * max(1.0, float(b.abs().max()))
-    err = (a - b).abs()
-    bad = err > atol + rtol * b.abs()
-    assert not bad.any(), f"{what}: {int(bad.sum())}/{bad.numel()} off, max err {float(err.max()):.4e} (atol {atol:.2e})"
 
 
 # ---------------------------------------------------------------------------------------------------- GEMM
