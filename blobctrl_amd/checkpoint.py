@@ -9,7 +9,9 @@ What the reference loads (README.md:115-128, scripts/blobctrl_inference.py:222-2
     (D/loaders/unet.py:271-340, D/utils/state_dict_utils.py:38-50,141-171); rank = lora_B.shape[1]; scale = alpha / rank
     with the alpha defaults of D/utils/peft_utils.py:150-192 (no alpha keys: alpha = the FIRST module's rank for every
     module).  Linear and Conv2d LoRA pairs (conv_in included) are merged into the base weights once - the engine has no
-    adapter path at run time.
+    adapter path at run time.  The same file may hold `text_encoder.` keys (load_lora_into_text_encoder), and it may be a kohya /
+    sd-scripts file (`lora_unet_*` / `lora_te_*`, D/loaders/lora_conversion_utils.py:126-328): `split_lora_state_dict` gives both
+    models their (lora, alphas) pair from either form.
 
 Pure host code (no GPU): safetensors files are read with a small reader of the published format (8-byte little-endian
 header length, JSON header, raw little-endian tensor bytes), so the converter works without the `safetensors` package.
@@ -138,22 +140,125 @@ def convert_unet_lora_key(k: str) -> str:
     return k
 
 
+# The text encoder's spellings (D/utils/state_dict_utils.py:54-80, convert_state_dict_to_peft): the old attention-processor names, the
+# `lora_linear_layer` names and peft's own; first matching pattern wins
+_TE_LORA_RENAMES = (
+    (".to_q_lora.down", ".q_proj.lora_A"), (".to_q_lora.up", ".q_proj.lora_B"),
+    (".to_k_lora.down", ".k_proj.lora_A"), (".to_k_lora.up", ".k_proj.lora_B"),
+    (".to_v_lora.down", ".v_proj.lora_A"), (".to_v_lora.up", ".v_proj.lora_B"),
+    (".to_out_lora.down", ".out_proj.lora_A"), (".to_out_lora.up", ".out_proj.lora_B"),
+    (".lora_linear_layer.down", ".lora_A"), (".lora_linear_layer.up", ".lora_B"),
+)
+
+
+def convert_text_encoder_lora_key(k: str) -> str:
+    for pat, new in _TE_LORA_RENAMES:
+        if pat in k:
+            return k.replace(pat, new)
+    return k
+
+
+# ---- kohya / sd-scripts files: `lora_unet_<module path, "." -> "_">.lora_down.weight | .lora_up.weight | .alpha`
+KOHYA_PREFIXES = ("lora_unet_", "lora_te_", "lora_te1_", "lora_te2_")
+_KOHYA_LDM = ("lora_unet_input_blocks_", "lora_unet_middle_block_", "lora_unet_output_blocks_")
+_KOHYA_SUFFIXES = ((".lora_down.weight", ".lora_A.weight"), (".lora_up.weight", ".lora_B.weight"), (".alpha", ".alpha"))
+
+
+def is_kohya(raw) -> bool:
+    """lora_pipeline.py:210-211: every key carries one of the sd-scripts prefixes."""
+    return len(raw) > 0 and all(k.startswith(KOHYA_PREFIXES) for k in raw)
+
+
+def kohya_table(modules) -> Dict[str, str]:
+    """flattened name -> module name.  sd-scripts flattens a module path by writing "_" for "."; module names hold "_" themselves
+    (`down_blocks`, `to_q`, `time_emb_proj`), so the way back is a table of the model's modules, not string surgery."""
+    return {m.replace(".", "_"): m for m in modules}
+
+
+def _weight_modules(shapes) -> list:
+    return [k[: -len(".weight")] for k, v in shapes.items() if k.endswith(".weight") and len(tuple(v)) >= 2]
+
+
+def sd15_lora_modules():
+    """(UNet modules, text-encoder modules) of SD-1.5 that can carry a LoRA pair: every Linear / Conv2d of the UNet schema and of CLIP-L
+    (names only - they do not depend on the widths).  The tables used when the caller has no model at hand."""
+    from . import synth
+    unet = _weight_modules(synth.trunk_param_shapes(4, (320, 640, 1280, 1280), 2, 768, 4, blobnet=False, time_cond_proj_dim=256))
+    te = [m for m in _weight_modules(synth.clip_text_param_shapes()) if ".encoder.layers." in m]
+    return unet, te
+
+
+def convert_kohya_state_dict(raw: Dict[str, torch.Tensor], unet_modules=None, te_modules=None, what: str = "state dict"):
+    """A kohya / sd-scripts state dict -> the same tensors under `unet.<module>.lora_A.weight | .lora_B.weight | .alpha` and
+    `text_encoder.<module>...`, in file order: what `_convert_non_diffusers_lora_to_diffusers` + the peft key conversion of the reference
+    arrive at (lora_conversion_utils.py:126-328).  `unet_modules` / `te_modules`: the module names of the models the adapter is for
+    (default: SD-1.5's)."""
+    if any("dora_scale" in k for k in raw):
+        raise NotImplementedError("DoRA adapters (dora_scale) are not supported")
+    if any(k.startswith("lora_te2_") for k in raw):
+        raise ValueError(f"{what}: lora_te2_ keys are for a second text encoder (SDXL); this pipeline has one")
+    ldm = [k for k in raw if k.startswith(_KOHYA_LDM)]
+    if ldm:
+        raise NotImplementedError(f"{what}: LDM block naming (lora_unet_input_blocks_ / middle_block / output_blocks, e.g. {ldm[0]}) is "
+                                  "not supported; convert the file to diffusers block names first")
+    if unet_modules is None or te_modules is None:
+        du, dt = sd15_lora_modules()
+        unet_modules, te_modules = (du if unet_modules is None else unet_modules), (dt if te_modules is None else te_modules)
+    tables = {"lora_unet_": ("unet.", kohya_table(unet_modules)), "lora_te_": ("text_encoder.", kohya_table(te_modules))}
+    tables["lora_te1_"] = tables["lora_te_"]
+    out, left = OrderedDict(), []
+    for k, v in raw.items():
+        flat, _, suffix = k.partition(".")
+        pre = next(p for p in KOHYA_PREFIXES if flat.startswith(p))
+        model, table = tables[pre]
+        mod = table.get(flat[len(pre):])
+        new = dict(_KOHYA_SUFFIXES).get("." + suffix)
+        if mod is None or new is None:
+            left.append(k)
+        else:
+            out[model + mod + new] = v
+    if left:                                                       # LyCORIS hada_* / lokr_* and the like (lora_conversion_utils.py:213-215)
+        raise ValueError(f"{what}: the following keys are not LoRA down / up / alpha tensors of a known module: {', '.join(left)}")
+    return out
+
+
 def load_lora(path: str, unet_identifier_key: str = "unet") -> Tuple[Dict[str, torch.Tensor], Dict[str, float]]:
     """-> (lora, alphas): `lora` has `<module>.lora_A.weight` / `<module>.lora_B.weight`; `alphas[<module>]` is the effective
     lora_alpha of each module, so `merge_lora(sd, lora, alphas)` applies W + (alpha / r) * B @ A exactly like the peft
-    adapter the reference injects."""
-    return lora_from_state_dict(read_safetensors(_model_file(path)), unet_identifier_key, what=path)
+    adapter the reference injects.  The UNet part of the file: diffusers or kohya keys, text-encoder keys beside them are left out."""
+    raw = read_safetensors(_model_file(path))
+    if is_kohya(raw) or any(k.startswith("text_encoder.") for k in raw):
+        unet, _ = split_lora_state_dict(raw, what=path)
+        if unet is None:
+            raise ValueError(f"{path}: no UNet LoRA tensors found")
+        return unet
+    return lora_from_state_dict(raw, unet_identifier_key, what=path)
 
 
-def lora_from_state_dict(raw: Dict[str, torch.Tensor], unet_identifier_key: str = "unet", what: str = "state dict"):
-    """The same conversion for an in-memory state dict (`pipeline.load_lora_weights(dict)`, lora_pipeline.py:94-100)."""
+def split_lora_state_dict(raw: Dict[str, torch.Tensor], unet_modules=None, te_modules=None, what: str = "state dict"):
+    """One adapter file -> ((lora, alphas) of the UNet or None, (lora, alphas) of the text encoder or None), from diffusers keys
+    (`unet.*` / bare, `text_encoder.*`) or kohya keys (lora_pipeline.py:94-117)."""
+    if is_kohya(raw):
+        raw = convert_kohya_state_dict(raw, unet_modules, te_modules, what)
+    if any(k.startswith("text_encoder_2.") for k in raw):
+        raise ValueError(f"{what}: text_encoder_2 keys are for a second text encoder (SDXL); this pipeline has one")
+    te = OrderedDict((k, v) for k, v in raw.items() if k.startswith("text_encoder."))
+    unet = OrderedDict((k, v) for k, v in raw.items() if k not in te)
+    return (lora_from_state_dict(unet, what=what) if unet else None,
+            lora_from_state_dict(te, "text_encoder", what=what, convert=convert_text_encoder_lora_key) if te else None)
+
+
+def lora_from_state_dict(raw: Dict[str, torch.Tensor], unet_identifier_key: str = "unet", what: str = "state dict",
+                         convert=convert_unet_lora_key):
+    """The same conversion for an in-memory state dict (`pipeline.load_lora_weights(dict)`, lora_pipeline.py:94-100).  `convert`: the key
+    renaming of the model the tensors are for (the UNet's, or `convert_text_encoder_lora_key`)."""
     path = what
     pre = unet_identifier_key + "."
     keys = [k for k in raw if k.startswith(pre)]
     sd = OrderedDict((k[len(pre):], raw[k]) for k in keys) if keys else raw           # unet.py:289-301
     net_alpha = {k[: -len(".alpha")]: float(v) for k, v in sd.items() if k.endswith(".alpha")}
     sd = OrderedDict((k, v) for k, v in sd.items() if not k.endswith(".alpha"))
-    lora = OrderedDict((convert_unet_lora_key(k), v.float()) for k, v in sd.items())
+    lora = OrderedDict((convert(k), v.float()) for k, v in sd.items())
     if any("lora_magnitude_vector" in k for k in lora):
         raise NotImplementedError("DoRA adapters (lora_magnitude_vector) are not supported")
     if not any(".lora_A." in k or ".lora_B." in k for k in lora):
@@ -167,7 +272,7 @@ def lora_from_state_dict(raw: Dict[str, torch.Tensor], unet_identifier_key: str 
     # alpha entries are keyed like the down weight they belong to ("<module>.lora.down.weight.alpha") or by the bare module
     conv_alpha = {}
     for k, a in net_alpha.items():
-        ck = convert_unet_lora_key(k)
+        ck = convert(k)
         conv_alpha[ck.split(".lora_A.")[0] if ".lora_A." in ck else ck] = a
     if conv_alpha:
         vals = list(conv_alpha.values())

@@ -6,13 +6,22 @@ Token + position embedding gather -> L x { x + out_proj(causal attention(LN1 x))
 LayerNorm.  Reuses the hot path's LayerNorm / MFMA GEMM / flash-attention kernels (causal-mask entry point); biases, quick_gelu
 and the residual adds are GEMM epilogues.  Tokenisation stays on the host (callers pass `input_ids`).
 """
+from collections import OrderedDict
+
 import torch
 
 from . import _lib
 from .launch import Recorder, run_graphed
+from .weights import LoraAdapters
 
 
-class CLIPTextModel:
+class CLIPTextModel(LoraAdapters):
+    """LoRA (load_lora_into_text_encoder of the reference): the fp32 state dict stays on the host with the adapter registry of the UNet
+    shell (weights.LoraAdapters).  Adapters are merged in fp32 before the fp16 cast and the q|k concatenation; when the merged weights
+    change, the device tensors are refilled IN PLACE, so every recorded plan keeps its addresses and gives the new result."""
+
+    _LORA_TARGETS = (("self_attn.v_proj", "v"), ("self_attn.out_proj", "o"), ("mlp.fc1", "fc1"), ("mlp.fc2", "fc2"))
+
     def __init__(self, state_dict, num_heads: int = 12, eps: float = 1e-5, device="cuda:0"):
         self.device = torch.device(device)
         # (a host device is accepted for CONSTRUCTION only - loading / inspecting checkpoints; running refuses it: `_need_gpu`)
@@ -20,6 +29,8 @@ class CLIPTextModel:
         # on-disk layout has a "text_model." prefix (transformers 4.x); 5.x dropped it
         sd = {(k[len("text_model."):] if k.startswith("text_model.") else k): v.detach().float().cpu()
               for k, v in state_dict.items()}
+        self._sd = sd
+        self._init_lora()
         dev = self.device
         self.heads, self.eps = num_heads, eps
         self.vocab, self.D = sd["embeddings.token_embedding.weight"].shape
@@ -35,17 +46,41 @@ class CLIPTextModel:
         for i in range(self.L):
             p = f"encoder.layers.{i}."
             a = p + "self_attn."
-            h[p + "qk.weight"] = torch.cat([sd[a + "q_proj.weight"], sd[a + "k_proj.weight"]], 0).half().to(dev)
             f[p + "qk.bias"] = torch.cat([sd[a + "q_proj.bias"], sd[a + "k_proj.bias"]], 0).to(dev)
-            for src, dst in ((a + "v_proj", "v"), (a + "out_proj", "o"), (p + "mlp.fc1", "fc1"), (p + "mlp.fc2", "fc2")):
-                h[p + dst + ".weight"] = sd[src + ".weight"].half().to(dev)
-                f[p + dst + ".bias"] = sd[src + ".bias"].to(dev)
+            for src, dst in self._LORA_TARGETS:
+                f[p + dst + ".bias"] = sd[p + src + ".bias"].to(dev)
             for nm in ("layer_norm1.weight", "layer_norm1.bias", "layer_norm2.weight", "layer_norm2.bias"):
                 f[p + nm] = sd[p + nm].to(dev)
         f["final.weight"] = sd["final_layer_norm.weight"].to(dev)
         f["final.bias"] = sd["final_layer_norm.bias"].to(dev)
         self.h, self.f = h, f
         self._plans = {}
+        self._fill(1.0)
+
+    # ---- the weights LoRA can target: q|k, v, out, fc1, fc2 of every layer, fp16 on the device
+    def _fill(self, lora_scale: float):
+        sd = self.effective_state_dict(lora_scale)
+        for i in range(self.L):
+            p = f"encoder.layers.{i}."
+            new = {p + "qk.weight": torch.cat([sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"]], 0).half()}
+            for src, dst in self._LORA_TARGETS:
+                new[p + dst + ".weight"] = sd[p + src + ".weight"].half()
+            for k, v in new.items():
+                if k in self.h:
+                    self.h[k].copy_(v)          # in place: the recorded plans hold this address
+                else:
+                    self.h[k] = v.to(self.device)
+        self._filled = self._lora_state(lora_scale)
+
+    def _lora_changed(self):
+        """No work now: `__call__` refills the device tensors when the state they were filled for is not the one it is asked for."""
+        self._filled = None
+
+    def load_lora_adapter(self, lora, alphas, adapter_name="default", weight: float = 1.0):
+        """`lora` / `alphas` as checkpoint.split_lora_state_dict returns them; module names with or without the `text_model.` prefix."""
+        strip = lambda k: k[len("text_model."):] if k.startswith("text_model.") else k
+        super().load_lora_adapter(OrderedDict((strip(k), v) for k, v in lora.items()), {strip(m): a for m, a in alphas.items()},
+                                  adapter_name, weight)
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, device="cuda:0", **_ignored):
@@ -111,15 +146,19 @@ class CLIPTextModel:
         return P
 
     @torch.no_grad()
-    def __call__(self, input_ids: torch.Tensor, attention_mask=None, clip_skip=None):
+    def __call__(self, input_ids: torch.Tensor, attention_mask=None, clip_skip=None, lora_scale: float = 1.0):
         """input_ids [B, T] int64 (T <= max_position_embeddings) -> (prompt_embeds [B, T, D] fp16,), as `text_encoder(ids)[0]`;
-        `clip_skip=k` returns final_layer_norm(hidden_states[-(k+1)]) (pipe:604-611)."""
+        `clip_skip=k` returns final_layer_norm(hidden_states[-(k+1)]) (pipe:604-611).  `lora_scale`: the per-call scale of the active
+        adapters (encode_prompt's scale_lora_layers, pipe:551-558); the device weights stay at the last scale asked for."""
         if attention_mask is not None:
             raise NotImplementedError("SD-1.5's text encoder config has no use_attention_mask (pipe:593-596)")
         B, T = input_ids.shape
         if T > self.max_pos:
             raise ValueError(f"sequence length {T} exceeds max_position_embeddings {self.max_pos}")
         P = self._plan(B, T)
+        if self._lora_state(lora_scale) != self._filled:
+            torch.cuda.synchronize(self.device)             # (no replay may still be reading the weights)
+            self._fill(lora_scale)
         if clip_skip not in P.final:
             raise ValueError(f"clip_skip={clip_skip} not supported (0 < clip_skip < min(layers, 4))")
         P.ids.copy_(input_ids.to(self.device, torch.int64))

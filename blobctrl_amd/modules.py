@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from .engine import Residuals, TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder, run_graphed
-from .weights import PackedTrunk, merge_lora, pad8
+from .weights import LoraAdapters, PackedTrunk, lora_scale_of, pad8
 
 
 def _stream():
@@ -35,7 +35,7 @@ class ModelConfig(dict):
             raise AttributeError(k) from e
 
 
-class _TrunkModule(torch.nn.Module):
+class _TrunkModule(LoraAdapters, torch.nn.Module):
     """An `nn.Module` (DiffusionPipeline.register_modules, D/pipelines/pipeline_utils.py:788, accepts it; `.parameters()`, `.dtype`,
     `.device`, `.eval()`, `.to()` behave) whose forward runs a compiled launch plan.  The weights are the packed fp16 / fp32 arenas;
     they are exposed as two frozen Parameters that SHARE the arenas' storage.  `.to()` / `.half()` / `.float()` are no-ops: the layouts
@@ -50,7 +50,8 @@ class _TrunkModule(torch.nn.Module):
         self.trunk_config = config
         self._sd = None if isinstance(state_dict, PackedTrunk) else OrderedDict(state_dict)
         self._packed = state_dict if isinstance(state_dict, PackedTrunk) else None
-        self._adapters = OrderedDict()          # name -> dict(lora=, alphas=, weight=, active=)
+        self._init_lora()
+        self._lora_scale = 1.0                  # the scale the packed copy is (or will be) made for: set_lora_scale
         self._version = 0
         self._plans = {}
         self._make_config()
@@ -72,21 +73,18 @@ class _TrunkModule(torch.nn.Module):
             conditioning_channels=(config.in_channels - latent) if config.is_blobnet else None)
 
     # ---- weights: packed lazily from the host state dict + the active LoRA adapters
-    def effective_state_dict(self):
-        """The host state dict with every ACTIVE adapter merged (W + weight * (alpha / r) * B A, weights.merge_lora)."""
+    def effective_state_dict(self, lora_scale: float = 1.0):
+        """The host state dict with every ACTIVE adapter merged (W + lora_scale * weight * (alpha / r) * B A, weights.merge_lora).
+        Without argument: scale 1.0, whatever scale the packed copy was made for."""
         if self._sd is None:
             raise _lib.BlobCtrlHipError("this module was built from packed weights: no host state dict to edit")
-        sd = self._sd
-        for ad in self._adapters.values():
-            if ad["active"] and ad["weight"] != 0.0:
-                sd = merge_lora(sd, ad["lora"], ad["alphas"], adapter_scale=ad["weight"])
-        return sd
+        return super().effective_state_dict(lora_scale)
 
     @property
     def weights(self) -> PackedTrunk:
         if self._packed is None:
             _lib.load()
-            self._packed = PackedTrunk(self.effective_state_dict(), self._device, self.trunk_config.block_out_channels)
+            self._packed = PackedTrunk(self.effective_state_dict(self._lora_scale), self._device, self.trunk_config.block_out_channels)
         return self._packed
 
     @property
@@ -116,37 +114,25 @@ class _TrunkModule(torch.nn.Module):
         self._version += 1
 
     # ---- LoRA (D/loaders/unet.py:271-340 semantics: W + (alpha / r) * B A per target module; merged when the weights are packed)
+    # the registry itself (load_lora_adapter, set_adapters, unload_lora, delete_adapters, disable_lora, enable_lora) is weights.LoraAdapters;
+    # every edit of it drops the packed copy
+    def _lora_changed(self):
+        self._invalidate()
+
     def load_lora_adapter(self, lora, alphas, adapter_name="default", weight: float = 1.0):
         if self._sd is None:
             raise _lib.BlobCtrlHipError("this module was built from packed weights: LoRA must be merged before packing")
-        missing = [m for m in alphas if m + ".weight" not in self._sd]
-        if missing:
-            raise KeyError(f"LoRA targets not present in the model: {missing[:4]}{' ...' if len(missing) > 4 else ''}")
-        if adapter_name in self._adapters:
-            raise ValueError(f"Adapter name {adapter_name} already in use in the model - please select a new adapter name.")
-        self._adapters[adapter_name] = dict(lora=lora, alphas=alphas, weight=float(weight), active=True)
-        self._invalidate()
+        super().load_lora_adapter(lora, alphas, adapter_name, weight)
 
-    def set_adapters(self, adapter_names, weights=None):
-        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
-        ws = [1.0] * len(names) if weights is None else ([weights] * len(names) if not isinstance(weights, (list, tuple)) else list(weights))
-        if len(ws) != len(names):
-            raise ValueError(f"Length of adapter names {len(names)} is not equal to the length of their weights {len(ws)}.")
-        unknown = [n for n in names if n not in self._adapters]
-        if unknown:
-            raise ValueError(f"Adapter name(s) {set(unknown)} not in the list of present adapters: {set(self._adapters)}.")
-        before = [(n, a["active"], a["weight"]) for n, a in self._adapters.items()]
-        for n, a in self._adapters.items():
-            a["active"] = n in names
-        for n, w in zip(names, ws):
-            self._adapters[n]["weight"] = 1.0 if w is None else float(w)
-        if before != [(n, a["active"], a["weight"]) for n, a in self._adapters.items()]:
+    def set_lora_scale(self, lora_scale: float = 1.0):
+        """The per-call LoRA scale (`cross_attention_kwargs={"scale": s}`, scale_lora_layers of the reference: every active adapter's
+        weight times s, in all LoRA layers).  The packed copy is made for one (adapters, scale) state: a scale that changes the merged
+        weights drops it like `set_adapters` does, and it stays at that scale until a call asks for another.  With nothing to scale - no
+        adapter merged - nothing is dropped."""
+        lora_scale = float(lora_scale)
+        if self._sd is not None and self._lora_state(lora_scale) != self._lora_state(self._lora_scale):
             self._invalidate()
-
-    def unload_lora(self):
-        if self._adapters:
-            self._adapters.clear()
-            self._invalidate()
+        self._lora_scale = lora_scale
 
     @property
     def device(self):
@@ -390,6 +376,7 @@ class UNet2DConditionModel(_TrunkModule):
                 raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
             if tuple(timestep_cond.shape) != (B, dim):
                 raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
+        self.set_lora_scale(lora_scale_of(cross_attention_kwargs))          # (a change of scale re-packs: the plans below are then new ones)
         # through the dispatcher (torch.ops.blobctrl.unet_forward, ops.py); `timestep_cond` is the op's optional trailing argument
         from . import ops
         extra = () if timestep_cond is None else (timestep_cond,)

@@ -25,7 +25,7 @@ from . import _lib
 from .engine import TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder
 from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, table_class
-from .weights import PackedTrunk, pad8
+from .weights import PackedTrunk, lora_scale_of, pad8
 
 
 def get_guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -895,33 +895,83 @@ class StableDiffusionBlobNetPipeline:
     def set_progress_bar_config(self, **k):
         pass
 
-    # ---- LoRA (D/loaders/lora_pipeline.py:60-117 -> D/loaders/unet.py:271-340): UNet adapters only, merged when the UNet is packed
+    # ---- LoRA (D/loaders/lora_pipeline.py:60-117 -> D/loaders/unet.py:271-340, load_lora_into_text_encoder): one registry per model
+    # (weights.LoraAdapters), merged when the UNet is packed / when the text encoder's device tensors are filled
+    def _lora_models(self):
+        return [m for m in (self.unet, self.text_encoder) if hasattr(m, "_adapters")]
+
     def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name=None, weight_name=None, **kwargs):
         """`pipeline.load_lora_weights(unet_lora_path, adapter_name="default")` (inf:270-273).  A directory (with
-        `pytorch_lora_weights.safetensors` or `weight_name`), a .safetensors file, or a state dict; keys under `unet.` go to the
-        UNet (lora_pipeline.py:102-110); text-encoder LoRA keys are refused (the released BlobCtrl adapter has none)."""
+        `pytorch_lora_weights.safetensors` or `weight_name`), a .safetensors file, or a state dict, with diffusers keys or kohya /
+        sd-scripts keys (`lora_unet_*` / `lora_te_*`, e.g. the published LCM-LoRA).  Keys under `unet.` go to the UNet
+        (lora_pipeline.py:102-110), keys under `text_encoder.` to the text encoder, both under the same adapter name."""
         import os
-        from .checkpoint import load_lora, lora_from_state_dict
+        from .checkpoint import _model_file, read_safetensors, split_lora_state_dict
         src = pretrained_model_name_or_path_or_dict
         if isinstance(src, dict):
-            if any(k.startswith("text_encoder.") for k in src):
-                raise NotImplementedError("text-encoder LoRA is not supported")
-            lora, alphas = lora_from_state_dict(src)
+            raw, what = src, "state dict"
         else:
-            path = os.path.join(src, weight_name) if weight_name and os.path.isdir(src) else src
-            lora, alphas = load_lora(path)
-        name = adapter_name if adapter_name is not None else f"default_{len(self.unet._adapters)}"
-        self.unet.load_lora_adapter(lora, alphas, adapter_name=name)
+            what = os.path.join(src, weight_name) if weight_name and os.path.isdir(src) else src
+            raw = read_safetensors(_model_file(what))
+        mods = lambda sd, pre: [pre + k[: -len(".weight")] for k, v in sd.items() if k.endswith(".weight") and v.ndim >= 2]
+        te_sd = getattr(self.text_encoder, "_sd", None)
+        unet_part, te_part = split_lora_state_dict(raw, mods(self.unet._sd, "") if self.unet._sd is not None else None,
+                                                   mods(te_sd, "text_model.") if te_sd is not None else None, what=str(what))
+        if te_part is not None and te_sd is None:
+            raise ValueError(f"{what} holds text-encoder LoRA tensors, but this pipeline was built without a text encoder "
+                             "(text_encoder=None): it cannot apply them")
+        name = adapter_name
+        if name is None:
+            name = f"default_{max(len(m._adapters) for m in self._lora_models())}"
+        parts = [(m, part) for m, part in ((self.unet, unet_part), (self.text_encoder, te_part)) if part is not None]
+        done = []
+        try:
+            for m, (lora, alphas) in parts:
+                m.load_lora_adapter(lora, alphas, adapter_name=name)
+                done.append(m)
+        except Exception:                                       # (one adapter name means the same file in both models, or in neither)
+            for m in done:
+                m.delete_adapters([name])
+            raise
 
     def set_adapters(self, adapter_names, adapter_weights=None):
-        """`pipeline.set_adapters(["default"])` (inf:274): the active adapters and their weights (merged on the next call)."""
-        self.unet.set_adapters(adapter_names, adapter_weights)
+        """`pipeline.set_adapters(["default"])` (inf:274): the active adapters and their weights (merged on the next call), in the UNet
+        and in the text encoder; a model that does not hold one of the named adapters keeps the others."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        ws = adapter_weights if isinstance(adapter_weights, (list, tuple)) else [adapter_weights] * len(names)
+        if len(ws) != len(names):
+            raise ValueError(f"Length of adapter names {len(names)} is not equal to the length of their weights {len(ws)}.")
+        known = set().union(*(m._adapters for m in self._lora_models()))
+        if set(names) - known:
+            raise ValueError(f"Adapter name(s) {set(names) - known} not in the list of present adapters: {known}.")
+        for m in self._lora_models():
+            mine = [(n, w) for n, w in zip(names, ws) if n in m._adapters]
+            m.set_adapters([n for n, _ in mine], [w for _, w in mine])
 
     def fuse_lora(self, *a, **k):
         """Adapters are always merged into the packed weights: nothing to do."""
 
     def unload_lora_weights(self):
-        self.unet.unload_lora()
+        for m in self._lora_models():
+            m.unload_lora()
+
+    def delete_adapters(self, adapter_names):
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        for m in self._lora_models():
+            m.delete_adapters([n for n in names if n in m._adapters])
+
+    def disable_lora(self):
+        for m in self._lora_models():
+            m.disable_lora()
+
+    def enable_lora(self):
+        for m in self._lora_models():
+            m.enable_lora()
+
+    def get_list_adapters(self):
+        """{"unet": [names], "text_encoder": [names]}: the models that hold adapters (lora_base.py get_list_adapters)."""
+        held = {"unet": self.unet, "text_encoder": self.text_encoder}
+        return {k: list(m._adapters) for k, m in held.items() if getattr(m, "_adapters", None)}
 
     # ---- FreeU (D/pipelines/pipeline_utils.py:1905-1929, StableDiffusionMixin): forwarded to the UNet; the loop engine reads the state there
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
@@ -936,7 +986,10 @@ class StableDiffusionBlobNetPipeline:
         self.unet.disable_freeu()
 
     def get_active_adapters(self):
-        return [n for n, a in self.unet._adapters.items() if a["active"]]
+        out = []
+        for m in self._lora_models():
+            out += [n for n in m.active_adapters() if n not in out]
+        return out
 
     @property
     def guidance_scale(self):
@@ -1004,6 +1057,8 @@ class StableDiffusionBlobNetPipeline:
     def encode_prompt(self, prompt, device, num_images_per_prompt, do_classifier_free_guidance, negative_prompt=None,
                       prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                       lora_scale: Optional[float] = None, clip_skip: Optional[int] = None):
+        """pipe:508-687.  `lora_scale`: the scale of the text encoder's active adapters for this call (pipe:551-558); None = 1.0."""
+        te_kw = {"lora_scale": 1.0 if lora_scale is None else float(lora_scale)} if hasattr(self.text_encoder, "_adapters") else {}
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -1014,7 +1069,7 @@ class StableDiffusionBlobNetPipeline:
             if self.tokenizer is None or self.text_encoder is None:
                 raise ValueError("this pipeline was built without tokenizer / text_encoder: pass prompt_embeds")
             ids = self._tokenize(prompt, getattr(self.tokenizer, "model_max_length", 77))
-            prompt_embeds = self.text_encoder(ids.to(self.device), clip_skip=clip_skip)[0]
+            prompt_embeds = self.text_encoder(ids.to(self.device), clip_skip=clip_skip, **te_kw)[0]
         prompt_embeds = prompt_embeds.to(self.device)
         bs_embed, seq_len, _ = prompt_embeds.shape
         prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs_embed * num_images_per_prompt, seq_len, -1)
@@ -1035,7 +1090,7 @@ class StableDiffusionBlobNetPipeline:
             if self.tokenizer is None or self.text_encoder is None:
                 raise ValueError("this pipeline was built without tokenizer / text_encoder: pass negative_prompt_embeds")
             ids = self._tokenize(uncond_tokens, prompt_embeds.shape[1])
-            negative_prompt_embeds = self.text_encoder(ids.to(self.device))[0]
+            negative_prompt_embeds = self.text_encoder(ids.to(self.device), **te_kw)[0]
         if do_classifier_free_guidance:
             seq_len = negative_prompt_embeds.shape[1]
             negative_prompt_embeds = negative_prompt_embeds.to(self.device).repeat(1, num_images_per_prompt, 1)
@@ -1101,8 +1156,10 @@ class StableDiffusionBlobNetPipeline:
         if timesteps is not None and getattr(self._scheduler, "kind", None) not in ("dpmsolver", "euler", "lcm"):
             # the reference's retrieve_timesteps (pipe:142-148) honours them only for schedulers whose set_timesteps takes them
             raise NotImplementedError("custom `timesteps` are not tabulated; pass num_inference_steps")
-        if cross_attention_kwargs:
-            raise NotImplementedError("cross_attention_kwargs (runtime LoRA scale) are not supported: LoRA is merged at load")
+        # pipe:934-945, 1084: {"scale": s} scales every active adapter for this call, in the text encoder when it encodes the prompt and in
+        # the UNet (BlobNet has no LoRA and never sees it).  The UNet re-packs when the scale differs from the packed one, and `engine`
+        # below is re-pointed exactly as after `set_adapters`.
+        lora_scale = lora_scale_of(cross_attention_kwargs)
         # 0.1 align the control-guidance format (pipe:884-893)
         if not isinstance(blobnet_control_guidance_start, list) and isinstance(blobnet_control_guidance_end, list):
             blobnet_control_guidance_start = len(blobnet_control_guidance_end) * [blobnet_control_guidance_start]
@@ -1125,10 +1182,12 @@ class StableDiffusionBlobNetPipeline:
             batch_size = prompt_embeds.shape[0]
         self._guidance_scale, self._clip_skip = guidance_scale, clip_skip
         cfg = self.do_classifier_free_guidance
+        self.unet.set_lora_scale(lora_scale)
         # 3. prompt (pipe:937-949)
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt, self.device, num_images_per_prompt, cfg, negative_prompt,
                                                                    prompt_embeds=prompt_embeds,
-                                                                   negative_prompt_embeds=negative_prompt_embeds, clip_skip=clip_skip)
+                                                                   negative_prompt_embeds=negative_prompt_embeds, lora_scale=lora_scale,
+                                                                   clip_skip=clip_skip)
         if cfg:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds])
         # 5./6. timesteps and latents (pipe:953-968); the noise is drawn BEFORE the images are encoded, like the reference

@@ -41,6 +41,101 @@ def merge_lora(sd: Dict[str, torch.Tensor], lora: Dict[str, torch.Tensor], alpha
     return out
 
 
+class LoraAdapters:
+    """The adapter registry of a model shell that keeps its host state dict in `self._sd` (the UNet shell, the CLIP text encoder): named
+    adapters with a weight and an active flag, merged into the base weights by `effective_state_dict`.  A shell calls `_init_lora()` in
+    its constructor and says in `_lora_changed()` what an edit of the registry costs it."""
+
+    def _init_lora(self):
+        self._adapters = OrderedDict()          # name -> dict(lora=, alphas=, weight=, active=)
+        self._lora_enabled = True               # disable_lora() / enable_lora(): the registry stays, nothing is merged
+
+    def _lora_changed(self):
+        raise NotImplementedError
+
+    def _lora_state(self, lora_scale: float = 1.0):
+        """What the merged weights depend on: [(adapter, lora_scale * weight)] of the adapters that take part in the merge."""
+        if not self._lora_enabled:
+            return []
+        return [(n, float(lora_scale) * a["weight"]) for n, a in self._adapters.items()
+                if a["active"] and float(lora_scale) * a["weight"] != 0.0]
+
+    def effective_state_dict(self, lora_scale: float = 1.0):
+        """The host state dict with every ACTIVE adapter merged (W + lora_scale * weight * (alpha / r) * B A, weights.merge_lora);
+        `lora_scale` is the per-call `cross_attention_kwargs={"scale": s}` of the reference (scale_lora_layers)."""
+        sd = self._sd
+        for n, scale in self._lora_state(lora_scale):
+            sd = merge_lora(sd, self._adapters[n]["lora"], self._adapters[n]["alphas"], adapter_scale=scale)
+        return sd
+
+    def load_lora_adapter(self, lora, alphas, adapter_name="default", weight: float = 1.0):
+        missing = [m for m in alphas if m + ".weight" not in self._sd]
+        if missing:
+            raise KeyError(f"LoRA targets not present in the model: {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+        if adapter_name in self._adapters:
+            raise ValueError(f"Adapter name {adapter_name} already in use in the model - please select a new adapter name.")
+        self._adapters[adapter_name] = dict(lora=lora, alphas=alphas, weight=float(weight), active=True)
+        self._lora_changed()
+
+    def set_adapters(self, adapter_names, weights=None):
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        ws = [1.0] * len(names) if weights is None else ([weights] * len(names) if not isinstance(weights, (list, tuple)) else list(weights))
+        if len(ws) != len(names):
+            raise ValueError(f"Length of adapter names {len(names)} is not equal to the length of their weights {len(ws)}.")
+        unknown = [n for n in names if n not in self._adapters]
+        if unknown:
+            raise ValueError(f"Adapter name(s) {set(unknown)} not in the list of present adapters: {set(self._adapters)}.")
+        before = [(n, a["active"], a["weight"]) for n, a in self._adapters.items()]
+        for n, a in self._adapters.items():
+            a["active"] = n in names
+        for n, w in zip(names, ws):
+            self._adapters[n]["weight"] = 1.0 if w is None else float(w)
+        if before != [(n, a["active"], a["weight"]) for n, a in self._adapters.items()]:
+            self._lora_changed()
+
+    def unload_lora(self):
+        if self._adapters:
+            self._adapters.clear()
+            self._lora_changed()
+
+    def delete_adapters(self, adapter_names):
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        unknown = [n for n in names if n not in self._adapters]
+        if unknown:
+            raise ValueError(f"Adapter name(s) {set(unknown)} not in the list of present adapters: {set(self._adapters)}.")
+        for n in names:
+            del self._adapters[n]
+        if names:
+            self._lora_changed()
+
+    def disable_lora(self):
+        if self._lora_enabled:
+            self._lora_enabled = False
+            self._lora_changed()
+
+    def enable_lora(self):
+        if not self._lora_enabled:
+            self._lora_enabled = True
+            self._lora_changed()
+
+    def active_adapters(self):
+        return [n for n, a in self._adapters.items() if a["active"]] if self._lora_enabled else []
+
+
+def lora_scale_of(cross_attention_kwargs) -> float:
+    """`cross_attention_kwargs={"scale": s}` -> s (unet_2d_condition.py:1183-1191 pops it and scales every LoRA layer); None / {} -> 1.0.
+    No other key has a meaning here: the attention processors are the HIP kernels and take no arguments."""
+    if not cross_attention_kwargs:
+        return 1.0
+    other = sorted(k for k in cross_attention_kwargs if k != "scale")
+    if other:
+        raise ValueError(f"cross_attention_kwargs supports only 'scale' (the LoRA scale of this call), got {other}")
+    s = cross_attention_kwargs["scale"]
+    if isinstance(s, bool) or not isinstance(s, (int, float)):
+        raise TypeError(f"cross_attention_kwargs['scale'] must be a number, got {type(s).__name__}")
+    return float(s)
+
+
 def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     co, ci = w.shape[:2]
     cip = pad8(ci)

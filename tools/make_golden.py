@@ -1676,6 +1676,60 @@ def golden_lora_keys():
     print("lora keys:", len(out["pairs"]), "pairs;", out["kwargs_no_alpha"], out["kwargs_alpha"])
 
 
+def golden_lora_kohya():
+    """kohya / sd-scripts key names of every LoRA-targetable module of the SD-1.5 UNet (Linear: to_q/k/v, to_out.0, proj_in/out,
+    ff.net.0.proj, ff.net.2, time_emb_proj; Conv2d: conv1, conv2, conv_shortcut, down/upsamplers.0.conv) and of CLIP-L (12 x 6), through the
+    reference's `_convert_non_diffusers_lora_to_diffusers` and its peft key conversion (convert_unet_state_dict_to_peft for the UNet,
+    convert_state_dict_to_diffusers + convert_state_dict_to_peft for the text encoder: lora_pipeline.py:317-320).  Recorded per module:
+    the kohya name, the final module name, the network_alphas key the conversion emits and the module whose down weight that key names.
+    For the UNet, `get_peft_kwargs` also says which module the alpha lands on (`alpha_pattern`); its text-encoder branch
+    (peft_utils.py:176) cuts attention keys back to `...self_attn`, which names no LoRA layer, so that column is recorded for the UNet only."""
+    from diffusers.loaders.lora_conversion_utils import _convert_non_diffusers_lora_to_diffusers
+    from diffusers.utils.peft_utils import get_peft_kwargs
+    from diffusers.utils.state_dict_utils import (convert_state_dict_to_diffusers, convert_state_dict_to_peft,
+                                                  convert_unet_state_dict_to_peft)
+    us = synth.trunk_param_shapes(5, (320, 640, 1280, 1280), 2, 768, 4, blobnet=False)
+    leaf = ("to_q", "to_k", "to_v", "to_out.0", "proj_in", "proj_out", "ff.net.0.proj", "ff.net.2", "time_emb_proj", "conv1", "conv2",
+            "conv_shortcut", "downsamplers.0.conv", "upsamplers.0.conv")
+    unet_mods = [k[: -len(".weight")] for k in us if k.endswith(".weight") and k[: -len(".weight")].endswith(leaf)]
+    te_mods = [f"text_model.encoder.layers.{i}.{m}" for i in range(12)
+               for m in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "mlp.fc1", "mlp.fc2")]
+    names = [("unet", "lora_unet_" + m.replace(".", "_"), m) for m in unet_mods]
+    names += [("text_encoder", "lora_te_" + m.replace(".", "_"), m) for m in te_mods]
+    sd = {}
+    for i, (_, k, _) in enumerate(names):                     # down = 3 i, up = 3 i + 1, alpha = 3 i + 2: every value names its key
+        sd[k + ".lora_down.weight"], sd[k + ".lora_up.weight"], sd[k + ".alpha"] = 3 * i, 3 * i + 1, torch.tensor(float(3 * i + 2))
+    conv, alphas = _convert_non_diffusers_lora_to_diffusers(dict(sd))
+    final = {"unet": convert_unet_state_dict_to_peft({k[len("unet."):]: v for k, v in conv.items() if k.startswith("unet.")}),
+             "text_encoder": convert_state_dict_to_peft(convert_state_dict_to_diffusers(
+                 {k[len("text_encoder."):]: v for k, v in conv.items() if k.startswith("text_encoder.")}))}
+    down_of = {v: k for k, v in conv.items()}                 # value -> key after the first conversion
+    where = {m: {v: k for k, v in d.items()} for m, d in final.items()}
+    alpha_key = {v: k for k, v in alphas.items()}
+    # get_peft_kwargs(is_unet=True): two extra entries share a value, so that every real alpha differs from the most common one
+    ua = convert_unet_state_dict_to_peft({k[len("unet."):]: v for k, v in alphas.items() if k.startswith("unet.")})
+    ua.update({"pad0.alpha": -1.0, "pad1.alpha": -1.0})
+    pattern = {v: k for k, v in get_peft_kwargs({"x.lora_B.weight": 4}, ua, {"x.lora_A.weight": 0})["alpha_pattern"].items()}
+    entries = []
+    for i, (model, k, want) in enumerate(names):
+        dk, uk = where[model][3 * i], where[model][3 * i + 1]
+        assert dk.endswith(".lora_A.weight") and uk == dk.replace(".lora_A.", ".lora_B."), (k, dk, uk)
+        ak = alpha_key[float(3 * i + 2)]
+        base = ak[: -len(".alpha")]
+        owners = [j for j in range(len(names)) if down_of[3 * j] == base or down_of[3 * j].startswith(base + ".")]
+        assert len(owners) == 1, (ak, owners)
+        j = owners[0]
+        e = {"kohya": k, "model": model, "module": dk[: -len(".lora_A.weight")], "alpha_key": ak,
+             "alpha_module": where[names[j][0]][3 * j][: -len(".lora_A.weight")]}
+        if model == "unet":
+            e["peft_alpha_pattern"] = pattern[float(3 * i + 2)]
+        assert e["module"] == want, (k, e["module"], want)    # (the kohya name is the path with "." -> "_": the conversion must undo it)
+        entries.append(e)
+    with open(os.path.join(OUT, "lora_kohya_keys.json"), "w") as f:
+        json.dump({"entries": entries}, f, indent=0)
+    print("lora kohya keys:", len(entries), "modules,", sum(e["model"] == "unet" for e in entries), "in the UNet")
+
+
 def golden_lora_merge():
     """The adapter arithmetic as the REFERENCE tree states it (peft is absent, but the vendored diffusers keeps its
     own LoRA layers): D/models/lora.py LoRALinearLayer / LoRAConv2dLayer forward (runtime branch: base(x) + lora_scale * up(down(x))
@@ -1965,6 +2019,7 @@ if __name__ == "__main__":
     check_full_schema()
     golden_pipeline_call()
     golden_lora_keys()
+    golden_lora_kohya()
     golden_lora_merge()
     golden_blob_edit()
     golden_blob_edit_cv()
