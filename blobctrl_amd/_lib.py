@@ -172,6 +172,14 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 
+# Entry points of include/blobctrl_vae.h (the tiled-VAE driver's blend / crop / scatter launch).  A table of its own: these are host-driven
+# helpers, not recordable plan ops, and EXPORTED_SYMBOLS stays the list of include/blobctrl_hip.h.
+VAE_SIGNATURES = {
+    "bc_vae_tile_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
+VAE_TILE_DECODE, VAE_TILE_ENCODE = 0, 1
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -225,7 +233,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:   # pragma: no cover
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -433,6 +433,24 @@ class BlobCtrlEngine:
         self.stream.synchronize()
         return emb
 
+    # ---- VAE slicing / tiling: forwarded to the VAE; encode_latents / decode_latents / denoise pick them up through vae.encode / vae.decode
+    def _vae_switch(self, name, *a):
+        if self.vae is None:
+            raise ValueError("this pipeline was built without a VAE: there is nothing to slice or tile")
+        getattr(self.vae, name)(*a)
+
+    def enable_vae_slicing(self):
+        self._vae_switch("enable_slicing")
+
+    def disable_vae_slicing(self):
+        self._vae_switch("disable_slicing")
+
+    def enable_vae_tiling(self):
+        self._vae_switch("enable_tiling")
+
+    def disable_vae_tiling(self):
+        self._vae_switch("disable_tiling")
+
     def encode_latents(self, image: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """pipe:300-309: image [1,3,H,W] in [-1,1] -> posterior sample * scaling_factor, [1,4,H/8,W/8] fp32."""
         if self.vae is None:
@@ -984,6 +1002,23 @@ class StableDiffusionBlobNetPipeline:
     def disable_freeu(self):
         """Disables the FreeU mechanism if enabled."""
         self.unet.disable_freeu()
+
+    # ---- VAE slicing / tiling (D/pipelines/pipeline_utils.py:1873-1903, StableDiffusionMixin): forwarded to the VAE, which the engine shares
+    def enable_vae_slicing(self):
+        """Sliced VAE encode / decode: a batch goes through the VAE one sample at a time."""
+        self.vae.enable_slicing()
+
+    def disable_vae_slicing(self):
+        """Back to encoding / decoding a batch in one step."""
+        self.vae.disable_slicing()
+
+    def enable_vae_tiling(self):
+        """Tiled VAE encode / decode: inputs above the VAE's tile size are processed as overlapping tiles and blended."""
+        self.vae.enable_tiling()
+
+    def disable_vae_tiling(self):
+        """Back to encoding / decoding an image in one step."""
+        self.vae.disable_tiling()
 
     def get_active_adapters(self):
         out = []

@@ -51,11 +51,61 @@ class _Dist:
         return self._mom.view(self._B, self._h, self._w, -1).permute(0, 3, 1, 2).float().contiguous()
 
 
+def tile_geometry(kind, H, W, tile_sample_min_size, tile_latent_min_size, tile_overlap_factor, scale):
+    """Tile grid of a tiled decode (`kind` "decode": H x W is the latent, tiles grow by `scale`) or a tiled encode ("encode": H x W is the
+    image, tiles shrink by `scale`), with the expressions of tiled_decode / tiled_encode (D/models/autoencoders/autoencoder_kl.py:359-361,
+    409-411) evaluated as the same Python expressions, so their truncation is the reference's.  Pure host arithmetic: no GPU, no weights.
+
+    Returns dict(overlap, extent, limit, rows, cols, out_h, out_w, tiles) with `tiles` in row-major order, each a dict:
+        i, j            grid position
+        y0, x0, in_h, in_w     the slice of the input the tile's plan runs on (clipped at the border)
+        out_h, out_w    the size of what the plan returns for it
+        ev, eh          blend extents against the tile above / to the left, clamped to min(neighbour size, own size, extent); 0 without one
+        ch, cw          the cropped size `[:limit, :limit]` that goes into the result
+        oy, ox          its origin there: the running sum of the cropped sizes before it (not index * limit)"""
+    if kind not in ("decode", "encode"):
+        raise ValueError(f"tile_geometry: kind {kind!r} (decode or encode)")
+    f = tile_overlap_factor
+    if kind == "decode":
+        tile_in = tile_latent_min_size
+        overlap = int(tile_latent_min_size * (1 - f))
+        extent = int(tile_sample_min_size * f)
+        limit = tile_sample_min_size - extent
+    else:
+        tile_in = tile_sample_min_size
+        overlap = int(tile_sample_min_size * (1 - f))
+        extent = int(tile_latent_min_size * f)
+        limit = tile_latent_min_size - extent
+    if overlap <= 0:
+        raise ValueError(f"tile_overlap_factor {f} leaves a tile step of {overlap}: tiles would never advance")
+    if limit <= 0 or extent < 0 or tile_in <= 0:
+        raise ValueError(f"tile sizes {tile_sample_min_size} / {tile_latent_min_size} with tile_overlap_factor {f} keep nothing of a tile "
+                         f"(blend extent {extent}, crop {limit})")
+    ys, xs = list(range(0, H, overlap)), list(range(0, W, overlap))
+    tiles, oy = [], 0
+    for i, y0 in enumerate(ys):
+        ox = 0
+        for j, x0 in enumerate(xs):
+            in_h, in_w = min(tile_in, H - y0), min(tile_in, W - x0)
+            out_h, out_w = (in_h * scale, in_w * scale) if kind == "decode" else (in_h // scale, in_w // scale)
+            t = dict(i=i, j=j, y0=y0, x0=x0, in_h=in_h, in_w=in_w, out_h=out_h, out_w=out_w, ev=0, eh=0,
+                     ch=min(out_h, limit), cw=min(out_w, limit), oy=oy, ox=ox)
+            if i > 0:
+                t["ev"] = min(tiles[(i - 1) * len(xs) + j]["out_h"], out_h, extent)
+            if j > 0:
+                t["eh"] = min(tiles[-1]["out_w"], out_w, extent)
+            tiles.append(t)
+            ox += t["cw"]
+        oy += tiles[-1]["ch"]
+    return dict(overlap=overlap, extent=extent, limit=limit, rows=len(ys), cols=len(xs), out_h=oy, out_w=ox, tiles=tiles)
+
+
 class AutoencoderKL:
     class _Cfg:
         scaling_factor = 0.18215
+        sample_size = 512
 
-    def __init__(self, state_dict, norm_num_groups: int = 32, layers_per_block: int = 2, device="cuda:0"):
+    def __init__(self, state_dict, norm_num_groups: int = 32, layers_per_block: int = 2, device="cuda:0", sample_size: int = 512):
         self.device = torch.device(device)
         # (a host device is accepted for CONSTRUCTION only - loading / inspecting checkpoints; running refuses it: `_need_gpu`)
         self.lib = _lib.load()
@@ -84,6 +134,13 @@ class AutoencoderKL:
             boc.append(sd[f"encoder.down_blocks.{i}.resnets.0.conv1.weight"].shape[0])
             i += 1
         self.config.block_out_channels = tuple(boc)
+        self.config.sample_size = sample_size
+        # tiling / slicing switches of the reference (autoencoder_kl.py:126-137): plain, settable attributes
+        self.use_slicing = False
+        self.use_tiling = False
+        self.tile_sample_min_size = sample_size
+        self.tile_latent_min_size = int(sample_size / (2 ** (len(boc) - 1)))
+        self.tile_overlap_factor = 0.25
         self._plans = {}
 
     @classmethod
@@ -94,7 +151,7 @@ class AutoencoderKL:
         d = os.path.join(path, subfolder) if subfolder else path
         cfg = _config(d)
         vae = cls(read_safetensors(_model_file(d)), norm_num_groups=cfg.get("norm_num_groups", 32),
-                  layers_per_block=cfg.get("layers_per_block", 2), device=device)
+                  layers_per_block=cfg.get("layers_per_block", 2), device=device, sample_size=cfg.get("sample_size", 512))
         vae.config.scaling_factor = cfg.get("scaling_factor", 0.18215)
         return vae
 
@@ -227,6 +284,90 @@ class AutoencoderKL:
         self._plans[key] = P
         return P
 
+    # ------------------------------------------------------------------------------------------------ tiling / slicing
+    def enable_tiling(self, use_tiling: bool = True):
+        """Encode / decode inputs above the tile size as overlapping tiles blended together (autoencoder_kl.py:143-149).  The result
+        differs from the plain one: every tile has its own GroupNorm statistics and its own mid-block attention."""
+        self.use_tiling = use_tiling
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def enable_slicing(self):
+        """Encode / decode a batch one sample at a time (autoencoder_kl.py:158-163)."""
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def _tiles(self, kind, H, W):
+        """The tile grid of an input, every tile checked against the mid-block attention's limit BEFORE anything is launched."""
+        scale = 2 ** (len(self.config.block_out_channels) - 1)
+        geo = tile_geometry(kind, H, W, self.tile_sample_min_size, self.tile_latent_min_size, self.tile_overlap_factor, scale)
+        for t in geo["tiles"]:
+            if kind == "encode" and (t["in_h"] % scale or t["in_w"] % scale):
+                raise ValueError(f"tiled encode: tile {t['in_h']}x{t['in_w']} at ({t['y0']}, {t['x0']}) is not a multiple of {scale} pixels")
+            lh, lw = (t["in_h"], t["in_w"]) if kind == "decode" else (t["out_h"], t["out_w"])
+            if (lh * lw) % 8:
+                raise ValueError(f"tiled {kind}: tile {t['in_h']}x{t['in_w']} at ({t['y0']}, {t['x0']}) has {lh}x{lw} = {lh * lw} latent "
+                                 "tokens; VAE attention needs a token count that is a multiple of 8")
+        return geo
+
+    def _blend(self, src, keeps, t, out, mode, B, H, W):
+        """One bc_vae_tile_blend launch on the caller's stream: tile `t` (plan output `src`) against its neighbours' keep-buffers."""
+        above = keeps.get((t["i"] - 1, t["j"]))
+        left = keeps.get((t["i"], t["j"] - 1))
+        keep = torch.empty(B, t["out_h"], t["out_w"], 3 if mode == _lib.VAE_TILE_DECODE else 8, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.bc_vae_tile_blend(
+            src.data_ptr(), above.data_ptr() if above is not None else None, left.data_ptr() if left is not None else None,
+            keep.data_ptr(), out.data_ptr(), mode, B, t["out_h"], t["out_w"], above.shape[1] if above is not None else 0,
+            left.shape[2] if left is not None else 0, t["ev"], t["eh"], t["oy"], t["ox"], t["ch"], t["cw"], H, W,
+            torch.cuda.current_stream().cuda_stream), "bc_vae_tile_blend")
+        keeps[(t["i"], t["j"])] = keep
+        keeps.pop((t["i"] - 2, t["j"]), None)            # (two tile rows of keep-buffers are alive at a time)
+
+    def _tiled_decode(self, z):
+        B, Cz, h, w = z.shape
+        geo = self._tiles("decode", h, w)
+        if self.h["decoder.conv_out.weight"].shape[0] != 3:
+            raise ValueError("tiled decode blends 3-channel images (bc_vae_tile_blend)")
+        for t in geo["tiles"]:
+            self._plan_decode(B, t["in_h"], t["in_w"])    # (every plan recorded before the first launch: a refusal launches nothing)
+        s = torch.cuda.current_stream().cuda_stream
+        H, W = geo["out_h"], geo["out_w"]
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
+        keeps = {}
+        for t in geo["tiles"]:                             # row-major: above and left are blended before they are read
+            P = self._plan_decode(B, t["in_h"], t["in_w"])
+            zt = z[:, :, t["y0"]:t["y0"] + t["in_h"], t["x0"]:t["x0"] + t["in_w"]].contiguous()
+            _lib.check(self.lib.bc_nchw_to_nhwc_f16(zt.data_ptr(), 1, B, Cz, t["in_h"] * t["in_w"], 8, P.z.data_ptr(), s),
+                       "bc_nchw_to_nhwc_f16")
+            run_graphed(P.seg, self.device)
+            # the plan's image lives in its arena and the next tile of this shape overwrites it: the blend is enqueued on the caller's
+            # stream now, and the next replay waits for that stream
+            self._blend(P.img.t, keeps, t, out, _lib.VAE_TILE_DECODE, B, H, W)
+        return out
+
+    def _tiled_encode(self, x):
+        B, _, Hi, Wi = x.shape
+        geo = self._tiles("encode", Hi, Wi)
+        if 2 * self.latent_channels != 8:
+            raise ValueError("tiled encode blends 8 moment channels (bc_vae_tile_blend): latent_channels must be 4")
+        for t in geo["tiles"]:
+            self._plan_encode(B, t["in_h"], t["in_w"])
+        s = torch.cuda.current_stream().cuda_stream
+        h, w = geo["out_h"], geo["out_w"]
+        mom = torch.empty(B, h * w, 2 * self.latent_channels, dtype=torch.float16, device=self.device)
+        keeps = {}
+        for t in geo["tiles"]:
+            P = self._plan_encode(B, t["in_h"], t["in_w"])
+            xt = x[:, :, t["y0"]:t["y0"] + t["in_h"], t["x0"]:t["x0"] + t["in_w"]].contiguous()
+            _lib.check(self.lib.bc_nchw_to_nhwc_f16(xt.data_ptr(), 1, B, 3, t["in_h"] * t["in_w"], 8, P.x.data_ptr(), s),
+                       "bc_nchw_to_nhwc_f16")
+            run_graphed(P.seg, self.device)
+            self._blend(P.moments, keeps, t, mom, _lib.VAE_TILE_ENCODE, B, h, w)
+        return mom, h, w
+
     # ------------------------------------------------------------------------------------------------ API
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = False, generator=None):
@@ -234,14 +375,22 @@ class AutoencoderKL:
         B, Cz, h, w = z.shape
         if Cz != self.latent_channels:
             raise ValueError(f"expected {self.latent_channels} latent channels, got {Cz}")
+        if self.use_slicing and B > 1:
+            return (torch.cat([self._decode(z[b:b + 1]) for b in range(B)]),)
+        return (self._decode(z),)
+
+    def _decode(self, z):
+        B, Cz, h, w = z.shape
+        self._need_gpu()
+        zz = z.to(self.device, torch.float32).contiguous()
+        if self.use_tiling and (w > self.tile_latent_min_size or h > self.tile_latent_min_size):
+            return self._tiled_decode(zz)
         P = self._plan_decode(B, h, w)
         s = torch.cuda.current_stream().cuda_stream
-        zz = z.to(self.device, torch.float32).contiguous()
         _lib.check(self.lib.bc_nchw_to_nhwc_f16(zz.data_ptr(), 1, B, Cz, h * w, 8, P.z.data_ptr(), s), "bc_nchw_to_nhwc_f16")
         run_graphed(P.seg, self.device)
         img = P.img
-        out = img.t.view(B, img.H, img.W, img.C).permute(0, 3, 1, 2).contiguous()
-        return (out,)
+        return img.t.view(B, img.H, img.W, img.C).permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor):
@@ -249,11 +398,27 @@ class AutoencoderKL:
         B, C, H, W = x.shape
         if C != 3 or H % 8 or W % 8:
             raise ValueError("image must be [B,3,H,W] with H, W multiples of 8")
+        self._need_gpu()
+        xx = x.to(self.device, torch.float32).contiguous()
+        out = type("AutoencoderKLOutput", (), {})()
+        if self.use_tiling and (W > self.tile_sample_min_size or H > self.tile_sample_min_size):
+            mom, h, w = self._tiled_encode(xx)                         # (the tiling test comes first, as in the reference)
+        elif self.use_slicing and B > 1:
+            parts = []
+            for b in range(B):                                         # (one batch-1 plan: its moments are copied out before the next replay)
+                m, (h, w) = self._encode_moments(xx[b:b + 1])
+                parts.append(m.clone())
+            mom = torch.cat(parts)
+        else:
+            mom, (h, w) = self._encode_moments(xx)
+        out.latent_dist = _Dist(self, mom, B, h, w)
+        return out
+
+    def _encode_moments(self, xx):
+        """The encode plan of xx's shape replayed on it: (moments [B * h * w, 8] fp16 in the plan's arena, (h, w))."""
+        B, _, H, W = xx.shape
         P = self._plan_encode(B, H, W)
         s = torch.cuda.current_stream().cuda_stream
-        xx = x.to(self.device, torch.float32).contiguous()
         _lib.check(self.lib.bc_nchw_to_nhwc_f16(xx.data_ptr(), 1, B, 3, H * W, 8, P.x.data_ptr(), s), "bc_nchw_to_nhwc_f16")
         run_graphed(P.seg, self.device)
-        out = type("AutoencoderKLOutput", (), {})()
-        out.latent_dist = _Dist(self, P.moments, B, P.hw[0], P.hw[1])
-        return out
+        return P.moments, P.hw

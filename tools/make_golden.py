@@ -1645,6 +1645,80 @@ def golden_vae():
     print("vae: decoded std %.4f moments std %.4f" % (out["decoded"].std(), out["moments"].std()))
 
 
+# cases of vae_tiled.npz: tag -> (latent h, w, batch, tile_overlap_factor); tile sizes 64 / 8 throughout
+VAE_TILED_CASES = {"A": (16, 12, 2, 0.25), "B": (10, 8, 1, 0.5), "C": (4, 12, 1, 0.25), "Cp": (12, 4, 1, 0.25), "D": (8, 8, 1, 0.25)}
+
+
+def golden_vae_tiled():
+    """The reference AutoencoderKL with enable_tiling() (tiled_decode / tiled_encode, autoencoder_kl.py:340-442) on golden_vae's tiny VAE,
+    tile_sample_min_size 64 and tile_latent_min_size 8: tiled `decoded` of a latent and tiled `moments` of an image of the matching size
+    per case.  The tiles the reference cut are RECORDED, not recomputed: forward hooks on its decoder / encoder log every tile's input
+    and output shape in call order (row-major), and the origin of a tile in the result is the running sum of the cropped pieces the
+    reference concatenated.  Case D is below the tile size: tiling is enabled and not triggered (bit-equal to the plain result)."""
+    from diffusers import AutoencoderKL
+    boc = (32, 32, 64, 64)
+    vae = AutoencoderKL(in_channels=3, out_channels=3, down_block_types=("DownEncoderBlock2D",) * 4,
+                        up_block_types=("UpDecoderBlock2D",) * 4, block_out_channels=boc, layers_per_block=2,
+                        latent_channels=4, norm_num_groups=8, sample_size=32).eval()
+    vae.load_state_dict(synth.synth_state_dict(synth.vae_param_shapes(boc, 2, 4), 21), strict=True)
+    assert (vae.tile_sample_min_size, vae.tile_latent_min_size, vae.tile_overlap_factor, vae.use_tiling, vae.use_slicing) == (32, 4, 0.25, False, False)
+    vae.tile_sample_min_size, vae.tile_latent_min_size = 64, 8
+    log = []
+    hooks = [m.register_forward_hook(lambda mod, args, res: log.append((tuple(args[0].shape[2:]), tuple(res.shape[2:]))))
+             for m in (vae.decoder, vae.encoder)]
+
+    def record(limit, result_hw, grid_w):
+        """[y0-free] tiles in call order -> per tile [in_h, in_w, out_h, out_w, oy, ox]; the grid is `grid_w` tiles wide"""
+        rows, oy = [], 0
+        for k, (i_hw, o_hw) in enumerate(log):
+            if k % grid_w == 0:
+                ox = 0
+            rows.append([i_hw[0], i_hw[1], o_hw[0], o_hw[1], oy, ox])
+            ox += min(o_hw[1], limit)
+            if k % grid_w == grid_w - 1:
+                oy += min(o_hw[0], limit)
+        assert (oy, ox) == tuple(result_hw), (oy, ox, result_hw)
+        return np.array(rows, np.int32)
+
+    out, meta = {}, {}
+    for k, (tag, (h, w, B, f)) in enumerate(VAE_TILED_CASES.items()):
+        vae.tile_overlap_factor = f
+        z = g(520 + 6 * k, B, 4, h, w)
+        x = g(540 + 6 * k, B, 3, 8 * h, 8 * w).clamp(-1, 1)
+        vae.disable_tiling()
+        plain_dec, plain_mom = vae.decode(z, return_dict=False)[0], vae.encode(x).latent_dist.parameters
+        vae.enable_tiling()
+        del log[:]
+        dec = vae.decode(z, return_dict=False)[0]
+        n_dec = len(log)
+        mom = vae.encode(x).latent_dist.parameters
+        out[f"{tag}_z"], out[f"{tag}_img"], out[f"{tag}_decoded"], out[f"{tag}_moments"] = z.numpy(), x.numpy(), dec.numpy(), mom.numpy()
+        m = dict(latent=[h, w], batch=B, f=f, tile_sample_min_size=64, tile_latent_min_size=8, decoded_shape=list(dec.shape),
+                 moments_shape=list(mom.shape))
+        if tag == "D":
+            assert n_dec == 1 and len(log) == 2 and torch.equal(dec, plain_dec) and torch.equal(mom, plain_mom)
+            m["tiled"] = False
+        else:
+            grid_w = len(range(0, w, int(8 * (1 - f))))
+            assert len(log) == 2 * n_dec and n_dec % grid_w == 0 and n_dec > 1
+            enc_log, log[:] = log[n_dec:], log[:n_dec]
+            out[f"{tag}_decode_tiles"] = record(64 - int(64 * f), dec.shape[2:], grid_w)
+            log[:] = enc_log
+            out[f"{tag}_encode_tiles"] = record(8 - int(8 * f), mom.shape[2:], grid_w)
+            m["tiled"], m["grid"] = True, [n_dec // grid_w, grid_w]
+            sc = dec.abs().max().item()
+            m["tiled_vs_plain_max_abs_over_scale"] = (dec - plain_dec).abs().max().item() / sc
+            print(f"vae_tiled {tag}: {n_dec} tiles, decode tiled-vs-plain {m['tiled_vs_plain_max_abs_over_scale']:.3f} of scale, "
+                  f"moments {(mom - plain_mom).abs().max().item() / mom.abs().max().item():.3f}")
+        meta[tag] = m
+    for hk in hooks:
+        hk.remove()
+    out["meta"] = np.array(json.dumps(meta))
+    path = os.path.join(OUT, "vae_tiled.npz")
+    np.savez_compressed(path, **out)
+    print("vae_tiled: %d arrays, %.1f KB" % (len(out), os.path.getsize(path) / 1024))
+
+
 def golden_lora_keys():
     """Key renaming + alpha defaults of the reference LoRA loader (peft itself is absent here, so only the parts that live in the
     vendored diffusers tree are pinned: convert_unet_state_dict_to_peft and get_peft_kwargs)."""
