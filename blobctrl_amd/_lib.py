@@ -180,6 +180,18 @@ VAE_SIGNATURES = {
 }
 VAE_TILE_DECODE, VAE_TILE_ENCODE = 0, 1
 
+# Entry points of include/blobctrl_requests.h (request batches whose requests run their own schedules).  A table of its own, as that
+# header is one of its own; unlike the VAE helpers these ARE recordable plan ops (REQUEST_OPS below).
+REQUEST_SIGNATURES = {
+    "bc_assemble_input_requests": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_assemble_input_im2col_requests": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_timestep_embedding_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_scheduler_step_requests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -191,15 +203,23 @@ OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused":
        "bc_cfg_scheduler_step_noise": 30, "bc_cfg_scheduler_step3": 31,
        "bc_assemble_input_scaled": 32, "bc_assemble_input_im2col_scaled": 33, "bc_scheduler_step_single": 34,
        "bc_timestep_embedding_table_cond": 35, "bc_timestep_embedding_cond": 36, "bc_freeu": 37}
+# ... and those of include/blobctrl_requests.h (plan file version 8); `op_code` looks a name up in both tables
+REQUEST_OPS = {"bc_scheduler_step_requests": 38, "bc_assemble_input_requests": 39, "bc_assemble_input_im2col_requests": 40,
+               "bc_timestep_embedding_rows": 41}
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
 _KIND = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l", C.c_char_p: "p"}
 
 
+def op_code(name):
+    """BC_OP_* code of a recordable entry point."""
+    return OPS[name] if name in OPS else REQUEST_OPS[name]
+
+
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
-    args = _SIGNATURES[name][1][:-1]
+    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -233,7 +253,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:   # pragma: no cover
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

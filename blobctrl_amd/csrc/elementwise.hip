@@ -2,6 +2,7 @@
 // timestep embedding, CFG + scheduler step, layout conversion at the nn.Module boundary, DINOv2 embedding glue.
 #include "bc_common.h"
 #include "bc_splat.h"
+#include "../../include/blobctrl_requests.h"
 
 namespace {
 
@@ -24,6 +25,15 @@ __global__ void splat_kernel(const SplatParams prm, int h, int w, double* __rest
 __device__ __forceinline__ float input_divisor(const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps) {
     const int step = *step_idx;
     return (step >= 0 && step < nsteps) ? coef[(size_t)step * 16 + 14] : 1.f;
+}
+
+// The divisor of image `b` in a REQUESTS assembly (a batch of edit requests with their own step counts): column 14 of ITS row of the
+// [Blat][nsteps][16] table.  A row whose column 14 is 0 ("do not divide": a table that does not scale its input) and a step index
+// outside the table give 1, as above.
+__device__ __forceinline__ float input_divisor_of(const float* __restrict__ coef, int step, int nsteps, int b) {
+    if (step < 0 || step >= nsteps) return 1.f;
+    const float d = coef[((size_t)b * nsteps + step) * 16 + 14];
+    return d != 0.f ? d : 1.f;
 }
 
 // pipeline_blobnet.py:724-739 + :706-721.  X[b][y][x][c], x in [0, 2w): left = clean image latents, right = noisy latents.
@@ -112,6 +122,87 @@ __global__ void assemble_im2col_kernel(const float* __restrict__ latents, int Bl
     }
 }
 
+// The two assemblies above in their SCALED form with the divisor PER IMAGE (a request batch whose requests run their own schedules,
+// coef [Blat][nsteps][16]): image b of the output divides by input_divisor_of(.., b % Blat).  Kernels of their own, so that the ones
+// above stay the code they compile to; everything but the divisor is theirs line for line.
+__global__ void assemble_requests_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
+                                         const float* __restrict__ score, const float* __restrict__ feat, int Bimg, int F, int Bout,
+                                         int h, int w, int Cpad, int dup_score, const float* __restrict__ coef,
+                                         const int* __restrict__ step_idx, int nsteps, h16* __restrict__ X) {
+    const long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
+    const int step = *step_idx;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const int nch = Cpad / 8;
+        int ch = (int)(idx % nch);
+        long long pix = idx / nch;
+        int x = (int)(pix % (2 * w));
+        int y = (int)((pix / (2 * w)) % h);
+        int b = (int)(pix / ((long long)2 * w * h));
+        const bool right = x >= w;
+        const int xs = right ? x - w : x;
+        const int bi = b % Bimg;
+        const float sc = score[((size_t)bi * h + y) * w + xs];
+        const float div = input_divisor_of(coef, step, nsteps, b % Blat);
+        uint4 raw;
+        h16* o = reinterpret_cast<h16*>(&raw);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            int c = ch * 8 + j;
+            float v = 0.f;
+            if (c < 4) {
+                v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + y) * w + xs] : img_lat[(((size_t)bi * 4 + c) * h + y) * w + xs];
+                if (right) v = v / div;
+            } else if (c == 4) {
+                v = sc;
+            } else if (c < 5 + F) {
+                v = sc * feat[(size_t)bi * F + c - 5];
+            } else if (dup_score && c == 5) {
+                v = sc;
+            }
+            o[j] = (h16)v;
+        }
+        bc_st16(X + (size_t)pix * Cpad + ch * 8, raw);
+    }
+}
+
+__global__ void assemble_im2col_requests_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
+                                                const float* __restrict__ score, int Bimg, int Bout, int h, int w, int dup_score,
+                                                const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps,
+                                                h16* __restrict__ X) {
+    const long long total = (long long)Bout * h * 2 * w * 16;
+    const int step = *step_idx;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int chunk = (int)(idx & 15);
+        const long long pix = idx >> 4;
+        const int x = (int)(pix % (2 * w));
+        const int y = (int)((pix / (2 * w)) % h);
+        const int b = (int)(pix / ((long long)2 * w * h));
+        const float div = input_divisor_of(coef, step, nsteps, b % Blat);
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (chunk < 9) {
+            const int yy = y + chunk / 3 - 1, xx = x + chunk % 3 - 1;
+            if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)(2 * w)) {
+                const bool right = xx >= w;
+                const int xs = right ? xx - w : xx;
+                const int bi = b % Bimg;
+                const float sc = score[((size_t)bi * h + yy) * w + xs];
+                h16* o = reinterpret_cast<h16*>(&raw);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    float v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + yy) * w + xs]
+                                    : img_lat[(((size_t)bi * 4 + c) * h + yy) * w + xs];
+                    if (right) v = v / div;
+                    o[c] = (h16)v;
+                }
+                o[4] = (h16)sc;
+                o[5] = dup_score ? (h16)sc : (h16)0.f;
+            }
+        }
+        bc_st16(X + (size_t)pix * 128 + chunk * 8, raw);
+    }
+}
+
 // embeddings.py:27-78: [cos(t*f_k) | sin(t*f_k)], f_k = exp(-ln(10000) * k / half)
 // rows_per_step > 0: row r belongs to step r / rows_per_step of the table (all steps of an edit at once)
 //   COND: `cond` fp32 [cond_rows][dim] = cond_proj(timestep_cond) of a UNet with time_cond_proj_dim (embeddings.py:559, 578: added to the
@@ -164,8 +255,11 @@ __global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, long
 //          launch then leaves every buffer as it is.  The plain entry point has no nsteps in its ABI, hence no guard.
 //   SINGLE: a guidance-free (single-pass) plan: eps holds B images, not 2B, and e is the right half of image b as it is - no second
 //          read, no guidance arithmetic, `guidance` and column 11 are not read (pipe:1031, 1095: do_classifier_free_guidance False).
+//   REQ:   a batch of edit requests with their own tables: coef is [B][nsteps][16] and image b applies ITS row, guidance (column 11)
+//          included.  Column 15 != 0 marks a request that has finished: its elements are left alone - nothing of image b is loaded from
+//          eps and nothing is stored, eps_out included - whatever the networks put out for it (a non-finite value included).
 // `noise` / `nsteps` are not read by an instantiation without NOISE / GUARD.
-template <bool SINGLE, bool NOISE, bool THIRD, bool GUARD>
+template <bool SINGLE, bool NOISE, bool THIRD, bool GUARD, bool REQ = false>
 __device__ __forceinline__ void cfg_step_body(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
                                               const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h,
                                               int w, const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
@@ -179,6 +273,10 @@ __device__ __forceinline__ void cfg_step_body(const float* __restrict__ eps, flo
     const int yy = (i / w) % h;
     const int c = (i / (w * h)) % 4;
     const int b = i / (4 * w * h);
+    if (REQ) {
+        cf = coef + ((size_t)b * nsteps + step) * 16;
+        if (cf[15] != 0.f) return;
+    }
     // eps token-major [2B][h][2w][4]; right half, uncond = batch b, cond = batch B + b   (pipe:1092-1098)
     const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
     float e;
@@ -220,6 +318,14 @@ __global__ void step_single_kernel(const float* __restrict__ eps, float* __restr
                                    const int* __restrict__ step_idx, float* __restrict__ hist, int B, int h, int w,
                                    const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
     cfg_step_body<true, NOISE, THIRD, true>(eps, latents, coef, step_idx, hist, 0.f, B, h, w, noise, nsteps, eps_out);
+}
+
+// The step of a requests plan: always guarded, guidance always from the row.
+template <bool SINGLE, bool NOISE, bool THIRD>
+__global__ void step_requests_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
+                                     const int* __restrict__ step_idx, float* __restrict__ hist, int B, int h, int w,
+                                     const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
+    cfg_step_body<SINGLE, NOISE, THIRD, true, true>(eps, latents, coef, step_idx, hist, -1.f, B, h, w, noise, nsteps, eps_out);
 }
 
 __global__ void advance_kernel(int* step_idx) { *step_idx += 1; }
@@ -397,6 +503,35 @@ extern "C" int bc_assemble_input_im2col_scaled(const float* latents, int Blat, c
                                         coef, step_idx, nsteps, X, stream);
 }
 
+// The `_requests` forms: the launchers' checks with SCALED, the per-image divisor kernels.
+extern "C" int bc_assemble_input_requests(const float* latents, int Blat, const float* img_lat, const float* score, const float* feat,
+                                          int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score, const float* coef,
+                                          const int* step_idx, int nsteps, bc_half* X, bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (!feat) F = 0;
+    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 && coef && step_idx && nsteps > 0 && h > 0 && w > 0,
+                 "bc_assemble_input_requests: bad args");
+    BC_CHECK_ARG(Cpad % 8 == 0 && Cpad >= 5 + F, "bc_assemble_input_requests: Cpad=%d must be a multiple of 8 and >= %d", Cpad, 5 + F);
+    long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
+    hipLaunchKernelGGL(assemble_requests_kernel, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, feat, Bimg,
+                       F, Bout, h, w, Cpad, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
+    BC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bc_assemble_input_im2col_requests(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg,
+                                                 int Bout, int h, int w, int dup_score, const float* coef, const int* step_idx,
+                                                 int nsteps, bc_half* X, bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 && coef && step_idx && nsteps > 0 && h > 0 && w > 0,
+                 "bc_assemble_input_im2col_requests: bad args");
+    long long total = (long long)Bout * h * 2 * w * 16;
+    hipLaunchKernelGGL(assemble_im2col_requests_kernel, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, Bimg,
+                       Bout, h, w, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
+    BC_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int bc_timestep_embedding(const float* t_table, const int* t_idx, float t_value, int rows, int dim,
                                      bc_half* out, bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -437,6 +572,23 @@ extern "C" int bc_timestep_embedding_table_cond(const float* t_table, int nsteps
     const int rows = nsteps * rows_per_step;
     hipLaunchKernelGGL(temb_cond_kernel, dim3(bc_ceil_div(rows * dim, 256)), dim3(256), 0, stream, t_table, nullptr, 0.f, rows, dim,
                        rows_per_step, cond, rows_per_step, reinterpret_cast<h16*>(out));
+    BC_CHECK_LAUNCH();
+    return 0;
+}
+
+// One timestep per ROW (a batch of edit requests with their own schedules): the table kernels with one row per "step", so the
+// arithmetic - and with it every bit of the output - is theirs for the same t.
+extern "C" int bc_timestep_embedding_rows(const float* t_rows, int rows, int dim, const float* cond, int cond_rows, bc_half* out,
+                                          bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(t_rows && out && rows > 0 && dim > 0 && dim % 2 == 0 && (!cond || cond_rows > 0) && (long long)rows * dim < (1ll << 31),
+                 "bc_timestep_embedding_rows: bad args");
+    if (cond)
+        hipLaunchKernelGGL(temb_cond_kernel, dim3(bc_ceil_div(rows * dim, 256)), dim3(256), 0, stream, t_rows, nullptr, 0.f, rows, dim, 1,
+                           cond, cond_rows, reinterpret_cast<h16*>(out));
+    else
+        hipLaunchKernelGGL(temb_kernel, dim3(bc_ceil_div(rows * dim, 256)), dim3(256), 0, stream, t_rows, nullptr, 0.f, rows, dim, 1,
+                           reinterpret_cast<h16*>(out));
     BC_CHECK_LAUNCH();
     return 0;
 }
@@ -508,6 +660,37 @@ extern "C" int bc_scheduler_step_single(const float* eps, float* latents, const 
         hipLaunchKernelGGL((step_single_kernel<false, true>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
     else
         hipLaunchKernelGGL((step_single_kernel<false, false>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
+    BC_CHECK_LAUNCH();
+    if (advance) {
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
+        BC_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// The step of a batch of edit requests: coef [B][nsteps][16], image b applies its own row (guidance from column 11) and is left alone
+// when the row's column 15 is set.  single != 0: eps holds B images (a single-pass plan), else the 2B of the CFG pairs.
+extern "C" int bc_scheduler_step_requests(const float* eps, float* latents, const float* coef, int* step_idx, float* hist, int B, int h,
+                                          int w, const float* noise, int nsteps, int third, int single, float* eps_out, int advance,
+                                          bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0 &&
+                 (long long)B * 4 * h * w < (1ll << 31), "bc_scheduler_step_requests: bad args");
+    const int n = B * 4 * h * w;
+    const dim3 grid(bc_ceil_div(n, 256)), block(256);
+#define BC_STEP_REQ(S, N, T) \
+    hipLaunchKernelGGL((step_requests_kernel<S, N, T>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out)
+    switch ((single ? 4 : 0) | (noise ? 2 : 0) | (third ? 1 : 0)) {
+        case 0: BC_STEP_REQ(false, false, false); break;
+        case 1: BC_STEP_REQ(false, false, true); break;
+        case 2: BC_STEP_REQ(false, true, false); break;
+        case 3: BC_STEP_REQ(false, true, true); break;
+        case 4: BC_STEP_REQ(true, false, false); break;
+        case 5: BC_STEP_REQ(true, false, true); break;
+        case 6: BC_STEP_REQ(true, true, false); break;
+        default: BC_STEP_REQ(true, true, true); break;
+    }
+#undef BC_STEP_REQ
     BC_CHECK_LAUNCH();
     if (advance) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);

@@ -20,6 +20,7 @@
 #include <vector>
 #include "bc_common.h"
 #include "plan_format.h"
+#include "../../include/blobctrl_requests.h"
 
 void bc_gemm_set_probe(hipEvent_t e);      // gemm.hip (timing probe between a split-K GEMM's main kernel and its reducer)
 bool bc_gemm_probe_hit();
@@ -145,6 +146,17 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
             return bc_timestep_embedding_table_cond(CP(float, 0), I(1), I(2), I(3), CP(float, 4), MP(bc_half, 5), s);
         case BC_OP_TIMESTEP_EMBEDDING_COND:
             return bc_timestep_embedding_cond(CP(float, 0), CP(int, 1), F(2), I(3), I(4), CP(float, 5), MP(bc_half, 6), s);
+        case BC_OP_SCHEDULER_STEP_REQUESTS:
+            return bc_scheduler_step_requests(CP(float, 0), MP(float, 1), CP(float, 2), MP(int, 3), MP(float, 4), I(5), I(6), I(7), CP(float, 8),
+                                              I(9), I(10), I(11), MP(float, 12), I(13), s);
+        case BC_OP_ASSEMBLE_INPUT_REQUESTS:
+            return bc_assemble_input_requests(CP(float, 0), I(1), CP(float, 2), CP(float, 3), CP(float, 4), I(5), I(6), I(7), I(8), I(9), I(10),
+                                              I(11), CP(float, 12), CP(int, 13), I(14), MP(bc_half, 15), s);
+        case BC_OP_ASSEMBLE_IM2COL_REQUESTS:
+            return bc_assemble_input_im2col_requests(CP(float, 0), I(1), CP(float, 2), CP(float, 3), I(4), I(5), I(6), I(7), I(8), CP(float, 9),
+                                                     CP(int, 10), I(11), MP(bc_half, 12), s);
+        case BC_OP_TIMESTEP_EMBEDDING_ROWS:
+            return bc_timestep_embedding_rows(CP(float, 0), I(1), I(2), CP(float, 3), I(4), MP(bc_half, 5), s);
         case BC_OP_FREEU:
             return bc_freeu(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), CP(float, 6), I(7), CP(float, 8), MP(bc_half, 9),
                             MP(bc_half, 10), MP(unsigned long long, 11), MP(unsigned long long, 12), s);

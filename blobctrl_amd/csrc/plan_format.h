@@ -16,13 +16,17 @@ namespace bcplan {
 
 constexpr int kMaxStreams = 8;
 const uint32_t kMagic = 0x4E4C5042u;   // "BPLN"
-const uint32_t kVersion = 7;           // 2: BcGemm grew ln_colsum / C_t, GroupNorm statistics totals; 3: + BC_OP_ROWCHAIN_MIDX / _PACK_KV (round 4);
+const uint32_t kVersion = 8;           // 2: BcGemm grew ln_colsum / C_t, GroupNorm statistics totals; 3: + BC_OP_ROWCHAIN_MIDX / _PACK_KV (round 4);
                                        // 4: + BC_OP_ROWCHAIN_SUM, BC_CHAIN_OUT_FFP; 5: BcGemm grew w_bstride / vec_bstride / sm_group / sm_valid,
                                        //    + BC_OP_CTX_FOLD (round 5); 6: + BC_OP_ASSEMBLE_INPUT_SCALED / _IM2COL_SCALED;
-                                       // 7: + BC_OP_SCHEDULER_STEP_SINGLE, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND / _COND, BC_OP_FREEU
+                                       // 7: + BC_OP_SCHEDULER_STEP_SINGLE, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND / _COND, BC_OP_FREEU;
+                                       // 8: + BC_OP_SCHEDULER_STEP_REQUESTS, BC_OP_ASSEMBLE_INPUT_REQUESTS / _IM2COL_REQUESTS,
+                                       //    BC_OP_TIMESTEP_EMBEDDING_ROWS (request batches with per-request schedules)
 // A file is written with the LOWEST version that describes it (op_min_version below): a plan without a version-6 op stays a version-5
 // file, byte for byte what the previous library wrote and still readable by it.
 inline uint32_t op_min_version(int op) {
+    if (op == BC_OP_SCHEDULER_STEP_REQUESTS || op == BC_OP_ASSEMBLE_INPUT_REQUESTS || op == BC_OP_ASSEMBLE_IM2COL_REQUESTS ||
+        op == BC_OP_TIMESTEP_EMBEDDING_ROWS) return 8u;
     // (BC_OP_FREEU joined version 7 without a new version number: a reader built before it refuses the record as an unknown op code)
     if (op == BC_OP_SCHEDULER_STEP_SINGLE || op == BC_OP_TIMESTEP_EMBEDDING_TABLE_COND || op == BC_OP_TIMESTEP_EMBEDDING_COND ||
         op == BC_OP_FREEU) return 7u;
@@ -70,6 +74,10 @@ inline const char* op_signature(int op) {
         case BC_OP_TIMESTEP_EMBEDDING_TABLE_COND: return "piiipp";
         case BC_OP_TIMESTEP_EMBEDDING_COND: return "ppfiipp";
         case BC_OP_FREEU: return "pipiiipippppp";
+        case BC_OP_SCHEDULER_STEP_REQUESTS: return "pppppiiipiiipi";
+        case BC_OP_ASSEMBLE_INPUT_REQUESTS: return "pipppiiiiiiippip";
+        case BC_OP_ASSEMBLE_IM2COL_REQUESTS: return "pippiiiiippip";
+        case BC_OP_TIMESTEP_EMBEDDING_ROWS: return "piipip";
         default: return nullptr;
     }
 }
@@ -184,6 +192,7 @@ inline std::string parse_plan(FILE* f, PlanImage& img, const std::function<uint6
     for (int s = 0; s < kMaxStreams; ++s) img.slab[s] = get_ptr();
     const uint32_t nseg = rd.u32();
     if (!rd.ok || nseg > (1u << 16)) return "corrupt segment count";
+    uint32_t needed = op_min_version(BC_OP_GEMM);    // the version the launches of this file need
     for (uint32_t si = 0; si < nseg; ++si) {
         img.segs.emplace_back();
         SegImage& sg = img.segs.back();
@@ -196,6 +205,7 @@ inline std::string parse_plan(FILE* f, PlanImage& img, const std::function<uint6
             if (!rd.ok || sid >= (uint32_t)kMaxStreams) return "stream id out of range";
             if (op != (uint32_t)BC_OP_GEMM && (!op_signature((int)op) || op_min_version((int)op) > version)) return "unknown op code";
             r.op = (int)op; r.sid = (int)sid; r.enabled = enabled ? 1 : 0;
+            if (op_min_version(r.op) > needed) needed = op_min_version(r.op);
             if (r.op == BC_OP_GEMM) {
                 rd.raw(&r.g, sizeof(r.g));
                 for (size_t fo : kGemmPtrFields) {
@@ -214,6 +224,9 @@ inline std::string parse_plan(FILE* f, PlanImage& img, const std::function<uint6
         }
     }
     if (bad_ptr) return "pointer outside its buffer";
+    // a file carries the LOWEST version that describes it (the writer's rule above), so the number in the header is the one its
+    // launches need: a header that claims more was not written by any library build
+    if (needed != version) return "unsupported plan version: not the one the file's launches need";
     return "";
 }
 

@@ -640,16 +640,22 @@ class TrunkPlan:
         h = self.dense(h, B, te, "time_embedding.linear_2", te, act=_lib.ACT_SILU, kind="temb")   # silu(emb)
         self.tproj = self.dense(h, B, te, "temb_all", pw.temb_total, kind="temb")
 
-    def record_time_table(self, t_table, nsteps, t_idx, cond=None):
+    def record_time_table(self, t_table, nsteps, t_idx, cond=None, per_image=False):
         """The same three GEMMs over ALL steps of an edit at once (prologue): tproj [nsteps * B][temb_total]; the ResBlock
         epilogues then pick the block of the current step through the device step counter (BcGemm.rowvec_idx), and no
-        time-embedding launch is left in the step.  `cond` as in record_time: row r of the table takes cond_proj(cond)[r % B]."""
+        time-embedding launch is left in the step.  `cond` as in record_time: row r of the table takes cond_proj(cond)[r % B].
+        `per_image`: t_table is [nsteps][B], a timestep per step AND image (a request batch whose requests run their own schedules):
+        the sinusoid comes from bc_timestep_embedding_rows, everything behind it is what it is."""
         rec, pw, B = self.rec, self.pw, self.B
         c0 = self.cfg.block_out_channels[0]
         te = c0 * 4
         rows = nsteps * B
         sin = rec.empty(rows, c0)
-        if cond is not None:
+        if per_image:
+            proj = self.record_cond_proj(cond) if cond is not None else None
+            rec.call("bc_timestep_embedding_rows", _ptr(t_table), rows, c0, _ptr(proj), B, sin.data_ptr(), kind="temb",
+                     keep=(t_table, proj, sin))
+        elif cond is not None:
             proj = self.record_cond_proj(cond)
             rec.call("bc_timestep_embedding_table_cond", _ptr(t_table), nsteps, B, c0, proj.data_ptr(), sin.data_ptr(), kind="temb",
                      keep=(t_table, proj, sin))

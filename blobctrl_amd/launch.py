@@ -595,7 +595,7 @@ class Recorder:
 
     # ------------------------------------------------------------------ norms
     def _op(self, name, args, kind, **meta):
-        self._add_op(_lib.OPS[name], _lib.op_signature(name), args, kind, **meta)
+        self._add_op(_lib.op_code(name), _lib.op_signature(name), args, kind, **meta)
 
     def gn_sources(self, x1, C1, x2, C2, B, HW, G):
         """GroupNorm statistics totals of (x1 | x2) for a GroupNorm of G groups: the tables the producers' epilogues added to when they
@@ -762,7 +762,7 @@ class Recorder:
 
     # ------------------------------------------------------------------ glue
     def call(self, name, *args, kind=None, keep=()):
-        """Record a generic `bc_<name>(*args, stream)` launch (any entry point listed in _lib.OPS)."""
+        """Record a generic `bc_<name>(*args, stream)` launch (any entry point listed in _lib.OPS / _lib.REQUEST_OPS)."""
         self.keep.append(keep)
         for t in keep if isinstance(keep, (tuple, list)) else (keep,):
             self.register(t)

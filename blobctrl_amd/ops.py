@@ -10,6 +10,7 @@ its hot path, FreeU, and the five steps of its blob visualisation / feature grid
     blobctrl::blobnet_forward  blobctrl/models/blobnet.py:720-945          (BlobNetModel.forward -> down / mid / up residuals)
     blobctrl::unet_forward     D/models/unets/unet_2d_condition.py:1039-1353 (patched forward with the three residual lists)
     blobctrl::denoise          blobctrl/pipelines/pipeline_blobnet.py:1025-1123 (the whole loop: one hipGraph launch per edit)
+    blobctrl::denoise_requests the same loop for a request batch with per-request step counts, guidance scales and control windows
     blobctrl::freeu            D/utils/torch_utils.py:93-148                (apply_freeu on (hidden, skip) in front of an up-block concat)
     blobctrl::splat_maps       blobctrl/utils/utils.py:120-135, 145-181    (raw and composed scores, channels-last)
     blobctrl::alpha_composite  blobctrl/utils/utils.py:179-181, 205-209    (compositing of raw scores a viz_score_fn changed)
@@ -213,6 +214,28 @@ def denoise(prompt_embeds: torch.Tensor, fg_image_latents: torch.Tensor, bg_imag
 @denoise.register_fake
 def _(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, latents, num_inference_steps, guidance_scale,
       conditioning_scales, guidance_start, guidance_end, handle, scales_are_per_request=False, eta=0.0, variance_noise=None):
+    eng = _get(handle)
+    return torch.empty(tuple(latents.shape), dtype=torch.float32, device=eng.device)
+
+
+@torch.library.custom_op("blobctrl::denoise_requests", mutates_args=())
+def denoise_requests(prompt_embeds: torch.Tensor, fg_image_latents: torch.Tensor, bg_image_latents: torch.Tensor, gs_score: torch.Tensor,
+                     dino_feats: torch.Tensor, latents: torch.Tensor, num_inference_steps: List[int], guidance_scale: List[float],
+                     conditioning_scales: List[float], guidance_start: List[float], guidance_end: List[float], handle: int) -> torch.Tensor:
+    """The denoise loop of a request batch whose requests run their own schedules: one entry per request in every list (step count,
+    guidance scale, conditioning scale, control window).  Final latents [B][4][h][w] fp32 on the engine's device; a request that ends
+    before the longest one keeps the latents of its own last step."""
+    eng = _get(handle)
+    return eng.denoise(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats,
+                       num_inference_steps=[int(v) for v in num_inference_steps], guidance_scale=[float(v) for v in guidance_scale],
+                       latents=latents, blobnet_conditioning_scale=[float(v) for v in conditioning_scales],
+                       blobnet_control_guidance_start=[float(v) for v in guidance_start],
+                       blobnet_control_guidance_end=[float(v) for v in guidance_end])
+
+
+@denoise_requests.register_fake
+def _(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, latents, num_inference_steps, guidance_scale,
+      conditioning_scales, guidance_start, guidance_end, handle):
     eng = _get(handle)
     return torch.empty(tuple(latents.shape), dtype=torch.float32, device=eng.device)
 

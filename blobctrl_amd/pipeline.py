@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .engine import TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder
-from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, table_class
+from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, stack_request_tables, table_class
 from .weights import PackedTrunk, lora_scale_of, pad8
 
 
@@ -94,7 +94,7 @@ class BlobCtrlEngine:
 
     # ------------------------------------------------------------------------------------------------ planning
     def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-              freeu=False):
+              freeu=False, requests=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
@@ -109,11 +109,19 @@ class BlobCtrlEngine:
         in bc_scheduler_step_single, which takes the right half of image b as eps.  BlobNet is what it is in every plan: batch B.
         freeu: FreeU is on (UNet2DConditionModel.enable_freeu) - every UNet forward runs bc_freeu in front of the six channel concats of
         up_blocks.0 / up_blocks.1, reading (s1, s2, b1, b2) from the named buffer `freeu` (fp32 [4], refilled per edit: one plan and its
-        graphs serve every setting).  A plan of its own; BlobNet's up blocks never run it."""
+        graphs serve every setting).  A plan of its own; BlobNet's up blocks never run it.
+        requests: a request batch (per_request) whose requests run their OWN schedules - step count, guidance scale, control window,
+        eta, timesteps.  The loop has nsteps = the longest request's evaluations; the plan owns `coef` [B][nsteps][16] (a table per
+        request, finished rows marked in column 15), `t_rows_unet` [nsteps][Bu] / `t_rows_blob` [nsteps][B] (a timestep per step and
+        image; no `t_table`) and `scale_table` [nsteps][B]; the time tables come from bc_timestep_embedding_rows, a scaling table
+        assembles through the `_requests` entry points (a divisor per image) and both step segments end in
+        bc_scheduler_step_requests.  The networks are what they are in every request batch."""
+        if requests and not per_request:
+            raise ValueError("per-request schedules need a request batch (per_request)")
         if stochastic and third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
         key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
-            (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ())
+            (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ()) + (("requests",) if requests else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -147,8 +155,15 @@ class BlobCtrlEngine:
         cond_dim = self.unet_cfg.time_cond_proj_dim
         P.timestep_cond = rec.zeros(Bu, pad8(cond_dim), name="timestep_cond") if cond_dim is not None else None
         P.step_idx = rec.zeros(1, dtype=torch.int32, name="step_idx")
-        P.t_table = rec.zeros(nsteps, dtype=f32, name="t_table")
-        P.coef = rec.zeros(nsteps, 16, dtype=f32, name="coef")
+        P.requests = bool(requests)
+        if requests:
+            P.t_table = None
+            P.t_rows_unet = rec.zeros(nsteps, Bu, dtype=f32, name="t_rows_unet")
+            P.t_rows_blob = rec.zeros(nsteps, B, dtype=f32, name="t_rows_blob")
+            P.coef = rec.zeros(B, nsteps, 16, dtype=f32, name="coef")
+        else:
+            P.t_table = rec.zeros(nsteps, dtype=f32, name="t_table")
+            P.coef = rec.zeros(nsteps, 16, dtype=f32, name="coef")
         P.scale_table = rec.zeros(nsteps * Bi, dtype=f32, name="scale_table")   # [step][image] conditioning_scale * keep
         P.hist = rec.zeros(3, B * 4 * h * w, dtype=f32, name="hist")
         P.eps_guided = rec.zeros(B, 4, h, w, dtype=f32, name="eps_guided")
@@ -183,7 +198,11 @@ class BlobCtrlEngine:
             blob.record_collapse(P.feat16, per_image=B if per_request else 0)
         # time-embedding path of every step, once per edit (read in the step through the device step counter)
         temb_per_step = False                                # (the per-edit table replaced the four launches per net inside every step)
-        if not temb_per_step:
+        if requests:
+            unet_a.record_time_table(P.t_rows_unet, nsteps, P.step_idx, per_image=True,
+                                     **({} if P.timestep_cond is None else dict(cond=P.timestep_cond)))
+            blob.record_time_table(P.t_rows_blob, nsteps, P.step_idx, per_image=True)
+        elif not temb_per_step:
             unet_a.record_time_table(P.t_table, nsteps, P.step_idx, **({} if P.timestep_cond is None else dict(cond=P.timestep_cond)))
             blob.record_time_table(P.t_table, nsteps, P.step_idx)          # (BlobNet never has a cond_proj: pipe:1063 passes no timestep_cond)
 
@@ -212,9 +231,9 @@ class BlobCtrlEngine:
             return hp
 
         # the input assembly of a net: the entry point's `_scaled` form, with (coef, step_idx, nsteps) in front of the output, when the
-        # table scales the model input
+        # table scales the model input (`_requests`: the same with a table, hence a divisor, per request)
         divisor = (P.coef.data_ptr(), P.step_idx.data_ptr(), nsteps) if P.scaled else ()
-        suffix = "_scaled" if P.scaled else ""
+        suffix = ("_requests" if requests else "_scaled") if P.scaled else ""
 
         def record_unet(plan, residuals):
             if P.unet_im2col:
@@ -239,6 +258,10 @@ class BlobCtrlEngine:
             else:
                 eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=not single)   # (images b and b + B: the CFG pair)
             P.eps = eps
+            if requests:                                          # one entry point, every step form: noise (or NULL), nsteps, third, single
+                rec.call("bc_scheduler_step_requests", eps, P.latents, P.coef, P.step_idx, P.hist, B, h, w, P.variance_noise, nsteps,
+                         int(P.third_order), int(single), P.eps_guided, 1, kind="cfg_step")
+                return
             if single:                                            # one entry point, every step form: noise (or NULL), nsteps, third
                 rec.call("bc_scheduler_step_single", eps, P.latents, P.coef, P.step_idx, P.hist, B, h, w, P.variance_noise, nsteps,
                          int(P.third_order), P.eps_guided, 1, kind="cfg_step")
@@ -473,6 +496,213 @@ class BlobCtrlEngine:
         self.stream.synchronize()
         return img if output_type == "pt" else img.permute(0, 2, 3, 1).cpu().float().numpy()
 
+    # ------------------------------------------------------------------------------------------------ per-request values
+    @staticmethod
+    def _listed(**kw):
+        """Names of the call arguments that were given per request: a list (for `timesteps`, a list of lists)."""
+        out = [k for k, v in kw.items() if k != "timesteps" and isinstance(v, (list, tuple))]
+        ts = kw.get("timesteps")
+        if ts is not None and len(ts) > 0 and isinstance(ts[0], (list, tuple)):
+            out.append("timesteps")
+        return out
+
+    def _request_values(self, B, per_request, blobnet_conditioning_scale, req_scales, num_inference_steps, guidance_scale, start, end, eta,
+                        timesteps):
+        """The per-request values of a request batch, validated: (steps or timestep lists, guidance scales, window starts, window ends,
+        etas), B entries each - a scalar argument means the same for every request.  Every refusal of a call with lists is raised here
+        or by the tables built from these values, before a plan is recorded."""
+        given = dict(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, blobnet_control_guidance_start=start,
+                     blobnet_control_guidance_end=end, eta=eta, timesteps=timesteps)
+        listed = self._listed(**given)
+        for k in listed:
+            if not per_request:
+                raise ValueError(f"{k}: a list of per-request values needs a request batch (fg_image_latents with a leading dimension "
+                                 f"B > 1, one entry per request); this call is one edit of B = {B}")
+            if len(given[k]) != B:
+                raise ValueError(f"{k}: expected {B} values (one per request, B = {B}), got {len(given[k])}")
+        for k in ("guidance_scale", "blobnet_control_guidance_start", "blobnet_control_guidance_end"):
+            if k in listed and not all(isinstance(v, float) for v in given[k]):
+                raise TypeError(f"per-request `{k}` must be a list of `float`.")
+        if "num_inference_steps" in listed and not all(isinstance(v, int) and not isinstance(v, bool) for v in num_inference_steps):
+            raise TypeError("per-request `num_inference_steps` must be a list of `int`.")
+        per = {k: list(v) if k in listed else [v] * B for k, v in given.items()}
+        if timesteps is not None:                                # (a request's edit has len(timesteps_b) steps, as in the scalar call)
+            per["num_inference_steps"] = [list(t) for t in per["timesteps"]]
+        self.check_inputs(blobnet_conditioning_scale, 0.0, 1.0, 1)              # (the type of the conditioning scales)
+        for b in range(B):
+            st = per["num_inference_steps"][b]
+            try:
+                self.check_inputs(req_scales[b], per["blobnet_control_guidance_start"][b], per["blobnet_control_guidance_end"][b],
+                                  len(st) if isinstance(st, list) else st)
+            except ValueError as e:
+                raise ValueError(f"request {b}: {e}") from None
+        etas = [float(v) for v in per["eta"]]
+        for v in etas:
+            self._check_eta(v)
+        return per["num_inference_steps"], per["guidance_scale"], per["blobnet_control_guidance_start"], \
+            per["blobnet_control_guidance_end"], etas
+
+    def _request_tables(self, steps, etas):
+        """The table object of every request (cached like any other table) and the step form of the plan they run on together: a noise
+        row or a third-order row in any of them puts the whole batch on that form."""
+        tables = [self._scheduler_table(len(st) if isinstance(st, list) else st, eta, st if isinstance(st, list) else None)
+                  for st, eta in zip(steps, etas)]
+        forms = [self._step_form(t, eta > 0) for t, eta in zip(tables, etas)]
+        return tables, any(f[0] for f in forms), any(f[1] for f in forms)
+
+    @staticmethod
+    def _request_scale_rows(evals, req_scales, starts, ends):
+        """scale_table [nmax][B] of a request batch with per-request schedules: request b's `blobnet_keep(n_b, start_b, end_b) *
+        scale_b`, and 0 from its end on (a finished image rides through BlobNet with conditioning scale 0)."""
+        nmax = max(evals)
+        keeps = [blobnet_keep(n, s_, e_) + [0.0] * (nmax - n) for n, s_, e_ in zip(evals, starts, ends)]
+        return [[sc * k[i] for sc, k in zip(req_scales, keeps)] for i in range(nmax)]
+
+    def _request_noise(self, tables, evals, h, w, generator, device):
+        """variance_noise [nmax][B][4][h][w] of a request batch with per-request schedules.  A list of generators (one per request):
+        request b draws what it would draw alone - one [1, 4, h, w] slice per step of its own, in step order, skipping the steps its
+        table does not draw for (`draws`, LCM) - and zeros behind its end.  One generator or None: one [B, 4, h, w] draw per step of
+        the loop, as the scalar request batch draws them (a step draws when any request's table draws in it)."""
+        nmax, B = max(evals), len(tables)
+        draws = [(list(getattr(t, "draws", None) or [True] * n) + [False] * (nmax - n)) for t, n in zip(tables, evals)]
+        if isinstance(generator, list) and len(generator) > 1:
+            zero = torch.zeros(1, 4, h, w, dtype=torch.float32, device=device)
+            per = [torch.cat([randn_tensor((1, 4, h, w), generator[b], device) if d else zero for d in draws[b]], 0) for b in range(B)]
+            return torch.stack(per, 1)
+        return draw_variance_noise(nmax, (B, 4, h, w), generator, device, [any(d[i] for d in draws) for i in range(nmax)])
+
+    def _denoise_requests(self, prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, num_inference_steps, guidance_scale,
+                          generator, latents, blobnet_conditioning_scale, start, end, output_type, callback_on_step_end, trace,
+                          teacher_latents, eta, do_classifier_free_guidance, callback_self, variance_noise, timesteps, single_pass,
+                          timestep_cond, freeu):
+        """`denoise` for a request batch with per-request values (a list for any of num_inference_steps, guidance_scale, the control
+        window, eta, timesteps): every request runs its own table rows, timesteps, window and guidance scale, left-aligned in a loop of
+        nmax = the longest request's evaluations; behind its last row a request is finished and the step leaves it alone."""
+        gs = list(guidance_scale) if isinstance(guidance_scale, (list, tuple)) else [guidance_scale]
+        prompt_embeds, B, T, Dc, single, guidance_off = self._prompt_layout(
+            prompt_embeds, latents, all(isinstance(v, (int, float)) for v in gs) and max(gs) > 1.0, do_classifier_free_guidance, single_pass)
+        h, w = fg_image_latents.shape[-2:]
+        per_request, Bi, req_scales = self._request_batch(B, fg_image_latents, bg_image_latents, gs_score, dino_feats,
+                                                          blobnet_conditioning_scale, generator)
+        steps, gs, starts, ends, etas = self._request_values(B, per_request, blobnet_conditioning_scale, req_scales, num_inference_steps,
+                                                             guidance_scale, start, end, eta, timesteps)
+        gs = [1.0 if guidance_off else max(1.0, float(v)) for v in gs]       # (a request at or below 1: its eps is its conditional half)
+        tables, stochastic, third_order = self._request_tables(steps, etas)
+        coef, t_rows, evals = stack_request_tables(tables, gs)
+        n = max(evals)
+        if timestep_cond is not None:
+            dim = self.unet_cfg.time_cond_proj_dim
+            if dim is None:
+                raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
+            if tuple(timestep_cond.shape) != (B, dim):
+                raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
+        if variance_noise is not None:
+            if not stochastic:
+                raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++, an Euler-ancestral or an LCM "
+                                 "scheduler")
+            if generator is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                                 " `variance_noise` stays `None`.")
+            if tuple(variance_noise.shape) != (n, B, 4, h, w):
+                raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (longest request's steps, batch, 4, h, w), got "
+                                 f"{tuple(variance_noise.shape)}")
+        freeu_on = freeu_enabled(freeu)
+        P = self._plan(B, h, w, T, Dc, n, True, stochastic, third_order, tables[0].scales_input, single, freeu_on, requests=True)
+        dev = self.device
+        self.timesteps = [t.timesteps for t in tables]
+        if latents is None:                                                          # pipe:438-453
+            g0 = generator[0] if isinstance(generator, list) else generator
+            latents = randn_tensor((B, 4, h, w), generator, g0.device if g0 is not None else "cpu")
+        if stochastic and variance_noise is None:
+            variance_noise = self._request_noise(tables, evals, h, w, generator, dev)
+        scale_rows = self._request_scale_rows(evals, req_scales, starts, ends)       # [step][image]
+        scales = [max(abs(v) for v in row) for row in scale_rows]                    # a step runs BlobNet when any request is active in it
+        bg, fg = gs_score.unbind(dim=1)                                              # pipe:974
+        self._join_caller()
+        with torch.cuda.stream(self.stream):
+            lat = latents.to(dev, torch.float32)
+            start_lat = torch.stack([lat[b] * t.init_noise_sigma for b, t in enumerate(tables)], 0)
+            self._fill_inputs(P, start_lat, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond)
+            P.t_rows_blob.copy_(t_rows)
+            P.t_rows_unet.copy_(t_rows if single else torch.cat([t_rows, t_rows], 1))     # (images b and B + b: the CFG pair of request b)
+            P.coef.copy_(coef)
+            P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
+            if stochastic:
+                P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
+            if freeu_on:
+                P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
+            P.step_idx.zero_()
+            P.hist.zero_()
+        live = [[i < e for e in evals] for i in range(n)]
+        return self._run(P, n, scales, start_lat, output_type, teacher_latents, callback_on_step_end, callback_self, trace,
+                         lambda i: torch.stack([t.timesteps[min(i, e - 1)] for t, e in zip(tables, evals)]), live=live)
+
+    def _prompt_layout(self, prompt_embeds, latents, guidance_on, do_classifier_free_guidance, single_pass):
+        """The layout of `prompt_embeds` and the plan form it asks for: (prompt_embeds as the plan's `ctx` takes them, B, T, ctx_dim,
+        single, guidance_off).  `guidance_on`: the call's guidance scale (any of them, in a request batch with its own) is above 1."""
+        if do_classifier_free_guidance is None:
+            do_classifier_free_guidance = guidance_on and self.unet_cfg.time_cond_proj_dim is None      # (pipe:497)
+            if not do_classifier_free_guidance:
+                if latents is None:
+                    raise ValueError("guidance_scale <= 1 without `latents`: pass do_classifier_free_guidance=False (prompt_embeds = "
+                                     "positive prompts only) or =True (negative and positive halves) - the layout cannot be inferred")
+                do_classifier_free_guidance = prompt_embeds.shape[0] != latents.shape[0]
+        guidance_off = not guidance_on or not do_classifier_free_guidance
+        single = self._single_pass(single_pass, guidance_off)
+        if not do_classifier_free_guidance and not single:
+            prompt_embeds = torch.cat([prompt_embeds, prompt_embeds], 0)
+        B2, T, Dc = prompt_embeds.shape
+        if single and not do_classifier_free_guidance:
+            B = B2                                                   # the positive prompts only, as the reference holds them
+        else:
+            if B2 % 2:
+                raise ValueError("prompt_embeds must hold the negative and positive halves (classifier-free guidance)")
+            B = B2 // 2
+            if single:
+                prompt_embeds = prompt_embeds[B:]                    # (both halves given, scale <= 1: eps is the positive half's)
+        return prompt_embeds, B, T, Dc, single, guidance_off
+
+    @staticmethod
+    def _request_batch(B, fg_image_latents, bg_image_latents, gs_score, dino_feats, blobnet_conditioning_scale, generator):
+        """(per_request, Bi, conditioning scale of every image) of a call, with the shape checks of a request batch."""
+        per_request = fg_image_latents.dim() == 4 and fg_image_latents.shape[0] > 1
+        Bi = B if per_request else 1
+        if per_request:
+            for name, t_ in (("fg_image_latents", fg_image_latents), ("bg_image_latents", bg_image_latents), ("gs_score", gs_score),
+                             ("dino_feats", dino_feats)):
+                if t_ is not None and t_.shape[0] != B:
+                    raise ValueError(f"request batch: {name} must have leading dimension {B} (one per request), got {t_.shape[0]}")
+        req_scales = list(blobnet_conditioning_scale) if isinstance(blobnet_conditioning_scale, (list, tuple)) else \
+            [blobnet_conditioning_scale] * Bi
+        if len(req_scales) != Bi:
+            raise ValueError(f"blobnet_conditioning_scale: expected {Bi} values, got {len(req_scales)}")
+        if isinstance(generator, list) and len(generator) != B:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                             f" size of {B}. Make sure the batch size matches the length of the generators.")
+        return per_request, Bi, req_scales
+
+    def _fill_inputs(self, P, start, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond):
+        """The per-edit inputs every plan form takes, into the plan's buffers (on the engine's stream)."""
+        dev, Bi = self.device, P.Bi
+        h, w = P.latents.shape[-2:]
+        P.latents.copy_(start)
+        P.fg_lat.copy_(fg_image_latents.to(dev, torch.float32).reshape(Bi, 4, h, w))
+        P.bg_lat.copy_(bg_image_latents.to(dev, torch.float32).reshape(Bi, 4, h, w))
+        P.fg_score.copy_(fg.to(dev, torch.float32).reshape(Bi, h, w))
+        P.bg_score.copy_(bg.to(dev, torch.float32).reshape(Bi, h, w))
+        if self.feat_dim > 0:
+            if dino_feats is None:
+                raise ValueError("dino_feats is required (BlobNet conditioning channels)")
+            P.feat.copy_(dino_feats.to(dev, torch.float32).reshape(Bi, self.feat_dim))
+            if P.collapse:
+                P.feat16[:, : self.feat_dim].copy_(P.feat)
+        P.ctx.copy_(prompt_embeds.to(dev, torch.float16))
+        if P.timestep_cond is not None:
+            P.timestep_cond.zero_()
+            if timestep_cond is not None:                # (both CFG halves of a sample take the sample's embedding)
+                tc = timestep_cond.to(dev, torch.float16)
+                P.timestep_cond[:, : tc.shape[1]].copy_(tc if P.single else torch.cat([tc, tc], 0))
+
     @torch.no_grad()
     def denoise(self, prompt_embeds: torch.Tensor, fg_image_latents: Optional[torch.Tensor] = None,
                  bg_image_latents: Optional[torch.Tensor] = None, gs_score: torch.Tensor = None, dino_feats: Optional[torch.Tensor] = None, num_inference_steps: int = 50,
@@ -515,7 +745,10 @@ class BlobCtrlEngine:
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
-        stochastic = self._check_eta(float(eta))
+        listed = self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                              blobnet_control_guidance_start=blobnet_control_guidance_start,
+                              blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps)
+        stochastic = None if listed else self._check_eta(float(eta))
         if output_type not in ("latent", "pt", "np"):
             raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
         if output_type != "latent" and self.vae is None:
@@ -530,6 +763,12 @@ class BlobCtrlEngine:
             if bg_image is None:
                 raise ValueError("give bg_image_latents or bg_image")
             bg_image_latents = self.encode_latents(bg_image)
+        if listed:                                               # per-request values: the `requests` plan form
+            return self._denoise_requests(
+                prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, num_inference_steps, guidance_scale, generator,
+                latents, blobnet_conditioning_scale, blobnet_control_guidance_start, blobnet_control_guidance_end, output_type,
+                callback_on_step_end, trace, teacher_latents, eta, do_classifier_free_guidance, callback_self, variance_noise, timesteps,
+                single_pass, timestep_cond, freeu)
         if timesteps is not None:
             num_inference_steps = len(timesteps)
         self.check_inputs(blobnet_conditioning_scale, blobnet_control_guidance_start, blobnet_control_guidance_end,
@@ -539,44 +778,14 @@ class BlobCtrlEngine:
         # fill both halves and the effective scale is 1, eps_u + 1 * (eps_c - eps_u) = eps_c.
         # `do_classifier_free_guidance=False` (what the reference derives from guidance_scale <= 1) says explicitly that prompt_embeds
         # holds the positive prompts only; without the flag the layout is inferred from `latents` and refused when ambiguous.
-        if do_classifier_free_guidance is None:
-            do_classifier_free_guidance = guidance_scale > 1.0 and self.unet_cfg.time_cond_proj_dim is None      # (pipe:497)
-            if not do_classifier_free_guidance:
-                if latents is None:
-                    raise ValueError("guidance_scale <= 1 without `latents`: pass do_classifier_free_guidance=False (prompt_embeds = "
-                                     "positive prompts only) or =True (negative and positive halves) - the layout cannot be inferred")
-                do_classifier_free_guidance = prompt_embeds.shape[0] != latents.shape[0]
-        guidance_off = guidance_scale <= 1.0 or not do_classifier_free_guidance
-        single = self._single_pass(single_pass, guidance_off)
-        if not do_classifier_free_guidance and not single:
-            prompt_embeds = torch.cat([prompt_embeds, prompt_embeds], 0)
+        prompt_embeds, B, T, Dc, single, guidance_off = self._prompt_layout(prompt_embeds, latents, guidance_scale > 1.0,
+                                                                            do_classifier_free_guidance, single_pass)
         if guidance_off:
             guidance_scale = 1.0
-        B2, T, Dc = prompt_embeds.shape
-        if single and not do_classifier_free_guidance:
-            B = B2                                                   # the positive prompts only, as the reference holds them
-        else:
-            if B2 % 2:
-                raise ValueError("prompt_embeds must hold the negative and positive halves (classifier-free guidance)")
-            B = B2 // 2
-            if single:
-                prompt_embeds = prompt_embeds[B:]                    # (both halves given, scale <= 1: eps is the positive half's)
         h, w = fg_image_latents.shape[-2:]
         n = num_inference_steps
-        per_request = fg_image_latents.dim() == 4 and fg_image_latents.shape[0] > 1
-        Bi = B if per_request else 1
-        if per_request:
-            for name, t_ in (("fg_image_latents", fg_image_latents), ("bg_image_latents", bg_image_latents), ("gs_score", gs_score),
-                             ("dino_feats", dino_feats)):
-                if t_ is not None and t_.shape[0] != B:
-                    raise ValueError(f"request batch: {name} must have leading dimension {B} (one per request), got {t_.shape[0]}")
-        req_scales = list(blobnet_conditioning_scale) if isinstance(blobnet_conditioning_scale, (list, tuple)) else \
-            [blobnet_conditioning_scale] * Bi
-        if len(req_scales) != Bi:
-            raise ValueError(f"blobnet_conditioning_scale: expected {Bi} values, got {len(req_scales)}")
-        if isinstance(generator, list) and len(generator) != B:
-            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
-                             f" size of {B}. Make sure the batch size matches the length of the generators.")
+        per_request, Bi, req_scales = self._request_batch(B, fg_image_latents, bg_image_latents, gs_score, dino_feats,
+                                                          blobnet_conditioning_scale, generator)
         sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
         n = len(sched.timesteps)                             # network evaluations (Heun: 2 * num_inference_steps - 1, pipe:1025 loops over them)
         stochastic, third_order = self._step_form(sched, stochastic)
@@ -611,23 +820,8 @@ class BlobCtrlEngine:
         bg, fg = gs_score.unbind(dim=1)                                              # pipe:974
         self._join_caller()
         with torch.cuda.stream(self.stream):
-            P.latents.copy_(latents.to(dev, torch.float32) * sched.init_noise_sigma)
-            P.fg_lat.copy_(fg_image_latents.to(dev, torch.float32).reshape(Bi, 4, h, w))
-            P.bg_lat.copy_(bg_image_latents.to(dev, torch.float32).reshape(Bi, 4, h, w))
-            P.fg_score.copy_(fg.to(dev, torch.float32).reshape(Bi, h, w))
-            P.bg_score.copy_(bg.to(dev, torch.float32).reshape(Bi, h, w))
-            if self.feat_dim > 0:
-                if dino_feats is None:
-                    raise ValueError("dino_feats is required (BlobNet conditioning channels)")
-                P.feat.copy_(dino_feats.to(dev, torch.float32).reshape(Bi, self.feat_dim))
-                if P.collapse:
-                    P.feat16[:, : self.feat_dim].copy_(P.feat)
-            P.ctx.copy_(prompt_embeds.to(dev, torch.float16))
-            if P.timestep_cond is not None:
-                P.timestep_cond.zero_()
-                if timestep_cond is not None:                # (both CFG halves of a sample take the sample's embedding)
-                    tc = timestep_cond.to(dev, torch.float16)
-                    P.timestep_cond[:, : tc.shape[1]].copy_(tc if P.single else torch.cat([tc, tc], 0))
+            start = latents.to(dev, torch.float32) * sched.init_noise_sigma
+            self._fill_inputs(P, start, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond)
             P.t_table.copy_(sched.timesteps.to(torch.float32))
             coef = sched.table().clone()
             coef[:, 11] = float(guidance_scale)          # read by the captured cfg/scheduler kernel
@@ -640,13 +834,21 @@ class BlobCtrlEngine:
             P.step_idx.zero_()
             P.hist.zero_()
         P.guidance[0] = float(guidance_scale)
+        return self._run(P, n, scales, start, output_type, teacher_latents, callback_on_step_end, callback_self, trace,
+                         lambda i: sched.timesteps[i].item())
+
+    def _run(self, P, n, scales, start, output_type, teacher_latents, callback_on_step_end, callback_self, trace, step_time, live=None):
+        """Run the edit whose inputs and tables are in the plan's buffers: `scales[i]` != 0 = step i runs BlobNet, `start` = the start
+        latents as P.latents holds them, `step_time(i)` = what a callback is given as the timestep of step i.  `live` (a request batch
+        with per-request schedules): per step, which requests still run - `teacher_latents` replace those and leave the others alone."""
+        dev = self.device
         s, side = self._streams()
         if teacher_latents is None and callback_on_step_end is None and trace is None and not P.captured:
             self.stream.synchronize()
             self._capture(P)
             # captured segments left the step counter advanced by the warm-up runs: reset per-edit state
             with torch.cuda.stream(self.stream):
-                P.latents.copy_(latents.to(dev, torch.float32) * sched.init_noise_sigma)
+                P.latents.copy_(start)
                 P.step_idx.zero_()
                 P.hist.zero_()
         plain = teacher_latents is None and callback_on_step_end is None and trace is None
@@ -669,7 +871,11 @@ class BlobCtrlEngine:
         for i in range(n):
             if teacher_latents is not None:
                 with torch.cuda.stream(self.stream):
-                    P.latents.copy_(teacher_latents[i].to(dev, torch.float32))
+                    if live is None:
+                        P.latents.copy_(teacher_latents[i].to(dev, torch.float32))
+                    else:                                                          # (entries past a request's end are ignored)
+                        for b in (b for b, on in enumerate(live[i]) if on):
+                            P.latents[b].copy_(teacher_latents[i][b].to(dev, torch.float32))
             seg = P.step_active if scales[i] != 0.0 else P.step_inactive
             seg.run(s, side, self._extra())
             if trace is not None:
@@ -677,7 +883,7 @@ class BlobCtrlEngine:
                 trace.append((P.eps_guided.clone(), P.latents.clone()))
             if callback_on_step_end is not None:
                 self.stream.synchronize()
-                ret = callback_on_step_end(callback_self or self, i, sched.timesteps[i].item(), {"latents": P.latents})
+                ret = callback_on_step_end(callback_self or self, i, step_time(i), {"latents": P.latents})
                 if isinstance(ret, dict) and ret.get("latents") is not None and ret["latents"] is not P.latents:
                     with torch.cuda.stream(self.stream):                         # pipe:1112 `latents = callback_outputs.pop(...)`
                         P.latents.copy_(ret["latents"].to(dev, torch.float32))
@@ -705,6 +911,22 @@ class BlobCtrlEngine:
         # (ints and anything else take `denoise` directly, which raises the reference's TypeError for them)
         is_list = isinstance(sc, (list, tuple))
         sc_ok = isinstance(sc, float) or (is_list and len(sc) > 0 and all(isinstance(v, float) for v in sc))
+        req = ("num_inference_steps", "guidance_scale", "blobnet_control_guidance_start", "blobnet_control_guidance_end")
+        if any(isinstance(kw.get(k), (list, tuple)) for k in req + ("eta",)):
+            # per-request values: torch.ops.blobctrl.denoise_requests, whose four list arguments hold one entry per request (a scalar is
+            # repeated); whatever its schema cannot carry (eta, noise, a malformed list) takes `denoise`, which runs or refuses it
+            B = fg_image_latents.shape[0] if torch.is_tensor(fg_image_latents) else 0
+            v = {k: list(kw[k]) if isinstance(kw.get(k), (list, tuple)) else [kw.get(k, d)] * B
+                 for k, d in zip(req, (50, 7.5, 0.0, 1.0))}
+            ok = (B > 1 and all(len(x) == B for x in v.values()) and all(isinstance(x, int) and not isinstance(x, bool) for x in v[req[0]])
+                  and all(isinstance(x, float) for k in req[1:] for x in v[k]))
+            if (ok and set(kw) <= set(req) | {"latents", "blobnet_conditioning_scale"} and kw.get("latents") is not None
+                    and bg_image_latents is not None and gs_score is not None and dino_feats is not None and sc_ok):
+                from . import ops
+                return torch.ops.blobctrl.denoise_requests(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, kw["latents"],
+                                                           v[req[0]], v[req[1]], [float(x) for x in sc] if is_list else [float(sc)] * B,
+                                                           v[req[2]], v[req[3]], ops.register(self))
+            return self.denoise(prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, **kw)
         if (set(kw) <= plain and kw.get("latents") is not None and fg_image_latents is not None and bg_image_latents is not None
                 and gs_score is not None and dino_feats is not None and kw.get("guidance_scale", 7.5) > 1.0 and sc_ok):   # (else: denoise raises)
             from . import ops
@@ -735,7 +957,15 @@ class BlobCtrlEngine:
         time_cond_proj_dim adds the named buffer `timestep_cond` (fp16 [B or 2B][pad8(dim)], zero-filled: the host writes the
         guidance-scale embedding of every UNet image into it before an edit).
         `freeu` = (s1, s2, b1, b2) as in `denoise`: a FreeU plan holds six BC_OP_FREEU launches per UNet forward, their basis tables, and
-        the named buffer `freeu` (fp32 [4]) saved with these values; a host writes other values into it before an edit."""
+        the named buffer `freeu` (fp32 [4]) saved with these values; a host writes other values into it before an edit.
+        A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps compiles the
+        mixed edit of a request batch of B: `_compile_requests`."""
+        if self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                        blobnet_control_guidance_start=blobnet_control_guidance_start,
+                        blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps):
+            return self._compile_requests(path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale, blobnet_conditioning_scale,
+                                          blobnet_control_guidance_start, blobnet_control_guidance_end, eta, variance_noise, timesteps,
+                                          single_pass, freeu)
         single = self._single_pass(single_pass, guidance_scale <= 1.0 or self.unet_cfg.time_cond_proj_dim is not None)   # (pipe:497)
         n = num_inference_steps if timesteps is None else len(timesteps)
         stochastic = self._check_eta(float(eta))
@@ -767,10 +997,54 @@ class BlobCtrlEngine:
         P.rec.save(path)
         return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
 
+    def _compile_requests(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale, blobnet_conditioning_scale, start, end, eta,
+                          variance_noise, timesteps, single_pass, freeu):
+        """`compile_plan` with per-request values (lists as `denoise` takes them; `blobnet_conditioning_scale` a float or a list of B):
+        the mixed edit of a request batch of B as a `.bcplan` of file version 8.  Beside the per-request inputs of a request batch
+        (fg_lat, bg_lat, fg_score, bg_score, feat / feat16 with a leading B) it holds, saved with their contents, `coef`
+        [B][nmax][16], `t_rows_unet` [nmax][2B or B], `t_rows_blob` [nmax][B] and `scale_table` [nmax][B]; `variance_noise`
+        [nmax][B][4][h][w] as in `compile_plan`.  Returns the per-step segment names of the nmax steps."""
+        gs = list(guidance_scale) if isinstance(guidance_scale, (list, tuple)) else [guidance_scale]
+        guidance_off = not (all(isinstance(v, (int, float)) for v in gs) and max(gs) > 1.0) or self.unet_cfg.time_cond_proj_dim is not None
+        single = self._single_pass(single_pass, guidance_off)
+        req_scales = list(blobnet_conditioning_scale) if isinstance(blobnet_conditioning_scale, (list, tuple)) else \
+            [blobnet_conditioning_scale] * B
+        if len(req_scales) != B:
+            raise ValueError(f"blobnet_conditioning_scale: expected {B} values, got {len(req_scales)}")
+        steps, gs, starts, ends, etas = self._request_values(B, B > 1, blobnet_conditioning_scale, req_scales, num_inference_steps,
+                                                             guidance_scale, start, end, eta, timesteps)
+        gs = [1.0 if guidance_off else max(1.0, float(v)) for v in gs]
+        tables, stochastic, third_order = self._request_tables(steps, etas)
+        coef, t_rows, evals = stack_request_tables(tables, gs)
+        n = max(evals)
+        if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
+            raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
+        freeu_on = freeu_enabled(freeu)
+        P = self._plan(B, h, w, T, ctx_dim, n, True, stochastic, third_order, tables[0].scales_input, single, freeu_on, requests=True)
+        if freeu_on:
+            P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
+        scale_rows = self._request_scale_rows(evals, req_scales, starts, ends)
+        P.t_rows_blob.copy_(t_rows)
+        P.t_rows_unet.copy_(t_rows if single else torch.cat([t_rows, t_rows], 1))
+        P.coef.copy_(coef)
+        P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
+        for t in (P.t_rows_blob, P.t_rows_unet, P.coef, P.scale_table) + ((P.freeu,) if freeu_on else ()):     # saved WITH their contents
+            P.rec._workspace.discard(t.untyped_storage().data_ptr())
+        if stochastic:
+            key = P.variance_noise.untyped_storage().data_ptr()
+            if variance_noise is not None:
+                P.variance_noise.copy_(variance_noise.to(P.variance_noise.device, torch.float32))
+                P.rec._workspace.discard(key)
+            else:
+                P.variance_noise.zero_()
+                P.rec._workspace.add(key)
+        P.rec.save(path)
+        return ["step_active" if any(v != 0.0 for v in row) else "step_inactive" for row in scale_rows]
+
     # convenience for bench / tests ------------------------------------------------------------------
     def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-                 freeu=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu)
+                 freeu=False, requests=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests)
 
 
 # ======================================================================================================================

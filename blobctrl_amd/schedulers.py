@@ -17,7 +17,11 @@ whose scalar coefficients are precomputed here per step index, uploaded once, an
                                                            Euler-ancestral and Heun: `bc_assemble_input_scaled`, `bc_assemble_input_im2col_scaled`).
                                                            0 in every other table: UniPC, DDIM and DPM-Solver++ do not scale their input and
                                                            never reach a kernel that reads the column
-    [15] unused
+    [15] finished                                          only in the per-request tables of a request batch whose requests run their own
+                                                           schedules (`request_tables`, coef [B][nmax][16], `bc_scheduler_step_requests`):
+                                                           != 0 marks a row past the request's last step - "leave this image alone", the
+                                                           step neither reads its eps nor writes its latents / history.  0 in every table
+                                                           a scheduler builds; no other kernel reads the column
 Scalar maths follows the reference in fp32 torch CPU ops (same operation order) so the tables match it to rounding.
 DPM-Solver++ (scheduling_dpmsolver_multistep.py) fills c0 / c1 (x0), c7 (x), c8 (x0), c9 (x0_{i-1}), c12 (SDE noise) and c13 (order 3).
 The sigma-space (k-diffusion) schedulers work on x = x0 + sigma * eps: an Euler step x' = x + (sigma_next - sigma) * eps is c0 = 1,
@@ -688,6 +692,47 @@ def apply_table_step(coef_row, eps, x, hist, noise=None):
         xn = xn + c[12] * noise
     hist["m1"], hist["m0"], hist["last"] = hist["m0"], x0, xc
     return xn
+
+
+def stack_request_tables(tables, guidance):
+    """Tables that have had their `set_timesteps` (one per request) -> (coef [B][nmax][16], t_rows [nmax][B] fp32, evals [B]): request
+    b's rows as they are, left-aligned, with its guidance scale in column 11; behind them FINISHED rows up to the longest request -
+    column 15 = 1 (the step leaves the image alone), column 14 = 1 (its input is not divided), every other column 0, the request's last
+    timestep repeated.  Nothing of a scheduler is restated: the rows are the tables' own."""
+    if len(tables) != len(guidance):
+        raise ValueError(f"{len(tables)} tables for {len(guidance)} guidance scales")
+    evals = [int(t.table().shape[0]) for t in tables]
+    nmax = max(evals)
+    coef = torch.zeros(len(tables), nmax, 16, dtype=torch.float32)
+    t_rows = torch.zeros(nmax, len(tables), dtype=torch.float32)
+    for b, (t, n) in enumerate(zip(tables, evals)):
+        coef[b, :n] = t.table()
+        coef[b, :, 11] = float(guidance[b])
+        coef[b, n:, 14] = 1.0
+        coef[b, n:, 15] = 1.0
+        ts = t.timesteps.to(torch.float32)
+        t_rows[:n, b] = ts
+        t_rows[n:, b] = ts[-1]
+    return coef, t_rows, evals
+
+
+def request_tables(table_factory, steps_or_timesteps, guidance, eta=None):
+    """The per-request tables of a request batch: `table_factory()` makes a fresh table object, request b gets its own
+    `set_timesteps(n_b)` (an int), `set_timesteps(timesteps=ts_b)` (a list) or, with `eta` (one per request, DDIM), `set_timesteps(n_b,
+    eta=eta_b)`; the results are stacked by `stack_request_tables`."""
+    if eta is not None and len(eta) != len(steps_or_timesteps):
+        raise ValueError(f"{len(eta)} eta values for {len(steps_or_timesteps)} requests")
+    tables = []
+    for b, st in enumerate(steps_or_timesteps):
+        t = table_factory()
+        if isinstance(st, (list, tuple)):
+            t.set_timesteps(timesteps=list(st))
+        elif eta is not None:
+            t.set_timesteps(int(st), eta=float(eta[b]))
+        else:
+            t.set_timesteps(int(st))
+        tables.append(t)
+    return stack_request_tables(tables, guidance)
 
 
 def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):

@@ -547,7 +547,10 @@ enum { BC_OP_GEMM = 0, BC_OP_GN_STATS = 1, BC_OP_GN_FINALIZE = 2, BC_OP_GN_APPLY
        BC_OP_MEMSET_ZERO = 24, BC_OP_ROWCHAIN_MIDX = 25, BC_OP_ROWCHAIN_PACK_KV = 26, BC_OP_ROWCHAIN_SUM = 27, BC_OP_CTX_FOLD = 28, BC_OP_DUP_HALVES = 29,
        BC_OP_CFG_SCHEDULER_STEP_NOISE = 30, BC_OP_CFG_SCHEDULER_STEP3 = 31, BC_OP_ASSEMBLE_INPUT_SCALED = 32,
        BC_OP_ASSEMBLE_IM2COL_SCALED = 33, BC_OP_SCHEDULER_STEP_SINGLE = 34, BC_OP_TIMESTEP_EMBEDDING_TABLE_COND = 35,
-       BC_OP_TIMESTEP_EMBEDDING_COND = 36, BC_OP_FREEU = 37, BC_OP_COUNT = 38 };
+       BC_OP_TIMESTEP_EMBEDDING_COND = 36, BC_OP_FREEU = 37,
+       /* 38-41: the entry points of include/blobctrl_requests.h */
+       BC_OP_SCHEDULER_STEP_REQUESTS = 38, BC_OP_ASSEMBLE_INPUT_REQUESTS = 39,
+       BC_OP_ASSEMBLE_IM2COL_REQUESTS = 40, BC_OP_TIMESTEP_EMBEDDING_ROWS = 41, BC_OP_COUNT = 42 };
 typedef struct BcPlanBuffer {
     const char* name;        /* "" for anonymous workspace; named buffers are found again with bc_plan_buffer */
     const void* address;     /* the address the launch records were built against */

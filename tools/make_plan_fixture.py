@@ -19,7 +19,12 @@ assembles its inputs with the `_scaled` entry points): "latents" is then the sta
 `--lcm TAG` compiles a case of tests/golden/loop_tiny_lcm.npz (e.g. lcm_nocfg_4: the LCM scheduler with guidance off, a single-pass plan
 whose `ctx` holds the positive prompt only and whose steps end in bc_scheduler_step_single; the noise the reference drew is embedded).
 
-    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG | --lcm TAG [--expected FILE.npy]]
+`--requests` compiles the MIXED edit of a request batch of 3 instead (REQUESTS below: own step counts, guidance scales, control windows
+and strengths per request; the Euler scheduler, so the inputs are assembled by the `_requests` entry points): a version-8 plan whose
+steps end in bc_scheduler_step_requests.  The inputs are seeded request-batch tensors (`request_inputs`), "latents" holds every
+request's start noise times its own init_noise_sigma, "expected_latents" is `--expected FILE.npy` (what the in-process engine computed).
+
+    python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG | --lcm TAG | --requests [--expected FILE.npy]]
 """
 import argparse
 import os
@@ -36,6 +41,48 @@ from tests.common import TINY, g, tiny_weights  # noqa: E402
 from tests.gpu_common import tiny_trunk_configs  # noqa: E402
 
 GOLD = os.path.join(REPO, "tests", "golden")
+# the mixed edit of `--requests`: one entry per request
+REQUESTS = dict(num_inference_steps=[4, 6, 5], guidance_scale=[7.5, 3.0, 1.0], blobnet_control_guidance_start=[0.0, 0.2, 0.0],
+                blobnet_control_guidance_end=[1.0, 0.7, 0.5], blobnet_conditioning_scale=[1.0, 0.0, 1.7])
+
+
+def request_inputs(B=3, h=8, w=8, T=7):
+    """The seeded request batch of `--requests` (every tensor with a leading B), as `BlobCtrlEngine.denoise` takes it."""
+    return dict(prompt=g(32, 2 * B, T, TINY["ctx"]), fg=g(33, B, 4, h, w) * 0.18215 * 5, bg=g(34, B, 4, h, w) * 0.18215 * 5,
+                score=g(36, B, 2, h, w).abs().clamp(max=1), dino=g(35, B, 1, TINY["feat"]), latents=g(31, B, 4, h, w))
+
+
+def write_io(path, recs):
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(recs)))
+        for name, arr in recs.items():
+            raw = np.ascontiguousarray(arr).tobytes()
+            f.write(name.encode().ljust(32, b"\0"))
+            f.write(struct.pack("<Q", len(raw)))
+            f.write(raw)
+
+
+def compile_requests(out, expected):
+    """The `--requests` fixture: the mixed Euler edit of REQUESTS as a plan file + its inputs."""
+    from blobctrl_amd import schedulers
+    sched = schedulers.EulerDiscreteScheduler(steps_offset=1)
+    usd, bsd = tiny_weights()
+    ucfg, bcfg = tiny_trunk_configs()
+    eng = BlobCtrlEngine(usd, bsd, ucfg, bcfg, device="cpu", scheduler="ddim", compile_only=True)
+    eng.set_scheduler(sched.kind, sched.table_params())
+    B, h, w, T = 3, 8, 8, 7
+    seq = eng.compile_plan(os.path.join(out, "tiny_edit.bcplan"), B, h, w, T, TINY["ctx"], **REQUESTS)
+    a = request_inputs(B, h, w, T)
+    sigma0 = [eng._scheduler_table(n).init_noise_sigma for n in REQUESTS["num_inference_steps"]]
+    feat16 = torch.zeros(B, 8, dtype=torch.float16)
+    feat16[:, : TINY["feat"]] = a["dino"].reshape(B, -1).half()
+    write_io(os.path.join(out, "tiny_edit_io.bin"), {
+        "latents": torch.stack([a["latents"][b] * sigma0[b] for b in range(B)]).numpy(),
+        "ctx": a["prompt"].half().numpy(), "fg_lat": a["fg"].numpy(), "bg_lat": a["bg"].numpy(),
+        "bg_score": a["score"][:, 0].contiguous().numpy(), "fg_score": a["score"][:, 1].contiguous().numpy(),
+        "feat": a["dino"].reshape(B, -1).numpy(), "feat16": feat16.numpy(),
+        "expected_latents": (expected if expected is not None else np.zeros((B, 4, h, w))).astype(np.float32),
+        "sequence": np.array([1 if s == "step_active" else 0 for s in seq], np.int32)})
 
 
 def main():
@@ -44,10 +91,16 @@ def main():
     ap.add_argument("--eta", type=float, default=0.0, help="stochastic DDIM: the eta of loop_tiny_eta.npz's 5-step run")
     ap.add_argument("--euler", default=None, help="a case of loop_tiny_euler.npz (Euler / Euler-ancestral / Heun)")
     ap.add_argument("--lcm", default=None, help="a case of loop_tiny_lcm.npz (LCM with or without guidance, single-pass DDIM / UniPC)")
+    ap.add_argument("--requests", action="store_true", help="the mixed edit of a request batch of 3 (REQUESTS), Euler")
     ap.add_argument("--expected", default=None, help=".npy file with the expected final latents (default: the reference loop's)")
     args = ap.parse_args()
     OUT = args.out
     os.makedirs(OUT, exist_ok=True)
+    if args.requests:
+        compile_requests(OUT, np.load(args.expected) if args.expected else None)
+        for fn in ("tiny_edit.bcplan", "tiny_edit_io.bin"):
+            print(fn, os.path.getsize(os.path.join(OUT, fn)), "bytes")
+        return
     z = np.load(os.path.join(GOLD, "loop_tiny.npz"))
     extra, expected = {}, z["ddim_5_final"]
     sigma0, steps, window, sched = 1.0, 5, (0.0, 1.0), None
@@ -115,13 +168,7 @@ def main():
         "expected_latents": expected.astype(np.float32),
         "sequence": np.array([1 if s == "step_active" else 0 for s in seq], np.int32),
     }
-    with open(os.path.join(OUT, "tiny_edit_io.bin"), "wb") as f:
-        f.write(struct.pack("<I", len(recs)))
-        for name, arr in recs.items():
-            raw = np.ascontiguousarray(arr).tobytes()
-            f.write(name.encode().ljust(32, b"\0"))
-            f.write(struct.pack("<Q", len(raw)))
-            f.write(raw)
+    write_io(os.path.join(OUT, "tiny_edit_io.bin"), recs)
     for fn in ("tiny_edit.bcplan", "tiny_edit_io.bin"):
         print(fn, os.path.getsize(os.path.join(OUT, fn)), "bytes")
 
