@@ -19,7 +19,7 @@ __global__ void splat_kernel(const SplatParams prm, int h, int w, double* __rest
     o[(size_t)h * w + idx] = s;
 }
 
-// The divisor of the noisy latents in a SCALED assembly (pipe:1032 `scheduler.scale_model_input`, the sigma-space schedulers):
+// The divisor of the noisy latents in a DIV_TABLE assembly (pipe:1032 `scheduler.scale_model_input`, the sigma-space schedulers):
 // column 14 of coefficient row *step_idx, sqrt(sigma_t^2 + 1).  A step index outside [0, nsteps) (the capture warm-ups advance the
 // counter) has no table row: the divisor is then 1 and x / 1 = x, the unscaled kernel's output bit for bit.
 __device__ __forceinline__ float input_divisor(const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps) {
@@ -27,7 +27,7 @@ __device__ __forceinline__ float input_divisor(const float* __restrict__ coef, c
     return (step >= 0 && step < nsteps) ? coef[(size_t)step * 16 + 14] : 1.f;
 }
 
-// The divisor of image `b` in a REQUESTS assembly (a batch of edit requests with their own step counts): column 14 of ITS row of the
+// The divisor of image `b` in a DIV_IMAGE assembly (a batch of edit requests with their own step counts): column 14 of ITS row of the
 // [Blat][nsteps][16] table.  A row whose column 14 is 0 ("do not divide": a table that does not scale its input) and a step index
 // outside the table give 1, as above.
 __device__ __forceinline__ float input_divisor_of(const float* __restrict__ coef, int step, int nsteps, int b) {
@@ -36,17 +36,22 @@ __device__ __forceinline__ float input_divisor_of(const float* __restrict__ coef
     return d != 0.f ? d : 1.f;
 }
 
+// How an assembly divides the noisy latents: not at all, by the row of the one table every image shares (input_divisor), or image b
+// by the row of its own table (input_divisor_of: a batch of edit requests).
+enum DivMode { DIV_NONE, DIV_TABLE, DIV_IMAGE };
+
 // pipeline_blobnet.py:724-739 + :706-721.  X[b][y][x][c], x in [0, 2w): left = clean image latents, right = noisy latents.
-//   SCALED: the noisy latents (right half, channels 0-3) are divided by input_divisor() in fp32 before the fp16 conversion, as the
-//           reference divides `latent_model_input`; the clean latents, the score and the feature channels are what they are without
-//           it.  `coef` / `step_idx` / `nsteps` are not read by the instantiation without SCALED.
-template <bool SCALED>
+//   DIV: unless DIV_NONE the noisy latents (right half, channels 0-3) are divided in fp32 before the fp16 conversion, as the reference
+//        divides `latent_model_input`; the clean latents, the score and the feature channels are what they are without it.  `coef`
+//        ([nsteps][16], DIV_IMAGE: [Blat][nsteps][16]) / `step_idx` / `nsteps` are not read by the DIV_NONE instantiation.
+template <DivMode DIV>
 __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
                                 const float* __restrict__ score, const float* __restrict__ feat, int Bimg, int F, int Bout,
                                 int h, int w, int Cpad, int dup_score, const float* __restrict__ coef,
                                 const int* __restrict__ step_idx, int nsteps, h16* __restrict__ X) {
     const long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
-    const float div = SCALED ? input_divisor(coef, step_idx, nsteps) : 1.f;
+    const float shared = DIV == DIV_TABLE ? input_divisor(coef, step_idx, nsteps) : 1.f;
+    const int step = DIV == DIV_IMAGE ? *step_idx : 0;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
         const int nch = Cpad / 8;
@@ -59,6 +64,7 @@ __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, con
         const int xs = right ? x - w : x;
         const int bi = b % Bimg;
         const float sc = score[((size_t)bi * h + y) * w + xs];
+        const float div = DIV == DIV_IMAGE ? input_divisor_of(coef, step, nsteps, b % Blat) : shared;
         uint4 raw;
         h16* o = reinterpret_cast<h16*>(&raw);
 #pragma unroll
@@ -67,7 +73,7 @@ __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, con
             float v = 0.f;
             if (c < 4) {
                 v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + y) * w + xs] : img_lat[(((size_t)bi * 4 + c) * h + y) * w + xs];
-                if (SCALED && right) v = v / div;
+                if (DIV != DIV_NONE && right) v = v / div;
             } else if (c == 4) {
                 v = sc;
             } else if (c < 5 + F) {
@@ -84,20 +90,22 @@ __global__ void assemble_kernel(const float* __restrict__ latents, int Blat, con
 // The same input (8 channels: 4 latents, score, [score], 0, 0) written as the 3x3 im2col operand of conv_in: row = canvas pixel,
 // k = tap * 8 + channel for the nine taps (zero outside the h x 2w canvas = the convolution's padding), zero-filled up to 128, so that
 // conv_in (K = 72: outside the LDS-DMA GEMM's K % 64 == 0 fast path, 41 us per launch on the register-staged kernel) runs as a dense
-// K = 128 GEMM.  One thread per (pixel, 16-byte chunk).  SCALED as in assemble_kernel: the noisy latents of every tap are divided.
-template <bool SCALED>
+// K = 128 GEMM.  One thread per (pixel, 16-byte chunk).  DIV as in assemble_kernel: the noisy latents of every tap are divided.
+template <DivMode DIV>
 __global__ void assemble_im2col_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
                                        const float* __restrict__ score, int Bimg, int Bout, int h, int w, int dup_score,
                                        const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps,
                                        h16* __restrict__ X) {
     const long long total = (long long)Bout * h * 2 * w * 16;
-    const float div = SCALED ? input_divisor(coef, step_idx, nsteps) : 1.f;
+    const float shared = DIV == DIV_TABLE ? input_divisor(coef, step_idx, nsteps) : 1.f;
+    const int step = DIV == DIV_IMAGE ? *step_idx : 0;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const int chunk = (int)(idx & 15);
         const long long pix = idx >> 4;
         const int x = (int)(pix % (2 * w));
         const int y = (int)((pix / (2 * w)) % h);
         const int b = (int)(pix / ((long long)2 * w * h));
+        const float div = DIV == DIV_IMAGE ? input_divisor_of(coef, step, nsteps, b % Blat) : shared;
         uint4 raw = make_uint4(0u, 0u, 0u, 0u);
         if (chunk < 9) {
             const int yy = y + chunk / 3 - 1, xx = x + chunk % 3 - 1;
@@ -111,88 +119,7 @@ __global__ void assemble_im2col_kernel(const float* __restrict__ latents, int Bl
                 for (int c = 0; c < 4; ++c) {
                     float v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + yy) * w + xs]
                                     : img_lat[(((size_t)bi * 4 + c) * h + yy) * w + xs];
-                    if (SCALED && right) v = v / div;
-                    o[c] = (h16)v;
-                }
-                o[4] = (h16)sc;
-                o[5] = dup_score ? (h16)sc : (h16)0.f;
-            }
-        }
-        bc_st16(X + (size_t)pix * 128 + chunk * 8, raw);
-    }
-}
-
-// The two assemblies above in their SCALED form with the divisor PER IMAGE (a request batch whose requests run their own schedules,
-// coef [Blat][nsteps][16]): image b of the output divides by input_divisor_of(.., b % Blat).  Kernels of their own, so that the ones
-// above stay the code they compile to; everything but the divisor is theirs line for line.
-__global__ void assemble_requests_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
-                                         const float* __restrict__ score, const float* __restrict__ feat, int Bimg, int F, int Bout,
-                                         int h, int w, int Cpad, int dup_score, const float* __restrict__ coef,
-                                         const int* __restrict__ step_idx, int nsteps, h16* __restrict__ X) {
-    const long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
-    const int step = *step_idx;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int nch = Cpad / 8;
-        int ch = (int)(idx % nch);
-        long long pix = idx / nch;
-        int x = (int)(pix % (2 * w));
-        int y = (int)((pix / (2 * w)) % h);
-        int b = (int)(pix / ((long long)2 * w * h));
-        const bool right = x >= w;
-        const int xs = right ? x - w : x;
-        const int bi = b % Bimg;
-        const float sc = score[((size_t)bi * h + y) * w + xs];
-        const float div = input_divisor_of(coef, step, nsteps, b % Blat);
-        uint4 raw;
-        h16* o = reinterpret_cast<h16*>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            int c = ch * 8 + j;
-            float v = 0.f;
-            if (c < 4) {
-                v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + y) * w + xs] : img_lat[(((size_t)bi * 4 + c) * h + y) * w + xs];
-                if (right) v = v / div;
-            } else if (c == 4) {
-                v = sc;
-            } else if (c < 5 + F) {
-                v = sc * feat[(size_t)bi * F + c - 5];
-            } else if (dup_score && c == 5) {
-                v = sc;
-            }
-            o[j] = (h16)v;
-        }
-        bc_st16(X + (size_t)pix * Cpad + ch * 8, raw);
-    }
-}
-
-__global__ void assemble_im2col_requests_kernel(const float* __restrict__ latents, int Blat, const float* __restrict__ img_lat,
-                                                const float* __restrict__ score, int Bimg, int Bout, int h, int w, int dup_score,
-                                                const float* __restrict__ coef, const int* __restrict__ step_idx, int nsteps,
-                                                h16* __restrict__ X) {
-    const long long total = (long long)Bout * h * 2 * w * 16;
-    const int step = *step_idx;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int chunk = (int)(idx & 15);
-        const long long pix = idx >> 4;
-        const int x = (int)(pix % (2 * w));
-        const int y = (int)((pix / (2 * w)) % h);
-        const int b = (int)(pix / ((long long)2 * w * h));
-        const float div = input_divisor_of(coef, step, nsteps, b % Blat);
-        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-        if (chunk < 9) {
-            const int yy = y + chunk / 3 - 1, xx = x + chunk % 3 - 1;
-            if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)(2 * w)) {
-                const bool right = xx >= w;
-                const int xs = right ? xx - w : xx;
-                const int bi = b % Bimg;
-                const float sc = score[((size_t)bi * h + yy) * w + xs];
-                h16* o = reinterpret_cast<h16*>(&raw);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float v = right ? latents[(((size_t)(b % Blat) * 4 + c) * h + yy) * w + xs]
-                                    : img_lat[(((size_t)bi * 4 + c) * h + yy) * w + xs];
-                    if (right) v = v / div;
+                    if (DIV != DIV_NONE && right) v = v / div;
                     o[c] = (h16)v;
                 }
                 o[4] = (h16)sc;
@@ -444,33 +371,33 @@ extern "C" int bc_splat_scores(const double* params_host, int n, int h, int w, d
     return 0;
 }
 
-// The launchers behind the assembly entry points (`name` = the entry point's own name for the error text); an unscaled entry point
-// passes coef = step_idx = nullptr / nsteps = 0, which its instantiation never reads.
-template <bool SCALED>
+// The launchers behind the six assembly entry points (`name` = the entry point's own name for the error text); an undivided entry
+// point passes coef = step_idx = nullptr / nsteps = 0, which its instantiation never reads.
+template <DivMode DIV>
 static int assemble_launch(const char* name, const float* latents, int Blat, const float* img_lat, const float* score, const float* feat,
                            int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score, const float* coef, const int* step_idx,
                            int nsteps, bc_half* X, bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!feat) F = 0;
     BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 &&
-                 (!SCALED || (coef && step_idx && nsteps > 0 && h > 0 && w > 0)), "%s: bad args", name);
+                 (DIV == DIV_NONE || (coef && step_idx && nsteps > 0 && h > 0 && w > 0)), "%s: bad args", name);
     BC_CHECK_ARG(Cpad % 8 == 0 && Cpad >= 5 + F, "%s: Cpad=%d must be a multiple of 8 and >= %d", name, Cpad, 5 + F);
     long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
-    hipLaunchKernelGGL(assemble_kernel<SCALED>, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, feat,
+    hipLaunchKernelGGL(assemble_kernel<DIV>, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, feat,
                        Bimg, F, Bout, h, w, Cpad, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
     BC_CHECK_LAUNCH();
     return 0;
 }
 
-template <bool SCALED>
+template <DivMode DIV>
 static int assemble_im2col_launch(const char* name, const float* latents, int Blat, const float* img_lat, const float* score, int Bimg,
                                   int Bout, int h, int w, int dup_score, const float* coef, const int* step_idx, int nsteps, bc_half* X,
                                   bc_stream stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 &&
-                 (!SCALED || (coef && step_idx && nsteps > 0 && h > 0 && w > 0)), "%s: bad args", name);
+                 (DIV == DIV_NONE || (coef && step_idx && nsteps > 0 && h > 0 && w > 0)), "%s: bad args", name);
     long long total = (long long)Bout * h * 2 * w * 16;
-    hipLaunchKernelGGL(assemble_im2col_kernel<SCALED>, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, Bimg,
+    hipLaunchKernelGGL(assemble_im2col_kernel<DIV>, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, Bimg,
                        Bout, h, w, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
     BC_CHECK_LAUNCH();
     return 0;
@@ -479,57 +406,42 @@ static int assemble_im2col_launch(const char* name, const float* latents, int Bl
 extern "C" int bc_assemble_input(const float* latents, int Blat, const float* img_lat, const float* score,
                                  const float* feat, int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score,
                                  bc_half* X, bc_stream stream) {
-    return assemble_launch<false>("bc_assemble_input", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad, dup_score, nullptr,
-                                  nullptr, 0, X, stream);
+    return assemble_launch<DIV_NONE>("bc_assemble_input", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad, dup_score,
+                                     nullptr, nullptr, 0, X, stream);
 }
 
 extern "C" int bc_assemble_input_scaled(const float* latents, int Blat, const float* img_lat, const float* score,
                                         const float* feat, int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score,
                                         const float* coef, const int* step_idx, int nsteps, bc_half* X, bc_stream stream) {
-    return assemble_launch<true>("bc_assemble_input_scaled", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad, dup_score,
-                                 coef, step_idx, nsteps, X, stream);
+    return assemble_launch<DIV_TABLE>("bc_assemble_input_scaled", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad,
+                                      dup_score, coef, step_idx, nsteps, X, stream);
+}
+
+extern "C" int bc_assemble_input_requests(const float* latents, int Blat, const float* img_lat, const float* score, const float* feat,
+                                          int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score, const float* coef,
+                                          const int* step_idx, int nsteps, bc_half* X, bc_stream stream) {
+    return assemble_launch<DIV_IMAGE>("bc_assemble_input_requests", latents, Blat, img_lat, score, feat, Bimg, F, Bout, h, w, Cpad,
+                                      dup_score, coef, step_idx, nsteps, X, stream);
 }
 
 extern "C" int bc_assemble_input_im2col(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg, int Bout,
                                         int h, int w, int dup_score, bc_half* X, bc_stream stream) {
-    return assemble_im2col_launch<false>("bc_assemble_input_im2col", latents, Blat, img_lat, score, Bimg, Bout, h, w, dup_score, nullptr,
-                                         nullptr, 0, X, stream);
+    return assemble_im2col_launch<DIV_NONE>("bc_assemble_input_im2col", latents, Blat, img_lat, score, Bimg, Bout, h, w, dup_score,
+                                            nullptr, nullptr, 0, X, stream);
 }
 
 extern "C" int bc_assemble_input_im2col_scaled(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg,
                                                int Bout, int h, int w, int dup_score, const float* coef, const int* step_idx, int nsteps,
                                                bc_half* X, bc_stream stream) {
-    return assemble_im2col_launch<true>("bc_assemble_input_im2col_scaled", latents, Blat, img_lat, score, Bimg, Bout, h, w, dup_score,
-                                        coef, step_idx, nsteps, X, stream);
-}
-
-// The `_requests` forms: the launchers' checks with SCALED, the per-image divisor kernels.
-extern "C" int bc_assemble_input_requests(const float* latents, int Blat, const float* img_lat, const float* score, const float* feat,
-                                          int Bimg, int F, int Bout, int h, int w, int Cpad, int dup_score, const float* coef,
-                                          const int* step_idx, int nsteps, bc_half* X, bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!feat) F = 0;
-    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 && coef && step_idx && nsteps > 0 && h > 0 && w > 0,
-                 "bc_assemble_input_requests: bad args");
-    BC_CHECK_ARG(Cpad % 8 == 0 && Cpad >= 5 + F, "bc_assemble_input_requests: Cpad=%d must be a multiple of 8 and >= %d", Cpad, 5 + F);
-    long long total = (long long)Bout * h * 2 * w * (Cpad / 8);
-    hipLaunchKernelGGL(assemble_requests_kernel, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, feat, Bimg,
-                       F, Bout, h, w, Cpad, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
-    BC_CHECK_LAUNCH();
-    return 0;
+    return assemble_im2col_launch<DIV_TABLE>("bc_assemble_input_im2col_scaled", latents, Blat, img_lat, score, Bimg, Bout, h, w,
+                                             dup_score, coef, step_idx, nsteps, X, stream);
 }
 
 extern "C" int bc_assemble_input_im2col_requests(const float* latents, int Blat, const float* img_lat, const float* score, int Bimg,
                                                  int Bout, int h, int w, int dup_score, const float* coef, const int* step_idx,
-                                                 int nsteps, bc_half* X, bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(latents && img_lat && score && X && Blat > 0 && Bout > 0 && Bimg > 0 && coef && step_idx && nsteps > 0 && h > 0 && w > 0,
-                 "bc_assemble_input_im2col_requests: bad args");
-    long long total = (long long)Bout * h * 2 * w * 16;
-    hipLaunchKernelGGL(assemble_im2col_requests_kernel, dim3(ew_blocks(total)), dim3(256), 0, stream, latents, Blat, img_lat, score, Bimg,
-                       Bout, h, w, dup_score, coef, step_idx, nsteps, reinterpret_cast<h16*>(X));
-    BC_CHECK_LAUNCH();
-    return 0;
+                                                 int nsteps, bc_half* X, bc_stream stream) {
+    return assemble_im2col_launch<DIV_IMAGE>("bc_assemble_input_im2col_requests", latents, Blat, img_lat, score, Bimg, Bout, h, w,
+                                             dup_score, coef, step_idx, nsteps, X, stream);
 }
 
 extern "C" int bc_timestep_embedding(const float* t_table, const int* t_idx, float t_value, int rows, int dim,
@@ -602,24 +514,31 @@ extern "C" int bc_silu(const bc_half* x, bc_half* y, long long n, bc_stream stre
     return 0;
 }
 
-// The launcher behind the three step entry points: `name` is the entry point's own name for the error text; an entry point without
-// NOISE / GUARD passes noise = nullptr / nsteps = 0, which its instantiation never reads.
-template <bool NOISE, bool THIRD, bool GUARD>
-static int cfg_step_launch(const char* name, const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
-                           float guidance_scale, int B, int h, int w, const float* noise, int nsteps, float* eps_out, int advance,
-                           bc_stream stream_) {
+// The host side of every step entry point: `ok` is the entry point's argument check (`name` = its own name for the error text), then
+// the launch of its kernel instance over the B * 4 * h * w latent elements and, with `advance`, of the step counter's increment.
+template <typename... Params, typename... Args>
+static int step_launch(const char* name, bool ok, void (*kernel)(Params...), int B, int h, int w, int* step_idx, int advance,
+                       bc_stream stream_, Args... args) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && (!NOISE || noise) && (!GUARD || (h > 0 && w > 0 && nsteps > 0)),
-                 "%s: bad args", name);
-    int n = B * 4 * h * w;
-    hipLaunchKernelGGL((cfg_step_kernel<NOISE, THIRD, GUARD>), dim3(bc_ceil_div(n, 256)), dim3(256), 0, stream, eps, latents, coef,
-                       step_idx, hist, guidance_scale, B, h, w, noise, nsteps, eps_out);
+    BC_CHECK_ARG(ok, "%s: bad args", name);
+    hipLaunchKernelGGL(kernel, dim3(bc_ceil_div(B * 4 * h * w, 256)), dim3(256), 0, stream, args...);
     BC_CHECK_LAUNCH();
     if (advance) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
         BC_CHECK_LAUNCH();
     }
     return 0;
+}
+
+// The three CFG entry points are one instance each; one without NOISE / GUARD passes noise = nullptr / nsteps = 0, which its
+// instantiation never reads.
+template <bool NOISE, bool THIRD, bool GUARD>
+static int cfg_step_launch(const char* name, const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
+                           float guidance_scale, int B, int h, int w, const float* noise, int nsteps, float* eps_out, int advance,
+                           bc_stream stream) {
+    return step_launch(name, eps && latents && coef && step_idx && hist && B > 0 && (!NOISE || noise) &&
+                       (!GUARD || (h > 0 && w > 0 && nsteps > 0)), cfg_step_kernel<NOISE, THIRD, GUARD>, B, h, w, step_idx, advance, stream,
+                       eps, latents, coef, step_idx, hist, guidance_scale, B, h, w, noise, nsteps, eps_out);
 }
 
 extern "C" int bc_cfg_scheduler_step(const float* eps, float* latents, const float* coef, int* step_idx, float* hist,
@@ -643,60 +562,36 @@ extern "C" int bc_cfg_scheduler_step3(const float* eps, float* latents, const fl
                                               nullptr, nsteps, eps_out, advance, stream);
 }
 
+// The entry points that take their step form at run time pick the instance from these tables, index noise * 2 + third (requests:
+// single * 4 + noise * 2 + third).
+using GuardedStep = void (*)(const float*, float*, const float*, const int*, float*, int, int, int, const float*, int, float*);
+static const GuardedStep single_steps[4] = {step_single_kernel<false, false>, step_single_kernel<false, true>,
+                                            step_single_kernel<true, false>, step_single_kernel<true, true>};
+static const GuardedStep request_steps[8] = {
+    step_requests_kernel<false, false, false>, step_requests_kernel<false, false, true>, step_requests_kernel<false, true, false>,
+    step_requests_kernel<false, true, true>,   step_requests_kernel<true, false, false>, step_requests_kernel<true, false, true>,
+    step_requests_kernel<true, true, false>,   step_requests_kernel<true, true, true>};
+
+static int step_form(bool single, bool noise, bool third) { return (single ? 4 : 0) | (noise ? 2 : 0) | (third ? 1 : 0); }
+
 // The step of a guidance-free (single-pass) plan: eps [B][h][2w][4], e = its right half.  noise != NULL adds cf[12] * noise[step],
 // third != 0 adds cf[13] * x0_{i-2}; a step index outside [0, nsteps) leaves every buffer as it is.
 extern "C" int bc_scheduler_step_single(const float* eps, float* latents, const float* coef, int* step_idx, float* hist, int B, int h,
                                         int w, const float* noise, int nsteps, int third, float* eps_out, int advance,
-                                        bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0, "bc_scheduler_step_single: bad args");
-    const int n = B * 4 * h * w;
-    const dim3 grid(bc_ceil_div(n, 256)), block(256);
-    if (noise && third)
-        hipLaunchKernelGGL((step_single_kernel<true, true>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
-    else if (noise)
-        hipLaunchKernelGGL((step_single_kernel<true, false>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
-    else if (third)
-        hipLaunchKernelGGL((step_single_kernel<false, true>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
-    else
-        hipLaunchKernelGGL((step_single_kernel<false, false>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
-    BC_CHECK_LAUNCH();
-    if (advance) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
-        BC_CHECK_LAUNCH();
-    }
-    return 0;
+                                        bc_stream stream) {
+    return step_launch("bc_scheduler_step_single", eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0,
+                       single_steps[step_form(false, noise, third)], B, h, w, step_idx, advance, stream,
+                       eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
 }
 
 // The step of a batch of edit requests: coef [B][nsteps][16], image b applies its own row (guidance from column 11) and is left alone
 // when the row's column 15 is set.  single != 0: eps holds B images (a single-pass plan), else the 2B of the CFG pairs.
 extern "C" int bc_scheduler_step_requests(const float* eps, float* latents, const float* coef, int* step_idx, float* hist, int B, int h,
                                           int w, const float* noise, int nsteps, int third, int single, float* eps_out, int advance,
-                                          bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0 &&
-                 (long long)B * 4 * h * w < (1ll << 31), "bc_scheduler_step_requests: bad args");
-    const int n = B * 4 * h * w;
-    const dim3 grid(bc_ceil_div(n, 256)), block(256);
-#define BC_STEP_REQ(S, N, T) \
-    hipLaunchKernelGGL((step_requests_kernel<S, N, T>), grid, block, 0, stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out)
-    switch ((single ? 4 : 0) | (noise ? 2 : 0) | (third ? 1 : 0)) {
-        case 0: BC_STEP_REQ(false, false, false); break;
-        case 1: BC_STEP_REQ(false, false, true); break;
-        case 2: BC_STEP_REQ(false, true, false); break;
-        case 3: BC_STEP_REQ(false, true, true); break;
-        case 4: BC_STEP_REQ(true, false, false); break;
-        case 5: BC_STEP_REQ(true, false, true); break;
-        case 6: BC_STEP_REQ(true, true, false); break;
-        default: BC_STEP_REQ(true, true, true); break;
-    }
-#undef BC_STEP_REQ
-    BC_CHECK_LAUNCH();
-    if (advance) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
-        BC_CHECK_LAUNCH();
-    }
-    return 0;
+                                          bc_stream stream) {
+    return step_launch("bc_scheduler_step_requests", eps && latents && coef && step_idx && hist && B > 0 && h > 0 && w > 0 && nsteps > 0 &&
+                       (long long)B * 4 * h * w < (1ll << 31), request_steps[step_form(single, noise, third)], B, h, w, step_idx, advance,
+                       stream, eps, latents, coef, step_idx, hist, B, h, w, noise, nsteps, eps_out);
 }
 
 extern "C" int bc_nchw_to_nhwc_f16(const void* src, int src_is_f32, int B, int C, int HW, int Cpad, bc_half* dst,

@@ -17,6 +17,7 @@ each captured once into a hipGraph and replayed per step; per-step scalars (time
 conditioning scale) live in device tables indexed by a device-side step counter.
 """
 import os
+from collections import namedtuple
 from typing import List, Optional, Union
 
 import torch
@@ -47,6 +48,24 @@ def get_guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtyp
 def blobnet_keep(num_steps, start, end):
     """pipe:1006-1012."""
     return [1.0 - float(i / num_steps < start or (i + 1) / num_steps > end) for i in range(num_steps)]
+
+
+class EditSetup(namedtuple("EditSetup", "requests tables n stochastic third_order scaled coef t_rows scale_rows evals")):
+    """What the arguments of an edit come to (`BlobCtrlEngine._setup`), for `denoise` to run and `compile_plan` to save.  A call without
+    lists is the case "one table, shared by every image" of a call with lists, which has a table per request:
+    requests: whether any argument was a list - the plan form; tables: the table objects, one or B; n: the loop length (the longest
+    table's evaluations); stochastic, third_order, scaled: the step form and input scaling of the plan (`_plan`);
+    coef: [n][16] with the guidance scale in column 11, or [B][n][16] (`stack_request_tables`); t_rows: [n][1 or B] fp32, the timestep of
+    every step and table; scale_rows: [n][Bi], conditioning scale * keep of every step and image; evals: evaluations per table."""
+
+    @property
+    def active(self):
+        """Per step, whether it runs BlobNet: when any image's conditioning scale is not 0 in it."""
+        return [any(v != 0.0 for v in row) for row in self.scale_rows]
+
+    @property
+    def segments(self):
+        return ["step_active" if a else "step_inactive" for a in self.active]
 
 
 class BlobCtrlEngine:
@@ -115,7 +134,9 @@ class BlobCtrlEngine:
         request, finished rows marked in column 15), `t_rows_unet` [nsteps][Bu] / `t_rows_blob` [nsteps][B] (a timestep per step and
         image; no `t_table`) and `scale_table` [nsteps][B]; the time tables come from bc_timestep_embedding_rows, a scaling table
         assembles through the `_requests` entry points (a divisor per image) and both step segments end in
-        bc_scheduler_step_requests.  The networks are what they are in every request batch."""
+        bc_scheduler_step_requests.  The networks are what they are in every request batch.
+        `denoise` and `compile_plan` take every one of these switches from the EditSetup of their call (`_setup`) and fill the tables
+        with `_write_tables`; a call without lists never asks for `requests`."""
         if requests and not per_request:
             raise ValueError("per-request schedules need a request batch (per_request)")
         if stochastic and third_order:
@@ -508,9 +529,10 @@ class BlobCtrlEngine:
 
     def _request_values(self, B, per_request, blobnet_conditioning_scale, req_scales, num_inference_steps, guidance_scale, start, end, eta,
                         timesteps):
-        """The per-request values of a request batch, validated: (steps or timestep lists, guidance scales, window starts, window ends,
-        etas), B entries each - a scalar argument means the same for every request.  Every refusal of a call with lists is raised here
-        or by the tables built from these values, before a plan is recorded."""
+        """The values behind every table of a call: (any argument was a list, steps or timestep lists, guidance scales, window starts,
+        window ends, etas).  A call with lists (a request batch) has B entries each, validated here - a scalar argument means the same
+        for every request; every refusal of such a call is raised here or by the tables built from these values, before a plan is
+        recorded.  A call without lists has one entry each: its own arguments (and its eta checked; its callers check the rest)."""
         given = dict(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, blobnet_control_guidance_start=start,
                      blobnet_control_guidance_end=end, eta=eta, timesteps=timesteps)
         listed = self._listed(**given)
@@ -525,11 +547,12 @@ class BlobCtrlEngine:
                 raise TypeError(f"per-request `{k}` must be a list of `float`.")
         if "num_inference_steps" in listed and not all(isinstance(v, int) and not isinstance(v, bool) for v in num_inference_steps):
             raise TypeError("per-request `num_inference_steps` must be a list of `int`.")
-        per = {k: list(v) if k in listed else [v] * B for k, v in given.items()}
-        if timesteps is not None:                                # (a request's edit has len(timesteps_b) steps, as in the scalar call)
+        per = {k: list(v) if k in listed else [v] * (B if listed else 1) for k, v in given.items()}
+        if timesteps is not None:                                # (an edit has len(timesteps) steps; num_inference_steps is not used)
             per["num_inference_steps"] = [list(t) for t in per["timesteps"]]
-        self.check_inputs(blobnet_conditioning_scale, 0.0, 1.0, 1)              # (the type of the conditioning scales)
-        for b in range(B):
+        if listed:
+            self.check_inputs(blobnet_conditioning_scale, 0.0, 1.0, 1)          # (the type of the conditioning scales)
+        for b in range(B if listed else 0):
             st = per["num_inference_steps"][b]
             try:
                 self.check_inputs(req_scales[b], per["blobnet_control_guidance_start"][b], per["blobnet_control_guidance_end"][b],
@@ -539,103 +562,113 @@ class BlobCtrlEngine:
         etas = [float(v) for v in per["eta"]]
         for v in etas:
             self._check_eta(v)
-        return per["num_inference_steps"], per["guidance_scale"], per["blobnet_control_guidance_start"], \
+        return bool(listed), per["num_inference_steps"], per["guidance_scale"], per["blobnet_control_guidance_start"], \
             per["blobnet_control_guidance_end"], etas
 
     def _request_tables(self, steps, etas):
-        """The table object of every request (cached like any other table) and the step form of the plan they run on together: a noise
-        row or a third-order row in any of them puts the whole batch on that form."""
+        """The table object of every request - of a call without lists: its one - (cached like any other table) and the step form of the
+        plan they run on together: a noise row or a third-order row in any of them puts the whole batch on that form."""
         tables = [self._scheduler_table(len(st) if isinstance(st, list) else st, eta, st if isinstance(st, list) else None)
                   for st, eta in zip(steps, etas)]
         forms = [self._step_form(t, eta > 0) for t, eta in zip(tables, etas)]
         return tables, any(f[0] for f in forms), any(f[1] for f in forms)
 
     @staticmethod
-    def _request_scale_rows(evals, req_scales, starts, ends):
-        """scale_table [nmax][B] of a request batch with per-request schedules: request b's `blobnet_keep(n_b, start_b, end_b) *
-        scale_b`, and 0 from its end on (a finished image rides through BlobNet with conditioning scale 0)."""
-        nmax = max(evals)
-        keeps = [blobnet_keep(n, s_, e_) + [0.0] * (nmax - n) for n, s_, e_ in zip(evals, starts, ends)]
-        return [[sc * k[i] for sc, k in zip(req_scales, keeps)] for i in range(nmax)]
+    def _guidance_on(guidance_scale):
+        """Whether classifier-free guidance is on (pipe:494-497): the scale - any of them, in a call with a list - is above 1."""
+        if isinstance(guidance_scale, (list, tuple)):
+            return all(isinstance(v, (int, float)) for v in guidance_scale) and max(guidance_scale) > 1.0
+        return guidance_scale > 1.0
 
-    def _request_noise(self, tables, evals, h, w, generator, device):
-        """variance_noise [nmax][B][4][h][w] of a request batch with per-request schedules.  A list of generators (one per request):
-        request b draws what it would draw alone - one [1, 4, h, w] slice per step of its own, in step order, skipping the steps its
-        table does not draw for (`draws`, LCM) - and zeros behind its end.  One generator or None: one [B, 4, h, w] draw per step of
-        the loop, as the scalar request batch draws them (a step draws when any request's table draws in it)."""
-        nmax, B = max(evals), len(tables)
-        draws = [(list(getattr(t, "draws", None) or [True] * n) + [False] * (nmax - n)) for t, n in zip(tables, evals)]
-        if isinstance(generator, list) and len(generator) > 1:
+    def _setup(self, B, per_request, blobnet_conditioning_scale, req_scales, num_inference_steps, timesteps, guidance_scale, start, end, eta,
+               guidance_off):
+        """The EditSetup of a call, scalar or with lists (`req_scales`: the conditioning scale of every image).  With lists every
+        request runs its own table rows, timesteps, window and guidance scale, left-aligned in a loop of the longest request's
+        evaluations; behind its last row a request is finished: the step leaves it alone and its conditioning scale is 0."""
+        requests, steps, gs, starts, ends, etas = self._request_values(B, per_request, blobnet_conditioning_scale, req_scales,
+                                                                       num_inference_steps, guidance_scale, start, end, eta, timesteps)
+        gs = [1.0 if guidance_off else float(v) for v in gs]
+        if requests:                                             # (a request at or below 1 beside guided ones: its eps is its conditional half)
+            gs = [max(1.0, v) for v in gs]
+        tables, stochastic, third_order = self._request_tables(steps, etas)
+        coef, t_rows, evals = stack_request_tables(tables, gs)
+        n = max(evals)                                           # network evaluations (Heun: 2 * num_inference_steps - 1, pipe:1025 loops over them)
+        per_image = 1 if requests else len(req_scales)           # (a call without lists: the one table and window serve every image)
+        keeps = [blobnet_keep(e, s_, e_) + [0.0] * (n - e) for e, s_, e_ in zip(evals * per_image, starts * per_image, ends * per_image)]
+        scale_rows = [[sc * k[i] for sc, k in zip(req_scales, keeps)] for i in range(n)]
+        return EditSetup(requests, tables, n, stochastic, third_order, tables[0].scales_input, coef if requests else coef[0], t_rows,
+                         scale_rows, evals)
+
+    def _check_timestep_cond(self, timestep_cond, B):
+        dim = self.unet_cfg.time_cond_proj_dim
+        if timestep_cond is not None and dim is None:
+            raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
+        if timestep_cond is not None and tuple(timestep_cond.shape) != (B, dim):
+            raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
+
+    @staticmethod
+    def _check_variance_noise(S, variance_noise, image_shape, generator=None, compiling=False):
+        """A caller's `variance_noise`: only for a plan with a noise step, never beside a generator, [S.n, *image_shape]."""
+        if variance_noise is None:
+            return
+        shape = (S.n,) + tuple(image_shape)
+        if compiling:
+            if not S.stochastic or tuple(variance_noise.shape) != shape:
+                raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {shape}")
+            return
+        if not S.stochastic:
+            raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++, an Euler-ancestral or an LCM "
+                             "scheduler")
+        if generator is not None:
+            raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                             " `variance_noise` stays `None`.")
+        if tuple(variance_noise.shape) != shape:
+            steps = "longest request's steps" if S.requests else "steps"
+            raise ValueError(f"variance_noise must have shape {shape} ({steps}, batch, 4, h, w), got {tuple(variance_noise.shape)}")
+
+    def _draw_noise(self, S, B, h, w, generator, device):
+        """variance_noise [S.n][B][4][h][w], drawn as the reference's scheduler.step draws it (scheduling_ddim.py:455-458 /
+        dpmsolver_multistep.py:979-982).  A call with lists and a list of generators (one per request): request b draws what it would
+        draw alone - one [1, 4, h, w] slice per step of its own, in step order, skipping the steps its table does not draw for (`draws`,
+        LCM) - and zeros behind its end.  Every other call: one [B, 4, h, w] draw per step of the loop (a step draws when any table
+        draws in it)."""
+        draws = [(list(getattr(t, "draws", None) or [True] * e) + [False] * (S.n - e)) for t, e in zip(S.tables, S.evals)]
+        if S.requests and isinstance(generator, list) and len(generator) > 1:
             zero = torch.zeros(1, 4, h, w, dtype=torch.float32, device=device)
             per = [torch.cat([randn_tensor((1, 4, h, w), generator[b], device) if d else zero for d in draws[b]], 0) for b in range(B)]
             return torch.stack(per, 1)
-        return draw_variance_noise(nmax, (B, 4, h, w), generator, device, [any(d[i] for d in draws) for i in range(nmax)])
+        return self.variance_noise(S.n, B, h, w, generator, device, [any(d[i] for d in draws) for i in range(S.n)])
 
-    def _denoise_requests(self, prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, num_inference_steps, guidance_scale,
-                          generator, latents, blobnet_conditioning_scale, start, end, output_type, callback_on_step_end, trace,
-                          teacher_latents, eta, do_classifier_free_guidance, callback_self, variance_noise, timesteps, single_pass,
-                          timestep_cond, freeu):
-        """`denoise` for a request batch with per-request values (a list for any of num_inference_steps, guidance_scale, the control
-        window, eta, timesteps): every request runs its own table rows, timesteps, window and guidance scale, left-aligned in a loop of
-        nmax = the longest request's evaluations; behind its last row a request is finished and the step leaves it alone."""
-        gs = list(guidance_scale) if isinstance(guidance_scale, (list, tuple)) else [guidance_scale]
-        prompt_embeds, B, T, Dc, single, guidance_off = self._prompt_layout(
-            prompt_embeds, latents, all(isinstance(v, (int, float)) for v in gs) and max(gs) > 1.0, do_classifier_free_guidance, single_pass)
-        h, w = fg_image_latents.shape[-2:]
-        per_request, Bi, req_scales = self._request_batch(B, fg_image_latents, bg_image_latents, gs_score, dino_feats,
-                                                          blobnet_conditioning_scale, generator)
-        steps, gs, starts, ends, etas = self._request_values(B, per_request, blobnet_conditioning_scale, req_scales, num_inference_steps,
-                                                             guidance_scale, start, end, eta, timesteps)
-        gs = [1.0 if guidance_off else max(1.0, float(v)) for v in gs]       # (a request at or below 1: its eps is its conditional half)
-        tables, stochastic, third_order = self._request_tables(steps, etas)
-        coef, t_rows, evals = stack_request_tables(tables, gs)
-        n = max(evals)
-        if timestep_cond is not None:
-            dim = self.unet_cfg.time_cond_proj_dim
-            if dim is None:
-                raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
-            if tuple(timestep_cond.shape) != (B, dim):
-                raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
-        if variance_noise is not None:
-            if not stochastic:
-                raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++, an Euler-ancestral or an LCM "
-                                 "scheduler")
-            if generator is not None:
-                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
-                                 " `variance_noise` stays `None`.")
-            if tuple(variance_noise.shape) != (n, B, 4, h, w):
-                raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (longest request's steps, batch, 4, h, w), got "
-                                 f"{tuple(variance_noise.shape)}")
-        freeu_on = freeu_enabled(freeu)
-        P = self._plan(B, h, w, T, Dc, n, True, stochastic, third_order, tables[0].scales_input, single, freeu_on, requests=True)
-        dev = self.device
-        self.timesteps = [t.timesteps for t in tables]
-        if latents is None:                                                          # pipe:438-453
-            g0 = generator[0] if isinstance(generator, list) else generator
-            latents = randn_tensor((B, 4, h, w), generator, g0.device if g0 is not None else "cpu")
-        if stochastic and variance_noise is None:
-            variance_noise = self._request_noise(tables, evals, h, w, generator, dev)
-        scale_rows = self._request_scale_rows(evals, req_scales, starts, ends)       # [step][image]
-        scales = [max(abs(v) for v in row) for row in scale_rows]                    # a step runs BlobNet when any request is active in it
-        bg, fg = gs_score.unbind(dim=1)                                              # pipe:974
-        self._join_caller()
-        with torch.cuda.stream(self.stream):
-            lat = latents.to(dev, torch.float32)
-            start_lat = torch.stack([lat[b] * t.init_noise_sigma for b, t in enumerate(tables)], 0)
-            self._fill_inputs(P, start_lat, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond)
-            P.t_rows_blob.copy_(t_rows)
-            P.t_rows_unet.copy_(t_rows if single else torch.cat([t_rows, t_rows], 1))     # (images b and B + b: the CFG pair of request b)
-            P.coef.copy_(coef)
-            P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
-            if stochastic:
-                P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
-            if freeu_on:
-                P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
-            P.step_idx.zero_()
-            P.hist.zero_()
-        live = [[i < e for e in evals] for i in range(n)]
-        return self._run(P, n, scales, start_lat, output_type, teacher_latents, callback_on_step_end, callback_self, trace,
-                         lambda i: torch.stack([t.timesteps[min(i, e - 1)] for t, e in zip(tables, evals)]), live=live)
+    @staticmethod
+    def _write_tables(P, S, freeu):
+        """The tables of an edit into the plan's buffers; returns the buffers written (what `compile_plan` saves with their contents)."""
+        f32 = torch.float32
+        if S.requests:
+            P.t_rows_blob.copy_(S.t_rows)
+            P.t_rows_unet.copy_(S.t_rows if P.single else torch.cat([S.t_rows, S.t_rows], 1))   # (images b and B + b: the CFG pair of request b)
+        else:
+            P.t_table.copy_(S.t_rows[:, 0])
+        P.coef.copy_(S.coef)                                     # (column 11, the guidance scale, is read by the captured step kernel)
+        P.scale_table.copy_(torch.tensor(S.scale_rows, dtype=f32).reshape(-1))
+        if P.freeu is not None:
+            P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=f32))
+        return ([P.t_rows_blob, P.t_rows_unet] if S.requests else [P.t_table]) + [P.coef, P.scale_table] + \
+            ([P.freeu] if P.freeu is not None else [])
+
+    @staticmethod
+    def _mark_stored(P, tables, variance_noise):
+        """What a plan file saves with its contents: the constants of the configuration (`tables`) and a `variance_noise` the caller
+        gave; without one the buffer is zero-filled workspace (a C host fills it through bc_plan_buffer before each edit)."""
+        for t in tables:
+            P.rec._workspace.discard(t.untyped_storage().data_ptr())
+        if P.variance_noise is not None:
+            key = P.variance_noise.untyped_storage().data_ptr()
+            if variance_noise is not None:
+                P.variance_noise.copy_(variance_noise.to(P.variance_noise.device, torch.float32))
+                P.rec._workspace.discard(key)
+            else:
+                P.variance_noise.zero_()
+                P.rec._workspace.add(key)
 
     def _prompt_layout(self, prompt_embeds, latents, guidance_on, do_classifier_free_guidance, single_pass):
         """The layout of `prompt_embeds` and the plan form it asks for: (prompt_embeds as the plan's `ctx` takes them, B, T, ctx_dim,
@@ -741,14 +774,19 @@ class BlobCtrlEngine:
         UNet runs without the add.
         `freeu` = (s1, s2, b1, b2) or None: FreeU (UNet2DConditionModel.enable_freeu) in up_blocks.0 / up_blocks.1 of the UNet.  As in the
         reference any value of 0.0 or None among the four runs the plain network - the plan every other call uses.  The values are
-        per-edit data of the FreeU plan: other values replay the same graph."""
+        per-edit data of the FreeU plan: other values replay the same graph.
+        A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps (a list of
+        lists): the requests of a request batch run their own schedules, on the `requests` plan form.  Both kinds of call are one
+        set-up (`_setup` -> EditSetup; a call without lists is "one table, shared by every image"), one plan, one run; `self.timesteps`
+        is then a list of tensors, one per request."""
         if return_sample:
             # pipe:1052-1061 reads blobnet.conv_norm_out / conv_out, which BlobNetModel does not have (626-tensor schema): dead code
             raise NotImplementedError("return_sample=True is not supported (the reference path dereferences layers BlobNet lacks)")
         listed = self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                               blobnet_control_guidance_start=blobnet_control_guidance_start,
                               blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps)
-        stochastic = None if listed else self._check_eta(float(eta))
+        if not listed:                                           # (a call without lists refuses its eta before anything else)
+            self._check_eta(float(eta))
         if output_type not in ("latent", "pt", "np"):
             raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
         if output_type != "latent" and self.vae is None:
@@ -763,79 +801,51 @@ class BlobCtrlEngine:
             if bg_image is None:
                 raise ValueError("give bg_image_latents or bg_image")
             bg_image_latents = self.encode_latents(bg_image)
-        if listed:                                               # per-request values: the `requests` plan form
-            return self._denoise_requests(
-                prompt_embeds, fg_image_latents, bg_image_latents, gs_score, dino_feats, num_inference_steps, guidance_scale, generator,
-                latents, blobnet_conditioning_scale, blobnet_control_guidance_start, blobnet_control_guidance_end, output_type,
-                callback_on_step_end, trace, teacher_latents, eta, do_classifier_free_guidance, callback_self, variance_noise, timesteps,
-                single_pass, timestep_cond, freeu)
-        if timesteps is not None:
-            num_inference_steps = len(timesteps)
-        self.check_inputs(blobnet_conditioning_scale, blobnet_control_guidance_start, blobnet_control_guidance_end,
-                          num_inference_steps)
+        if not listed:                                           # (with lists: per request, once the batch is known - `_request_values`)
+            self.check_inputs(blobnet_conditioning_scale, blobnet_control_guidance_start, blobnet_control_guidance_end,
+                              num_inference_steps if timesteps is None else len(timesteps))
         # pipe:494-497: guidance_scale <= 1 switches classifier-free guidance OFF in the reference (prompt_embeds then holds the
         # positive prompt only and the UNet output is used as is).  The engine keeps its CFG-batch-2 plan: the positive embeddings
         # fill both halves and the effective scale is 1, eps_u + 1 * (eps_c - eps_u) = eps_c.
         # `do_classifier_free_guidance=False` (what the reference derives from guidance_scale <= 1) says explicitly that prompt_embeds
         # holds the positive prompts only; without the flag the layout is inferred from `latents` and refused when ambiguous.
-        prompt_embeds, B, T, Dc, single, guidance_off = self._prompt_layout(prompt_embeds, latents, guidance_scale > 1.0,
+        prompt_embeds, B, T, Dc, single, guidance_off = self._prompt_layout(prompt_embeds, latents, self._guidance_on(guidance_scale),
                                                                             do_classifier_free_guidance, single_pass)
-        if guidance_off:
-            guidance_scale = 1.0
         h, w = fg_image_latents.shape[-2:]
-        n = num_inference_steps
         per_request, Bi, req_scales = self._request_batch(B, fg_image_latents, bg_image_latents, gs_score, dino_feats,
                                                           blobnet_conditioning_scale, generator)
-        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
-        n = len(sched.timesteps)                             # network evaluations (Heun: 2 * num_inference_steps - 1, pipe:1025 loops over them)
-        stochastic, third_order = self._step_form(sched, stochastic)
-        if timestep_cond is not None:
-            dim = self.unet_cfg.time_cond_proj_dim
-            if dim is None:
-                raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
-            if tuple(timestep_cond.shape) != (B, dim):
-                raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
-        if variance_noise is not None:
-            if not stochastic:
-                raise ValueError("variance_noise is only used with eta > 0 (DDIM), an SDE-DPM-Solver++, an Euler-ancestral or an LCM "
-                                 "scheduler")
-            if generator is not None:
-                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
-                                 " `variance_noise` stays `None`.")
-            if tuple(variance_noise.shape) != (n, B, 4, h, w):
-                raise ValueError(f"variance_noise must have shape {(n, B, 4, h, w)} (steps, batch, 4, h, w), got "
-                                 f"{tuple(variance_noise.shape)}")
-        freeu_on = freeu_enabled(freeu)
-        P = self._plan(B, h, w, T, Dc, n, per_request, stochastic, third_order, sched.scales_input, single, freeu_on)
+        S = self._setup(B, per_request, blobnet_conditioning_scale, req_scales, num_inference_steps, timesteps, guidance_scale,
+                        blobnet_control_guidance_start, blobnet_control_guidance_end, eta, guidance_off)
+        self._check_timestep_cond(timestep_cond, B)
+        self._check_variance_noise(S, variance_noise, (B, 4, h, w), generator)
+        P = self._plan(B, h, w, T, Dc, S.n, per_request, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
+                       requests=S.requests)
         dev = self.device
-        self.timesteps = sched.timesteps
+        self.timesteps = [t.timesteps for t in S.tables] if S.requests else S.tables[0].timesteps
         if latents is None:                                                          # pipe:438-453
             g0 = generator[0] if isinstance(generator, list) else generator
             latents = randn_tensor((B, 4, h, w), generator, g0.device if g0 is not None else "cpu")
-        if stochastic and variance_noise is None:            # scheduling_ddim.py:455-458 / dpmsolver_multistep.py:979-982, after the latents
-            variance_noise = self.variance_noise(n, B, h, w, generator, dev, getattr(sched, "draws", None))
-        keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
-        scale_rows = [[sc * k for sc in req_scales] for k in keep]                   # [step][image]
-        scales = [max(abs(v) for v in row) for row in scale_rows]                    # a step is BlobNet-free iff every scale is 0
+        if S.stochastic and variance_noise is None:                                  # (after the latents)
+            variance_noise = self._draw_noise(S, B, h, w, generator, dev)
         bg, fg = gs_score.unbind(dim=1)                                              # pipe:974
         self._join_caller()
         with torch.cuda.stream(self.stream):
-            start = latents.to(dev, torch.float32) * sched.init_noise_sigma
+            sigma = torch.tensor([t.init_noise_sigma for t in S.tables], dtype=torch.float32, device=dev)    # (one, or one per request)
+            start = latents.to(dev, torch.float32) * sigma.view(-1, 1, 1, 1)
             self._fill_inputs(P, start, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond)
-            P.t_table.copy_(sched.timesteps.to(torch.float32))
-            coef = sched.table().clone()
-            coef[:, 11] = float(guidance_scale)          # read by the captured cfg/scheduler kernel
-            P.coef.copy_(coef)
-            P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
-            if stochastic:
+            self._write_tables(P, S, freeu)
+            if S.stochastic:
                 P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
-            if freeu_on:
-                P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
             P.step_idx.zero_()
             P.hist.zero_()
-        P.guidance[0] = float(guidance_scale)
-        return self._run(P, n, scales, start, output_type, teacher_latents, callback_on_step_end, callback_self, trace,
-                         lambda i: sched.timesteps[i].item())
+        if S.requests:
+            live = [[i < e for e in S.evals] for i in range(S.n)]
+            step_time = lambda i: torch.stack([t.timesteps[min(i, e - 1)] for t, e in zip(S.tables, S.evals)])
+        else:
+            P.guidance[0] = 1.0 if guidance_off else float(guidance_scale)
+            live, step_time = None, lambda i: S.tables[0].timesteps[i].item()
+        return self._run(P, S.n, S.active, start, output_type, teacher_latents, callback_on_step_end, callback_self, trace, step_time,
+                         live=live)
 
     def _run(self, P, n, scales, start, output_type, teacher_latents, callback_on_step_end, callback_self, trace, step_time, live=None):
         """Run the edit whose inputs and tables are in the plan's buffers: `scales[i]` != 0 = step i runs BlobNet, `start` = the start
@@ -958,88 +968,31 @@ class BlobCtrlEngine:
         guidance-scale embedding of every UNet image into it before an edit).
         `freeu` = (s1, s2, b1, b2) as in `denoise`: a FreeU plan holds six BC_OP_FREEU launches per UNet forward, their basis tables, and
         the named buffer `freeu` (fp32 [4]) saved with these values; a host writes other values into it before an edit.
-        A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps compiles the
-        mixed edit of a request batch of B: `_compile_requests`."""
-        if self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                        blobnet_control_guidance_start=blobnet_control_guidance_start,
-                        blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps):
-            return self._compile_requests(path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale, blobnet_conditioning_scale,
-                                          blobnet_control_guidance_start, blobnet_control_guidance_end, eta, variance_noise, timesteps,
-                                          single_pass, freeu)
-        single = self._single_pass(single_pass, guidance_scale <= 1.0 or self.unet_cfg.time_cond_proj_dim is not None)   # (pipe:497)
-        n = num_inference_steps if timesteps is None else len(timesteps)
-        stochastic = self._check_eta(float(eta))
-        sched = self._scheduler_table(n, float(eta) if stochastic else 0.0, timesteps)
-        n = len(sched.timesteps)
-        stochastic, third_order = self._step_form(sched, stochastic)
-        if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
-            raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
-        freeu_on = freeu_enabled(freeu)
-        P = self._plan(B, h, w, T, ctx_dim, n, False, stochastic, third_order, sched.scales_input, single, freeu_on)
-        if freeu_on:
-            P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
-        keep = blobnet_keep(n, blobnet_control_guidance_start, blobnet_control_guidance_end)
-        P.t_table.copy_(sched.timesteps.to(torch.float32))
-        coef = sched.table().clone()
-        coef[:, 11] = float(guidance_scale)
-        P.coef.copy_(coef)
-        P.scale_table.copy_(torch.tensor([blobnet_conditioning_scale * k for k in keep], dtype=torch.float32))
-        for t in (P.t_table, P.coef, P.scale_table) + ((P.freeu,) if freeu_on else ()):     # constants of this configuration: saved WITH their contents
-            P.rec._workspace.discard(t.untyped_storage().data_ptr())
-        if stochastic:
-            key = P.variance_noise.untyped_storage().data_ptr()
-            if variance_noise is not None:
-                P.variance_noise.copy_(variance_noise.to(P.variance_noise.device, torch.float32))
-                P.rec._workspace.discard(key)
-            else:
-                P.variance_noise.zero_()
-                P.rec._workspace.add(key)
-        P.rec.save(path)
-        return ["step_active" if blobnet_conditioning_scale * k != 0.0 else "step_inactive" for k in keep]
-
-    def _compile_requests(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale, blobnet_conditioning_scale, start, end, eta,
-                          variance_noise, timesteps, single_pass, freeu):
-        """`compile_plan` with per-request values (lists as `denoise` takes them; `blobnet_conditioning_scale` a float or a list of B):
-        the mixed edit of a request batch of B as a `.bcplan` of file version 8.  Beside the per-request inputs of a request batch
-        (fg_lat, bg_lat, fg_score, bg_score, feat / feat16 with a leading B) it holds, saved with their contents, `coef`
-        [B][nmax][16], `t_rows_unet` [nmax][2B or B], `t_rows_blob` [nmax][B] and `scale_table` [nmax][B]; `variance_noise`
-        [nmax][B][4][h][w] as in `compile_plan`.  Returns the per-step segment names of the nmax steps."""
-        gs = list(guidance_scale) if isinstance(guidance_scale, (list, tuple)) else [guidance_scale]
-        guidance_off = not (all(isinstance(v, (int, float)) for v in gs) and max(gs) > 1.0) or self.unet_cfg.time_cond_proj_dim is not None
+        A list (one entry per request, as `denoise` takes them; `blobnet_conditioning_scale` a float or a list of B) for any of
+        num_inference_steps, guidance_scale, the control window, eta or timesteps compiles the mixed edit of a request batch of B, a
+        `.bcplan` of file version 8: the same set-up (`_setup`) with a table per request.  Beside the per-request inputs of a request batch
+        (fg_lat, bg_lat, fg_score, bg_score, feat / feat16 with a leading B) it holds, saved with their contents, `coef` [B][nmax][16],
+        `t_rows_unet` [nmax][2B or B], `t_rows_blob` [nmax][B] and `scale_table` [nmax][B] instead of `t_table` / `coef` [n][16] /
+        `scale_table` [n]; `variance_noise` [nmax][B][4][h][w] as above; the segment names returned are those of the nmax steps."""
+        listed = bool(self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                   blobnet_control_guidance_start=blobnet_control_guidance_start,
+                                   blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps))
+        guidance_off = not self._guidance_on(guidance_scale) or self.unet_cfg.time_cond_proj_dim is not None      # (pipe:497)
         single = self._single_pass(single_pass, guidance_off)
+        Bi = B if listed else 1
         req_scales = list(blobnet_conditioning_scale) if isinstance(blobnet_conditioning_scale, (list, tuple)) else \
-            [blobnet_conditioning_scale] * B
-        if len(req_scales) != B:
-            raise ValueError(f"blobnet_conditioning_scale: expected {B} values, got {len(req_scales)}")
-        steps, gs, starts, ends, etas = self._request_values(B, B > 1, blobnet_conditioning_scale, req_scales, num_inference_steps,
-                                                             guidance_scale, start, end, eta, timesteps)
-        gs = [1.0 if guidance_off else max(1.0, float(v)) for v in gs]
-        tables, stochastic, third_order = self._request_tables(steps, etas)
-        coef, t_rows, evals = stack_request_tables(tables, gs)
-        n = max(evals)
-        if variance_noise is not None and (not stochastic or tuple(variance_noise.shape) != (n, B, 4, h, w)):
-            raise ValueError(f"variance_noise needs eta > 0 (or an SDE scheduler) and shape {(n, B, 4, h, w)}")
-        freeu_on = freeu_enabled(freeu)
-        P = self._plan(B, h, w, T, ctx_dim, n, True, stochastic, third_order, tables[0].scales_input, single, freeu_on, requests=True)
-        if freeu_on:
-            P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
-        scale_rows = self._request_scale_rows(evals, req_scales, starts, ends)
-        P.t_rows_blob.copy_(t_rows)
-        P.t_rows_unet.copy_(t_rows if single else torch.cat([t_rows, t_rows], 1))
-        P.coef.copy_(coef)
-        P.scale_table.copy_(torch.tensor(scale_rows, dtype=torch.float32).reshape(-1))
-        for t in (P.t_rows_blob, P.t_rows_unet, P.coef, P.scale_table) + ((P.freeu,) if freeu_on else ()):     # saved WITH their contents
-            P.rec._workspace.discard(t.untyped_storage().data_ptr())
-        if stochastic:
-            key = P.variance_noise.untyped_storage().data_ptr()
-            if variance_noise is not None:
-                P.variance_noise.copy_(variance_noise.to(P.variance_noise.device, torch.float32))
-                P.rec._workspace.discard(key)
-            else:
-                P.variance_noise.zero_()
-                P.rec._workspace.add(key)
+            [blobnet_conditioning_scale] * Bi
+        if len(req_scales) != Bi:
+            raise ValueError(f"blobnet_conditioning_scale: expected {Bi} values, got {len(req_scales)}")
+        # (a plan without lists stores the guidance scale it was given, at or below 1 too: what a C host's two `ctx` halves are mixed by)
+        S = self._setup(B, listed and B > 1, blobnet_conditioning_scale, req_scales, num_inference_steps, timesteps, guidance_scale,
+                        blobnet_control_guidance_start, blobnet_control_guidance_end, eta, guidance_off and listed)
+        self._check_variance_noise(S, variance_noise, (B, 4, h, w), compiling=True)
+        P = self._plan(B, h, w, T, ctx_dim, S.n, S.requests, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
+                       requests=S.requests)
+        self._mark_stored(P, self._write_tables(P, S, freeu), variance_noise)
         P.rec.save(path)
-        return ["step_active" if any(v != 0.0 for v in row) else "step_inactive" for row in scale_rows]
+        return S.segments
 
     # convenience for bench / tests ------------------------------------------------------------------
     def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,

@@ -2,7 +2,8 @@
 request's rows are its own table's bit for bit, finished rows behind them), the host trajectory of two requests of different lengths at
 once against the scheduler fixtures, every refusal of a call with lists (before a plan is recorded), what a compiled mixed plan holds
 (a version-8 file whose step segments end in bc_scheduler_step_requests), the dispatcher op, and that scalar plans compile to the listing
-they had (plan_listings_before_requests.json: written by the commit before per-request schedules)."""
+they had (plan_listings_before_requests.json: written by the commit before per-request schedules) and store the tables they stored
+(plan_tables_before_setup_merge.json: written by the commit before `denoise` / `compile_plan` got one shared set-up)."""
 import hashlib
 import json
 import os
@@ -335,6 +336,64 @@ def test_scalar_plans_compile_to_the_listings_and_versions_they_had(plan_dump, d
         assert len(r.stdout.splitlines()) == want[key]["lines"], key
         assert hashlib.sha256(r.stdout.encode()).hexdigest() == want[key]["sha256"], key
     assert not any("requests" in k for k in eng._plans)
+
+
+STORED = ("t_table", "t_rows_unet", "t_rows_blob", "coef", "scale_table", "freeu", "variance_noise")
+
+
+def stored_table_cases():
+    """name -> (scheduler object, B, compile_plan keywords): the configurations of plan_tables_before_setup_merge.json - ten scalar ones
+    at B = 1 and B = 3, and the MIXED lists at B = 3, steps STEPS."""
+    from blobctrl_amd.schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler,
+                                         LCMScheduler, UniPCMultistepScheduler)
+    cases = {}
+    for B in (1, 3):
+        for name, s, kw in (
+                ("unipc", UniPCMultistepScheduler(), dict(num_inference_steps=6, blobnet_control_guidance_end=0.67)),
+                ("ddim_eta_noise", DDIMScheduler(), dict(num_inference_steps=6, eta=0.5, variance_noise=g(7, 6, B, 4, 8, 8))),
+                ("ddim_eta", DDIMScheduler(), dict(num_inference_steps=6, eta=0.5)),
+                ("euler", EulerDiscreteScheduler(**SD), dict(num_inference_steps=6)),
+                ("heun", HeunDiscreteScheduler(**SD), dict(num_inference_steps=4)),
+                ("dpm_3m", DPMSolverMultistepScheduler(solver_order=3), dict(num_inference_steps=6)),
+                ("dpm_sde", DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++"), dict(num_inference_steps=6)),
+                ("lcm_single", LCMScheduler(), dict(num_inference_steps=4, guidance_scale=1.0)),
+                ("unipc_freeu", UniPCMultistepScheduler(), dict(num_inference_steps=6, freeu=(0.9, 0.2, 1.2, 1.4))),
+                ("dpm_timesteps", DPMSolverMultistepScheduler(), dict(num_inference_steps=None, timesteps=[999, 500, 10]))):
+            cases[f"{name}_b{B}"] = (s, B, kw)
+    for name, s, kw in (("ddim_eta", DDIMScheduler(), dict(MIXED, eta=[0.0, 0.5, 1.0])), ("euler", EulerDiscreteScheduler(**SD), MIXED),
+                        ("lcm", LCMScheduler(), MIXED), ("lcm_single", LCMScheduler(), dict(MIXED, guidance_scale=[1.0, 1.0, 0.5]))):
+        cases[f"mixed_{name}"] = (s, 3, dict(kw, num_inference_steps=list(STEPS)))
+    return cases
+
+
+def stored_tables(workdir):
+    """name -> {"segments": what compile_plan returned, "stored": {buffer: sha256 of its stored bytes}} of every case above; a buffer the
+    file keeps as workspace (a `variance_noise` nobody gave) has no entry."""
+    eng, out = _engine(), {}
+    for name, (s, B, kw) in stored_table_cases().items():
+        eng.set_scheduler(s.kind, s.table_params())
+        path = os.path.join(str(workdir), name + ".bcplan")
+        seq = eng.compile_plan(path, B, 8, 8, 7, TINY["ctx"], **kw)
+        st = _stored(path)
+        out[name] = dict(segments=seq, stored={k: hashlib.sha256(st[k]).hexdigest() for k in STORED if k in st})
+        os.remove(path)
+    return out
+
+
+def test_compiled_plans_store_the_tables_they_stored_before_the_setup_merge(tmp_path):
+    """Scalar and list calls of compile_plan: the bytes of every table saved with its contents and the returned segment list are what
+    the commit before `denoise` / `compile_plan` got their one shared set-up wrote (tools/make_plan_fixture.py --stored-tables, run
+    on that commit)."""
+    want = json.load(open(os.path.join(GOLD, "plan_tables_before_setup_merge.json")))
+    got = stored_tables(tmp_path)
+    assert sorted(got) == sorted(want) and len(want) == 24
+    for name in sorted(want):
+        assert got[name] == want[name], name
+        names = set(got[name]["stored"])
+        lists, noise = name.startswith("mixed_"), "noise" in name
+        assert names - {"freeu", "variance_noise"} == ({"t_rows_unet", "t_rows_blob", "coef", "scale_table"} if lists else
+                                                      {"t_table", "coef", "scale_table"}), name
+        assert ("freeu" in names) == ("freeu" in name) and ("variance_noise" in names) == noise, name
 
 
 # ------------------------------------------------------------------------------------------------------------ C ABI and dispatcher

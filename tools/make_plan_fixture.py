@@ -24,7 +24,13 @@ and strengths per request; the Euler scheduler, so the inputs are assembled by t
 steps end in bc_scheduler_step_requests.  The inputs are seeded request-batch tensors (`request_inputs`), "latents" holds every
 request's start noise times its own init_noise_sigma, "expected_latents" is `--expected FILE.npy` (what the in-process engine computed).
 
+`--stored-tables` writes tests/golden/plan_tables_before_setup_merge.json instead: per configuration of
+tests/test_request_tables_cpu.py:stored_table_cases, the sha256 of every table `compile_plan` stores with its contents and the returned
+segment list.  The committed file was written by the commit BEFORE `denoise` / `compile_plan` got their shared set-up; regenerating it
+from later code makes the test that reads it vacuous.
+
     python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG | --lcm TAG | --requests [--expected FILE.npy]]
+    python tools/make_plan_fixture.py --stored-tables
 """
 import argparse
 import os
@@ -93,7 +99,19 @@ def main():
     ap.add_argument("--lcm", default=None, help="a case of loop_tiny_lcm.npz (LCM with or without guidance, single-pass DDIM / UniPC)")
     ap.add_argument("--requests", action="store_true", help="the mixed edit of a request batch of 3 (REQUESTS), Euler")
     ap.add_argument("--expected", default=None, help=".npy file with the expected final latents (default: the reference loop's)")
+    ap.add_argument("--stored-tables", action="store_true", help="write tests/golden/plan_tables_before_setup_merge.json")
     args = ap.parse_args()
+    if args.stored_tables:
+        import json
+        import tempfile
+        from tests.test_request_tables_cpu import stored_tables
+        with tempfile.TemporaryDirectory() as tmp:
+            tables = stored_tables(tmp)
+        with open(os.path.join(GOLD, "plan_tables_before_setup_merge.json"), "w") as f:
+            json.dump(tables, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("plan_tables_before_setup_merge.json:", len(tables), "configurations")
+        return
     OUT = args.out
     os.makedirs(OUT, exist_ok=True)
     if args.requests:
