@@ -192,6 +192,22 @@ REQUEST_SIGNATURES = {
                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# Entry points of include/blobctrl_sam.h (the Segment-Anything path of blobctrl_amd/sam.py).  A table of its own like the request forms;
+# all are recordable (SAM_OPS below), but SAM segments live in-process only - nothing of them is written to a plan file.
+_ATTN_RELPOS_ARGS = [C.c_void_p] * 4 + [C.c_int] * 11 + [C.c_longlong] * 4 + [C.c_float] + [C.c_void_p] * 3 + [C.c_void_p]
+SAM_SIGNATURES = {
+    "bc_attention_relpos": (C.c_int, _ATTN_RELPOS_ARGS),
+    "bc_window_partition": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_window_unpartition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_add_pos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_add_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_act_rows": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    "bc_bilinear_resize_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_float, C.c_void_p, C.c_void_p]),
+    "bc_sam_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                C.c_void_p, C.c_void_p]),
+    "bc_sam_masks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -206,6 +222,9 @@ OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused":
 # ... and those of include/blobctrl_requests.h (plan file version 8); `op_code` looks a name up in both tables
 REQUEST_OPS = {"bc_scheduler_step_requests": 38, "bc_assemble_input_requests": 39, "bc_assemble_input_im2col_requests": 40,
                "bc_timestep_embedding_rows": 41}
+# ... and those of include/blobctrl_sam.h
+SAM_OPS = {"bc_attention_relpos": 42, "bc_window_partition": 43, "bc_window_unpartition": 44, "bc_add_pos": 45, "bc_add_rows": 46,
+           "bc_act_rows": 47, "bc_bilinear_resize_f32": 48, "bc_sam_tokens": 49, "bc_sam_masks": 50}
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
@@ -214,12 +233,12 @@ _KIND = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l", C.c_c
 
 def op_code(name):
     """BC_OP_* code of a recordable entry point."""
-    return OPS[name] if name in OPS else REQUEST_OPS[name]
+    return OPS[name] if name in OPS else REQUEST_OPS[name] if name in REQUEST_OPS else SAM_OPS[name]
 
 
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
-    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES[name])[1][:-1]
+    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -253,7 +272,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:   # pragma: no cover
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
+            list(SAM_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -225,6 +225,19 @@ def ellipse_from_mask(mask: np.ndarray) -> Ellipse:
     return fit_ellipse(convex_hull(np.stack([xs, ys], 1)))
 
 
+def ellipse_from_click(predictor, image, points, labels=None) -> Ellipse:
+    """app:1019-1043 `segmentation()`: the click(s) on `image` -> SAM mask (`predict(..., multimask_output=False)`, mask 0) ->
+    `ellipse_from_mask`, the first blob of an edit.  `predictor` is a `blobctrl_amd.sam.SamPredictor` (or anything with its call surface).
+    `image` = None keeps the image the predictor already holds: a further click then costs the mask decoder only.  `points` [n][2] are
+    (x, y) pixels of the image; `labels` default to 1 (foreground) for every point, as in the app."""
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 2)
+    lab = np.ones(len(pts), dtype=np.int32) if labels is None else np.asarray(labels, dtype=np.int32).reshape(-1)
+    if image is not None:
+        predictor.set_image(np.asarray(image))
+    masks, _, _ = predictor.predict(point_coords=pts, point_labels=lab, multimask_output=False)
+    return ellipse_from_mask(np.asarray(masks[0]).astype(np.uint8))
+
+
 def blob_overlay(ellipse: Ellipse, height: int, width: int, viz_colors, device: str = "cuda:0") -> np.ndarray:
     """app:611-650 chained: ellipse -> normalised Gaussian -> the app's `splat_features(..., viz_size=(H, W), is_viz=True,
     only_vis=True)` call -> `* 255` -> uint8 [H, W, 3].  `viz_colors` [K, 3] is the caller's palette (row 0 background, row 1 the blob).

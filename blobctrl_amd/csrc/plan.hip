@@ -21,6 +21,7 @@
 #include "bc_common.h"
 #include "plan_format.h"
 #include "../../include/blobctrl_requests.h"
+#include "../../include/blobctrl_sam.h"
 
 void bc_gemm_set_probe(hipEvent_t e);      // gemm.hip (timing probe between a split-K GEMM's main kernel and its reducer)
 bool bc_gemm_probe_hit();
@@ -157,6 +158,22 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
                                                      CP(int, 10), I(11), MP(bc_half, 12), s);
         case BC_OP_TIMESTEP_EMBEDDING_ROWS:
             return bc_timestep_embedding_rows(CP(float, 0), I(1), I(2), CP(float, 3), I(4), MP(bc_half, 5), s);
+        case BC_OP_ATTENTION_RELPOS:
+            return bc_attention_relpos(CP(bc_half, 0), CP(bc_half, 1), CP(bc_half, 2), MP(bc_half, 3), I(4), I(5), I(6), I(7), I(8), I(9), I(10),
+                                       I(11), I(12), I(13), I(14), L(15), L(16), L(17), L(18), F(19), CP(bc_half, 20), CP(bc_half, 21),
+                                       MP(float, 22), s);
+        case BC_OP_WINDOW_PARTITION: return bc_window_partition(CP(bc_half, 0), I(1), I(2), I(3), I(4), I(5), MP(bc_half, 6), s);
+        case BC_OP_WINDOW_UNPARTITION:
+            return bc_window_unpartition(CP(bc_half, 0), CP(bc_half, 1), I(2), I(3), I(4), I(5), I(6), MP(bc_half, 7), s);
+        case BC_OP_ADD_POS: return bc_add_pos(CP(bc_half, 0), CP(float, 1), I(2), I(3), I(4), MP(bc_half, 5), s);
+        case BC_OP_ADD_ROWS: return bc_add_rows(CP(bc_half, 0), CP(bc_half, 1), I(2), I(3), I(4), MP(bc_half, 5), s);
+        case BC_OP_ACT_ROWS: return bc_act_rows(MP(bc_half, 0), L(1), I(2), s);
+        case BC_OP_BILINEAR_RESIZE_F32:
+            return bc_bilinear_resize_f32(CP(float, 0), I(1), I(2), I(3), I(4), I(5), I(6), I(7), I(8), F(9), P(10), s);
+        case BC_OP_SAM_TOKENS:
+            return bc_sam_tokens(CP(float, 0), I(1), CP(float, 2), CP(int, 3), I(4), CP(float, 5), I(6), CP(float, 7), CP(float, 8), F(9),
+                                 MP(bc_half, 10), s);
+        case BC_OP_SAM_MASKS: return bc_sam_masks(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), I(6), I(7), MP(float, 8), s);
         case BC_OP_FREEU:
             return bc_freeu(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), CP(float, 6), I(7), CP(float, 8), MP(bc_half, 9),
                             MP(bc_half, 10), MP(unsigned long long, 11), MP(unsigned long long, 12), s);
@@ -472,12 +489,13 @@ extern "C" int bc_plan_save(BcPlan* pl, const char* path, const BcPlanBuffer* bu
         tb[i].addr = (uint64_t)(uintptr_t)bufs[i].address;
         tb[i].bytes = (uint64_t)bufs[i].bytes;
     }
-    FILE* f = fopen(path, "wb");
-    BC_CHECK_ARG(f != nullptr, "bc_plan_save: cannot open %s", path);
-    Writer w{f};
     uint32_t version = op_min_version(BC_OP_GEMM);    // the lowest version that has every recorded op
     for (Seg& sg : pl->segs)
         for (Rec& r : sg.recs) version = std::max(version, op_min_version(r.op));
+    BC_CHECK_ARG(version != kNoFileVersion, "bc_plan_save: the plan holds launches that exist in-process only (include/blobctrl_sam.h)");
+    FILE* f = fopen(path, "wb");
+    BC_CHECK_ARG(f != nullptr, "bc_plan_save: cannot open %s", path);
+    Writer w{f};
     w.u32(kMagic); w.u32(version); w.u32((uint32_t)sizeof(BcGemm)); w.u32((uint32_t)nbufs);
     for (int i = 0; i < nbufs; ++i) {
         w.str(tb[i].name);

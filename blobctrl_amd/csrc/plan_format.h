@@ -24,7 +24,9 @@ const uint32_t kVersion = 8;           // 2: BcGemm grew ln_colsum / C_t, GroupN
                                        //    BC_OP_TIMESTEP_EMBEDDING_ROWS (request batches with per-request schedules)
 // A file is written with the LOWEST version that describes it (op_min_version below): a plan without a version-6 op stays a version-5
 // file, byte for byte what the previous library wrote and still readable by it.
+const uint32_t kNoFileVersion = 0xffffffffu;     // ops that exist in-process only: bc_plan_save refuses them and no file version admits them
 inline uint32_t op_min_version(int op) {
+    if (op >= BC_OP_ATTENTION_RELPOS && op <= BC_OP_SAM_MASKS) return kNoFileVersion;      // include/blobctrl_sam.h
     if (op == BC_OP_SCHEDULER_STEP_REQUESTS || op == BC_OP_ASSEMBLE_INPUT_REQUESTS || op == BC_OP_ASSEMBLE_IM2COL_REQUESTS ||
         op == BC_OP_TIMESTEP_EMBEDDING_ROWS) return 8u;
     // (BC_OP_FREEU joined version 7 without a new version number: a reader built before it refuses the record as an unknown op code)
@@ -78,6 +80,15 @@ inline const char* op_signature(int op) {
         case BC_OP_ASSEMBLE_INPUT_REQUESTS: return "pipppiiiiiiippip";
         case BC_OP_ASSEMBLE_IM2COL_REQUESTS: return "pippiiiiippip";
         case BC_OP_TIMESTEP_EMBEDDING_ROWS: return "piipip";
+        case BC_OP_ATTENTION_RELPOS: return "ppppiiiiiiiiiiillllfppp";      // include/blobctrl_sam.h: in-process segments only
+        case BC_OP_WINDOW_PARTITION: return "piiiiip";
+        case BC_OP_WINDOW_UNPARTITION: return "ppiiiiip";
+        case BC_OP_ADD_POS:
+        case BC_OP_ADD_ROWS: return "ppiiip";
+        case BC_OP_ACT_ROWS: return "pli";
+        case BC_OP_BILINEAR_RESIZE_F32: return "piiiiiiiifp";
+        case BC_OP_SAM_TOKENS: return "pippipippfp";
+        case BC_OP_SAM_MASKS: return "pipiiiiip";
         default: return nullptr;
     }
 }

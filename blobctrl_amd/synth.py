@@ -190,6 +190,83 @@ def clip_text_param_shapes(vocab: int = 49408, hidden: int = 768, layers: int = 
     return s
 
 
+def sam_param_shapes(image: int = 1024, patch: int = 16, window: int = 14, layers: int = 32, global_attn_indexes=(7, 15, 23, 31),
+                     hidden: int = 1280, heads: int = 16, mlp_dim: int = 5120, out_channels: int = 256, decoder_layers: int = 2,
+                     decoder_mlp_dim: int = 2048, iou_head_hidden_dim: int = 256, num_mask_tokens: int = 4,
+                     mask_input_channels: int = 16) -> "OrderedDict[str, tuple]":
+    """transformers `SamModel.state_dict()` layout (call site scripts/blobctrl_app.py:1019-1043; defaults = ViT-H).  The prompt / decoder
+    width is `out_channels`; `num_pos_feats` is half of it (the model does not run otherwise)."""
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    grid, d, C = image // patch, hidden // heads, out_channels
+    s["shared_image_embedding.positional_embedding"] = (2, C // 2)
+    v = "vision_encoder."
+    s[v + "pos_embed"] = (1, grid, grid, hidden)
+    s[v + "patch_embed.projection.weight"] = (hidden, 3, patch, patch)
+    s[v + "patch_embed.projection.bias"] = (hidden,)
+    for i in range(layers):
+        p = f"{v}layers.{i}."
+        side = grid if i in global_attn_indexes else window
+        s[p + "layer_norm1.weight"] = (hidden,); s[p + "layer_norm1.bias"] = (hidden,)
+        s[p + "attn.rel_pos_h"] = (2 * side - 1, d)
+        s[p + "attn.rel_pos_w"] = (2 * side - 1, d)
+        s[p + "attn.qkv.weight"] = (3 * hidden, hidden); s[p + "attn.qkv.bias"] = (3 * hidden,)
+        s[p + "attn.proj.weight"] = (hidden, hidden); s[p + "attn.proj.bias"] = (hidden,)
+        s[p + "layer_norm2.weight"] = (hidden,); s[p + "layer_norm2.bias"] = (hidden,)
+        s[p + "mlp.lin1.weight"] = (mlp_dim, hidden); s[p + "mlp.lin1.bias"] = (mlp_dim,)
+        s[p + "mlp.lin2.weight"] = (hidden, mlp_dim); s[p + "mlp.lin2.bias"] = (hidden,)
+    s[v + "neck.conv1.weight"] = (C, hidden, 1, 1)
+    s[v + "neck.layer_norm1.weight"] = (C,); s[v + "neck.layer_norm1.bias"] = (C,)
+    s[v + "neck.conv2.weight"] = (C, C, 3, 3)
+    s[v + "neck.layer_norm2.weight"] = (C,); s[v + "neck.layer_norm2.bias"] = (C,)
+    pe = "prompt_encoder."
+    s[pe + "shared_embedding.positional_embedding"] = (2, C // 2)
+    m4 = mask_input_channels // 4
+    s[pe + "mask_embed.conv1.weight"] = (m4, 1, 2, 2); s[pe + "mask_embed.conv1.bias"] = (m4,)
+    s[pe + "mask_embed.conv2.weight"] = (mask_input_channels, m4, 2, 2); s[pe + "mask_embed.conv2.bias"] = (mask_input_channels,)
+    s[pe + "mask_embed.conv3.weight"] = (C, mask_input_channels, 1, 1); s[pe + "mask_embed.conv3.bias"] = (C,)
+    s[pe + "mask_embed.layer_norm1.weight"] = (m4,); s[pe + "mask_embed.layer_norm1.bias"] = (m4,)
+    s[pe + "mask_embed.layer_norm2.weight"] = (mask_input_channels,); s[pe + "mask_embed.layer_norm2.bias"] = (mask_input_channels,)
+    s[pe + "no_mask_embed.weight"] = (1, C)
+    for i in range(4):
+        s[pe + f"point_embed.{i}.weight"] = (1, C)
+    s[pe + "not_a_point_embed.weight"] = (1, C)
+    md = "mask_decoder."
+    s[md + "iou_token.weight"] = (1, C)
+    s[md + "mask_tokens.weight"] = (num_mask_tokens, C)
+
+    def attn(p, inner):
+        for n in ("q_proj", "k_proj", "v_proj"):
+            s[p + n + ".weight"] = (inner, C); s[p + n + ".bias"] = (inner,)
+        s[p + "out_proj.weight"] = (C, inner); s[p + "out_proj.bias"] = (C,)
+
+    for i in range(decoder_layers):
+        p = f"{md}transformer.layers.{i}."
+        attn(p + "self_attn.", C)
+        s[p + "layer_norm1.weight"] = (C,); s[p + "layer_norm1.bias"] = (C,)
+        attn(p + "cross_attn_token_to_image.", C // 2)
+        s[p + "layer_norm2.weight"] = (C,); s[p + "layer_norm2.bias"] = (C,)
+        s[p + "mlp.lin1.weight"] = (decoder_mlp_dim, C); s[p + "mlp.lin1.bias"] = (decoder_mlp_dim,)
+        s[p + "mlp.lin2.weight"] = (C, decoder_mlp_dim); s[p + "mlp.lin2.bias"] = (C,)
+        s[p + "layer_norm3.weight"] = (C,); s[p + "layer_norm3.bias"] = (C,)
+        s[p + "layer_norm4.weight"] = (C,); s[p + "layer_norm4.bias"] = (C,)
+        attn(p + "cross_attn_image_to_token.", C // 2)
+    attn(md + "transformer.final_attn_token_to_image.", C // 2)
+    s[md + "transformer.layer_norm_final_attn.weight"] = (C,); s[md + "transformer.layer_norm_final_attn.bias"] = (C,)
+    s[md + "upscale_conv1.weight"] = (C, C // 4, 2, 2); s[md + "upscale_conv1.bias"] = (C // 4,)
+    s[md + "upscale_conv2.weight"] = (C // 4, C // 8, 2, 2); s[md + "upscale_conv2.bias"] = (C // 8,)
+    s[md + "upscale_layer_norm.weight"] = (C // 4,); s[md + "upscale_layer_norm.bias"] = (C // 4,)
+
+    def mlp3(p, hid, out):
+        s[p + "proj_in.weight"] = (hid, C); s[p + "proj_in.bias"] = (hid,)
+        s[p + "layers.0.weight"] = (hid, hid); s[p + "layers.0.bias"] = (hid,)
+        s[p + "proj_out.weight"] = (out, hid); s[p + "proj_out.bias"] = (out,)
+
+    for i in range(num_mask_tokens):
+        mlp3(f"{md}output_hypernetworks_mlps.{i}.", C, C // 8)
+    mlp3(md + "iou_prediction_head.", iou_head_hidden_dim, num_mask_tokens)
+    return s
+
+
 def vae_param_shapes(block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, in_channels=3,
                      out_channels=3) -> "OrderedDict[str, tuple]":
     """`AutoencoderKL.state_dict()` layout of the SD-1.5 VAE (D/models/autoencoders/autoencoder_kl.py:72-137, vae.py:47-348)."""
@@ -257,6 +334,14 @@ def synth_tensor(name: str, shape: tuple, seed: int) -> np.ndarray:
         return (0.2 + 0.05 * x).astype(np.float32)
     if "cls_token" in name or "mask_token" in name or "position_embeddings" in name:
         return (0.05 * x).astype(np.float32)
+    # SAM: with the framework's default initialisation rel_pos_* are zero and the embeddings vanish; here the relative-position tables give a
+    # bias of the scores' own order, pos_embed is of the tokens' order and the Fourier matrix spans a few periods over the image
+    if "attn.rel_pos_" in name:
+        return (x / np.sqrt(shape[-1])).astype(np.float32)
+    if name.endswith("vision_encoder.pos_embed"):
+        return (0.5 * x).astype(np.float32)
+    if name.endswith(".positional_embedding"):
+        return x.astype(np.float32)
     if leaf == "bias":
         return (0.02 * x).astype(np.float32)
     if len(shape) == 1:                       # norm weight

@@ -4,7 +4,10 @@
    -> 50-step blob-conditioned denoise loop -> VAE decode -> image.
 With --models DIR it loads the released layout (README.md:115-128: DIR/stable-diffusion-v1-5/{unet,vae,text_encoder},
 DIR/blobnet, DIR/unet_lora, DIR/dinov2-large); without it, seeded synthetic weights of the same architectures are used (no
-checkpoints exist offline), which exercises every kernel and prints per-stage timings but produces noise, not a picture."""
+checkpoints exist offline), which exercises every kernel and prints per-stage timings but produces noise, not a picture.
+With --sam DIR_OR_PTH --click X,Y the edit starts where the app's does: Segment-Anything turns the click on the foreground image into a
+mask and the mask into the blob's ellipse (DIR = a transformers directory, PTH = the original sam_vit_h_4b8939.pth, "synth" = seeded
+synthetic ViT-H weights)."""
 import argparse
 import os
 import sys
@@ -23,7 +26,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--out", default=None, help="write the edited image as a .npy [H,W,3] float array")
+    ap.add_argument("--sam", default=None, help="SAM weights: a transformers directory, the original .pth, or 'synth'")
+    ap.add_argument("--click", default=None, help="X,Y pixel of the click on the foreground image (with --sam)")
     args = ap.parse_args()
+    if args.click and not args.sam:
+        ap.error("--click needs --sam")
     import bench
     from blobctrl_amd import synth
     from blobctrl_amd.clip_text import CLIPTextModel
@@ -61,6 +68,24 @@ def main():
     bg = torch.from_numpy(rng.uniform(-1, 1, (1, 3, R, R)).astype(np.float32))
     s = R / 512.0
     ellipse = [[361.1067 * s, 367.8526 * s], [85.4812 * s, 103.6543 * s], 87.3739]            # the README's move_hat target blob
+    if args.sam:
+        from blobctrl_amd.blob_edit import ellipse_from_click
+        from blobctrl_amd.sam import SamModel, SamPredictor
+        if args.sam == "synth":
+            sd = synth.synth_state_dict(synth.sam_param_shapes(), 131)
+            sam = SamModel(sd)
+        else:
+            sam = SamModel.from_pretrained(args.sam) if os.path.isdir(args.sam) else SamModel.from_checkpoint(args.sam)
+        click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
+        image = ((fg[0].permute(1, 2, 0).numpy() + 1) * 127.5).round().clip(0, 255).astype(np.uint8)
+        ts = sync()
+        predictor = SamPredictor(sam)
+        e = ellipse_from_click(predictor, image, [click])
+        te = sync()
+        e2 = ellipse_from_click(predictor, None, [click])
+        print(f"SAM click {click} -> ellipse {e} in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); "
+              f"second click {1e3 * (sync() - te):.1f} ms, same ellipse: {e2 == e}")
+        ellipse = [list(e[0]), list(e[1]), e[2]]
     score = splat_features(**blob_dict_from_ellipse(ellipse, R, R), score_size=(R // 8, R // 8), return_d_score=True)
     t2 = sync()
     crop = torch.nn.functional.interpolate(fg, size=(224, 224), mode="bilinear", align_corners=False)

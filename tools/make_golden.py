@@ -1508,6 +1508,107 @@ def golden_dinov2():
     print("dinov2: pooled std %.4f" % out["native_pooled"].std())
 
 
+def golden_sam():
+    """tests/golden/sam_tiny.npz: transformers' SamModel (CPU, fp32, synth weights) on the two tiny configurations of tests/sam_common.py -
+    image embeddings, low-res logits and IoU scores for two click sets, the final masks at a non-square original size, the same with the
+    qkv biases x 8 (the padded-window case), and SamPredictor's preprocessing from transformers' SAM image processor."""
+    from transformers import SamConfig, SamMaskDecoderConfig, SamModel, SamPromptEncoderConfig, SamVisionConfig
+    from transformers import SamImageProcessor
+    from tests import sam_common as sc
+    out = {}
+
+    def hf_model(cfg, sd):
+        C = cfg["out_channels"]
+        vc = SamVisionConfig(hidden_size=cfg["hidden"], output_channels=C, num_hidden_layers=cfg["layers"], num_attention_heads=cfg["heads"],
+                             image_size=cfg["image"], patch_size=cfg["patch"], window_size=cfg["window"],
+                             global_attn_indexes=list(cfg["global_attn_indexes"]), mlp_dim=cfg["mlp_dim"], num_pos_feats=C // 2)
+        pc = SamPromptEncoderConfig(hidden_size=C, image_size=cfg["image"], patch_size=cfg["patch"], mask_input_channels=16)
+        mc = SamMaskDecoderConfig(hidden_size=C, num_hidden_layers=cfg["decoder_layers"], num_attention_heads=sc.DECODER_HEADS,
+                                  mlp_dim=cfg["decoder_mlp_dim"], iou_head_hidden_dim=cfg["iou_head_hidden_dim"])
+        model = SamModel(SamConfig(vision_config=vc, prompt_encoder_config=pc, mask_decoder_config=mc)).eval()
+        assert set(sd.keys()) == set(model.state_dict().keys()), set(sd.keys()) ^ set(model.state_dict().keys())
+        model.load_state_dict(sd, strict=True)
+        return model
+
+    def run(tag, cfg, sd, masks, pixel_seed=7):
+        S = cfg["image"]
+        model = hf_model(cfg, sd)
+        # (pixels on a 1/32 grid, stored as int8: three fp32 frames would not fit the size limit of a committed file)
+        q8 = torch.clamp(torch.round(32 * g(cfg["seed"] + pixel_seed, 1, 3, S, S)), -127, 127)
+        x = q8 / 32
+        if masks:
+            x[..., sc.INPUT_SIZE[0]:, :] = 0
+            x[..., :, sc.INPUT_SIZE[1]:] = 0
+        with torch.no_grad():
+            emb = model.get_image_embeddings(x)
+        out[f"{tag}_pixels_q8"], out[f"{tag}_emb"] = (32 * x).round().to(torch.int8).numpy(), emb.numpy()
+        peak = float(emb.abs().max())
+        assert 0.1 < peak < 100, f"{tag}: |embedding| max {peak}"
+        out[f"{tag}_emb_absmax"] = np.float32(peak)
+        for name, (pts, labs) in sc.CLICKS.items():
+            for multi in (False, True):
+                with torch.no_grad():
+                    r = model(image_embeddings=emb, input_points=torch.tensor([[pts]]), input_labels=torch.tensor([[labs]]),
+                              multimask_output=multi)
+                low, iou = r.pred_masks[0, 0], r.iou_scores[0, 0]
+                key = f"{tag}_{name}_{'multi' if multi else 'single'}"
+                out[key + "_low"], out[key + "_iou"] = low.numpy(), iou.numpy()
+                if masks:
+                    logits = sc.postprocess(low, S, sc.INPUT_SIZE, sc.ORIGINAL_SIZE)
+                    m = 1e-2 * float(logits.abs().max())
+                    share = float((logits.abs() < m).float().mean())
+                    assert share <= 0.10, f"{key}: {share:.3f} of the mask pixels lie within {m:.3e} of the threshold: pick another seed"
+                    out[key + "_mask"], out[key + "_margin"], out[key + "_near_share"] = (logits > 0).numpy(), np.float32(m), np.float32(share)
+        return emb
+
+    def run_seeded(tag, cfg, sd, masks):
+        """`run` with the first pixel seed whose masks pass the builder's margin assertion ("pick another seed")."""
+        for pixel_seed in range(7, 47):
+            try:
+                emb = run(tag, cfg, sd, masks, pixel_seed)
+            except AssertionError as e:
+                if "pick another seed" not in str(e):
+                    raise
+                continue
+            out[f"{tag}_pixel_seed"] = np.int32(pixel_seed)
+            return emb
+        raise AssertionError(f"{tag}: no pixel seed in 7 .. 46 keeps the masks clear of their threshold")
+
+    run_seeded("a", sc.TINY_A, sc.weights_of(sc.TINY_A), True)
+    run_seeded("b", sc.TINY_B, sc.weights_of(sc.TINY_B), False)
+    # the padded-window case: qkv biases x 8 make the zero-padded tokens' keys and values matter.  How far the reference moves when those
+    # tokens are masked out instead of attended to (the restatement of tests/sam_common.py, which tests/test_sam_cpu.py holds to this file):
+    sd8 = sc.weights_of(sc.TINY_A, 8.0)
+    emb8 = run_seeded("a8", sc.TINY_A, sd8, True)
+    a = sc.TINY_A
+    x8 = torch.from_numpy(out["a8_pixels_q8"]).float() / 32
+    with torch.no_grad():
+        same = sc.vision_encoder(x8, sd8, a["heads"], a["window"], a["global_attn_indexes"])
+        masked = sc.vision_encoder(x8, sd8, a["heads"], a["window"], a["global_attn_indexes"], mask_padded=True)
+    assert sc.rel_err(same, emb8) < 1e-5
+    moved = sc.rel_err(masked, emb8) / 1e-2                       # in bars of the GPU tests (rel_err < 1e-2)
+    assert moved > 10, f"masking the padded tokens moves the embeddings by only {moved:.1f} bars"
+    out["a8_masked_padding_moves_bars"] = np.float32(moved)
+    # SamPredictor.set_image's host side, from transformers' own SAM image processor (long side 64 keeps the fixture small)
+    rng = np.random.Generator(np.random.PCG64(133))
+    yy, xx = np.mgrid[0:200, 0:150]
+    img = np.stack([127 + 100 * np.sin(xx / 9.0 + c) * np.cos(yy / 13.0 - c) for c in range(3)], -1) + rng.normal(0, 12, (200, 150, 3))
+    img = np.clip(img, 0, 255).astype(np.uint8)
+    proc = SamImageProcessor(size={"longest_edge": 64}, pad_size={"height": 64, "width": 64})
+    full = proc(images=img, return_tensors="np")
+    raw = proc(images=img, do_rescale=False, do_normalize=False, do_pad=False, return_tensors="np")["pixel_values"][0]
+    assert tuple(full["reshaped_input_sizes"][0]) == (64, 48) and raw.shape == (3, 64, 48)
+    assert np.array_equal(raw, np.round(raw)) and raw.min() >= 0 and raw.max() <= 255
+    out["predictor_pre_image"] = img
+    out["predictor_pre_resized"] = raw.transpose(1, 2, 0).astype(np.uint8)
+    out["predictor_pre_tensor"] = full["pixel_values"].astype(np.float32)
+    path = os.path.join(OUT, "sam_tiny.npz")
+    np.savez_compressed(path, **out)
+    print("sam: %d arrays, %d bytes; |emb| max a %.3f b %.3f a8 %.3f; masked padding moves a8 by %.1f bars" % (
+        len(out), os.path.getsize(path), out["a_emb_absmax"], out["b_emb_absmax"], out["a8_emb_absmax"], moved))
+    assert os.path.getsize(path) < 1 << 20
+
+
 def golden_blob_edit():
     """Pure-geometry functions of scripts/blobctrl_app.py (the app itself needs gradio / cv2 / SAM and loads models at import, so
     only the wanted function definitions are taken out of its source with `ast` and executed here; cv2.boundingRect is the one
@@ -2103,6 +2204,7 @@ if __name__ == "__main__":
     golden_blob_viz()
     golden_schedulers()
     golden_dinov2()
+    golden_sam()
     golden_nets()
     golden_loop()
     golden_blocks()
