@@ -207,6 +207,14 @@ SAM_SIGNATURES = {
                                 C.c_void_p, C.c_void_p]),
     "bc_sam_masks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
+# ... and the entry points behind batched prompts / SamAutomaticMaskGenerator, declared in the same header: a table of their own
+# (SAM_BATCH_OPS below), recordable and in-process only like SAM_OPS.  bc_mask_stats_chunks is a host query, not a launch.
+SAM_BATCH_SIGNATURES = {
+    "bc_sam_tokens_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_float, C.c_void_p, C.c_void_p]),
+    "bc_mask_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+SAM_HOST_SIGNATURES = {"bc_mask_stats_chunks": (C.c_int, [C.c_int, C.c_int])}
 
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
@@ -225,6 +233,8 @@ REQUEST_OPS = {"bc_scheduler_step_requests": 38, "bc_assemble_input_requests": 3
 # ... and those of include/blobctrl_sam.h
 SAM_OPS = {"bc_attention_relpos": 42, "bc_window_partition": 43, "bc_window_unpartition": 44, "bc_add_pos": 45, "bc_add_rows": 46,
            "bc_act_rows": 47, "bc_bilinear_resize_f32": 48, "bc_sam_tokens": 49, "bc_sam_masks": 50}
+SAM_BATCH_OPS = {"bc_sam_tokens_batch": 51, "bc_mask_stats": 52}
+_OP_TABLES = (OPS, REQUEST_OPS, SAM_OPS, SAM_BATCH_OPS)
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
@@ -233,12 +243,15 @@ _KIND = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l", C.c_c
 
 def op_code(name):
     """BC_OP_* code of a recordable entry point."""
-    return OPS[name] if name in OPS else REQUEST_OPS[name] if name in REQUEST_OPS else SAM_OPS[name]
+    for table in _OP_TABLES:
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
-    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES[name])[1][:-1]
+    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES.get(name) or SAM_BATCH_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -273,7 +286,7 @@ def load():
     except OSError as e:   # pragma: no cover
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
-            list(SAM_SIGNATURES.items()):
+            list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

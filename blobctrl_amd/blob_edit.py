@@ -238,6 +238,30 @@ def ellipse_from_click(predictor, image, points, labels=None) -> Ellipse:
     return ellipse_from_mask(np.asarray(masks[0]).astype(np.uint8))
 
 
+def ellipses_from_image(generator, image, min_area: int = 0):
+    """"Segment everything": every mask of `generator.generate(image)` (a `blobctrl_amd.sam.SamAutomaticMaskGenerator`, or anything with
+    its call surface) as a blob to move, resize or remove -> [(ellipse, annotation), ...], largest area first (ties keep the generator's
+    order).  Masks of fewer than `min_area` pixels are left out, and so is a mask no ellipse can be fitted to (`fit_ellipse` refuses a hull of
+    fewer than five points and points that determine no ellipse: a speck of a few pixels, or a mask whose hull is the frame's rectangle)."""
+    anns = [a for a in generator.generate(np.asarray(image)) if a["area"] >= min_area]
+    anns.sort(key=lambda a: -a["area"])
+    out = []
+    for a in anns:
+        # `ellipse_from_mask` of the mask, from fewer points: every vertex of the hull of the set pixels is the first or the last set pixel of
+        # its row, and `convex_hull` returns the strict vertices only, so the hull - and the ellipse - of these 2 H points is the same one
+        # (hundreds of masks of 10^5 pixels each would otherwise spend seconds in the hull)
+        ind = np.asarray(a["segmentation"]) > 0
+        ys = np.nonzero(ind.any(1))[0]
+        if len(ys) == 0:
+            continue
+        first, last = ind[ys].argmax(1), ind.shape[1] - 1 - ind[ys, ::-1].argmax(1)
+        try:
+            out.append((fit_ellipse(convex_hull(np.concatenate([np.stack([first, ys], 1), np.stack([last, ys], 1)]))), a))
+        except ValueError:
+            continue
+    return out
+
+
 def blob_overlay(ellipse: Ellipse, height: int, width: int, viz_colors, device: str = "cuda:0") -> np.ndarray:
     """app:611-650 chained: ellipse -> normalised Gaussian -> the app's `splat_features(..., viz_size=(H, W), is_viz=True,
     only_vis=True)` call -> `* 255` -> uint8 [H, W, 3].  `viz_colors` [K, 3] is the caller's palette (row 0 background, row 1 the blob).

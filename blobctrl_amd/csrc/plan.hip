@@ -174,6 +174,10 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
             return bc_sam_tokens(CP(float, 0), I(1), CP(float, 2), CP(int, 3), I(4), CP(float, 5), I(6), CP(float, 7), CP(float, 8), F(9),
                                  MP(bc_half, 10), s);
         case BC_OP_SAM_MASKS: return bc_sam_masks(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), I(6), I(7), MP(float, 8), s);
+        case BC_OP_SAM_TOKENS_BATCH:
+            return bc_sam_tokens_batch(CP(float, 0), I(1), CP(float, 2), CP(int, 3), I(4), I(5), CP(float, 6), I(7), CP(float, 8), CP(float, 9),
+                                       F(10), MP(bc_half, 11), s);
+        case BC_OP_MASK_STATS: return bc_mask_stats(CP(float, 0), I(1), I(2), I(3), F(4), F(5), MP(int, 6), MP(int, 7), s);
         case BC_OP_FREEU:
             return bc_freeu(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), CP(float, 6), I(7), CP(float, 8), MP(bc_half, 9),
                             MP(bc_half, 10), MP(unsigned long long, 11), MP(unsigned long long, 12), s);

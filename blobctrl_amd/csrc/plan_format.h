@@ -26,7 +26,7 @@ const uint32_t kVersion = 8;           // 2: BcGemm grew ln_colsum / C_t, GroupN
 // file, byte for byte what the previous library wrote and still readable by it.
 const uint32_t kNoFileVersion = 0xffffffffu;     // ops that exist in-process only: bc_plan_save refuses them and no file version admits them
 inline uint32_t op_min_version(int op) {
-    if (op >= BC_OP_ATTENTION_RELPOS && op <= BC_OP_SAM_MASKS) return kNoFileVersion;      // include/blobctrl_sam.h
+    if (op >= BC_OP_ATTENTION_RELPOS && op <= BC_OP_MASK_STATS) return kNoFileVersion;      // include/blobctrl_sam.h
     if (op == BC_OP_SCHEDULER_STEP_REQUESTS || op == BC_OP_ASSEMBLE_INPUT_REQUESTS || op == BC_OP_ASSEMBLE_IM2COL_REQUESTS ||
         op == BC_OP_TIMESTEP_EMBEDDING_ROWS) return 8u;
     // (BC_OP_FREEU joined version 7 without a new version number: a reader built before it refuses the record as an unknown op code)
@@ -89,6 +89,8 @@ inline const char* op_signature(int op) {
         case BC_OP_BILINEAR_RESIZE_F32: return "piiiiiiiifp";
         case BC_OP_SAM_TOKENS: return "pippipippfp";
         case BC_OP_SAM_MASKS: return "pipiiiiip";
+        case BC_OP_SAM_TOKENS_BATCH: return "pippiipippfp";
+        case BC_OP_MASK_STATS: return "piiiffpp";
         default: return nullptr;
     }
 }

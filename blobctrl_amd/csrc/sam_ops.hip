@@ -138,6 +138,125 @@ __global__ __launch_bounds__(256) void sam_masks_kernel(const h16* __restrict__ 
     out[idx] = acc;
 }
 
+// sam_tokens_kernel with a leading prompt index: the same expressions in the same order, so prompt 0 is bit-identical to what that kernel writes
+__global__ __launch_bounds__(256) void sam_tokens_batch_kernel(const float* __restrict__ tokens, int ntok, const float* __restrict__ points,
+                                                               const int* __restrict__ labels, int npts, const float* __restrict__ gauss, int F,
+                                                               const float* __restrict__ label_embed, const float* __restrict__ not_a_point,
+                                                               float size, long long total, h16* __restrict__ out) {
+    const int Cc = 2 * F, rows = ntok + npts + 1;
+    const long long gidx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gidx >= total) return;
+    const long long b = gidx / ((long long)rows * Cc);
+    const int idx = (int)(gidx - b * rows * Cc);
+    points += b * npts * 2;
+    labels += b * npts;
+    const int r = idx / Cc, c = idx % Cc;
+    float v;
+    if (r < ntok) {
+        v = tokens[r * Cc + c];
+    } else if (r == rows - 1) {
+        v = not_a_point[c];
+    } else {
+        const int p = r - ntok, f = c < F ? c : c - F;
+        const double cx = 2.0 * (((double)points[2 * p] + 0.5) / (double)size) - 1.0, cy = 2.0 * (((double)points[2 * p + 1] + 0.5) / (double)size) - 1.0;
+        const double ang = 6.283185307179586 * (cx * (double)gauss[f] + cy * (double)gauss[F + f]);
+        const int lab = labels[p];
+        v = (float)(c < F ? sin(ang) : cos(ang)) + ((lab == 0 || lab == 1) ? label_embed[lab * Cc + c] : 0.f);
+        if (lab == -1) v = not_a_point[c];
+    }
+    out[gidx] = (h16)v;
+}
+
+// ---- bc_mask_stats: per mask, three counts and the bounding box of v > t.  All integers, so any split of a mask over workgroups and any
+// order of combining gives the same result: a workgroup reduces MS_CHUNK elements (registers -> wave shuffles -> LDS across its waves)
+// and stores seven partials; one wave per mask combines the partials in a second launch.  No atomics, nothing to zero.
+constexpr int MS_THREADS = 256, MS_CHUNK = 16384;          // elements of one mask per workgroup (a multiple of 4 * MS_THREADS)
+constexpr int MS_EMPTY_LO = 0x7fffffff, MS_EMPTY_HI = -1;
+
+struct MaskAcc {
+    int hi, lo, area, x0, y0, x1, y1;
+};
+
+__device__ __forceinline__ void ms_take(float v, int x, int y, float t_hi, float t_lo, float t, MaskAcc& a) {
+    a.hi += v > t_hi ? 1 : 0;
+    a.lo += v > t_lo ? 1 : 0;
+    if (v > t) {
+        a.area += 1;
+        a.x0 = min(a.x0, x); a.x1 = max(a.x1, x);
+        a.y0 = min(a.y0, y); a.y1 = max(a.y1, y);
+    }
+}
+
+__device__ __forceinline__ void ms_wave_reduce(MaskAcc& a) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        a.hi += __shfl_xor(a.hi, d, 64);
+        a.lo += __shfl_xor(a.lo, d, 64);
+        a.area += __shfl_xor(a.area, d, 64);
+        a.x0 = min(a.x0, __shfl_xor(a.x0, d, 64)); a.y0 = min(a.y0, __shfl_xor(a.y0, d, 64));
+        a.x1 = max(a.x1, __shfl_xor(a.x1, d, 64)); a.y1 = max(a.y1, __shfl_xor(a.y1, d, 64));
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(MS_THREADS) void mask_stats_partial_kernel(const float* __restrict__ logits, int HW, int W, float t_hi, float t_lo,
+                                                                        float t, int chunks, int* __restrict__ partial) {
+    const long long m = blockIdx.x / chunks;                            // grid = n * chunks workgroups, a mask's chunks side by side
+    const int chunk = blockIdx.x % chunks;
+    const float* src = logits + m * HW;
+    const int lo = chunk * MS_CHUNK, hi = min(HW, lo + MS_CHUNK);      // (HW <= INT_MAX - MS_CHUNK: checked by the caller)
+    MaskAcc a = {0, 0, 0, MS_EMPTY_LO, MS_EMPTY_LO, MS_EMPTY_HI, MS_EMPTY_HI};
+    if constexpr (VEC) {                                                // HW % 4 == 0 and a 16-byte aligned base: every mask starts aligned
+        for (int e = lo + 4 * (int)threadIdx.x; e < hi; e += 4 * MS_THREADS) {
+            const float4 v = *reinterpret_cast<const float4*>(src + e);
+            int y = e / W, x = e - y * W;
+            const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ms_take(vv[j], x, y, t_hi, t_lo, t, a);
+                if (++x == W) { x = 0; ++y; }
+            }
+        }
+    } else {
+        for (int e = lo + (int)threadIdx.x; e < hi; e += MS_THREADS) {
+            const int y = e / W;
+            ms_take(src[e], e - y * W, y, t_hi, t_lo, t, a);
+        }
+    }
+    ms_wave_reduce(a);
+    __shared__ int part[MS_THREADS / 64][7];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[wave][0] = a.hi; part[wave][1] = a.lo; part[wave][2] = a.area;
+        part[wave][3] = a.x0; part[wave][4] = a.y0; part[wave][5] = a.x1; part[wave][6] = a.y1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const int k = threadIdx.x;
+        int r = part[0][k];
+#pragma unroll
+        for (int w = 1; w < MS_THREADS / 64; ++w) r = k < 3 ? r + part[w][k] : k < 5 ? min(r, part[w][k]) : max(r, part[w][k]);
+        partial[(m * chunks + chunk) * 7 + k] = r;
+    }
+}
+
+__global__ __launch_bounds__(64) void mask_stats_combine_kernel(const int* __restrict__ partial, int chunks, int* __restrict__ out) {
+    const long long m = blockIdx.x;
+    MaskAcc a = {0, 0, 0, MS_EMPTY_LO, MS_EMPTY_LO, MS_EMPTY_HI, MS_EMPTY_HI};
+    for (int c = threadIdx.x; c < chunks; c += 64) {
+        const int* p = partial + (m * chunks + c) * 7;
+        a.hi += p[0]; a.lo += p[1]; a.area += p[2];
+        a.x0 = min(a.x0, p[3]); a.y0 = min(a.y0, p[4]); a.x1 = max(a.x1, p[5]); a.y1 = max(a.y1, p[6]);
+    }
+    ms_wave_reduce(a);
+    if (threadIdx.x == 0) {
+        int* o = out + m * 7;
+        const bool any = a.area > 0;                                     // an empty mask has the box 0, 0, 0, 0
+        o[0] = a.hi; o[1] = a.lo; o[2] = a.area;
+        o[3] = any ? a.x0 : 0; o[4] = any ? a.y0 : 0; o[5] = any ? a.x1 : 0; o[6] = any ? a.y1 : 0;
+    }
+}
+
 inline int blocks_for(long long total) { return (int)((total + 255) / 256); }
 
 }  // namespace
@@ -204,4 +323,40 @@ extern "C" int bc_sam_masks(const bc_half* up, int C2, const bc_half* hyper, int
     BC_CHECK_ARG(up && hyper && out && B > 0 && h > 0 && w > 0 && ntok > 0 && C2 > 0 && ldh >= C2, "bc_sam_masks: bad args");
     const long long total = (long long)B * ntok * 16 * h * w;
     SAM_LAUNCH(sam_masks_kernel, total, reinterpret_cast<const h16*>(up), C2, reinterpret_cast<const h16*>(hyper), ldh, h, w, ntok, total, out);
+}
+
+extern "C" int bc_sam_tokens_batch(const float* tokens, int ntok, const float* points, const int* labels, int B, int npts, const float* gauss,
+                                   int F, const float* label_embed, const float* not_a_point, float size, bc_half* out, bc_stream stream) {
+    BC_CHECK_ARG(tokens && points && labels && gauss && label_embed && not_a_point && out && B > 0 && ntok > 0 && npts > 0 && F > 0 && size > 0.f,
+                 "bc_sam_tokens_batch: bad args");
+    BC_CHECK_ARG((long long)(ntok + npts + 1) * 2 * F <= 0x7fffffffll, "bc_sam_tokens_batch: the rows of one prompt must fit 2^31 elements");
+    const long long total = (long long)B * (ntok + npts + 1) * 2 * F;
+    SAM_LAUNCH(sam_tokens_batch_kernel, total, tokens, ntok, points, labels, npts, gauss, F, label_embed, not_a_point, size, total,
+               reinterpret_cast<h16*>(out));
+}
+
+extern "C" int bc_mask_stats_chunks(int H, int W) {
+    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffll - MS_CHUNK) return -1;
+    return (int)(((long long)H * W + MS_CHUNK - 1) / MS_CHUNK);
+}
+
+extern "C" int bc_mask_stats(const float* logits, int n, int H, int W, float threshold, float offset, int* partial, int* out, bc_stream stream) {
+    BC_CHECK_ARG(logits && partial && out && n > 0 && H > 0 && W > 0, "bc_mask_stats: bad args");
+    const int chunks = bc_mask_stats_chunks(H, W);
+    BC_CHECK_ARG(chunks > 0, "bc_mask_stats: a mask of %d x %d does not fit 2^31 elements", H, W);
+    BC_CHECK_ARG((long long)n * chunks <= 0x7fffffffll, "bc_mask_stats: %d masks of %d chunks exceed the grid", n, chunks);
+    BC_CHECK_ARG(offset >= 0.f && threshold == threshold && offset == offset, "bc_mask_stats: the offset must be >= 0 and no NaN");
+    // the two outer thresholds are the fp32 roundings of the sums: what comparing an fp32 tensor with the scalar t +- o does
+    const float t_hi = (float)((double)threshold + (double)offset), t_lo = (float)((double)threshold - (double)offset);
+    const int HW = H * W;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool vec = HW % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(mask_stats_partial_kernel<true>, dim3(n * chunks), dim3(MS_THREADS), 0, s, logits, HW, W, t_hi, t_lo, threshold, chunks, partial);
+    else
+        hipLaunchKernelGGL(mask_stats_partial_kernel<false>, dim3(n * chunks), dim3(MS_THREADS), 0, s, logits, HW, W, t_hi, t_lo, threshold, chunks, partial);
+    BC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mask_stats_combine_kernel, dim3(n), dim3(64), 0, s, partial, chunks, out);
+    BC_CHECK_LAUNCH();
+    return 0;
 }

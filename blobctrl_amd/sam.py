@@ -12,7 +12,13 @@
                    stride-2 transposed convolutions as GEMMs whose sub-pixels stay rows, the hypernetwork MLPs, the IoU head, and
                    bc_sam_masks (hypernetwork product + pixel shuffle).  Then two bc_bilinear_resize_f32 launches.
 
-`SamPredictor.set_image` runs the encoder once; every `predict` on that image costs the decoder only.
+  batched prompts  `decode_batch` / `SamPredictor.predict_torch`: the decoder's launches over [Bp] prompt sets in one graph replay; what does not
+                   depend on the prompt (layer 0's image side) exists once and is read with a batch stride of 0.
+  segment all      `SamAutomaticMaskGenerator.generate`: a grid of single-point prompts through `predict_torch` in batches, one
+                   bc_mask_stats pass over the full-size logits (the stability counts, the area and the box of every mask), the two
+                   filters on the device, box NMS on the host, and only the surviving masks cross to the host.
+
+`SamPredictor.set_image` runs the encoder once; every `predict` / `predict_torch` on that image costs the decoder only.
 """
 import math
 import re
@@ -512,6 +518,155 @@ class SamModel:
         sel = slice(None) if multimask_output is None else slice(1, None) if multimask_output else slice(0, 1)
         return P.masks[0, sel].clone(), P.iou[0, sel].clone()
 
+    # ------------------------------------------------------------------------------------------------ batched prompts
+    def _attn_batch(self, rec, name, Bp, xq, nq, q_shared, xk, xv, nk, kv_shared, R=None):
+        """`_attn` over Bp prompts: xq [Bp][nq][C], xk / xv [Bp][nk][C] -> [Bp][nq][C].  A side that is the same for every prompt
+        (`q_shared` / `kv_shared`: [nq][C] / [nk][C]) is projected once and the attention reads it with a batch stride of 0."""
+        hw, fw, C, heads = self.h, self.f, self.C, self.config.decoder_heads
+        inner = hw[name + "q_proj.weight"].shape[0]
+        d = inner // heads
+        Bq, Bk = 1 if q_shared else Bp, 1 if kv_shared else Bp
+        q, k = rec.empty(Bq * nq, inner), rec.empty(Bk * nk, inner)
+        rec.gemm(A=xq, W=hw[name + "q_proj.weight"], M=Bq * nq, N=inner, K=C, out=q, bias=fw[name + "q_proj.bias"], kind="dec_qkv")
+        rec.gemm(A=xk, W=hw[name + "k_proj.weight"], M=Bk * nk, N=inner, K=C, out=k, bias=fw[name + "k_proj.bias"], kind="dec_qkv")
+        ldvt = (nk + 63) // 64 * 64
+        vt = rec.zeros(Bk, inner, ldvt)
+        rec.gemm(A=xv, W=hw[name + "v_proj.weight"], M=Bk * nk, N=inner, K=C, out=vt, bias=fw[name + "v_proj.bias"], out_mode=_lib.OUT_F16_T,
+                 ldc=ldvt, rows_per_batch=nk, kind="dec_qkv")
+        a = rec.empty(Bp * nq, inner)
+        rec.attention(q, k, vt, a, Bp, heads, d, nq, nk, inner, inner, ldvt, inner, 0 if q_shared else nq * inner, 0 if kv_shared else nk * inner,
+                      0 if kv_shared else inner * ldvt, nq * inner, d ** -0.5)
+        out = rec.empty(Bp * nq, C)
+        kw = dict(R=R, ldr=C) if R is not None else {}
+        rec.gemm(A=a, W=hw[name + "out_proj.weight"], M=Bp * nq, N=C, K=inner, out=out, bias=fw[name + "out_proj.bias"], kind="dec_out", **kw)
+        return out
+
+    def _mlp3_batch(self, rec, name, Bp, x, x_off, ldx, out, out_off, ldo, n_out, out_mode=_lib.OUT_F16):
+        """`_mlp3` on the same token row of Bp prompts: rows x[b * ldx + x_off ...] -> out[b * ldo + out_off ...]."""
+        hw, fw = self.h, self.f
+        Hd = hw[name + "proj_in.weight"].shape[0]
+        Hp = pad8(Hd)
+        t1, t2 = rec.zeros(Bp, Hp), rec.zeros(Bp, Hp)
+        rec.gemm(A=x, a_offset=x_off, lda=ldx, W=hw[name + "proj_in.weight"], M=Bp, N=Hd, K=self.C, out=t1, ldc=Hp, bias=fw[name + "proj_in.bias"],
+                 kind="dec_mlp")
+        rec.call("bc_act_rows", t1, Bp * Hp, 1, kind="relu", keep=t1)
+        rec.gemm(A=t1, W=hw[name + "layers.0.weight"], M=Bp, N=Hd, K=Hp, out=t2, ldc=Hp, bias=fw[name + "layers.0.bias"], kind="dec_mlp")
+        rec.call("bc_act_rows", t2, Bp * Hp, 1, kind="relu", keep=t2)
+        rec.gemm(A=t2, W=hw[name + "proj_out.weight"], M=Bp, N=n_out, K=Hp, out=out, out_offset=out_off, ldc=ldo, out_mode=out_mode,
+                 bias=fw[name + "proj_out.bias"], kind="dec_mlp")
+
+    def _decoder_plan_batch(self, Bp, npts):
+        """`_decoder_plan` for Bp prompt sets of npts points on the one image of the last `encode`: the same launches in the same order over
+        [Bp][nq][C] token rows and, from the first cross_attn_image_to_token on, [Bp][T][C] image rows.  Until then the image side is the
+        same for every prompt - embedding + no_mask, + image_pe, layer 0's K / V (and the image-to-token Q) projections - and exists once."""
+        self._need_gpu()
+        key = ("dec_batch", Bp, npts)
+        if key in self._plans:
+            return self._plans[key]
+        if self.dec_layers < 1:
+            raise ValueError("SamModel: the batched decoder needs at least one two-way transformer layer")
+        rec = Recorder(self.device)
+        P = type("Plan", (), {})()
+        P.rec = rec
+        cfg, hw, fw = self.config, self.h, self.f
+        C, g_, ntok = self.C, self.grid, self.ntok
+        T, nq, eps = g_ * g_, ntok + npts + 1, cfg.decoder_layer_norm_eps
+        P.points = rec.zeros(Bp, npts, 2, dtype=torch.float32)
+        P.labels = rec.zeros(Bp, npts, dtype=torch.int32)
+        P.seg = rec.begin("sam_decoder_batch")
+        qpe = rec.empty(Bp * nq, C)
+        rec.call("bc_sam_tokens_batch", fw["tokens"], ntok, P.points, P.labels, Bp, npts, fw["gauss"], self.F, fw["label_embed"], fw["not_a_point"],
+                 float(self.image_size), qpe, kind="sam_tokens", keep=(fw["tokens"], fw["gauss"], fw["label_embed"], fw["not_a_point"], qpe))
+        kpe = hw["image_pe"]
+        keys, shared = self._add(rec, self._emb16, hw["no_mask"], T, 1), True    # [T][C] while `shared`, [Bp][T][C] afterwards
+        queries = qpe
+        for i in range(self.dec_layers):
+            p = f"transformer.layers.{i}."
+            if i == 0:
+                queries = self._attn_batch(rec, p + "self_attn.", Bp, queries, nq, False, queries, queries, nq, False)
+            else:
+                qq = self._add(rec, queries, qpe, Bp * nq)
+                queries = self._attn_batch(rec, p + "self_attn.", Bp, qq, nq, False, qq, queries, nq, False, R=queries)
+            queries = rec.layernorm(queries, Bp * nq, C, fw[p + "layer_norm1.weight"], fw[p + "layer_norm1.bias"], eps)
+            krows = T if shared else Bp * T
+            qq, kk = self._add(rec, queries, qpe, Bp * nq), self._add(rec, keys, kpe, krows, T)
+            queries = self._attn_batch(rec, p + "cross_attn_token_to_image.", Bp, qq, nq, False, kk, keys, T, shared, R=queries)
+            queries = rec.layernorm(queries, Bp * nq, C, fw[p + "layer_norm2.weight"], fw[p + "layer_norm2.bias"], eps)
+            Fm = hw[p + "mlp.lin1.weight"].shape[0]
+            m1 = rec.empty(Bp * nq, Fm)
+            rec.gemm(A=queries, W=hw[p + "mlp.lin1.weight"], M=Bp * nq, N=Fm, K=C, out=m1, bias=fw[p + "mlp.lin1.bias"], kind="dec_mlp")
+            rec.call("bc_act_rows", m1, Bp * nq * Fm, 1, kind="relu", keep=m1)
+            m2 = rec.empty(Bp * nq, C)
+            rec.gemm(A=m1, W=hw[p + "mlp.lin2.weight"], M=Bp * nq, N=C, K=Fm, out=m2, bias=fw[p + "mlp.lin2.bias"], R=queries, ldr=C, kind="dec_mlp")
+            queries = rec.layernorm(m2, Bp * nq, C, fw[p + "layer_norm3.weight"], fw[p + "layer_norm3.bias"], eps)
+            qq = self._add(rec, queries, qpe, Bp * nq)
+            if shared:
+                # the residual is the one shared [T][C] block under Bp blocks of output rows: a GEMM epilogue reads R row for row, so the add
+                # is its own launch here (one more fp16 rounding than the single-prompt plan's fused residual, in this layer only)
+                k2 = self._attn_batch(rec, p + "cross_attn_image_to_token.", Bp, kk, T, True, qq, queries, nq, False)
+                k2 = self._add(rec, k2, keys, Bp * T, T)
+            else:
+                k2 = self._attn_batch(rec, p + "cross_attn_image_to_token.", Bp, kk, T, False, qq, queries, nq, False, R=keys)
+            keys, shared = rec.layernorm(k2, Bp * T, C, fw[p + "layer_norm4.weight"], fw[p + "layer_norm4.bias"], eps), False
+        qq, kk = self._add(rec, queries, qpe, Bp * nq), self._add(rec, keys, kpe, Bp * T, T)
+        queries = self._attn_batch(rec, "transformer.final_attn_token_to_image.", Bp, qq, nq, False, kk, keys, T, False, R=queries)
+        queries = rec.layernorm(queries, Bp * nq, C, fw["transformer.layer_norm_final_attn.weight"], fw["transformer.layer_norm_final_attn.bias"], 1e-5)
+        C1, C2 = C // 4, C // 8
+        u1 = rec.empty(Bp * T, 4 * C1)
+        rec.gemm(A=keys, W=hw["upscale_conv1.weight"], M=Bp * T, N=4 * C1, K=C, out=u1, bias=fw["upscale_conv1.bias"], kind="upscale")
+        l1 = rec.layernorm(u1, 4 * Bp * T, C1, fw["upscale_layer_norm.weight"], fw["upscale_layer_norm.bias"], 1e-6)
+        rec.call("bc_act_rows", l1, 4 * Bp * T * C1, 0, kind="gelu", keep=l1)
+        u2 = rec.empty(4 * Bp * T, 4 * C2)
+        rec.gemm(A=l1, W=hw["upscale_conv2.weight"], M=4 * Bp * T, N=4 * C2, K=C1, out=u2, bias=fw["upscale_conv2.bias"], act=_lib.ACT_GELU,
+                 kind="upscale")
+        ldh = pad8(C2)
+        hyper = rec.zeros(Bp, ntok - 1, ldh)
+        for t in range(ntok - 1):
+            self._mlp3_batch(rec, f"output_hypernetworks_mlps.{t}.", Bp, queries, (1 + t) * C, nq * C, hyper, t * ldh, (ntok - 1) * ldh, C2)
+        P.iou = rec.zeros(Bp, ntok - 1, dtype=torch.float32)
+        self._mlp3_batch(rec, "iou_prediction_head.", Bp, queries, 0, nq * C, P.iou, 0, ntok - 1, ntok - 1, out_mode=_lib.OUT_F32)
+        P.masks = rec.empty(Bp, ntok - 1, 4 * g_, 4 * g_, dtype=torch.float32)
+        rec.call("bc_sam_masks", u2, C2, hyper, ldh, Bp, g_, g_, ntok - 1, P.masks, kind="sam_masks", keep=(u2, hyper, P.masks))
+        self._plans[key] = P
+        self.plans_recorded += 1
+        return P
+
+    @torch.no_grad()
+    def decode_batch(self, points, labels, multimask_output=True):
+        """Bp prompt sets at once on the image of the last `encode`: points [Bp][npts][2] (input frame), labels [Bp][npts] - device tensors or
+        anything `torch.as_tensor` takes - -> (low-res logits [Bp][n][4 grid][4 grid], IoU scores [Bp][n]) fp32 on the device, n as in
+        `decode`.  One graph replay per call; a plan per (Bp, npts) is recorded on first use and kept."""
+        pts = torch.as_tensor(points, dtype=torch.float32) if not torch.is_tensor(points) else points.to(torch.float32)
+        lab = torch.as_tensor(labels) if not torch.is_tensor(labels) else labels
+        if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] == 0 or pts.shape[1] == 0 or tuple(lab.shape) != tuple(pts.shape[:2]):
+            raise ValueError("decode_batch needs points [Bp][npts][2] and labels [Bp][npts] with Bp, npts >= 1")
+        P = self._decoder_plan_batch(pts.shape[0], pts.shape[1])
+        P.points.copy_(pts.to(self.device))
+        P.labels.copy_(lab.to(self.device, torch.int32))
+        run_graphed(P.seg, self.device)
+        sel = slice(None) if multimask_output is None else slice(1, None) if multimask_output else slice(0, 1)
+        return P.masks[:, sel].clone(), P.iou[:, sel].clone()
+
+    @torch.no_grad()
+    def mask_stats(self, logits, threshold=0.0, offset=1.0):
+        """bc_mask_stats (include/blobctrl_sam.h): logits fp32 [n][H][W] on the device -> int32 [n][7] = count(v > t + o), count(v > t - o),
+        count(v > t), and the inclusive box x0, y0, x1, y1 of v > t (zeros for an empty mask)."""
+        self._need_gpu()
+        lib = _lib.load()
+        if logits.ndim != 3 or logits.shape[0] == 0:
+            raise ValueError("mask_stats takes logits [n][H][W] with n >= 1")
+        src = logits.to(self.device, torch.float32).contiguous()
+        n, H, W = src.shape
+        chunks = lib.bc_mask_stats_chunks(H, W)
+        if chunks <= 0:
+            raise ValueError(f"mask_stats: a mask of {H} x {W} is too large")
+        partial = torch.empty(n, chunks, 7, dtype=torch.int32, device=self.device)
+        out = torch.empty(n, 7, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(lib.bc_mask_stats(src.data_ptr(), n, H, W, float(threshold), float(offset), partial.data_ptr(), out.data_ptr(), stream),
+                   "bc_mask_stats")
+        return out
+
     @torch.no_grad()
     def postprocess(self, low_res, input_size, original_size, return_logits=False, threshold=0.0):
         """low-res logits [n][h][w] -> the padded frame (bilinear) -> crop the unpadded region -> the original size; bool unless
@@ -529,11 +684,34 @@ class SamModel:
         return out if return_logits else out.bool()
 
 
+class ResizeLongestSide:
+    """`segment_anything.utils.transforms.ResizeLongestSide` for coordinates: plain scaling by new / old of `preprocess_shape`."""
+
+    def __init__(self, target_length: int):
+        self.target_length = int(target_length)
+
+    @staticmethod
+    def get_preprocess_shape(oldh: int, oldw: int, long_side_length: int):
+        return preprocess_shape(oldh, oldw, long_side_length)
+
+    def apply_coords(self, coords, original_size) -> np.ndarray:
+        """(x, y) in the original image [...][2] -> the resized frame, fp32 (the arithmetic of `scale_points`)."""
+        c = np.asarray(coords)
+        return scale_points(c, original_size, self.target_length).reshape(c.shape)
+
+    def apply_coords_torch(self, coords: torch.Tensor, original_size) -> torch.Tensor:
+        oh, ow = original_size
+        nh, nw = preprocess_shape(oh, ow, self.target_length)
+        scale = torch.tensor([nw / ow, nh / oh], dtype=torch.float64, device=coords.device)
+        return (coords.to(torch.float64) * scale).to(torch.float32)
+
+
 class SamPredictor:
-    """The `segment_anything.SamPredictor` calls the reference app makes, on a `SamModel`."""
+    """The `segment_anything.SamPredictor` surface on a `SamModel`: `predict` (the call the reference app makes) and `predict_torch`."""
 
     def __init__(self, model: SamModel):
         self.model = model
+        self.transform = ResizeLongestSide(model.image_size)
         self.reset_image()
 
     def reset_image(self):
@@ -570,3 +748,142 @@ class SamPredictor:
         low, iou = self.model.decode(pts, point_labels, multimask_output)
         masks = self.model.postprocess(low, self.input_size, self.original_size, return_logits=return_logits)
         return masks.cpu().numpy(), iou.cpu().numpy(), low.cpu().numpy()
+
+    @torch.no_grad()
+    def predict_torch(self, point_coords, point_labels, boxes=None, mask_input=None, multimask_output=True, return_logits=False):
+        """B prompts at once, device tensors in and out: point_coords [B][N][2] ALREADY in the input frame (`transform.apply_coords_torch`),
+        point_labels [B][N] -> (masks [B][C][H][W] bool - fp32 logits with return_logits -, IoU [B][C], low-res logits [B][C][4 g][4 g])."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        if boxes is not None:
+            raise NotImplementedError("SamPredictor.predict_torch: box prompts are not implemented (points only)")
+        if mask_input is not None:
+            raise NotImplementedError("SamPredictor.predict_torch: mask_input prompts are not implemented (points only)")
+        if point_coords is None or point_labels is None:
+            raise ValueError("SamPredictor.predict_torch needs point_coords and point_labels")
+        if getattr(self.model, "_emb_owner", None) != id(self):
+            raise RuntimeError("another SamPredictor has set an image on this model since: call set_image again")
+        return self._predict_batch(point_coords, point_labels, multimask_output, return_logits)
+
+    def _predict_batch(self, point_coords, point_labels, multimask_output, return_logits, mark=None):
+        """The device work of `predict_torch`; `mark()` is called between the decoder replay and the resizes (the generator's timing)."""
+        low, iou = self.model.decode_batch(point_coords, point_labels, multimask_output)
+        if mark is not None:
+            mark()
+        B, n = iou.shape
+        masks = self.model.postprocess(low.flatten(0, 1), self.input_size, self.original_size, return_logits=return_logits)
+        return masks.view(B, n, *masks.shape[1:]), iou, low
+
+
+def box_nms(boxes_xyxy, scores, iou_threshold: float) -> np.ndarray:
+    """torchvision.ops.nms on the host: indices of the kept boxes, by descending score (ties: the lower index first).  Area is
+    (x2 - x1)(y2 - y1) without + 1; a box is suppressed when its IoU with a kept, better box is > iou_threshold; a NaN IoU (two boxes of zero
+    area) suppresses nothing."""
+    b = np.asarray(boxes_xyxy, dtype=np.float32).reshape(-1, 4)
+    sc = np.asarray(scores, dtype=np.float32).reshape(-1)
+    if len(b) != len(sc):
+        raise ValueError("box_nms needs one score per box")
+    order = np.argsort(-sc, kind="stable")
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    dead = np.zeros(len(b), dtype=bool)
+    keep = []
+    for pos, i in enumerate(order):
+        if dead[i]:
+            continue
+        keep.append(int(i))
+        rest = order[pos + 1:]
+        w = np.clip(np.minimum(b[i, 2], b[rest, 2]) - np.maximum(b[i, 0], b[rest, 0]), 0, None)
+        h = np.clip(np.minimum(b[i, 3], b[rest, 3]) - np.maximum(b[i, 1], b[rest, 1]), 0, None)
+        inter = w * h
+        with np.errstate(invalid="ignore", divide="ignore"):
+            iou = inter / (area[i] + area[rest] - inter)
+        dead[rest[iou > iou_threshold]] = True                      # (NaN > x is False)
+    return np.asarray(keep, dtype=np.int64)
+
+
+def build_point_grid(n_per_side: int) -> np.ndarray:
+    """`segment_anything.utils.amg.build_point_grid`: n x n points in [0, 1]^2 at offset 1 / (2 n), x fastest, float64 [n * n][2]."""
+    offset = 1 / (2 * n_per_side)
+    side = np.linspace(offset, 1 - offset, n_per_side)
+    return np.stack([np.tile(side[None, :], (n_per_side, 1)), np.tile(side[:, None], (1, n_per_side))], -1).reshape(-1, 2)
+
+
+class SamAutomaticMaskGenerator:
+    """`segment_anything.SamAutomaticMaskGenerator` on a `SamModel`, whole-image crop only: a grid of single-point prompts through the
+    batched decoder, the predicted-IoU and stability filters from one bc_mask_stats pass over the full-size logits, box NMS on the host."""
+
+    def __init__(self, model: SamModel, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.88, stability_score_thresh=0.95,
+                 stability_score_offset=1.0, box_nms_thresh=0.7, crop_n_layers=0, crop_nms_thresh=0.7, crop_overlap_ratio=512 / 1500,
+                 crop_n_points_downscale_factor=1, point_grids=None, min_mask_region_area=0, output_mode="binary_mask"):
+        if (points_per_side is None) == (point_grids is None):
+            raise ValueError("Exactly one of points_per_side or point_grid must be provided.")
+        if crop_n_layers > 0:
+            raise NotImplementedError("SamAutomaticMaskGenerator: crop_n_layers > 0 is not implemented (the whole-image crop only)")
+        if min_mask_region_area > 0:
+            raise NotImplementedError("SamAutomaticMaskGenerator: min_mask_region_area > 0 is not implemented (needs connected components)")
+        if output_mode != "binary_mask":
+            raise NotImplementedError(f"SamAutomaticMaskGenerator: output_mode {output_mode!r} is not implemented ('binary_mask' only)")
+        if points_per_batch < 1:
+            raise ValueError("points_per_batch must be >= 1")
+        self.point_grids = [build_point_grid(points_per_side)] if point_grids is None else [np.asarray(g_, dtype=np.float64) for g_ in point_grids]
+        self.predictor = SamPredictor(model)
+        self.points_per_batch = int(points_per_batch)
+        self.pred_iou_thresh, self.stability_score_thresh = pred_iou_thresh, stability_score_thresh
+        self.stability_score_offset, self.box_nms_thresh = stability_score_offset, box_nms_thresh
+        self.mask_threshold = 0.0
+        self.crop_n_layers, self.crop_nms_thresh, self.crop_overlap_ratio = crop_n_layers, crop_nms_thresh, crop_overlap_ratio
+        self.crop_n_points_downscale_factor, self.min_mask_region_area, self.output_mode = crop_n_points_downscale_factor, min_mask_region_area, output_mode
+        self.last_timing = {}
+
+    @torch.no_grad()
+    def generate(self, image):
+        """image uint8 [H][W][3] -> a list of dicts (segmentation, area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box) in NMS
+        order, i.e. by descending predicted IoU.  A ragged last batch runs a decoder plan of its own size (recorded once, like the full one).
+        `last_timing` holds HIP-event milliseconds of the call's phases (decode, resize, stats) and the host time around them."""
+        import time
+        pred, model, dev = self.predictor, self.predictor.model, self.predictor.model.device
+        t_start = time.perf_counter()
+        pred.set_image(image)
+        torch.cuda.synchronize(dev)
+        t_set = time.perf_counter()
+        H, W = pred.original_size
+        grid = self.point_grids[0] * np.array([[W, H]], dtype=np.float64)               # (x, y) in the original image
+        pts_in = torch.from_numpy(pred.transform.apply_coords(grid, pred.original_size)).to(dev)
+        ev = lambda: torch.cuda.Event(enable_timing=True)
+        marks, kept = [], []
+        for lo in range(0, len(grid), self.points_per_batch):
+            hi = min(len(grid), lo + self.points_per_batch)
+            e = [ev() for _ in range(4)]
+            e[0].record()
+            logits, iou, _ = pred._predict_batch(pts_in[lo:hi, None, :], torch.ones(hi - lo, 1, dtype=torch.int32, device=dev), True, True,
+                                                 mark=e[1].record)
+            e[2].record()
+            logits, iou = logits.flatten(0, 1), iou.flatten()
+            # one pass over every mask of the batch (the statistics of a mask do not depend on the others), then both filters on the small
+            # arrays: the same kept set as filtering by predicted IoU first, without gathering the logits in between
+            stats = model.mask_stats(logits, self.mask_threshold, self.stability_score_offset)
+            stability = stats[:, 0].to(torch.float32) / stats[:, 1].to(torch.float32)       # (0 / 0 is NaN and fails the test below)
+            sel = torch.nonzero((iou > self.pred_iou_thresh) & (stability >= self.stability_score_thresh)).flatten()
+            if sel.numel():
+                point = torch.arange(lo, hi, device=dev).repeat_interleave(iou.numel() // (hi - lo))
+                kept.append((logits[sel] > self.mask_threshold, iou[sel], point[sel], stats[sel], stability[sel]))
+            e[3].record()
+            marks.append(e)
+        torch.cuda.synchronize(dev)
+        out = []
+        if kept:
+            # the NMS needs boxes and scores only: the masks stay on the device until it has chosen
+            masks = torch.cat([k[0] for k in kept])
+            iou, point, stats, stability = (torch.cat([k[j] for k in kept]).cpu().numpy() for j in range(1, 5))
+            order = box_nms(stats[:, 3:7], iou, self.box_nms_thresh)
+            masks = masks[torch.from_numpy(order).to(dev)].cpu().numpy()
+            for m, i in zip(masks, order):
+                x0, y0, x1, y1 = (int(v) for v in stats[i, 3:7])
+                out.append({"segmentation": m, "area": int(stats[i, 2]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(iou[i]),
+                            "point_coords": [[float(grid[point[i], 0]), float(grid[point[i], 1])]], "stability_score": float(stability[i]),
+                            "crop_box": [0, 0, W, H]})
+        t_end = time.perf_counter()
+        gpu = [sum(e[j].elapsed_time(e[j + 1]) for e in marks) for j in range(3)]
+        self.last_timing = {"set_image_ms": 1e3 * (t_set - t_start), "decode_ms": gpu[0], "resize_ms": gpu[1], "stats_ms": gpu[2],
+                            "host_ms": 1e3 * (t_end - t_set) - sum(gpu), "generate_ms": 1e3 * (t_end - t_start), "masks": len(out)}
+        return out

@@ -553,7 +553,8 @@ enum { BC_OP_GEMM = 0, BC_OP_GN_STATS = 1, BC_OP_GN_FINALIZE = 2, BC_OP_GN_APPLY
        BC_OP_ASSEMBLE_IM2COL_REQUESTS = 40, BC_OP_TIMESTEP_EMBEDDING_ROWS = 41,
        /* the entry points of include/blobctrl_sam.h (recorded and replayed in-process only, never written to a plan file) */
        BC_OP_ATTENTION_RELPOS = 42, BC_OP_WINDOW_PARTITION = 43, BC_OP_WINDOW_UNPARTITION = 44, BC_OP_ADD_POS = 45, BC_OP_ADD_ROWS = 46,
-       BC_OP_ACT_ROWS = 47, BC_OP_BILINEAR_RESIZE_F32 = 48, BC_OP_SAM_TOKENS = 49, BC_OP_SAM_MASKS = 50, BC_OP_COUNT = 51 };
+       BC_OP_ACT_ROWS = 47, BC_OP_BILINEAR_RESIZE_F32 = 48, BC_OP_SAM_TOKENS = 49, BC_OP_SAM_MASKS = 50,
+       BC_OP_SAM_TOKENS_BATCH = 51, BC_OP_MASK_STATS = 52, BC_OP_COUNT = 53 };
 typedef struct BcPlanBuffer {
     const char* name;        /* "" for anonymous workspace; named buffers are found again with bc_plan_buffer */
     const void* address;     /* the address the launch records were built against */

@@ -1,6 +1,6 @@
 /* Entry points of the Segment-Anything path (blobctrl_amd/sam.py): SAM's attention form - windowed attention over zero-padded windows
  * with the decomposed relative-position bias - and the small launches around it that no entry point of include/blobctrl_hip.h
- * expresses.  A header of its own beside that one; all of them are recordable plan ops (BC_OP_ATTENTION_RELPOS .. BC_OP_SAM_MASKS in the
+ * expresses.  A header of its own beside that one; all launches are recordable plan ops (BC_OP_ATTENTION_RELPOS .. BC_OP_MASK_STATS in the
  * BC_OP_* table there).  SAM segments are recorded and replayed in-process only: these ops are never written to a .bcplan file.
  * Conventions as in blobctrl_hip.h: fp16 activations, fp32 accumulation, all work on the caller's stream, 0 on success. */
 #ifndef BLOBCTRL_SAM_H
@@ -53,6 +53,21 @@ int bc_sam_tokens(const float* tokens, int ntok, const float* points, const int*
  * dy2 * 2 + dx2: the two 2x2 stride-2 transposed convolutions run as GEMMs whose sub-pixels stay rows), hyper fp16 [B][ntok][ldh]
  * -> out fp32 [B][ntok][4 h][4 w], out[b][t][4 y + 2 dy + dy2][4 x + 2 dx + dx2] = sum_c hyper[b][t][c] * up[row][c]. */
 int bc_sam_masks(const bc_half* up, int C2, const bc_half* hyper, int ldh, int B, int h, int w, int ntok, float* out, bc_stream stream);
+
+/* ---- batched prompts and automatic mask generation (BC_OP_SAM_TOKENS_BATCH, BC_OP_MASK_STATS; in-process only like the ops above) ---- */
+
+/* bc_sam_tokens for B prompt sets at once: points fp32 [B][npts][2], labels int32 [B][npts] -> out fp16 [B][ntok + npts + 1][C].  The
+ * arithmetic per row is that of bc_sam_tokens; prompt 0 is bit-identical to what bc_sam_tokens writes for the same points. */
+int bc_sam_tokens_batch(const float* tokens, int ntok, const float* points, const int* labels, int B, int npts, const float* gauss, int F,
+                        const float* label_embed, const float* not_a_point, float size, bc_half* out, bc_stream stream);
+
+/* What SamAutomaticMaskGenerator needs of a mask's logits, in one pass over them: logits fp32 [n][H][W] -> out int32 [n][7] =
+ *   count(v > t + o), count(v > t - o), count(v > t), then the inclusive bounding box x0, y0, x1, y1 of v > t (0, 0, 0, 0 when empty).
+ * The comparisons are strict and in fp32 against t, fl32(t + o) and fl32(t - o), so the counts are exact and the result does not depend on
+ * how the launch splits a mask.  H, W arbitrary with H * W < 2^31 - 2^14; partial = int32 scratch [n][bc_mask_stats_chunks(H, W)][7]
+ * (written, then read by the combining launch; no zeroing needed). */
+int bc_mask_stats_chunks(int H, int W);                       /* workgroups per mask; -1 if the mask is too large */
+int bc_mask_stats(const float* logits, int n, int H, int W, float threshold, float offset, int* partial, int* out, bc_stream stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@ DIR/blobnet, DIR/unet_lora, DIR/dinov2-large); without it, seeded synthetic weig
 checkpoints exist offline), which exercises every kernel and prints per-stage timings but produces noise, not a picture.
 With --sam DIR_OR_PTH --click X,Y the edit starts where the app's does: Segment-Anything turns the click on the foreground image into a
 mask and the mask into the blob's ellipse (DIR = a transformers directory, PTH = the original sam_vit_h_4b8939.pth, "synth" = seeded
-synthetic ViT-H weights)."""
+synthetic ViT-H weights).  With --sam ... --sam-auto K there is no click: SamAutomaticMaskGenerator segments everything in the image and
+the K-th largest mask gives the blob."""
 import argparse
 import os
 import sys
@@ -28,9 +29,13 @@ def main():
     ap.add_argument("--out", default=None, help="write the edited image as a .npy [H,W,3] float array")
     ap.add_argument("--sam", default=None, help="SAM weights: a transformers directory, the original .pth, or 'synth'")
     ap.add_argument("--click", default=None, help="X,Y pixel of the click on the foreground image (with --sam)")
+    ap.add_argument("--sam-auto", type=int, default=None, metavar="K",
+                    help="take the blob from the K-th largest mask of SamAutomaticMaskGenerator instead of a click (with --sam)")
     args = ap.parse_args()
-    if args.click and not args.sam:
-        ap.error("--click needs --sam")
+    if (args.click or args.sam_auto is not None) and not args.sam:
+        ap.error("--click / --sam-auto need --sam")
+    if args.click and args.sam_auto is not None:
+        ap.error("--click and --sam-auto exclude each other")
     import bench
     from blobctrl_amd import synth
     from blobctrl_amd.clip_text import CLIPTextModel
@@ -76,15 +81,29 @@ def main():
             sam = SamModel(sd)
         else:
             sam = SamModel.from_pretrained(args.sam) if os.path.isdir(args.sam) else SamModel.from_checkpoint(args.sam)
-        click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
         image = ((fg[0].permute(1, 2, 0).numpy() + 1) * 127.5).round().clip(0, 255).astype(np.uint8)
-        ts = sync()
-        predictor = SamPredictor(sam)
-        e = ellipse_from_click(predictor, image, [click])
-        te = sync()
-        e2 = ellipse_from_click(predictor, None, [click])
-        print(f"SAM click {click} -> ellipse {e} in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); "
-              f"second click {1e3 * (sync() - te):.1f} ms, same ellipse: {e2 == e}")
+        if args.sam_auto is not None:
+            from blobctrl_amd.blob_edit import ellipses_from_image
+            from blobctrl_amd.sam import SamAutomaticMaskGenerator
+            # (seeded synthetic weights predict IoUs and stabilities far below the package's thresholds and masks that all span the frame:
+            # keep every mask of a coarser grid then, or nothing would be left to choose from)
+            kw = dict(points_per_side=8, pred_iou_thresh=-1e9, stability_score_thresh=0.0, box_nms_thresh=1.0) if args.sam == "synth" else {}
+            ts = sync()
+            blobs = ellipses_from_image(SamAutomaticMaskGenerator(sam, **kw), image)
+            if not 0 <= args.sam_auto < len(blobs):
+                raise SystemExit(f"--sam-auto {args.sam_auto}: the generator found {len(blobs)} masks")
+            e, ann = blobs[args.sam_auto]
+            print(f"SAM segment-everything: {len(blobs)} masks in {1e3 * (sync() - ts):.1f} ms (first call: planning + graph capture); mask "
+                  f"{args.sam_auto}: area {ann['area']}, bbox {ann['bbox']}, predicted IoU {ann['predicted_iou']:.3f} -> ellipse {e}")
+        else:
+            click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
+            ts = sync()
+            predictor = SamPredictor(sam)
+            e = ellipse_from_click(predictor, image, [click])
+            te = sync()
+            e2 = ellipse_from_click(predictor, None, [click])
+            print(f"SAM click {click} -> ellipse {e} in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); "
+                  f"second click {1e3 * (sync() - te):.1f} ms, same ellipse: {e2 == e}")
         ellipse = [list(e[0]), list(e[1]), e[2]]
     score = splat_features(**blob_dict_from_ellipse(ellipse, R, R), score_size=(R // 8, R // 8), return_d_score=True)
     t2 = sync()

@@ -1508,27 +1508,31 @@ def golden_dinov2():
     print("dinov2: pooled std %.4f" % out["native_pooled"].std())
 
 
+def _hf_sam_model(cfg, sd):
+    """transformers' SamModel for one of the tiny configurations of tests/sam_common.py, holding the synth weights `sd`."""
+    from transformers import SamConfig, SamMaskDecoderConfig, SamModel, SamPromptEncoderConfig, SamVisionConfig
+    from tests import sam_common as sc
+    C = cfg["out_channels"]
+    vc = SamVisionConfig(hidden_size=cfg["hidden"], output_channels=C, num_hidden_layers=cfg["layers"], num_attention_heads=cfg["heads"],
+                         image_size=cfg["image"], patch_size=cfg["patch"], window_size=cfg["window"],
+                         global_attn_indexes=list(cfg["global_attn_indexes"]), mlp_dim=cfg["mlp_dim"], num_pos_feats=C // 2)
+    pc = SamPromptEncoderConfig(hidden_size=C, image_size=cfg["image"], patch_size=cfg["patch"], mask_input_channels=16)
+    mc = SamMaskDecoderConfig(hidden_size=C, num_hidden_layers=cfg["decoder_layers"], num_attention_heads=sc.DECODER_HEADS,
+                              mlp_dim=cfg["decoder_mlp_dim"], iou_head_hidden_dim=cfg["iou_head_hidden_dim"])
+    model = SamModel(SamConfig(vision_config=vc, prompt_encoder_config=pc, mask_decoder_config=mc)).eval()
+    assert set(sd.keys()) == set(model.state_dict().keys()), set(sd.keys()) ^ set(model.state_dict().keys())
+    model.load_state_dict(sd, strict=True)
+    return model
+
+
 def golden_sam():
     """tests/golden/sam_tiny.npz: transformers' SamModel (CPU, fp32, synth weights) on the two tiny configurations of tests/sam_common.py -
     image embeddings, low-res logits and IoU scores for two click sets, the final masks at a non-square original size, the same with the
     qkv biases x 8 (the padded-window case), and SamPredictor's preprocessing from transformers' SAM image processor."""
-    from transformers import SamConfig, SamMaskDecoderConfig, SamModel, SamPromptEncoderConfig, SamVisionConfig
     from transformers import SamImageProcessor
     from tests import sam_common as sc
     out = {}
-
-    def hf_model(cfg, sd):
-        C = cfg["out_channels"]
-        vc = SamVisionConfig(hidden_size=cfg["hidden"], output_channels=C, num_hidden_layers=cfg["layers"], num_attention_heads=cfg["heads"],
-                             image_size=cfg["image"], patch_size=cfg["patch"], window_size=cfg["window"],
-                             global_attn_indexes=list(cfg["global_attn_indexes"]), mlp_dim=cfg["mlp_dim"], num_pos_feats=C // 2)
-        pc = SamPromptEncoderConfig(hidden_size=C, image_size=cfg["image"], patch_size=cfg["patch"], mask_input_channels=16)
-        mc = SamMaskDecoderConfig(hidden_size=C, num_hidden_layers=cfg["decoder_layers"], num_attention_heads=sc.DECODER_HEADS,
-                                  mlp_dim=cfg["decoder_mlp_dim"], iou_head_hidden_dim=cfg["iou_head_hidden_dim"])
-        model = SamModel(SamConfig(vision_config=vc, prompt_encoder_config=pc, mask_decoder_config=mc)).eval()
-        assert set(sd.keys()) == set(model.state_dict().keys()), set(sd.keys()) ^ set(model.state_dict().keys())
-        model.load_state_dict(sd, strict=True)
-        return model
+    hf_model = _hf_sam_model
 
     def run(tag, cfg, sd, masks, pixel_seed=7):
         S = cfg["image"]
@@ -1607,6 +1611,78 @@ def golden_sam():
     print("sam: %d arrays, %d bytes; |emb| max a %.3f b %.3f a8 %.3f; masked padding moves a8 by %.1f bars" % (
         len(out), os.path.getsize(path), out["a_emb_absmax"], out["b_emb_absmax"], out["a8_emb_absmax"], moved))
     assert os.path.getsize(path) < 1 << 20
+
+
+AMG_OFFSET = 0.05          # synthetic weights give logits of magnitude ~1: the package's offset of 1.0 makes every stability score 0
+AMG_STORED = (0, 5, 10, 15)
+
+
+def _middle_gap(values):
+    """The midpoint of the widest gap between neighbours in the middle half of the sorted values."""
+    v = np.sort(np.asarray(values, dtype=np.float64))
+    mid = v[len(v) // 4: len(v) - len(v) // 4]
+    k = int(np.argmax(np.diff(mid)))
+    return float((mid[k] + mid[k + 1]) / 2), float(mid[k + 1] - mid[k])
+
+
+def golden_sam_amg():
+    """tests/golden/sam_amg.npz: transformers' SamModel on fixture (a)'s stored pixels with ONE batched call of 16 single-point prompts (the
+    4 x 4 grid over ORIGINAL_SIZE in the input frame), the quantities SamAutomaticMaskGenerator filters on from transformers' own helpers
+    (image_processing_pil_sam) over the reference's logits at ORIGINAL_SIZE, and thresholds for the end-to-end test that sit in the widest
+    gaps of the reference's values."""
+    from transformers.models.sam.image_processing_pil_sam import _batched_mask_to_box, _build_point_grid, _compute_stability_score
+    from blobctrl_amd import sam
+    from tests import sam_common as sc
+    cfg = sc.TINY_A
+    z = np.load(os.path.join(OUT, "sam_tiny.npz"))
+    model = _hf_sam_model(cfg, sc.weights_of(cfg))
+    x = torch.from_numpy(z["a_pixels_q8"]).float() / 32
+    H, W = sc.ORIGINAL_SIZE
+    grid = _build_point_grid(4) * np.array([[W, H]], dtype=np.float64)                  # x fastest, (x, y) in the original image
+    pts = sam.scale_points(grid, sc.ORIGINAL_SIZE, cfg["image"])                         # fp32 [16][2] in the input frame
+    assert sam.preprocess_shape(H, W, cfg["image"]) == sc.INPUT_SIZE
+    with torch.no_grad():
+        emb = model.get_image_embeddings(x)
+        assert sc.rel_err(emb, z["a_emb"]) < 1e-6
+        r = model(image_embeddings=emb, input_points=torch.from_numpy(pts).reshape(1, 16, 1, 2), input_labels=torch.ones(1, 16, 1, dtype=torch.long),
+                  multimask_output=True)
+    low, iou = r.pred_masks[0], r.iou_scores[0]                                          # [16][3][64][64], [16][3]
+    assert tuple(low.shape) == (16, 3, 64, 64) and tuple(iou.shape) == (16, 3)
+    logits = sc.postprocess(low.flatten(0, 1), cfg["image"], sc.INPUT_SIZE, sc.ORIGINAL_SIZE)        # [48][H][W]
+    stability = _compute_stability_score(logits, 0.0, AMG_OFFSET).numpy().astype(np.float32)
+    binary = logits > 0.0
+    boxes = _batched_mask_to_box(binary).numpy().astype(np.int32)
+    areas = binary.flatten(1).sum(1).numpy().astype(np.int32)
+    iou_flat = iou.flatten().numpy()
+    # the chain on the reference's own numbers, with thresholds in the widest gaps: every stage must drop something and leave something
+    iou_thr, iou_gap = _middle_gap(iou_flat)
+    keep1 = np.nonzero(iou_flat > iou_thr)[0]
+    stab_thr, stab_gap = _middle_gap(stability[keep1])
+    keep2 = keep1[stability[keep1] >= stab_thr]
+    b = boxes[keep2].astype(np.float64)
+    pair = []
+    for i in range(len(b)):
+        for j in range(i + 1, len(b)):
+            iw = max(0.0, min(b[i, 2], b[j, 2]) - max(b[i, 0], b[j, 0]))
+            ih = max(0.0, min(b[i, 3], b[j, 3]) - max(b[i, 1], b[j, 1]))
+            union = (b[i, 2] - b[i, 0]) * (b[i, 3] - b[i, 1]) + (b[j, 2] - b[j, 0]) * (b[j, 3] - b[j, 1]) - iw * ih
+            pair.append(iw * ih / union)
+    nms_thr = float(np.median(pair))
+    keep3 = keep2[sam.box_nms(boxes[keep2], iou_flat[keep2], nms_thr)]
+    msg = f"48 -> {len(keep1)} (IoU > {iou_thr:.4f}) -> {len(keep2)} (stability >= {stab_thr:.4f}) -> {len(keep3)} (NMS at {nms_thr:.4f})"
+    # Both filters must drop something and leave something, and two masks at least must come out of the NMS.  The NMS itself cannot be made to
+    # drop one here: on seeded weights nearly every mask touches all four borders, every pair of surviving boxes has IoU exactly 1, the median is
+    # 1 and nothing is > 1 (the count is stored as `nms_dropped`; the geometry of box_nms is the unit test's, tests/test_sam_amg_cpu.py).
+    assert 48 > len(keep1) > len(keep2) >= len(keep3) >= 2, msg + ": pick another seed"
+    out = dict(grid=grid, points=pts, iou=iou.numpy(), low=low[list(AMG_STORED)].numpy(), stored=np.array(AMG_STORED, dtype=np.int32),
+               stability=stability, boxes=boxes, areas=areas, offset=np.float32(AMG_OFFSET), pred_iou_thresh=np.float32(iou_thr),
+               stability_score_thresh=np.float32(stab_thr), box_nms_thresh=np.float32(nms_thr), ref_kept=keep3.astype(np.int32),
+               nms_dropped=np.int32(len(keep2) - len(keep3)))
+    path = os.path.join(OUT, "sam_amg.npz")
+    np.savez_compressed(path, **out)
+    print("sam_amg: %s; gaps IoU %.4f stability %.4f; IoU %.3f .. %.3f, stability %.3f .. %.3f; %d bytes" % (
+        msg, iou_gap, stab_gap, iou_flat.min(), iou_flat.max(), stability.min(), stability.max(), os.path.getsize(path)))
+    assert os.path.getsize(path) < 400 << 10
 
 
 def golden_blob_edit():
