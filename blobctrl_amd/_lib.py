@@ -216,6 +216,17 @@ SAM_BATCH_SIGNATURES = {
 }
 SAM_HOST_SIGNATURES = {"bc_mask_stats_chunks": (C.c_int, [C.c_int, C.c_int])}
 
+# Entry points of include/blobctrl_masks.h (connected components and small-region removal, blobctrl_amd/masks.py).  A table of its own:
+# these are DIRECT launches on the caller's stream - no BC_OP_* code, in none of the op tables below, never recorded into a plan.
+_MASK_REMOVE_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+MASK_SIGNATURES = {
+    "bc_mask_label": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_mask_remove_small": (C.c_int, _MASK_REMOVE_ARGS + [C.c_void_p]),
+    "bc_mask_remove_small_phase": (C.c_int, _MASK_REMOVE_ARGS + [C.c_int, C.c_void_p]),
+}
+MASK_HOLES, MASK_ISLANDS = 0, 1
+MASK_REGION_PHASES = 5                # launch groups of bc_mask_remove_small (BC_MASK_REGION_PHASES)
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -286,7 +297,8 @@ def load():
     except OSError as e:   # pragma: no cover
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
-            list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()):
+            list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
+            list(MASK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -225,25 +225,40 @@ def ellipse_from_mask(mask: np.ndarray) -> Ellipse:
     return fit_ellipse(convex_hull(np.stack([xs, ys], 1)))
 
 
-def ellipse_from_click(predictor, image, points, labels=None) -> Ellipse:
+def ellipse_from_click(predictor, image, points, labels=None, min_region_area: int = 0) -> Ellipse:
     """app:1019-1043 `segmentation()`: the click(s) on `image` -> SAM mask (`predict(..., multimask_output=False)`, mask 0) ->
     `ellipse_from_mask`, the first blob of an edit.  `predictor` is a `blobctrl_amd.sam.SamPredictor` (or anything with its call surface).
     `image` = None keeps the image the predictor already holds: a further click then costs the mask decoder only.  `points` [n][2] are
-    (x, y) pixels of the image; `labels` default to 1 (foreground) for every point, as in the app."""
+    (x, y) pixels of the image; `labels` default to 1 (foreground) for every point, as in the app.  `min_region_area` > 0 despeckles the
+    mask first (`blobctrl_amd.masks.remove_small_regions`, "holes" then "islands", on the GPU): the ellipse is fitted to the hull of ALL set
+    pixels, so one detached speck far from the object would otherwise be a hull vertex."""
+    if min_region_area < 0:
+        raise ValueError("ellipse_from_click: min_region_area must be >= 0")
     pts = np.asarray(points, dtype=np.float32).reshape(-1, 2)
     lab = np.ones(len(pts), dtype=np.int32) if labels is None else np.asarray(labels, dtype=np.int32).reshape(-1)
     if image is not None:
         predictor.set_image(np.asarray(image))
     masks, _, _ = predictor.predict(point_coords=pts, point_labels=lab, multimask_output=False)
-    return ellipse_from_mask(np.asarray(masks[0]).astype(np.uint8))
+    mask = np.asarray(masks[0])
+    if min_region_area > 0:
+        from .masks import remove_small_regions
+        mask, _ = remove_small_regions(mask != 0, min_region_area, "holes")
+        mask, _ = remove_small_regions(mask, min_region_area, "islands")
+    return ellipse_from_mask(mask.astype(np.uint8))
 
 
-def ellipses_from_image(generator, image, min_area: int = 0):
+def ellipses_from_image(generator, image, min_area: int = 0, min_region_area: int = 0):
     """"Segment everything": every mask of `generator.generate(image)` (a `blobctrl_amd.sam.SamAutomaticMaskGenerator`, or anything with
     its call surface) as a blob to move, resize or remove -> [(ellipse, annotation), ...], largest area first (ties keep the generator's
     order).  Masks of fewer than `min_area` pixels are left out, and so is a mask no ellipse can be fitted to (`fit_ellipse` refuses a hull of
-    fewer than five points and points that determine no ellipse: a speck of a few pixels, or a mask whose hull is the frame's rectangle)."""
-    anns = [a for a in generator.generate(np.asarray(image)) if a["area"] >= min_area]
+    fewer than five points and points that determine no ellipse: a speck of a few pixels, or a mask whose hull is the frame's rectangle).
+    `min_region_area` > 0 is handed to the generator as `generate(image, min_mask_region_area=...)`: holes and islands below it are removed
+    from every mask on the GPU before it is fitted; with 0 the generator is called with the image alone."""
+    if min_region_area < 0:
+        raise ValueError("ellipses_from_image: min_region_area must be >= 0")
+    found = generator.generate(np.asarray(image)) if min_region_area == 0 else \
+        generator.generate(np.asarray(image), min_mask_region_area=min_region_area)
+    anns = [a for a in found if a["area"] >= min_area]
     anns.sort(key=lambda a: -a["area"])
     out = []
     for a in anns:

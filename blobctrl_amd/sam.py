@@ -16,7 +16,9 @@
                    depend on the prompt (layer 0's image side) exists once and is read with a batch stride of 0.
   segment all      `SamAutomaticMaskGenerator.generate`: a grid of single-point prompts through `predict_torch` in batches, one
                    bc_mask_stats pass over the full-size logits (the stability counts, the area and the box of every mask), the two
-                   filters on the device, box NMS on the host, and only the surviving masks cross to the host.
+                   filters on the device, box NMS on the host, and only the surviving masks cross to the host.  With
+                   `generate(image, min_mask_region_area=N)` the survivors are despeckled on the device first (blobctrl_amd/masks.py:
+                   connected components, holes filled and islands removed below N pixels), as the package's post-processing does.
 
 `SamPredictor.set_image` runs the encoder once; every `predict` / `predict_torch` on that image costs the decoder only.
 """
@@ -820,7 +822,8 @@ class SamAutomaticMaskGenerator:
         if crop_n_layers > 0:
             raise NotImplementedError("SamAutomaticMaskGenerator: crop_n_layers > 0 is not implemented (the whole-image crop only)")
         if min_mask_region_area > 0:
-            raise NotImplementedError("SamAutomaticMaskGenerator: min_mask_region_area > 0 is not implemented (needs connected components)")
+            raise NotImplementedError("SamAutomaticMaskGenerator: min_mask_region_area is a per-call argument here - generate(image, "
+                                      "min_mask_region_area=N) - or the method postprocess_small_regions; the constructor takes 0 only")
         if output_mode != "binary_mask":
             raise NotImplementedError(f"SamAutomaticMaskGenerator: output_mode {output_mode!r} is not implemented ('binary_mask' only)")
         if points_per_batch < 1:
@@ -836,11 +839,15 @@ class SamAutomaticMaskGenerator:
         self.last_timing = {}
 
     @torch.no_grad()
-    def generate(self, image):
+    def generate(self, image, min_mask_region_area=0):
         """image uint8 [H][W][3] -> a list of dicts (segmentation, area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box) in NMS
         order, i.e. by descending predicted IoU.  A ragged last batch runs a decoder plan of its own size (recorded once, like the full one).
-        `last_timing` holds HIP-event milliseconds of the call's phases (decode, resize, stats) and the host time around them."""
+        `last_timing` holds HIP-event milliseconds of the call's phases (decode, resize, stats, regions) and the host time around them.
+        `min_mask_region_area` > 0 is the package's post-processing of the kept masks, on the device before any mask crosses to the host
+        (`_small_regions`): the order is then unchanged masks first, each group in its NMS order."""
         import time
+        if min_mask_region_area < 0:
+            raise ValueError("generate: min_mask_region_area must be >= 0")
         pred, model, dev = self.predictor, self.predictor.model, self.predictor.model.device
         t_start = time.perf_counter()
         pred.set_image(image)
@@ -870,20 +877,61 @@ class SamAutomaticMaskGenerator:
             e[3].record()
             marks.append(e)
         torch.cuda.synchronize(dev)
-        out = []
+        out, regions_ms = [], 0.0
         if kept:
             # the NMS needs boxes and scores only: the masks stay on the device until it has chosen
             masks = torch.cat([k[0] for k in kept])
             iou, point, stats, stability = (torch.cat([k[j] for k in kept]).cpu().numpy() for j in range(1, 5))
             order = box_nms(stats[:, 3:7], iou, self.box_nms_thresh)
-            masks = masks[torch.from_numpy(order).to(dev)].cpu().numpy()
-            for m, i in zip(masks, order):
-                x0, y0, x1, y1 = (int(v) for v in stats[i, 3:7])
-                out.append({"segmentation": m, "area": int(stats[i, 2]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(iou[i]),
+            masks = masks[torch.from_numpy(order).to(dev)]
+            area_box = stats[order, 2:7]
+            if min_mask_region_area > 0:
+                masks, keep, area_box, regions_ms = self._small_regions(masks, min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
+                order = order[keep]                    # (masks and area_box come back as the kept ones, already in that order)
+            masks = masks.cpu().numpy()
+            for m, i, ab in zip(masks, order, area_box):
+                x0, y0, x1, y1 = (int(v) for v in ab[1:5])
+                out.append({"segmentation": m, "area": int(ab[0]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(iou[i]),
                             "point_coords": [[float(grid[point[i], 0]), float(grid[point[i], 1])]], "stability_score": float(stability[i]),
                             "crop_box": [0, 0, W, H]})
         t_end = time.perf_counter()
         gpu = [sum(e[j].elapsed_time(e[j + 1]) for e in marks) for j in range(3)]
         self.last_timing = {"set_image_ms": 1e3 * (t_set - t_start), "decode_ms": gpu[0], "resize_ms": gpu[1], "stats_ms": gpu[2],
-                            "host_ms": 1e3 * (t_end - t_set) - sum(gpu), "generate_ms": 1e3 * (t_end - t_start), "masks": len(out)}
+                            "regions_ms": regions_ms, "host_ms": 1e3 * (t_end - t_set) - sum(gpu) - regions_ms,
+                            "generate_ms": 1e3 * (t_end - t_start), "masks": len(out)}
+        return out
+
+    @staticmethod
+    def _small_regions(masks, min_area, nms_thresh):
+        """The package's `postprocess_small_regions` on device masks bool [n][H][W]: `masks.clean_masks` (holes, then islands), then box NMS
+        over the NEW boxes with score 1 for an unchanged mask and 0 for a changed one, so that a cleaned mask which has become the duplicate
+        of an untouched one is the one to go.  -> (cleaned masks of the kept ones on the device, kept indices in NMS order - unchanged first,
+        each group in its previous order -, int32 [kept][5] = area, x0, y0, x1, y1, HIP-event ms of the device pass)."""
+        from .masks import clean_masks
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        cleaned, changed, stats = clean_masks(masks, min_area)
+        e1.record()
+        changed, stats = changed.cpu().numpy(), stats.cpu().numpy()                         # (synchronises: the events are complete)
+        keep = box_nms(stats[:, 1:5], 1.0 - changed.astype(np.float32), nms_thresh)
+        return cleaned[torch.from_numpy(keep).to(masks.device)], keep, stats[keep], e0.elapsed_time(e1)
+
+    @torch.no_grad()
+    def postprocess_small_regions(self, anns, min_area, nms_thresh):
+        """The step `generate(image, min_mask_region_area=min_area)` applies, on a list of annotation dicts from anywhere (their
+        `segmentation` arrays must share one shape): a NEW list in the package's order; a changed mask gets its new `segmentation`, `area`
+        and `bbox`, every other key stays (`predicted_iou` and `stability_score` are those of the mask before, as in the package)."""
+        if min_area < 0:
+            raise ValueError("postprocess_small_regions: min_area must be >= 0")
+        anns = list(anns)
+        if not anns or min_area == 0:
+            return [dict(a) for a in anns]
+        self.predictor.model._need_gpu()
+        dev = self.predictor.model.device
+        masks = torch.from_numpy(np.stack([np.asarray(a["segmentation"]) != 0 for a in anns])).to(dev)
+        cleaned, keep, area_box, _ = self._small_regions(masks, min_area, nms_thresh)
+        out = []
+        for m, i, ab in zip(cleaned.cpu().numpy(), keep, area_box):
+            x0, y0, x1, y1 = (int(v) for v in ab[1:5])
+            out.append(dict(anns[i], segmentation=m, area=int(ab[0]), bbox=[x0, y0, x1 - x0, y1 - y0]))
         return out

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--click", default=None, help="X,Y pixel of the click on the foreground image (with --sam)")
     ap.add_argument("--sam-auto", type=int, default=None, metavar="K",
                     help="take the blob from the K-th largest mask of SamAutomaticMaskGenerator instead of a click (with --sam)")
+    ap.add_argument("--min-region-area", type=int, default=0, metavar="N",
+                    help="despeckle the SAM mask(s) on the GPU first: fill holes and remove islands of fewer than N pixels (with --sam)")
     args = ap.parse_args()
     if (args.click or args.sam_auto is not None) and not args.sam:
         ap.error("--click / --sam-auto need --sam")
@@ -89,7 +91,7 @@ def main():
             # keep every mask of a coarser grid then, or nothing would be left to choose from)
             kw = dict(points_per_side=8, pred_iou_thresh=-1e9, stability_score_thresh=0.0, box_nms_thresh=1.0) if args.sam == "synth" else {}
             ts = sync()
-            blobs = ellipses_from_image(SamAutomaticMaskGenerator(sam, **kw), image)
+            blobs = ellipses_from_image(SamAutomaticMaskGenerator(sam, **kw), image, min_region_area=args.min_region_area)
             if not 0 <= args.sam_auto < len(blobs):
                 raise SystemExit(f"--sam-auto {args.sam_auto}: the generator found {len(blobs)} masks")
             e, ann = blobs[args.sam_auto]
@@ -99,9 +101,9 @@ def main():
             click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
             ts = sync()
             predictor = SamPredictor(sam)
-            e = ellipse_from_click(predictor, image, [click])
+            e = ellipse_from_click(predictor, image, [click], min_region_area=args.min_region_area)
             te = sync()
-            e2 = ellipse_from_click(predictor, None, [click])
+            e2 = ellipse_from_click(predictor, None, [click], min_region_area=args.min_region_area)
             print(f"SAM click {click} -> ellipse {e} in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); "
                   f"second click {1e3 * (sync() - te):.1f} ms, same ellipse: {e2 == e}")
         ellipse = [list(e[0]), list(e[1]), e[2]]
