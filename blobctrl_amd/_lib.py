@@ -49,6 +49,15 @@ class BcGemm(C.Structure):
     ]
 
 
+FAMILIES = ("gemm", "gemm_fast", "conv_halo", "conv_wreg", "gemm_wreg", "gemm256")       # BC_FAMILY_*: the kernel family of a resolved BcGemm
+
+
+class BcGemmInfo(C.Structure):
+    """Mirror of `struct BcGemmInfo` (include/blobctrl_hip.h): how the library launches a BcGemm (bc_gemm_resolve)."""
+    _fields_ = [("family", C.c_int), ("tile_cfg", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("splitk", C.c_int), ("n_out", C.c_int),
+                ("slab_elems", C.c_longlong), ("stat_rows", C.c_int), ("gn_finalize_fits", C.c_int), ("kernel", C.c_char * 64)]
+
+
 _SIGNATURES = {
     "bc_last_error": (C.c_char_p, []),
     "bc_version": (C.c_int, []),
@@ -57,6 +66,7 @@ _SIGNATURES = {
     "bc_sizeof_gemm": (C.c_int, []),
     "bc_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bc_gemm_resolve": (C.c_int, [C.POINTER(BcGemm), C.POINTER(BcGemmInfo)]),
     "bc_conv_halo_eligible": (C.c_int, [C.c_int] * 8),
     "bc_conv_halo_max_chunks": (C.c_int, []),
     "bc_conv_wreg_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -478,7 +478,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmArgs g) {
 
 int bc_conv_halo_max_chunks_impl() { return MAX_CH; }
 
-// Eligibility of the halo kernel for a conv problem (the host-side planners mirror this).
+// Eligibility of the halo kernel for a conv problem.
 int bc_conv_halo_ok(const BcGemm& p) {
     if (p.a_mode != BC_A_CONV3X3 || p.stride != 1 || p.conv_nopad_lo) return 0;
     // BC_TILE_WREG also takes the exact 2x nearest upsample in front of a plain convolution (no GroupNorm prologue, single source)
@@ -490,11 +490,30 @@ int bc_conv_halo_ok(const BcGemm& p) {
     return 1;
 }
 
+int bc_conv_halo_split(GemmArgs& g) {
+    BcGemm& p = g.p;
+    g.halo_nch = p.Cin / 64;
+    g.halo_nsc = g.halo_cps_sc = 0;
+    const int sk = std::max(1, std::min(p.splitk, g.halo_nch));
+    g.halo_cps = bc_ceil_div(g.halo_nch, sk);
+    p.splitk = bc_ceil_div(g.halo_nch, g.halo_cps);
+    BC_CHECK_ARG(g.halo_cps <= MAX_CH, "bc_gemm(halo conv): %d channel chunks per split exceed %d (raise splitk)", g.halo_cps, MAX_CH);
+    return 0;
+}
+
+int bc_conv_halo_fin_fits(const GemmArgs& g) {
+    const int span = g.halo_cps * 64 + 2 * (g.p.Cin / g.p.a_groups);      // (incl. the groups straddling either end)
+    return span <= FIN_MAX_CH && (8 * span + g.p.a_groups + 8) * 8 <= 2 * HALO_BYTES;
+}
+
+void bc_conv_halo_kernel_name(const GemmArgs& g, char* out, int n) {
+    snprintf(out, n, "conv_halo_kernel<%d>", g.p.a_tot1 ? 2 : g.p.a_affine ? 1 : 0);      // (AFFINE, as bc_conv_halo_launch picks it)
+}
+
 int bc_conv_halo_launch(GemmArgs& g, hipStream_t stream) {
     BcGemm& p = g.p;
     g.halo_tx = p.Wout / TW;
     g.halo_tpi = g.halo_tx * (p.Hout / TH);
-    g.halo_nch = p.Cin / 64;
 #ifdef BC_DIAGNOSTICS
     // ablation bits of the kernel (1 no weight DMA, 2 no halo path, 4 no MFMA, 8 no fragment reads, 16 no barriers, 32 no transform, 64 no
     // raw DMA): WRONG results by design, so they exist only in a library built with -DBC_DIAGNOSTICS (round 6: no switch that can break
@@ -504,11 +523,6 @@ int bc_conv_halo_launch(GemmArgs& g, hipStream_t stream) {
 #else
     g.halo_dbg = 0;
 #endif
-    int sk = std::max(1, std::min(p.splitk, g.halo_nch));
-    g.halo_cps = bc_ceil_div(g.halo_nch, sk);
-    p.splitk = bc_ceil_div(g.halo_nch, g.halo_cps);
-    BC_CHECK_ARG(g.halo_cps <= MAX_CH, "bc_gemm(halo conv): %d channel chunks per split exceed %d (raise splitk)", g.halo_cps, MAX_CH);
-    BC_CHECK_ARG(p.splitk == 1 || p.slab != nullptr, "bc_gemm(halo conv): splitk=%d needs a slab", p.splitk);
     const int B = p.M / (p.Hout * p.Wout);
     dim3 grid(p.N / HBN, B * g.halo_tpi, p.splitk);
     {
@@ -549,12 +563,6 @@ int bc_conv_halo_launch(GemmArgs& g, hipStream_t stream) {
     } report{stream, nwg_s, g.halo_stamps, p, g.halo_cps};
     static std::atomic<unsigned long long> set_a{0}, set_p{0}, set_f{0};
     if (p.a_tot1) {
-        BC_CHECK_ARG(p.a_gamma && p.a_beta && p.a_groups > 0 && p.Cin % p.a_groups == 0 && (!p.A2 || p.a_tot2),
-                     "bc_gemm(halo conv): in-kernel GroupNorm finalize needs a_gamma, a_beta, a_groups | Cin and the partials of every source");
-        const int cpg = p.Cin / p.a_groups;
-        BC_CHECK_ARG(g.halo_cps * 64 + 2 * cpg <= FIN_MAX_CH && (8 * (g.halo_cps * 64 + 2 * cpg) + p.a_groups + 8) * 8 <= 2 * HALO_BYTES,
-                     "bc_gemm(halo conv): channel span %d per workgroup too wide for the in-kernel GroupNorm finalize (max %d): use "
-                     "bc_gn_finalize + a_affine or raise splitk", g.halo_cps * 64 + 2 * cpg, FIN_MAX_CH);
         BC_CHECK_HIP(bc_set_max_lds(set_f, reinterpret_cast<const void*>(&conv_halo_kernel<2>), LDS_TOTAL));
         hipLaunchKernelGGL((conv_halo_kernel<2>), grid, dim3(512), LDS_TOTAL, stream, g);
     } else if (p.a_affine) {

@@ -988,25 +988,37 @@ int bc_conv_wreg_sc_ok(const BcGemm& p) {
     return 1;
 }
 
-int bc_conv_wreg_launch(GemmArgs& g, hipStream_t stream) {
+int bc_conv_wreg_split(GemmArgs& g) {
     BcGemm& p = g.p;
-    g.halo_tx = p.Wout / TW;
-    g.halo_tpi = g.halo_tx * (p.Hout / TH);
     g.halo_nch = p.Cin / 64;
     g.halo_nsc = p.S ? p.Cs / 64 : 0;                // (the folded 1x1 shortcut's one-tap chunks: every split takes its share of both kinds)
-    g.halo_dbg = 0;                                  // (bit 0x100 = the round-4 in-prologue finalize: kept in the kernel for reference, not selectable)
-    g.halo_stamps = nullptr;
-    int sk = std::max(1, std::min(p.splitk, g.halo_nch + g.halo_nsc));
+    const int sk = std::max(1, std::min(p.splitk, g.halo_nch + g.halo_nsc));
     g.halo_cps = bc_ceil_div(g.halo_nch, sk);
     g.halo_cps_sc = bc_ceil_div(g.halo_nsc, sk);
     p.splitk = std::max(bc_ceil_div(g.halo_nch, g.halo_cps), g.halo_nsc ? bc_ceil_div(g.halo_nsc, g.halo_cps_sc) : 1);
     BC_CHECK_ARG(g.halo_cps <= MAX_CH, "bc_gemm(wreg conv): %d channel chunks per split exceed %d (raise splitk)", g.halo_cps, MAX_CH);
-    BC_CHECK_ARG(p.splitk == 1 || p.slab != nullptr, "bc_gemm(wreg conv): splitk=%d needs a slab", p.splitk);
-    const int B = p.M / (p.Hout * p.Wout);
     BC_CHECK_ARG((long long)p.M * std::max(p.lda, p.lda2) < 2147483647LL, "bc_gemm(wreg conv): activation of %d pixels x stride %d exceeds 32-bit element offsets",
                  p.M, std::max(p.lda, p.lda2));
     BC_CHECK_ARG(!p.S || (bc_conv_wreg_sc_ok(p) && (long long)p.M * std::max(p.lds, p.lds2) < 2147483647LL),
                  "bc_gemm(wreg conv): folded shortcut outside the kernel's limits (Cs=%d S1=%d)", p.Cs, p.S1);
+    return 0;
+}
+
+int bc_conv_wreg_fin_fits(const GemmArgs& g) {
+    return g.halo_cps * 64 + 2 * (g.p.Cin / g.p.a_groups) <= FIN_MAX_CH && g.p.a_groups * 8 <= 1024;      // (span incl. the straddling groups)
+}
+
+void bc_conv_wreg_kernel_name(const GemmArgs& g, char* out, int n) {
+    snprintf(out, n, "conv_wreg_kernel<%d>", g.p.a_tot1 ? 2 : g.p.a_affine ? 1 : 0);      // (AFFINE, as bc_conv_wreg_launch picks it)
+}
+
+int bc_conv_wreg_launch(GemmArgs& g, hipStream_t stream) {
+    BcGemm& p = g.p;
+    g.halo_tx = p.Wout / TW;
+    g.halo_tpi = g.halo_tx * (p.Hout / TH);
+    g.halo_dbg = 0;                                  // (bit 0x100 = the round-4 in-prologue finalize: kept in the kernel for reference, not selectable)
+    g.halo_stamps = nullptr;
+    const int B = p.M / (p.Hout * p.Wout);
     dim3 grid(p.N / HBN, B * g.halo_tpi, p.splitk);
     g.wr_plane = make_fastdiv(grid.x * grid.y);
     g.wr_gx = make_fastdiv(grid.x);
@@ -1063,14 +1075,8 @@ int bc_conv_wreg_launch(GemmArgs& g, hipStream_t stream) {
     } report{stream, nwg_s, g.halo_stamps, p, g.halo_cps};
     static std::atomic<unsigned long long> set_a{0}, set_p{0}, set_f{0};
     if (p.a_tot1) {
-        BC_CHECK_ARG(p.a_gamma && p.a_beta && p.a_groups > 0 && p.Cin % p.a_groups == 0 && (!p.A2 || p.a_tot2),
-                     "bc_gemm(wreg conv): in-kernel GroupNorm finalize needs a_gamma, a_beta, a_groups | Cin and the partials of every source");
-        const int cpg = p.Cin / p.a_groups;
-        BC_CHECK_ARG(g.halo_cps * 64 + 2 * cpg <= FIN_MAX_CH && p.a_groups * 8 <= 1024,
-                     "bc_gemm(wreg conv): channel span %d per workgroup too wide for the in-kernel GroupNorm finalize (max %d): use "
-                     "bc_gn_finalize + a_affine or raise splitk", g.halo_cps * 64 + 2 * cpg, FIN_MAX_CH);
         BC_CHECK_HIP(bc_set_max_lds(set_f, reinterpret_cast<const void*>(&conv_wreg_kernel<2>), LDS_TOTAL_FIN));
-        const int lds_fin = std::max(LDS_TOTAL, OFF_FIN + (g.halo_cps * 64 + 2 * cpg) * 16 + 1024);    // (scratch for this span only)
+        const int lds_fin = std::max(LDS_TOTAL, OFF_FIN + (g.halo_cps * 64 + 2 * (p.Cin / p.a_groups)) * 16 + 1024);    // (scratch for this span only)
         hipLaunchKernelGGL((conv_wreg_kernel<2>), grid, dim3(512), lds_fin, stream, g);
     } else if (p.a_affine) {
         BC_CHECK_HIP(bc_set_max_lds(set_a, reinterpret_cast<const void*>(&conv_wreg_kernel<1>), LDS_TOTAL));

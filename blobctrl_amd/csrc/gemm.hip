@@ -329,6 +329,12 @@ int launch_gemm(const GemmArgs& g, hipStream_t stream) {
     return 0;
 }
 
+// the two instantiations of the generic kernel, picked by the tile bc_gemm_plan gave the problem - and what a profiler calls them
+int launch_generic(const GemmArgs& g, hipStream_t stream) {
+    return g.bn == 64 ? launch_gemm<256, 64, 4, 1>(g, stream) : launch_gemm<128, 128, 2, 2>(g, stream);
+}
+const char* generic_kernel_name(const GemmArgs& g) { return g.bn == 64 ? "gemm_kernel<256, 64, 4, 1>" : "gemm_kernel<128, 128, 2, 2>"; }
+
 }  // namespace
 
 namespace {
@@ -445,11 +451,23 @@ static thread_local bool tl_probe_hit = false;
 void bc_gemm_set_probe(hipEvent_t e) { tl_probe = e; tl_probe_hit = false; }
 bool bc_gemm_probe_hit() { return tl_probe_hit; }
 
-extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(pp != nullptr, "bc_gemm: null params");
-    GemmArgs g;
-    g.p = *pp;
+namespace {
+
+// the rows of a workgroup when the launch `ok` accepts can add its output's GroupNorm statistics to a table, else 0: `ok` judges the
+// problem with gn_tot set (a record is resolved before its table exists)
+template <class Ok>
+int stat_rows_if(const BcGemm& p, int rows, Ok ok) {
+    BcGemm q = p;
+    q.gn_tot = reinterpret_cast<unsigned long long*>(&q);                 // (only tested for non-null)
+    return ok(q) ? rows : 0;
+}
+
+// How a BcGemm turns into a launch: every argument check, the defaults, n_out, the fast-path rule, the environment overrides, the tile and
+// the final split count, into `g` (what the launchers read) and `info` (all but the kernel's name).  The ONE owner of these decisions:
+// bc_gemm launches what this resolved, bc_gemm_resolve reports it to planners.  Host arithmetic only, no allocation (it is on the eager
+// replay path).  Two checks are the caller's because they need pointers a planner binds later: slab (bc_gemm) and gn_tot (stat_rows).
+// choose_split: splitk <= 0 asks for the cost model's split (bc_gemm_resolve); bc_gemm runs such a struct unsplit.
+int resolve(GemmArgs& g, BcGemmInfo& info, bool choose_split) {
     BcGemm& p = g.p;
     BC_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "bc_gemm: bad dims M=%d N=%d K=%d", p.M, p.N, p.K);
     BC_CHECK_ARG(p.A && p.W && p.C, "bc_gemm: null A/W/C");
@@ -488,6 +506,7 @@ extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
     }
     if (p.rows_per_batch <= 0) p.rows_per_batch = p.M;
     if (p.out_w <= 0) p.out_w = p.rows_per_batch;
+    const bool choose = choose_split && p.splitk < 1;
     if (p.splitk < 1) p.splitk = 1;
     g.n_out = p.N;
     if (p.act == BC_ACT_GEGLU) {
@@ -510,111 +529,166 @@ extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
     } else {
         BC_CHECK_ARG(p.ldc >= (p.C_t ? p.n_t0 : g.n_out), "bc_gemm: ldc=%d < n_out=%d", p.ldc, g.n_out);
     }
-    if (gw) {
-        BC_CHECK_ARG(bc_gemm_wreg_ok(p, p.tile_cfg), "bc_gemm: BC_TILE_GW* needs dense A, M%%64==0, N%%(64 NT)==0, K%%320==0 (C1%%320==0), fp16 row-major "
-                     "output, no split-K / row vector / affine table (a_tot1: one source, groups | K <= 2560, no activation) (M=%d N=%d K=%d C1=%d)", p.M, p.N, p.K, p.C1);
-        g.nk = p.K / 32; g.kt_per_split = g.nk; p.splitk = 1;
-        g.div_rpb = make_fastdiv((unsigned)p.rows_per_batch);
-        g.div_outw = make_fastdiv((unsigned)p.out_w);
-        g.div_wout = make_fastdiv(1u);
-        g.cfg = p.tile_cfg; g.bm = 64; g.bn = 64 * bc_gemm_wreg_nt(p.tile_cfg);
-        auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-        g.vec_epilogue = g.n_out % 8 == 0 && p.ldc % 8 == 0 && al16(p.C) && (!p.R || (p.ldr % 8 == 0 && al16(p.R))) &&
-                         (!p.R2 || (p.ldr2 % 8 == 0 && al16(p.R2))) && (!p.C_t || al16(p.C_t));
-        BC_CHECK_ARG(g.vec_epilogue, "bc_gemm: BC_TILE_GW* needs 16-byte aligned C / R / R2 / C_t and widths %% 8 == 0");
-        g.vec_transposed = 0; g.nband = 1;
-        return bc_gemm_wreg_launch(g, stream);
-    }
-    if (p.tile_cfg == BC_TILE_G256) {
-        BC_CHECK_ARG(bc_gemm256_ok(p), "bc_gemm: BC_TILE_G256 needs dense A (C1%%128==0), M%%256==0, N%%256==0, K%%128==0, no split-K, fp16 row-major "
-                     "or transposed (bias / alpha only) output, n_t0%%256==0 with C_t (M=%d N=%d K=%d out_mode=%d)", p.M, p.N, p.K, p.out_mode);
-        g.nk = p.K / BK; g.kt_per_split = g.nk; p.splitk = 1;
-        g.div_rpb = make_fastdiv((unsigned)p.rows_per_batch);
-        g.div_outw = make_fastdiv((unsigned)p.out_w);
-        g.div_wout = make_fastdiv(1u);
-        g.cfg = BC_TILE_G256; g.bm = 256; g.bn = 256;
-        auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-        g.vec_epilogue = g.n_out % 8 == 0 && p.ldc % 8 == 0 && al16(p.C) && (!p.R || (p.ldr % 8 == 0 && al16(p.R))) &&
-                         (!p.R2 || (p.ldr2 % 8 == 0 && al16(p.R2))) && (!p.rowvec || p.ld_rowvec % 8 == 0) && (!p.C_t || al16(p.C_t)) &&
-                         (!p.A2 || al16(p.A2));
-        BC_CHECK_ARG(g.vec_epilogue, "bc_gemm: BC_TILE_G256 needs 16-byte aligned C / C_t / R / R2 / A2 and widths %% 8 == 0");
-        BC_CHECK_ARG(!p.gn_tot || (p.rows_per_batch % 256 == 0 && p.M % p.rows_per_batch == 0),
-                     "bc_gemm: BC_TILE_G256 with GroupNorm statistics needs rows_per_batch%%256==0 (a tile's rows inside one image)");
-        g.vec_transposed = p.out_mode == BC_OUT_F16_T; g.nband = 0;
-        return bc_gemm256_launch(g, stream);
-    }
-    const bool wreg = p.tile_cfg == BC_TILE_WREG;
-    const bool halo = p.tile_cfg == BC_TILE_HALO || wreg;
-    if (halo) {
-        if (p.lda <= 0) p.lda = p.A2 ? p.C1 : p.Cin;          // pixel stride of A: 0 = its channel count (a wider NHWC view passes its own)
-        if (p.A2 && p.lda2 <= 0) p.lda2 = p.Cin - p.C1;
-        BC_CHECK_ARG(p.lda >= (p.A2 ? p.C1 : p.Cin) && p.lda % 8 == 0, "bc_gemm: BC_TILE_HALO lda=%d must be >= the channel count and a multiple of 8", p.lda);
-        BC_CHECK_ARG(!p.A2 || (p.lda2 >= p.Cin - p.C1 && p.lda2 % 8 == 0), "bc_gemm: BC_TILE_HALO lda2=%d must be >= Cin - C1 and a multiple of 8", p.lda2);
-        BC_CHECK_ARG(bc_conv_halo_ok(p), "bc_gemm: BC_TILE_HALO needs a 3x3 stride-1 pad-1 convolution with Cin%%64==0, N%%160==0, "
-                                         "Wout%%16==0, Hout%%8==0 (Cin=%d N=%d %dx%d)", p.Cin, p.N, p.Hout, p.Wout);
-        BC_CHECK_ARG(!p.a_affine || p.a_act == BC_ACT_NONE || p.a_act == BC_ACT_SILU, "bc_gemm: a_act must be NONE or SILU");
-    } else {
-        BC_CHECK_ARG(p.a_affine == nullptr && p.a_tot1 == nullptr, "bc_gemm: the fused GroupNorm prologue is only available on BC_TILE_HALO");
-    }
-    g.nk = bc_ceil_div(p.K, BK);
-    if (halo) g.nk = p.Cin / BK;                    // split-K counts 64-channel chunks (each covers the nine taps)
-    if (wreg && p.S) g.nk += p.Cs / BK;             // ... and those of the folded 1x1 shortcut (bc_conv_wreg_launch deals both kinds out to the splits)
-    if (p.splitk > g.nk) p.splitk = g.nk;
-    if (p.splitk > 1) BC_CHECK_ARG(p.slab != nullptr, "bc_gemm: splitk=%d needs a slab", p.splitk);
-    g.kt_per_split = bc_ceil_div(g.nk, p.splitk);
-    p.splitk = bc_ceil_div(g.nk, g.kt_per_split);   // no empty splits
+    info.n_out = g.n_out;
+    info.gn_finalize_fits = 0;
     g.div_rpb = make_fastdiv((unsigned)p.rows_per_batch);
     g.div_outw = make_fastdiv((unsigned)p.out_w);
     g.div_wout = make_fastdiv((unsigned)(p.a_mode == BC_A_CONV3X3 ? p.Wout : 1));
-
-    // ---- resolve tile configuration (explicit from the caller's plan, or heuristic) ----
-    bool fast_ok = (p.K % BK == 0);
-    if (p.a_mode == BC_A_CONV3X3) {
-        bool ups = (p.Hv != p.Hin) || (p.Wv != p.Win);
-        fast_ok = fast_ok && (p.Cin % BK == 0) && (!ups || (p.Hv == 2 * p.Hin && p.Wv == 2 * p.Win && p.stride == 1));
-    } else if (p.A2) {
-        fast_ok = fast_ok && (p.C1 % BK == 0);
-    }
-    BC_CHECK_ARG(!p.S || wreg, "bc_gemm: a folded shortcut (S) needs BC_TILE_WREG");
-    if (p.S) {
-        if (p.lds <= 0) p.lds = p.S2 ? p.S1 : p.Cs;
-        if (p.S2 && p.lds2 <= 0) p.lds2 = p.Cs - p.S1;
-        BC_CHECK_ARG(bc_conv_wreg_sc_ok(p), "bc_gemm: folded shortcut needs Cs%%64==0, S1%%64==0, pixel strides >= the channel counts and %%8==0, 16-byte "
-                                            "aligned sources, no upsample and no residual R (Cs=%d S1=%d lds=%d lds2=%d)", p.Cs, p.S1, p.lds, p.lds2);
-    }
-    static const bool force_generic = getenv("BC_GEMM_GENERIC") != nullptr;
-    static const int force_tile = getenv("BC_GEMM_TILE") ? atoi(getenv("BC_GEMM_TILE")) : 0;
-    if (force_generic) fast_ok = false;
-    if (halo) {
-        g.cfg = wreg ? BC_TILE_WREG : BC_TILE_HALO; g.bm = 128; g.bn = 160;
-    } else {
-        int cfg = (force_tile > 0 && force_tile < BC_TILE_COUNT) ? force_tile : p.tile_cfg;
-        int sk = p.splitk, bm = 0, bn = 0;
-        int rc0 = bc_gemm_plan(p.M, p.N, p.K, fast_ok ? 1 : 0, &cfg, &sk, &bm, &bn);
-        if (rc0) return rc0;
-        g.cfg = cfg; g.bm = bm; g.bn = bn;
-    }
     auto aligned16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-    g.vec_epilogue = p.out_mode == BC_OUT_F16 && g.n_out % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) &&
-                     (!p.R || (p.ldr % 8 == 0 && aligned16(p.R))) && (!p.R2 || (p.ldr2 % 8 == 0 && aligned16(p.R2)));
-    g.vec_transposed = p.out_mode == BC_OUT_F16_T && p.rows_per_batch % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) &&
-                       p.act == BC_ACT_NONE && !p.rowvec && !p.colscale && !p.R && !p.R2;
-    // (conv_halo.hip / conv_wreg.hip store an unsplit launch with the 8-column epilogue, 16-byte loads and stores, whatever the output's layout)
-    BC_CHECK_ARG(!halo || g.vec_epilogue, "bc_gemm: BC_TILE_HALO / BC_TILE_WREG need an fp16 row-major output, 16-byte aligned C / R / R2 and widths %% 8 == 0");
-    if (p.gn_tot) {
-        // (a workgroup's rows must belong to one image: its statistics go to that image's totals)
+    if (gw || p.tile_cfg == BC_TILE_G256) {
+        if (gw) {
+            BC_CHECK_ARG(bc_gemm_wreg_ok(p, p.tile_cfg), "bc_gemm: BC_TILE_GW* needs dense A, M%%64==0, N%%(64 NT)==0, K%%320==0 (C1%%320==0), fp16 row-major "
+                         "output, no split-K / row vector / affine table (a_tot1: one source, groups | K <= 2560, no activation) (M=%d N=%d K=%d C1=%d)", p.M, p.N, p.K, p.C1);
+            g.nk = p.K / 32;
+            g.bm = 64; g.bn = 64 * bc_gemm_wreg_nt(p.tile_cfg);
+            g.vec_epilogue = g.n_out % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) && (!p.R || (p.ldr % 8 == 0 && aligned16(p.R))) &&
+                             (!p.R2 || (p.ldr2 % 8 == 0 && aligned16(p.R2))) && (!p.C_t || aligned16(p.C_t));
+            BC_CHECK_ARG(g.vec_epilogue, "bc_gemm: BC_TILE_GW* needs 16-byte aligned C / R / R2 / C_t and widths %% 8 == 0");
+            g.vec_transposed = 0; g.nband = 1;
+            info.family = BC_FAMILY_GEMM_WREG;
+            info.stat_rows = stat_rows_if(p, g.bm, [&](const BcGemm& q) { return bc_gemm_wreg_ok(q, q.tile_cfg); });
+        } else {
+            BC_CHECK_ARG(bc_gemm256_ok(p), "bc_gemm: BC_TILE_G256 needs dense A (C1%%128==0), M%%256==0, N%%256==0, K%%128==0, no split-K, fp16 row-major "
+                         "or transposed (bias / alpha only) output, n_t0%%256==0 with C_t (M=%d N=%d K=%d out_mode=%d)", p.M, p.N, p.K, p.out_mode);
+            g.nk = p.K / BK;
+            g.bm = 256; g.bn = 256;
+            g.vec_epilogue = g.n_out % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) && (!p.R || (p.ldr % 8 == 0 && aligned16(p.R))) &&
+                             (!p.R2 || (p.ldr2 % 8 == 0 && aligned16(p.R2))) && (!p.rowvec || p.ld_rowvec % 8 == 0) && (!p.C_t || aligned16(p.C_t)) &&
+                             (!p.A2 || aligned16(p.A2));
+            BC_CHECK_ARG(g.vec_epilogue, "bc_gemm: BC_TILE_G256 needs 16-byte aligned C / C_t / R / R2 / A2 and widths %% 8 == 0");
+            g.vec_transposed = p.out_mode == BC_OUT_F16_T; g.nband = 0;
+            info.family = BC_FAMILY_G256;
+            // (a tile's 256 rows inside one image)
+            info.stat_rows = (p.rows_per_batch % 256 == 0 && p.M % p.rows_per_batch == 0) ? stat_rows_if(p, g.bm, [](const BcGemm& q) { return bc_gemm256_ok(q); }) : 0;
+        }
+        g.kt_per_split = g.nk; p.splitk = 1;
+        g.div_wout = make_fastdiv(1u);
+        g.cfg = p.tile_cfg;
+    } else {
+        const bool wreg = p.tile_cfg == BC_TILE_WREG;
+        const bool halo = p.tile_cfg == BC_TILE_HALO || wreg;
+        if (halo) {
+            if (p.lda <= 0) p.lda = p.A2 ? p.C1 : p.Cin;          // pixel stride of A: 0 = its channel count (a wider NHWC view passes its own)
+            if (p.A2 && p.lda2 <= 0) p.lda2 = p.Cin - p.C1;
+            BC_CHECK_ARG(p.lda >= (p.A2 ? p.C1 : p.Cin) && p.lda % 8 == 0, "bc_gemm: BC_TILE_HALO lda=%d must be >= the channel count and a multiple of 8", p.lda);
+            BC_CHECK_ARG(!p.A2 || (p.lda2 >= p.Cin - p.C1 && p.lda2 % 8 == 0), "bc_gemm: BC_TILE_HALO lda2=%d must be >= Cin - C1 and a multiple of 8", p.lda2);
+            BC_CHECK_ARG(bc_conv_halo_ok(p), "bc_gemm: BC_TILE_HALO needs a 3x3 stride-1 pad-1 convolution with Cin%%64==0, N%%160==0, "
+                                             "Wout%%16==0, Hout%%8==0 (Cin=%d N=%d %dx%d)", p.Cin, p.N, p.Hout, p.Wout);
+            BC_CHECK_ARG(!p.a_affine || p.a_act == BC_ACT_NONE || p.a_act == BC_ACT_SILU, "bc_gemm: a_act must be NONE or SILU");
+            BC_CHECK_ARG(!p.a_tot1 || (p.a_gamma && p.a_beta && p.a_groups > 0 && p.Cin % p.a_groups == 0 && (!p.A2 || p.a_tot2)),
+                         "bc_gemm(halo conv): in-kernel GroupNorm finalize needs a_gamma, a_beta, a_groups | Cin and the partials of every source");
+        } else {
+            BC_CHECK_ARG(p.a_affine == nullptr && p.a_tot1 == nullptr, "bc_gemm: the fused GroupNorm prologue is only available on BC_TILE_HALO");
+        }
+        BC_CHECK_ARG(!p.S || wreg, "bc_gemm: a folded shortcut (S) needs BC_TILE_WREG");
+        if (p.S) {
+            if (p.lds <= 0) p.lds = p.S2 ? p.S1 : p.Cs;
+            if (p.S2 && p.lds2 <= 0) p.lds2 = p.Cs - p.S1;
+            BC_CHECK_ARG(bc_conv_wreg_sc_ok(p), "bc_gemm: folded shortcut needs Cs%%64==0, S1%%64==0, pixel strides >= the channel counts and %%8==0, 16-byte "
+                                                "aligned sources, no upsample and no residual R (Cs=%d S1=%d lds=%d lds2=%d)", p.Cs, p.S1, p.lds, p.lds2);
+        }
+        // ---- the fast-path rule and the environment overrides (read here and nowhere else) ----
+        bool fast_ok = (p.K % BK == 0);
+        if (p.a_mode == BC_A_CONV3X3) {
+            bool ups = (p.Hv != p.Hin) || (p.Wv != p.Win);
+            fast_ok = fast_ok && (p.Cin % BK == 0) && (!ups || (p.Hv == 2 * p.Hin && p.Wv == 2 * p.Win && p.stride == 1));
+        } else if (p.A2) {
+            fast_ok = fast_ok && (p.C1 % BK == 0);
+        }
+        static const bool force_generic = getenv("BC_GEMM_GENERIC") != nullptr;
+        static const int force_tile = getenv("BC_GEMM_TILE") ? atoi(getenv("BC_GEMM_TILE")) : 0;
+        if (force_generic) fast_ok = false;
+        int cfg = (force_tile > 0 && force_tile < BC_TILE_COUNT) ? force_tile : p.tile_cfg, bm = 0, bn = 0;
+        if (choose && !halo) {                          // the cost model's (tile, split) pair
+            int sk = -1;
+            int rc0 = bc_gemm_plan(p.M, p.N, p.K, fast_ok ? 1 : 0, &cfg, &sk, &bm, &bn);
+            if (rc0) return rc0;
+            p.splitk = sk;
+        }
+        // ---- the final split count ----
+        g.nk = bc_ceil_div(p.K, BK);
+        if (halo) g.nk = p.Cin / BK;                    // split-K counts 64-channel chunks (each covers the nine taps)
+        if (wreg && p.S) g.nk += p.Cs / BK;             // ... and those of the folded 1x1 shortcut (bc_conv_wreg_split deals both kinds out to the splits)
+        if (p.splitk > g.nk) p.splitk = g.nk;
+        g.kt_per_split = bc_ceil_div(g.nk, p.splitk);
+        p.splitk = bc_ceil_div(g.nk, g.kt_per_split);   // no empty splits
+        // ---- the tile configuration (explicit from the caller's plan, or the cost model's) ----
+        if (halo) {
+            g.cfg = wreg ? BC_TILE_WREG : BC_TILE_HALO; g.bm = 128; g.bn = 160;
+            int rc0 = wreg ? bc_conv_wreg_split(g) : bc_conv_halo_split(g);
+            if (rc0) return rc0;
+            if (p.a_groups > 0 && p.Cin % p.a_groups == 0) info.gn_finalize_fits = wreg ? bc_conv_wreg_fin_fits(g) : bc_conv_halo_fin_fits(g);
+            info.family = wreg ? BC_FAMILY_CONV_WREG : BC_FAMILY_HALO;
+        } else {
+            int sk = p.splitk;
+            int rc0 = bc_gemm_plan(p.M, p.N, p.K, fast_ok ? 1 : 0, &cfg, &sk, &bm, &bn);
+            if (rc0) return rc0;
+            g.cfg = cfg; g.bm = bm; g.bn = bn;
+            info.family = fast_ok ? BC_FAMILY_FAST : BC_FAMILY_GENERIC;
+        }
+        g.vec_epilogue = p.out_mode == BC_OUT_F16 && g.n_out % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) &&
+                         (!p.R || (p.ldr % 8 == 0 && aligned16(p.R))) && (!p.R2 || (p.ldr2 % 8 == 0 && aligned16(p.R2)));
+        g.vec_transposed = p.out_mode == BC_OUT_F16_T && p.rows_per_batch % 8 == 0 && p.ldc % 8 == 0 && aligned16(p.C) &&
+                           p.act == BC_ACT_NONE && !p.rowvec && !p.colscale && !p.R && !p.R2;
+        // (conv_halo.hip / conv_wreg.hip store an unsplit launch with the 8-column epilogue, 16-byte loads and stores, whatever the output's layout)
+        BC_CHECK_ARG(!halo || g.vec_epilogue, "bc_gemm: BC_TILE_HALO / BC_TILE_WREG need an fp16 row-major output, 16-byte aligned C / R / R2 and widths %% 8 == 0");
+        // statistics come from the fast-path / convolution epilogues or the split-K reducer, 16 bytes at a time; a workgroup's rows must belong
+        // to one image: its statistics go to that image's totals
         const int slab_rows = p.splitk > 1 ? SK_ROWS : g.bm;
-        BC_CHECK_ARG((fast_ok || halo || p.splitk > 1) && g.vec_epilogue && p.N % 4 == 0 && p.rows_per_batch % slab_rows == 0 &&
-                         p.M % p.rows_per_batch == 0,
-                     "bc_gemm: fused GroupNorm statistics need the fast path or split-K, fp16 row-major output and rows_per_batch%%%d==0", slab_rows);
+        info.stat_rows = ((fast_ok || halo || p.splitk > 1) && g.vec_epilogue && p.N % 4 == 0 && p.rows_per_batch % slab_rows == 0 &&
+                          p.M % p.rows_per_batch == 0) ? slab_rows : 0;
     }
-    int rc = wreg ? bc_conv_wreg_launch(g, stream) : halo ? bc_conv_halo_launch(g, stream) : fast_ok ? bc_gemm_fast_try(g, stream) : -1;
-    if (rc > 0) return rc;
-    if (rc < 0) {
-        BC_CHECK_ARG(!p.gn_tot || p.splitk > 1, "bc_gemm: fused GroupNorm statistics are only produced by the fast path or the split-K reducer");
-        rc = (g.bn == 64) ? launch_gemm<256, 64, 4, 1>(g, stream) : launch_gemm<128, 128, 2, 2>(g, stream);
-        if (rc) return rc;
+    info.tile_cfg = g.cfg; info.bm = g.bm; info.bn = g.bn;
+    info.splitk = p.splitk;
+    info.slab_elems = p.splitk > 1 ? (long long)p.splitk * p.M * p.N : 0;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int bc_gemm_resolve(const BcGemm* in, BcGemmInfo* out) {
+    BC_CHECK_ARG(in != nullptr && out != nullptr, "bc_gemm_resolve: null argument");
+    GemmArgs g;
+    g.p = *in;
+    int rc = resolve(g, *out, true);
+    if (rc) return rc;
+    switch (out->family) {
+        case BC_FAMILY_FAST: bc_gemm_fast_kernel_name(g, out->kernel, sizeof(out->kernel)); break;
+        case BC_FAMILY_HALO: bc_conv_halo_kernel_name(g, out->kernel, sizeof(out->kernel)); break;
+        case BC_FAMILY_CONV_WREG: bc_conv_wreg_kernel_name(g, out->kernel, sizeof(out->kernel)); break;
+        case BC_FAMILY_GEMM_WREG: bc_gemm_wreg_kernel_name(g, out->kernel, sizeof(out->kernel)); break;
+        case BC_FAMILY_G256: snprintf(out->kernel, sizeof(out->kernel), "gemm256_kernel"); break;
+        default: snprintf(out->kernel, sizeof(out->kernel), "%s", generic_kernel_name(g)); break;
     }
+    return 0;
+}
+
+extern "C" int bc_gemm(const BcGemm* pp, bc_stream stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BC_CHECK_ARG(pp != nullptr, "bc_gemm: null params");
+    GemmArgs g;
+    g.p = *pp;
+    BcGemmInfo info;
+    int rc = resolve(g, info, false);
+    if (rc) return rc;
+    const BcGemm& p = g.p;
+    // the two checks that need the pointers a planner binds after it resolved the record
+    BC_CHECK_ARG(p.splitk == 1 || p.slab != nullptr, "bc_gemm: splitk=%d needs a slab", p.splitk);
+    BC_CHECK_ARG(!p.gn_tot || info.stat_rows > 0, "bc_gemm: this launch cannot produce GroupNorm statistics: they need the fast path, a BC_TILE_* kernel of "
+                 "its own or split-K, an fp16 row-major output in 16-byte steps and whole workgroups (%d rows) inside one image (rows_per_batch=%d)",
+                 p.splitk > 1 ? SK_ROWS : g.bm, p.rows_per_batch);
+    BC_CHECK_ARG(!p.a_tot1 || info.family == BC_FAMILY_GEMM_WREG || info.gn_finalize_fits,
+                 "bc_gemm: channel span %d per workgroup too wide for the in-kernel GroupNorm finalize: use bc_gn_finalize + a_affine or raise splitk",
+                 g.halo_cps * 64 + 2 * (p.Cin / std::max(1, p.a_groups)));
+    switch (info.family) {
+        case BC_FAMILY_GEMM_WREG: return bc_gemm_wreg_launch(g, stream);
+        case BC_FAMILY_G256: return bc_gemm256_launch(g, stream);
+        case BC_FAMILY_CONV_WREG: rc = bc_conv_wreg_launch(g, stream); break;
+        case BC_FAMILY_HALO: rc = bc_conv_halo_launch(g, stream); break;
+        case BC_FAMILY_FAST: rc = bc_gemm_fast_launch(g, stream); break;
+        default: rc = launch_generic(g, stream); break;
+    }
+    if (rc) return rc;
     if (p.splitk > 1) {
         if (tl_probe) {                                       // (profiling replays: where the main kernel ends and the reducer starts)
             BC_CHECK_HIP(hipEventRecord(tl_probe, stream));

@@ -367,21 +367,36 @@ __device__ __forceinline__ void tile_epilogue_transposed(const GemmArgs& g, cons
 
 }  // namespace bcg
 
-// gemm_fast.hip: returns 0 when it launched the GEMM, -1 when the problem is outside its fast path, >0 on error.
-int bc_gemm_fast_try(const bcg::GemmArgs& g, hipStream_t stream);
+// bc_gemm (gemm.hip) is "resolve, then launch": the family, tile, final split and limits of a BcGemm are decided ONCE, on the host, by gemm.hip's
+// resolve (also behind bc_gemm_resolve); the launchers below run what it resolved.  Each file that owns a launcher's switch also writes the
+// name of the instantiation it picks (*_kernel_name: as a profiler prints it; built by bc_gemm_resolve only, never on the launch path).
+// gemm_fast.hip: the LDS-DMA fast path (BC_FAMILY_FAST).
+int bc_gemm_fast_launch(const bcg::GemmArgs& g, hipStream_t stream);
+void bc_gemm_fast_kernel_name(const bcg::GemmArgs& g, char* out, int n);
 // conv_halo.hip: LDS-resident input-halo 3x3 convolution with the fused GroupNorm prologue (BC_TILE_HALO).
 int bc_conv_halo_ok(const BcGemm& p);
 int bc_conv_halo_max_chunks_impl();
 void bc_gemm_set_probe(hipEvent_t e);      // gemm.hip: event recorded between the main kernel and the split-K reducer (nullptr: off)
 bool bc_gemm_probe_hit();
+// the K split of a launch from p.splitk: chunks in total / per split and the final split count (no empty splits) into g; refuses more chunks
+// per workgroup than its affine table holds
+int bc_conv_halo_split(bcg::GemmArgs& g);
+// 1 when a workgroup's channel span at that split fits the scratch of the in-kernel GroupNorm finalize (a_groups > 0 divides Cin)
+int bc_conv_halo_fin_fits(const bcg::GemmArgs& g);
 int bc_conv_halo_launch(bcg::GemmArgs& g, hipStream_t stream);
-// conv_wreg.hip: the same convolution with the weights streamed into VGPRs from a packed fragment stream (BC_TILE_WREG).
+void bc_conv_halo_kernel_name(const bcg::GemmArgs& g, char* out, int n);
+// conv_wreg.hip: the same convolution with the weights streamed into VGPRs from a packed fragment stream (BC_TILE_WREG); its split also
+// deals the one-tap chunks of a folded shortcut (BcGemm.S) out to the splits.
+int bc_conv_wreg_split(bcg::GemmArgs& g);
+int bc_conv_wreg_fin_fits(const bcg::GemmArgs& g);
 int bc_conv_wreg_launch(bcg::GemmArgs& g, hipStream_t stream);
+void bc_conv_wreg_kernel_name(const bcg::GemmArgs& g, char* out, int n);
 int bc_conv_wreg_sc_ok(const BcGemm& p);     // the folded 1x1 shortcut (BcGemm.S) of a BC_TILE_WREG convolution is within the kernel's limits
 // gemm_wreg.hip: small-M projections with the weights streamed into VGPRs (BC_TILE_GW*).
 int bc_gemm_wreg_nt(int tile_cfg);
 int bc_gemm_wreg_ok(const BcGemm& p, int tile_cfg);
 int bc_gemm_wreg_launch(const bcg::GemmArgs& g, hipStream_t stream);
+void bc_gemm_wreg_kernel_name(const bcg::GemmArgs& g, char* out, int n);
 // gemm256.hip: large-M dense projections on 256 x 256 tiles, 8 waves, 8-phase LDS-DMA pipeline, persistent (BC_TILE_G256).
 int bc_gemm256_ok(const BcGemm& p);
 int bc_gemm256_launch(const bcg::GemmArgs& g, hipStream_t stream);

@@ -328,26 +328,38 @@ int launch_mode(const GemmArgs& g, bool conv, bool ups, hipStream_t stream) {
 
 }  // namespace
 
-int bc_gemm_fast_try(const GemmArgs& g, hipStream_t stream) {
-    const BcGemm& p = g.p;
-    if (p.K % BK != 0) return -1;
-    const bool conv = p.a_mode == BC_A_CONV3X3;
-    bool ups = false;
-    if (conv) {
-        if (p.Cin % BK != 0) return -1;
-        ups = (p.Hv != p.Hin) || (p.Wv != p.Win);
-        if (ups && !(p.Hv == 2 * p.Hin && p.Wv == 2 * p.Win && p.stride == 1)) return -1;
-    } else if (p.A2 && (p.C1 % BK != 0)) {
-        return -1;
-    }
+// The tile configurations of this kernel: BC_TILE_* -> the template arguments BM, BN, WM, WN, NS.  ONE table for the launcher's switch and
+// for the name a profiler prints, so that the two cannot drift.
+#define BC_FAST_TILES(X)                 \
+    X(BC_TILE_256x128, 256, 128, 4, 2, 3)    \
+    X(BC_TILE_128x128_S3, 128, 128, 2, 2, 3) \
+    X(BC_TILE_128x128_S2, 128, 128, 2, 2, 2) \
+    X(BC_TILE_256x64_S2, 256, 64, 4, 1, 2)   \
+    X(BC_TILE_256x64_S3, 256, 64, 4, 1, 3)   \
+    X(BC_TILE_128x64, 128, 64, 2, 2, 3)      \
+    X(BC_TILE_64x64, 64, 64, 2, 2, 4)
+
+static bool fast_upsamples(const BcGemm& p) { return p.a_mode == BC_A_CONV3X3 && (p.Hv != p.Hin || p.Wv != p.Win); }
+
+// Launches a problem bc_gemm_resolve put on the fast path (BC_FAMILY_FAST: the eligibility is decided there, once).
+int bc_gemm_fast_launch(const GemmArgs& g, hipStream_t stream) {
+    const bool conv = g.p.a_mode == BC_A_CONV3X3, ups = fast_upsamples(g.p);
     switch (g.cfg) {
-        case BC_TILE_256x128:    return launch_mode<256, 128, 4, 2, 3>(g, conv, ups, stream);
-        case BC_TILE_128x128_S3: return launch_mode<128, 128, 2, 2, 3>(g, conv, ups, stream);
-        case BC_TILE_128x128_S2: return launch_mode<128, 128, 2, 2, 2>(g, conv, ups, stream);
-        case BC_TILE_256x64_S2:  return launch_mode<256, 64, 4, 1, 2>(g, conv, ups, stream);
-        case BC_TILE_256x64_S3:  return launch_mode<256, 64, 4, 1, 3>(g, conv, ups, stream);
-        case BC_TILE_128x64:     return launch_mode<128, 64, 2, 2, 3>(g, conv, ups, stream);
-        case BC_TILE_64x64:      return launch_mode<64, 64, 2, 2, 4>(g, conv, ups, stream);
-        default: return -1;
+#define X(cfg, ...) case cfg: return launch_mode<__VA_ARGS__>(g, conv, ups, stream);
+        BC_FAST_TILES(X)
+#undef X
+        default: bc_set_error("bc_gemm: not a fast-path tile configuration (%d)", g.cfg); return 1;
     }
+}
+
+void bc_gemm_fast_kernel_name(const GemmArgs& g, char* out, int n) {
+    const char* tile = "?";
+    switch (g.cfg) {
+#define X(cfg, ...) case cfg: tile = #__VA_ARGS__; break;
+        BC_FAST_TILES(X)
+#undef X
+        default: break;
+    }
+    const bool conv = g.p.a_mode == BC_A_CONV3X3;
+    snprintf(out, n, "gemm_fast_kernel<%s, %s, %s>", tile, conv ? "true" : "false", fast_upsamples(g.p) ? "true" : "false");
 }

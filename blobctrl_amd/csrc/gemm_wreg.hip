@@ -682,6 +682,12 @@ int bc_gemm_wreg_launch(const GemmArgs& g, hipStream_t stream) {
     }
 }
 
+// ... and what a profiler calls the instantiation that switch picks: gemm_wreg_kernel<NT, R, SM>
+void bc_gemm_wreg_kernel_name(const GemmArgs& g, char* out, int n) {
+    const int nt = bc_gemm_wreg_nt(g.cfg);
+    snprintf(out, n, "gemm_wreg_kernel<%d, %d, %s>", nt, nt == 5 ? 10 : 20, nt == 2 && g.p.sm_group ? "true" : "false");
+}
+
 extern "C" int bc_gemm_wreg_eligible(int M, int N, int K, int C1, int tile_cfg) {
     BcGemm p = {};
     p.a_mode = BC_A_DENSE; p.M = M; p.N = N; p.K = K; p.C1 = C1; p.out_mode = BC_OUT_F16; p.splitk = 1; p.alpha = 1.0f;

@@ -65,6 +65,37 @@ def encode_gn_tot(sums: torch.Tensor) -> torch.Tensor:
     return sl.reshape(*sums.shape[:-1], 6).contiguous()
 
 
+def conv_split_request(nch, base, wreg):
+    """The K split asked of a BC_TILE_HALO / BC_TILE_WREG (`wreg`) convolution of `nch` 64-channel chunks whose unsplit launch has `base`
+    workgroups: the planner's POLICY (how many workgroups a pass should have); what a split count then means - chunks per split, the limits
+    of one workgroup - is the library's (bc_gemm_resolve)."""
+    # Workgroups a split pass aims for and the fewest 64-channel chunks per workgroup.  With conv_wreg.hip (tap loop 867
+    # instead of 1445 cycles) a workgroup's fixed costs weigh more and a pass that leaves CUs to the other trunk is worth
+    # more than one that fills the chip: 192 / 3 instead of round 2's 256 / 2 - the UNet's 32 x 64 convolutions (128 pixel x
+    # column tiles) now run unsplit, the 8 x 16 level in 5 instead of 10 splits - is 9.53 -> 9.29 ms per step (same box,
+    # two rounds; 128 ... 192 within 0.05 ms of each other, 224: 9.56, 384: 9.79).
+    # Round 5, re-swept on the final kernels (two boxes, two rounds each, ms per step): 192: 9.386 / 9.382 and 9.160 / 9.148;
+    # 144: 9.354 / 9.339; 128: 9.323 / 9.330 and 9.081 / 9.087; 112: 9.070 / 9.049; 96: 9.474 / 9.493 - the UNet's 16 x 32
+    # convolutions in 2 instead of 3 splits, BlobNet's in 4 instead of 6 (fewer slabs for the reducer); batch 2: 15.58 / 15.74
+    # vs 15.85 / 15.78; batch 8 and 768^2 batch 4 unchanged (52.8 / 52.7 vs 52.7 / 52.6; 80.5 / 80.4 vs 80.5 / 80.4).
+    target = opt("halo_ctas") or (128 if wreg else 256)
+    min_cps = opt("halo_min_cps") or (3 if wreg else 2)
+    # workgroups from which one pass is taken unsplit: 2/3 of the target.  (From half fill - BC_HALO_FULL=128 - the 64 x 128
+    # BlobNet and 32 x 64 UNet convolutions run as one pass instead of two K halves + a reducer: 13 reducer launches and
+    # 0.7 GB of slab traffic less, and the step gains 0.4 % (10.59 -> 10.55 ms, round 3, same box) because the other trunk's
+    # kernels fill the idle CUs - but this kernel's own average goes from 37.5 to 45.8 us (0.24 -> 0.19 of peak) and the
+    # serialised kernel time of a step rises by 0.76 ms: not the default.)
+    full = opt("halo_full") or target * 2 // 3
+    # conv_wreg.hip: with five chunks or fewer a half-filled pass is also the faster one in isolation (64 x 128 BlobNet: 43.8 us
+    # unsplit vs 45.7 us as two K halves + reducer, cold weights); with ten chunks the split wins (32 x 64 UNet: 61.4 vs 54.5)
+    short = wreg and base >= target // 2 and nch <= 5
+    splitk = 1 if (base >= full or short) else max(1, min(nch // min_cps, -(-target // base)))
+    # asked for without empty splits.  A folded 1x1 shortcut does not change the request: the K split is chosen as for the convolution alone
+    # and every split takes its share of the nine-tap chunks AND of the shortcut's one-tap chunks (a twentieth of the cost each: splitting the
+    # chunk sequence by count gave one split all the convolution - [1024, 1280, 9 * 1280 + 2560] 120.9 us against 98.2 us for the two launches).
+    return -(-nch // -(-nch // splitk))
+
+
 def ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
@@ -381,17 +412,12 @@ class Recorder:
         return h_out, s_out
 
     # ------------------------------------------------------------------ GEMM family
-    def plan_gemm(self, M, N, K, fast, mode, tile_cfg=0, splitk=None):
-        """(tile_cfg, splitk, bm, bn) for a GEMM: tuning table first, then the library's cost model (bc_gemm_plan)."""
-        sk = -1 if splitk is None else splitk
-        if tile_cfg == 0 and splitk is None and fast:
-            hit = tuning_table().get(f"{mode}|{M}|{N}|{K}")
-            if hit:
-                tile_cfg, sk = int(hit[0]), int(hit[1])
-        c, s_, bm, bn = C.c_int(tile_cfg), C.c_int(sk), C.c_int(0), C.c_int(0)
-        _lib.check(self.lib.bc_gemm_plan(M, N, K, 1 if fast else 0, C.byref(c), C.byref(s_), C.byref(bm), C.byref(bn)),
-                   "bc_gemm_plan")
-        return c.value, s_.value, bm.value, bn.value
+    def resolve(self, g, kind="gemm"):
+        """How the library launches the BcGemm `g` (include/blobctrl_hip.h: bc_gemm_resolve - kernel family, tile, final split count, slab,
+        statistics rows, kernel name): the one owner of those decisions.  Raises with the library's message when bc_gemm would refuse it."""
+        info = _lib.BcGemmInfo()
+        _lib.check(self.lib.bc_gemm_resolve(C.byref(g), C.byref(info)), f"bc_gemm({kind})")
+        return info
 
     def gemm(self, *, A, W, M, N, K, out=None, out_mode=_lib.OUT_F16, ldc=None, A2=None, C1=0, lda=None, lda2=0,
              conv=None, bias=None, rowvec=None, ld_rowvec=0, rowvec_idx=None, rowvec_step=0, rows_per_batch=0, act=_lib.ACT_NONE, colscale=None,
@@ -401,6 +427,7 @@ class Recorder:
              w_bstride=0, vec_bstride=0, sm_group=0, sm_valid=0, sm_keep=0, gn_tot_out=None, S=None, S2=None, lds=0, lds2=0, S1=0, Cs=0):
         """Record one bc_gemm.  `conv` = dict(Cin, Hin, Win, Hv, Wv, Hout, Wout, stride) for the 3x3 gather mode.
         Pointer offsets are in ELEMENTS of the respective tensor."""
+        # (the output's width as BcGemm defines it: the ldc default and the overlap test below come before the library can be asked)
         n_out = N // 2 if act == _lib.ACT_GEGLU else (N // sm_group * sm_keep if sm_group else N)
         g = BcGemm()
         g.A = A.data_ptr() + a_offset * A.element_size()
@@ -445,88 +472,40 @@ class Recorder:
         g.C_t, g.ldc_t, g.n_t0 = ptr(C_t), ldc_t, n_t0
         g.w_bstride, g.vec_bstride, g.sm_group, g.sm_valid, g.sm_keep = w_bstride, vec_bstride, sm_group, sm_valid, sm_keep
         if S is not None:                # 1x1 shortcut over (S | S2) folded into a BC_TILE_WREG convolution: one-tap chunks behind the nine-tap ones
-            assert tile_cfg == _lib.TILE_WREG and R is None and Cs % 64 == 0 and Cs > 0
             g.S, g.S2, g.lds, g.lds2, g.S1, g.Cs = ptr(S), ptr(S2), lds, lds2, S1, Cs
-        # mirror of the C-side fast-path eligibility (bc_gemm)
-        fast = K % 64 == 0
-        mode = "dense"
-        if conv:
-            hv, wv = conv.get("Hv", conv["Hin"]), conv.get("Wv", conv["Win"])
-            ups = (hv, wv) != (conv["Hin"], conv["Win"])
-            fast = fast and conv["Cin"] % 64 == 0 and (not ups or ((hv, wv) == (2 * conv["Hin"], 2 * conv["Win"])
-                                                                  and conv.get("stride", 1) == 1))
-            mode = "ups" if ups else f"conv{conv.get('stride', 1)}"
-        elif A2 is not None:
-            fast = fast and C1 % 64 == 0
-        if os.environ.get("BC_GEMM_GENERIC"):
-            fast = False
+        g.tile_cfg, g.splitk = tile_cfg, (-1 if splitk is None else splitk)           # (-1: the library's cost model chooses)
+        # a problem the library refuses raises here: nothing recorded, nothing carved.  What it says of the struct so far (tile shape, family)
+        # is what the policies below look at; what they change is resolved again before it is recorded.
+        info = self.resolve(g, kind)
         if tile_cfg in (_lib.TILE_HALO, _lib.TILE_WREG):
-            # LDS-resident input-halo convolution (conv_halo.hip): split-K counts 64-channel chunks; fill ~one workgroup per CU
-            nch = conv["Cin"] // 64
-            base = (M // 128) * (N // 160)
-            explicit_sk, sk_req = splitk, None
+            # LDS-resident input-halo convolution (conv_halo.hip / conv_wreg.hip): split-K counts 64-channel chunks
             if splitk is None:
-                # Workgroups a split pass aims for and the fewest 64-channel chunks per workgroup.  With conv_wreg.hip (tap loop 867
-                # instead of 1445 cycles) a workgroup's fixed costs weigh more and a pass that leaves CUs to the other trunk is worth
-                # more than one that fills the chip: 192 / 3 instead of round 2's 256 / 2 - the UNet's 32 x 64 convolutions (128 pixel x
-                # column tiles) now run unsplit, the 8 x 16 level in 5 instead of 10 splits - is 9.53 -> 9.29 ms per step (same box,
-                # two rounds; 128 ... 192 within 0.05 ms of each other, 224: 9.56, 384: 9.79).
-                # Round 5, re-swept on the final kernels (two boxes, two rounds each, ms per step): 192: 9.386 / 9.382 and 9.160 / 9.148;
-                # 144: 9.354 / 9.339; 128: 9.323 / 9.330 and 9.081 / 9.087; 112: 9.070 / 9.049; 96: 9.474 / 9.493 - the UNet's 16 x 32
-                # convolutions in 2 instead of 3 splits, BlobNet's in 4 instead of 6 (fewer slabs for the reducer); batch 2: 15.58 / 15.74
-                # vs 15.85 / 15.78; batch 8 and 768^2 batch 4 unchanged (52.8 / 52.7 vs 52.7 / 52.6; 80.5 / 80.4 vs 80.5 / 80.4).
-                target = opt("halo_ctas") or (128 if tile_cfg == _lib.TILE_WREG else 256)
-                min_cps = opt("halo_min_cps") or (3 if tile_cfg == _lib.TILE_WREG else 2)
-                # workgroups from which one pass is taken unsplit: 2/3 of the target.  (From half fill - BC_HALO_FULL=128 - the 64 x 128
-                # BlobNet and 32 x 64 UNet convolutions run as one pass instead of two K halves + a reducer: 13 reducer launches and
-                # 0.7 GB of slab traffic less, and the step gains 0.4 % (10.59 -> 10.55 ms, round 3, same box) because the other trunk's
-                # kernels fill the idle CUs - but this kernel's own average goes from 37.5 to 45.8 us (0.24 -> 0.19 of peak) and the
-                # serialised kernel time of a step rises by 0.76 ms: not the default.)
-                full = opt("halo_full") or target * 2 // 3
-                # conv_wreg.hip: with five chunks or fewer a half-filled pass is also the faster one in isolation (64 x 128 BlobNet: 43.8 us
-                # unsplit vs 45.7 us as two K halves + reducer, cold weights); with ten chunks the split wins (32 x 64 UNet: 61.4 vs 54.5)
-                short = tile_cfg == _lib.TILE_WREG and base >= target // 2 and nch <= 5
-                splitk = 1 if (base >= full or short) else max(1, min(nch // min_cps, -(-target // base)))
-            splitk = max(splitk, -(-nch // self.lib.bc_conv_halo_max_chunks()))     # (the workgroup's affine table lives in LDS)
-            cps = -(-nch // max(1, splitk))
-            cfg, sk, bm, bn = tile_cfg, -(-nch // cps), 128, 160
-            if Cs:
-                # a folded 1x1 shortcut: the K split is chosen as for the convolution alone (above) and every split takes its share of the
-                # nine-tap chunks AND of the shortcut's one-tap chunks (a twentieth of the cost each: splitting the chunk sequence by count gave
-                # one split all the convolution - [1024, 1280, 9 * 1280 + 2560] 120.9 us against 98.2 us for the two launches).  The numbers
-                # below are bc_gemm's and bc_conv_wreg_launch's own arithmetic (the slab is reserved for the resulting split count).
-                nsc = Cs // 64
-                sk_req = min(sk if explicit_sk is None else splitk, nch + nsc)      # (what bc_gemm is given: it repeats this arithmetic)
-                s2 = -(-(nch + nsc) // -(-(nch + nsc) // sk_req))
-                cps = -(-nch // s2)
-                sk = max(-(-nch // cps), -(-nsc // -(-nsc // s2)))
-            fast, mode = True, "halo"
-            sc_mode = "_sc" if S is not None else ""
+                g.splitk = conv_split_request(conv["Cin"] // 64, (M // info.bm) * (N // info.bn), tile_cfg == _lib.TILE_WREG)
+            mode = "halo"
             if a_gn is not None:
                 # GroupNorm in front of the convolution: a_gn = dict(x1, C1, x2, C2, B, HW, G, eps, gamma, beta).  The finalize runs
                 # inside the convolution's prologue - every workgroup reads the statistics totals (six words per channel) of the groups
-                # overlapping its channel span - whenever that span fits the kernel's scratch, else as its own launch.
-                G_ = a_gn["G"]
-                span = cps * 64 + 2 * (conv["Cin"] // G_)
+                # overlapping its channel span - whenever that span fits the kernel's scratch at the resolved split, else as its own launch.
                 t1, t2 = self.gn_sources(a_gn["x1"], a_gn["C1"], a_gn["x2"], a_gn["C2"], a_gn["B"], a_gn["HW"], a_gn["G"])
-                fin_max = 2752 if tile_cfg == _lib.TILE_WREG else 712          # (FIN_MAX_CH of conv_wreg.hip / conv_halo.hip)
-                if span <= fin_max and not opt("gn_finalize_launch"):
+                fused = not opt("gn_finalize_launch")
+                if fused:
                     g.a_tot1, g.a_tot2 = ptr(t1), ptr(t2)
-                    g.a_gamma, g.a_beta, g.a_groups, g.a_eps = ptr(a_gn["gamma"]), ptr(a_gn["beta"]), G_, a_gn["eps"]
+                    g.a_gamma, g.a_beta, g.a_groups, g.a_eps = ptr(a_gn["gamma"]), ptr(a_gn["beta"]), a_gn["G"], a_gn["eps"]
+                    fused = bool(self.resolve(g, kind).gn_finalize_fits)
+                if fused:
                     self.keep.append((t1, t2, a_gn["gamma"], a_gn["beta"]))
                     for t in (t1, t2, a_gn["gamma"], a_gn["beta"]):
                         self.register(t)
                     mode = "halo_gnfin"
                 else:
-                    a_affine = self.gn_affine(a_gn["x1"], a_gn["C1"], a_gn["x2"], a_gn["C2"], a_gn["B"], a_gn["HW"], G_, a_gn["eps"],
+                    a_affine = self.gn_affine(a_gn["x1"], a_gn["C1"], a_gn["x2"], a_gn["C2"], a_gn["B"], a_gn["HW"], a_gn["G"], a_gn["eps"],
                                               a_gn["gamma"], a_gn["beta"])
+                    g.a_tot1, g.a_tot2, g.a_gamma, g.a_beta, g.a_groups, g.a_eps = None, None, None, None, 0, 0.0
                     g.a_affine = ptr(a_affine)
-            mode += sc_mode
+            mode += "_sc" if S is not None else ""
         elif tile_cfg in _lib.GW_TILES:
             # small-M projection with the weights streamed into VGPRs (gemm_wreg.hip); W is the stream packed for this configuration
-            assert not conv and a_affine is None and splitk in (None, 1) and rowvec is None
-            cfg, sk, bm, bn = tile_cfg, 1, 64, 64 * _lib.GW_TILES[tile_cfg]
-            fast, mode = True, "gw" + ("_ln" if ln_colsum is not None else "") + ("_qkv" if C_t is not None else "") + ("_gn" if a_gn is not None else "") + \
+            mode = "gw" + ("_ln" if ln_colsum is not None else "") + ("_qkv" if C_t is not None else "") + ("_gn" if a_gn is not None else "") + \
                 ("_softmax" if sm_group else "") + ("_wimg" if w_bstride else "")
             if a_gn is not None:          # GroupNorm(x) -> projection: finalize in the kernel's prologue from the statistics totals of x
                 t1, _ = self.gn_sources(a_gn["x1"], a_gn["C1"], None, 0, a_gn["B"], a_gn["HW"], a_gn["G"])
@@ -537,31 +516,33 @@ class Recorder:
                     self.register(t)
         elif tile_cfg == _lib.TILE_G256:
             # large-M dense projection on 256 x 256 tiles, 8 waves, 8-phase LDS-DMA pipeline, persistent workgroups (gemm256.hip)
-            assert not conv and a_affine is None and splitk in (None, 1)
-            cfg, sk, bm, bn = tile_cfg, 1, 256, 256
-            fast, mode = True, "g256" + ("_qkv" if C_t is not None else "") + ("_2src" if A2 is not None else "")
+            mode = "g256" + ("_qkv" if C_t is not None else "") + ("_2src" if A2 is not None else "")
         else:
-            assert a_affine is None and (not conv or A2 is None), "fused GroupNorm prologue / two-source conv need TILE_HALO / TILE_WREG"
-            cfg, sk, bm, bn = self.plan_gemm(M, N, K, fast, mode, tile_cfg, splitk)
-        g.splitk = sk
-        if Cs:
-            g.splitk = sk_req
-        g.tile_cfg = cfg
+            mode = "dense"
+            if conv:
+                ups = (conv.get("Hv", conv["Hin"]), conv.get("Wv", conv["Win"])) != (conv["Hin"], conv["Win"])
+                mode = "ups" if ups else f"conv{conv.get('stride', 1)}"
+            if tile_cfg == 0 and splitk is None and info.family == _lib.FAMILIES.index("gemm_fast"):
+                hit = tuning_table().get(f"{mode}|{M}|{N}|{K}")        # (measured on the fast path: the cost model's choice stands elsewhere)
+                if hit:
+                    g.tile_cfg, g.splitk = int(hit[0]), int(hit[1])
+        info = self.resolve(g, kind)
+        # the record holds the tile and the split as resolved (resolving them again changes nothing); with a folded shortcut the library deals
+        # the chunks of both parts out from the REQUEST, so that stays
+        g.tile_cfg = info.tile_cfg
+        if not Cs:
+            g.splitk = info.splitk
+        sk = info.splitk
         if sk > 1:
-            self.reserve_slab(sk * M * N)
+            self.reserve_slab(info.slab_elems)
         part = None
-        if want_gn:
+        if want_gn and info.stat_rows:
             rpb = rows_per_batch if rows_per_batch > 0 else (conv["Hout"] * conv["Wout"] if conv else M)
-            vec = out_mode == _lib.OUT_F16 and n_out % 8 == 0 and g.ldc % 8 == 0 and (R is None or ldr % 8 == 0) and \
-                (R2 is None or ldr2 % 8 == 0)
-            slab_rows = bm if sk == 1 else 32            # (a workgroup's rows must lie inside one image)
-            if vec and (fast or sk > 1) and N % 4 == 0 and rpb % slab_rows == 0 and M % rpb == 0 and \
-                    not os.environ.get("BC_GEMM_TILE"):
-                # (gn_tot_out: the caller's table - the first half of a [2 B'] table that bc_dup_halves fans out afterwards)
-                part = gn_tot_out if gn_tot_out is not None else self.new_tot(M // rpb, n_out)
-                assert tuple(part.shape[:2]) == (M // rpb, n_out)
-                g.gn_tot = part.data_ptr()
-                self.tots[g.C] = part
+            # (gn_tot_out: the caller's table - the first half of a [2 B'] table that bc_dup_halves fans out afterwards)
+            part = gn_tot_out if gn_tot_out is not None else self.new_tot(M // rpb, n_out)
+            assert tuple(part.shape[:2]) == (M // rpb, n_out)
+            g.gn_tot = part.data_ptr()
+            self.tots[g.C] = part
 
         idx = self.lib.bc_plan_add_gemm(self.plan, self.seg.id, self.sid, C.byref(g))
         if idx < 0 or idx != len(self.seg.meta):
@@ -570,23 +551,8 @@ class Recorder:
         self.keep.append(refs)
         for t in refs:
             self.register(t)
-        variant = ("conv_halo_kernel<" if cfg == _lib.TILE_HALO else "conv_wreg_kernel<" if cfg == _lib.TILE_WREG else
-                   "gemm_wreg_kernel<" if cfg in _lib.GW_TILES else "gemm256_kernel<" if cfg == _lib.TILE_G256 else "gemm_fast_kernel<" if fast else "gemm_kernel<") + _lib.TILE_NAMES[cfg] + "," + mode + ">" + \
-            ("+splitk_reduce" if sk > 1 else "")
-        # the instantiation rocprofv3 reports for this launch (csrc/*.hip launchers)
-        FAST = {1: "256, 128, 4, 2, 3", 2: "128, 128, 2, 2, 3", 3: "128, 128, 2, 2, 2", 4: "256, 64, 4, 1, 2", 5: "256, 64, 4, 1, 3",
-                6: "128, 64, 2, 2, 3", 7: "64, 64, 2, 2, 4"}
-        if cfg in (_lib.TILE_HALO, _lib.TILE_WREG):
-            rp = ("conv_wreg_kernel" if cfg == _lib.TILE_WREG else "conv_halo_kernel") + f"<{2 if g.a_tot1 else 1 if g.a_affine else 0}>"
-        elif cfg == _lib.TILE_G256:
-            rp = "gemm256_kernel"
-        elif cfg in _lib.GW_TILES:
-            rp = f"gemm_wreg_kernel<{_lib.GW_TILES[cfg]}, {10 if _lib.GW_TILES[cfg] == 5 else 20}, {'true' if sm_group else 'false'}>"
-        elif fast:
-            ups_ = bool(conv) and (conv.get("Hv", conv["Hin"]), conv.get("Wv", conv["Win"])) != (conv["Hin"], conv["Win"])
-            rp = f"gemm_fast_kernel<{FAST[cfg]}, {'true' if conv else 'false'}, {'true' if ups_ else 'false'}>"
-        else:
-            rp = "gemm_kernel<" + ("256, 64, 4, 1" if bn == 64 else "128, 128, 2, 2") + ">"
+        variant = f"{_lib.FAMILIES[info.family]}_kernel<{_lib.TILE_NAMES[info.tile_cfg]},{mode}>" + ("+splitk_reduce" if sk > 1 else "")
+        rp = info.kernel.decode()                      # the instantiation rocprofv3 reports for this launch, named by the launcher that picks it
         # algorithmic HBM bytes: activation (a convolution reads each input pixel once), weights and the result once
         a_elems = (M // (conv["Hout"] * conv["Wout"])) * conv["Hin"] * conv["Win"] * conv["Cin"] if conv else M * K
         alg_bytes = 2 * (a_elems + N * K + M * n_out) + (2 * M * n_out if R is not None else 0) + 2 * (M + N) * Cs

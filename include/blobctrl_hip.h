@@ -92,7 +92,8 @@ typedef struct BcGemm {
     /* ---- optional fused GroupNorm statistics of the (fp16-rounded) OUTPUT: every workgroup ADDS the per-channel (sum, sumsq) of its
      *      rows to the totals gn_tot[B][n_out][BC_GN_TOT_WORDS] (see "GroupNorm statistics totals" below; the table must be zero before
      *      the launch).  Fast path or split-K reducer only; needs BC_OUT_F16, widths % 8 == 0 and rows_per_batch % slab_rows == 0
-     *      (slab_rows = bm of bc_gemm_plan, or 32 with split-K: a workgroup's rows lie in one image).  Replaces the bc_gn_stats pass. ---- */
+     *      (slab_rows = BcGemmInfo.stat_rows: the tile's rows, or 32 with split-K; a workgroup's rows lie in one image).  Replaces the
+     *      bc_gn_stats pass. ---- */
     unsigned long long* gn_tot;
     /* ---- tile configuration: 0 = library heuristic, else one of BC_TILE_* (see bc_gemm_plan) ---- */
     int tile_cfg;
@@ -138,6 +139,8 @@ typedef struct BcGemm {
     int lds, lds2, S1, Cs;
 } BcGemm;
 
+/* Resolves the struct (bc_gemm_resolve below: checks, defaults, kernel family, tile, final split count), then launches it - and the
+ * split-K reducer behind it when the final split count is > 1. */
 int bc_gemm(const BcGemm* p, bc_stream stream);
 int bc_sizeof_gemm(void);            /* sizeof(BcGemm), lets FFI bindings verify their struct mirror */
 /* Tile configurations of the LDS-DMA fast path (block tile BM x BN, waves, LDS stages). */
@@ -195,10 +198,33 @@ int bc_conv_wreg_sc_eligible(int Cin, int N, int H, int W, int Cs, int S1, int r
 int bc_conv_halo_eligible(int Cin, int C1, int N, int Hin, int Win, int Hout, int Wout, int stride);
 /* most 64-channel chunks one workgroup of BC_TILE_HALO may take: callers keep ceil(Cin / 64 / splitk) <= this */
 int bc_conv_halo_max_chunks(void);
-/* Resolve the plan for a GEMM: in/out *tile_cfg (AUTO -> heuristic choice), in/out *splitk (<= 0 -> heuristic), out *bm,
+/* The cost model behind BC_TILE_AUTO: in/out *tile_cfg (AUTO -> heuristic choice), in/out *splitk (<= 0 -> heuristic), out *bm,
  * *bn = tile shape.  `fast` = 1 when the problem meets the fast-path conditions
- * (K % 64 == 0, conv Cin % 64 == 0, concat split % 64 == 0); otherwise only 128x128 / 256x64 generic tiles exist. */
+ * (K % 64 == 0, conv Cin % 64 == 0, concat split % 64 == 0); otherwise only 128x128 / 256x64 generic tiles exist.
+ * A piece of bc_gemm_resolve, which decides `fast` itself: callers that hold a BcGemm ask that. */
 int bc_gemm_plan(int M, int N, int K, int fast, int* tile_cfg, int* splitk, int* bm, int* bn);
+/* How a BcGemm turns into a launch - THE one place that decides it: bc_gemm is "bc_gemm_resolve, then launch", and a planner that
+ * records a BcGemm asks here instead of working it out again (launch.py: Recorder.gemm).  Host arithmetic only: nothing is launched and
+ * no device is needed.  Runs every argument check of bc_gemm (same messages through bc_last_error) except the two that need pointers
+ * bound at replay: `slab` may be NULL whatever the split, and `gn_tot` is judged by stat_rows below.  One extension over bc_gemm:
+ * in->splitk <= 0 asks for the cost model's split (bc_gemm_plan; bc_gemm itself runs such a struct unsplit) - a record holds the
+ * resolved tile_cfg and splitk, for which resolving again changes nothing (except with BcGemm.S, where the request is kept).
+ * BC_GEMM_GENERIC / BC_GEMM_TILE are read here and nowhere else. */
+enum { BC_FAMILY_GENERIC = 0 /* gemm.hip */, BC_FAMILY_FAST = 1 /* gemm_fast.hip */, BC_FAMILY_HALO = 2 /* conv_halo.hip */,
+       BC_FAMILY_CONV_WREG = 3 /* conv_wreg.hip */, BC_FAMILY_GEMM_WREG = 4 /* gemm_wreg.hip */, BC_FAMILY_G256 = 5 /* gemm256.hip */ };
+typedef struct BcGemmInfo {
+    int family;              /* BC_FAMILY_* */
+    int tile_cfg, bm, bn;    /* the BC_TILE_* configuration that launches and its tile shape */
+    int splitk;              /* final split count (no empty splits); > 1: the launch is followed by the split-K reducer */
+    int n_out;               /* output columns (N; N / 2 with GEGLU; the kept columns with the softmax epilogue) */
+    long long slab_elems;    /* floats of `slab` the launch needs (0 when unsplit) */
+    int stat_rows;           /* rows one workgroup adds to a GroupNorm statistics table (gn_tot), every one inside one image; 0: this
+                              * launch cannot emit statistics (bc_gemm refuses it with gn_tot set) */
+    int gn_finalize_fits;    /* BC_TILE_HALO / BC_TILE_WREG with a_groups > 0: 1 when a workgroup's channel span at this split fits the
+                              * in-kernel GroupNorm finalize (a_tot1); 0: bc_gemm refuses a_tot1 - run bc_gn_finalize and pass a_affine */
+    char kernel[64];         /* the main kernel's name as a profiler prints it (template instantiation) */
+} BcGemmInfo;
+int bc_gemm_resolve(const BcGemm* in, BcGemmInfo* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * GroupNorm (+SiLU) over NHWC, optionally over a channel-concat of two tensors.

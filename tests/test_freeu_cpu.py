@@ -339,7 +339,7 @@ OLD_OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fus
 def test_bc_freeu_is_exported_beside_every_symbol_that_was_there():
     from blobctrl_amd import _lib
     lib = _lib.load()                                                  # (raises when a declared symbol does not resolve)
-    assert "bc_freeu" in _lib.EXPORTED_SYMBOLS and lib.bc_freeu is not None and len(_lib.EXPORTED_SYMBOLS) == 91
+    assert "bc_freeu" in _lib.EXPORTED_SYMBOLS and lib.bc_freeu is not None and len(_lib.EXPORTED_SYMBOLS) == 92
     assert _lib.OPS == dict(OLD_OPS, bc_freeu=OP_FREEU) and set(OLD_OPS) < set(_lib.EXPORTED_SYMBOLS)
     assert _lib.op_signature("bc_freeu") == "pipiiipippppp"
     for name in ("bc_plan_save", "bc_plan_load", "bc_plan_capture_loop", "bc_splat_scores", "bc_conv_wreg_pack", "bc_graph_launch"):

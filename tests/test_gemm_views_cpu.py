@@ -138,8 +138,34 @@ def test_the_case_tables_name_every_family_and_mode_once():
     ids = [c.id for c in gv.generic_cases() + gv.gw_cases() + gv.g256_cases() + gv.halo_cases("halo") + gv.halo_cases("wreg")]
     ids += [gv.fast_case(cfg, mode).id for cfg in range(1, 8) for mode in gv.FAST_MODES]
     assert len(ids) == len(set(ids)) and len(gv.gw_cases()) == 3 * 2 * len(gv.GW_MODES) + 2 * 2
-    # the uneven splits the issue names: chunks -> per-split counts of bc_conv_halo_launch (cps = ceil(nch / sk))
+    # the uneven splits the issue names: chunks -> per-split counts of bc_conv_halo_split (cps = ceil(nch / sk))
     for cin, sk, want in ((192, 2, [2, 1]), (320, 2, [3, 2]), (320, 3, [2, 2, 1])):
         nch = cin // 64
         cps = -(-nch // sk)
         assert [min(cps, nch - s * cps) for s in range(-(-nch // cps))] == want
+
+
+# ---------------------------------------------------------------------------------------------------- refusals at record time
+def test_a_refused_problem_is_refused_by_the_recorder_and_every_other_one_records():
+    """Recorder.gemm asks the library (bc_gemm_resolve) before it records: a problem bc_gemm refuses raises there with the library's message -
+    on a CPU recorder, no launch attempted - and leaves no record, no launch entry and no table behind; every other problem records."""
+    from blobctrl_amd import _lib
+    from blobctrl_amd.launch import Recorder
+    from tests.gemm_records_common import record_view, view_problems
+    rec = Recorder(CPU)
+    seg = rec.begin("views")
+    refused = recorded = 0
+    for prob in view_problems():
+        n, tables = len(seg.meta), dict(rec._tot_chunk)
+        if prob.refused:
+            with pytest.raises(_lib.BlobCtrlHipError, match=r"bc_gemm\(gemm\) failed \(rc=1\): bc_gemm"):
+                record_view(rec, prob)
+            assert len(seg.meta) == n and rec.lib.bc_plan_num_launches(rec.plan, seg.id) == n and rec._tot_chunk == tables, prob.name
+            refused += 1
+        else:
+            record_view(rec, prob)
+            assert len(seg.meta) > n and rec.lib.bc_plan_num_launches(rec.plan, seg.id) == len(seg.meta), prob.name
+            assert seg.meta[-1]["variant"].startswith(prob.variant), (prob.name, seg.meta[-1]["variant"])
+            recorded += 1
+    rec.close()
+    assert (refused, recorded) == (89, 247)                     # (168 cases in two flavours)

@@ -29,8 +29,15 @@ tests/test_request_tables_cpu.py:stored_table_cases, the sha256 of every table `
 segment list.  The committed file was written by the commit BEFORE `denoise` / `compile_plan` got their shared set-up; regenerating it
 from later code makes the test that reads it vacuous.
 
+`--gemm-records` writes tests/golden/gemm_records_before_resolve.json instead: per source of tests/gemm_records_common.py:sources (planner
+cases, full-width plans, tiny-net plans, view problems), the count of launches and GEMMs and the sha256 of the canonical text of every
+launch's `meta`, every `BcGemm` handed to bc_plan_add_gemm and the slab reserved per stream.  The committed file was written by the commit
+BEFORE `Recorder.gemm` asked bc_gemm_resolve; regenerating it from later code makes the test that reads it vacuous.  `--gemm-records-text
+NAME` prints the canonical text of one source instead (to diff a mismatch).
+
     python tools/make_plan_fixture.py [OUT_DIR] [--eta ETA | --euler TAG | --lcm TAG | --requests [--expected FILE.npy]]
     python tools/make_plan_fixture.py --stored-tables
+    python tools/make_plan_fixture.py --gemm-records | --gemm-records-text NAME
 """
 import argparse
 import os
@@ -100,7 +107,24 @@ def main():
     ap.add_argument("--requests", action="store_true", help="the mixed edit of a request batch of 3 (REQUESTS), Euler")
     ap.add_argument("--expected", default=None, help=".npy file with the expected final latents (default: the reference loop's)")
     ap.add_argument("--stored-tables", action="store_true", help="write tests/golden/plan_tables_before_setup_merge.json")
+    ap.add_argument("--gemm-records", action="store_true", help="write tests/golden/gemm_records_before_resolve.json")
+    ap.add_argument("--gemm-records-text", default=None, metavar="NAME", help="print the canonical text of one source of --gemm-records")
     args = ap.parse_args()
+    if args.gemm_records or args.gemm_records_text:
+        import json
+        from tests.gemm_records_common import sources
+        if args.gemm_records_text:
+            sys.stdout.write(dict(sources())[args.gemm_records_text]().text())
+            return
+        records = {}
+        for name, record in sources():
+            records[name] = record().entry()
+            print(name, records[name], flush=True)
+        with open(os.path.join(GOLD, "gemm_records_before_resolve.json"), "w") as f:
+            json.dump(records, f, indent=0, sort_keys=True)
+            f.write("\n")
+        print("gemm_records_before_resolve.json:", len(records), "sources,", sum(r["gemms"] for r in records.values()), "GEMMs")
+        return
     if args.stored_tables:
         import json
         import tempfile

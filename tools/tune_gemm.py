@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measure every (tile configuration, split-K) candidate for the distinct GEMM shapes of the hot path on the MI355X the
-script runs on, and write blobctrl_amd/gemm_tuning.json (consumed by launch.Recorder.plan_gemm).
+script runs on, and write blobctrl_amd/gemm_tuning.json (consumed by launch.Recorder.gemm).
 
 Usage (GPU box):  python tools/tune_gemm.py [--res 512] [--out blobctrl_amd/gemm_tuning.json]
 The shapes are collected by planning one BlobNet-active denoise step of the full-size model (no weights needed:
@@ -153,7 +153,9 @@ def main():
                 cost = us + (args.gn_penalty_us if (sk > 1 and mode != "dense") else 0.0)
                 if best is None or cost < best[3]:
                     best = (us, cfg, sk, cost)
-        auto_cfg, auto_sk, _, _ = rec.plan_gemm(M, N, K, True, mode)
+        c_, s_, bm_, bn_ = C.c_int(0), C.c_int(-1), C.c_int(0), C.c_int(0)          # what the cost model picks for this fast-path shape
+        _lib.check(rec.lib.bc_gemm_plan(M, N, K, 1, C.byref(c_), C.byref(s_), C.byref(bm_), C.byref(bn_)), "bc_gemm_plan")
+        auto_cfg, auto_sk = c_.value, s_.value
         auto_us = [r[0] for r in results if r[1] == auto_cfg and r[2] == auto_sk]
         table[f"{mode}|{M}|{N}|{K}"] = [best[1], best[2]]
         tf = 2.0 * M * N * K / best[0] / 1e6
