@@ -237,6 +237,16 @@ MASK_SIGNATURES = {
 MASK_HOLES, MASK_ISLANDS = 0, 1
 MASK_REGION_PHASES = 5                # launch groups of bc_mask_remove_small (BC_MASK_REGION_PHASES)
 
+# Entry points of include/blobctrl_edit.h (an edit's inputs built on the device, blobctrl_amd/edit_inputs.py).  A table of its own, as for
+# the masks: DIRECT launches on the caller's stream - no BC_OP_* code, in none of the op tables below, never recorded into a plan.
+EDIT_SIGNATURES = {
+    "bc_ellipse_cover": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_ellipse_paint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bc_mask_row_extents": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_mask_cutout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+EDIT_MAX_DIM = 16384                  # largest H and W those entry points take (BC_EDIT_MAX_DIM)
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -308,7 +318,7 @@ def load():
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
-            list(MASK_SIGNATURES.items()):
+            list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

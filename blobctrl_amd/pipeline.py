@@ -1000,6 +1000,11 @@ class BlobCtrlEngine:
         return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests)
 
 
+def _is_device_image(image):
+    """uint8 [H][W][3] tensor: pixels as `blobctrl_amd.edit_inputs` leaves them on the device (a CPU one is refused there: no CPU fallback)."""
+    return torch.is_tensor(image) and image.dtype == torch.uint8 and image.ndim == 3 and image.shape[-1] == 3
+
+
 # ======================================================================================================================
 # The reference's pipeline surface (SURVEY 8b): same constructor keywords, same __call__ signature, same error behaviour,
 # `.images` output - so that scripts/blobctrl_inference.py:191-205 runs unchanged on the MI355X modules.
@@ -1363,7 +1368,16 @@ class StableDiffusionBlobNetPipeline:
     def encode_latents(self, image, device=None, dtype=None, prompt_embeds=None, height=512, width=512, generator=None):
         if self.vae is None:
             raise ValueError("this pipeline was built without a VAE: it cannot encode images")
-        if not torch.is_tensor(image):
+        if _is_device_image(image):
+            # pixels that are on the device already (blobctrl_amd.edit_inputs): the PIL branch of `preprocess`, bit for bit, at their own size
+            from .edit_inputs import vae_input
+            f = self.image_processor.config.vae_scale_factor
+            want = tuple(v - v % f for v in (image.shape[0] if height is None else height, image.shape[1] if width is None else width))
+            if tuple(image.shape[:2]) != tuple(want):
+                raise ValueError(f"a uint8 device image of {tuple(image.shape[:2])} cannot be resized to {tuple(want)} on the device: hand "
+                                 "the host path a PIL image (it resizes with lanczos), or build the inputs at (height, width)")
+            image = vae_input(image)
+        elif not torch.is_tensor(image):
             image = self.image_processor.preprocess(image, height=height, width=width)
         lat = self.engine.encode_latents(image.to(self.device, torch.float32), generator)
         return lat if prompt_embeds is None else lat.repeat(prompt_embeds.shape[0], 1, 1, 1)
@@ -1372,6 +1386,9 @@ class StableDiffusionBlobNetPipeline:
     def encode_image_dinov2(self, image, device=None):
         if self.dinov2 is None:
             raise ValueError("this pipeline was built without dinov2: it cannot embed the foreground image")
+        if _is_device_image(image):
+            # the foreground canvas comes to the host (3 H W bytes) for the unchanged PIL preprocessing: `pixel_values` are the host path's
+            image = image.cpu().numpy()
         if not torch.is_tensor(image):
             image = self.dinov2_processor.preprocess(images=image, do_resize=True, return_tensors="pt", do_convert_rgb=True)["pixel_values"]
         emb = self.dinov2(pixel_values=torch.as_tensor(image).to(self.device, torch.float32)).pooler_output
@@ -1409,7 +1426,8 @@ class StableDiffusionBlobNetPipeline:
                  **kwargs):
         """pipeline_blobnet.py:743-1166 with the same keyword names, defaults and error behaviour.  Returns
         StableDiffusionBlobNetPipelineOutput(images=..., nsfw_content_detected=None) or `(images, None)` for return_dict=False;
-        `output_type` "pil" | "np" | "pt" | "latent"."""
+        `output_type` "pil" | "np" | "pt" | "latent".  Beyond the reference: `fg_image` / `bg_image` may be uint8 DEVICE tensors [H][W][3] of
+        exactly (height, width), as `blobctrl_amd.edit_inputs` builds them; they give the latents the same pixels give as PIL images."""
         callback_steps = kwargs.pop("callback_steps", None)
         if kwargs.pop("callback", None) is not None:
             raise NotImplementedError("`callback` is deprecated in the reference (pipe:868-875): use callback_on_step_end")

@@ -8,7 +8,9 @@ checkpoints exist offline), which exercises every kernel and prints per-stage ti
 With --sam DIR_OR_PTH --click X,Y the edit starts where the app's does: Segment-Anything turns the click on the foreground image into a
 mask and the mask into the blob's ellipse (DIR = a transformers directory, PTH = the original sam_vit_h_4b8939.pth, "synth" = seeded
 synthetic ViT-H weights).  With --sam ... --sam-auto K there is no click: SamAutomaticMaskGenerator segments everything in the image and
-the K-th largest mask gives the blob."""
+the K-th largest mask gives the blob.  With --sam ... --click X,Y --device-inputs the mask never leaves the GPU: `predict_torch` -> `masks.clean_masks`
+-> `edit_inputs.ellipses_from_masks` (the row extents come to the host, n * H * 8 bytes) -> `object_regions` / `build_edit_inputs_batch` ->
+`vae_input`, and the edit is a "move" of the clicked object; only the DINOv2 preprocessing sees the foreground on the host."""
 import argparse
 import os
 import sys
@@ -33,7 +35,11 @@ def main():
                     help="take the blob from the K-th largest mask of SamAutomaticMaskGenerator instead of a click (with --sam)")
     ap.add_argument("--min-region-area", type=int, default=0, metavar="N",
                     help="despeckle the SAM mask(s) on the GPU first: fill holes and remove islands of fewer than N pixels (with --sam)")
+    ap.add_argument("--device-inputs", action="store_true",
+                    help="build the edit's inputs on the GPU from the device mask (with --sam, click prompts): blobctrl_amd.edit_inputs")
     args = ap.parse_args()
+    if args.device_inputs and (not args.sam or args.sam_auto is not None):
+        ap.error("--device-inputs needs --sam and a click prompt")
     if (args.click or args.sam_auto is not None) and not args.sam:
         ap.error("--click / --sam-auto need --sam")
     if args.click and args.sam_auto is not None:
@@ -97,6 +103,32 @@ def main():
             e, ann = blobs[args.sam_auto]
             print(f"SAM segment-everything: {len(blobs)} masks in {1e3 * (sync() - ts):.1f} ms (first call: planning + graph capture); mask "
                   f"{args.sam_auto}: area {ann['area']}, bbox {ann['bbox']}, predicted IoU {ann['predicted_iou']:.3f} -> ellipse {e}")
+        elif args.device_inputs:
+            from blobctrl_amd import edit_inputs, masks as bc_masks
+            from blobctrl_amd.image_processor import Dinov2ImageProcessor
+            click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
+            ts = sync()
+            predictor = SamPredictor(sam)
+            predictor.set_image(image)
+            pts = predictor.transform.apply_coords_torch(torch.tensor([[click]], dtype=torch.float32, device="cuda"), predictor.original_size)
+            found, _, _ = predictor.predict_torch(pts, torch.ones(1, 1, dtype=torch.int32, device="cuda"), multimask_output=False)
+            te = sync()
+            clean, _, _ = bc_masks.clean_masks(found[:, 0], args.min_region_area)
+            ells, boxes = edit_inputs.ellipses_from_masks(clean)
+            if boxes[0] is None:
+                raise SystemExit(f"--device-inputs: the mask of click {click} is empty")
+            if ells[0] is None:                           # (seeded synthetic SAM weights give masks that span the frame: nothing to fit)
+                print(f"no ellipse can be fitted to the mask of click {click} (box {boxes[0]}): the README's blob stands in for it")
+                ells = [((ellipse[0][0], ellipse[0][1]), (ellipse[1][0], ellipse[1][1]), ellipse[2])]
+            image_dev = torch.from_numpy(image).cuda()
+            target = ((ells[0][0][0] + 0.1 * R, ells[0][0][1]), ells[0][1], ells[0][2])          # the edit: move the object right
+            fg_u8 = edit_inputs.object_regions(image_dev, clean, boxes)
+            bg_u8, score, _ = edit_inputs.build_edit_inputs_batch(["move"], image_dev, ells, [target], [1.0])
+            fg, bg = edit_inputs.vae_input(fg_u8), edit_inputs.vae_input(bg_u8)
+            dino_px = Dinov2ImageProcessor().preprocess(images=fg_u8[0].cpu().numpy())["pixel_values"]
+            print(f"SAM click {click} -> device mask in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); mask -> ellipse {ells[0]}, "
+                  f"box {boxes[0]}, fg / bg / score on the device in {1e3 * (sync() - te):.1f} ms")
+            e = target
         else:
             click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
             ts = sync()
@@ -107,9 +139,10 @@ def main():
             print(f"SAM click {click} -> ellipse {e} in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); "
                   f"second click {1e3 * (sync() - te):.1f} ms, same ellipse: {e2 == e}")
         ellipse = [list(e[0]), list(e[1]), e[2]]
-    score = splat_features(**blob_dict_from_ellipse(ellipse, R, R), score_size=(R // 8, R // 8), return_d_score=True)
+    if not args.device_inputs:
+        score = splat_features(**blob_dict_from_ellipse(ellipse, R, R), score_size=(R // 8, R // 8), return_d_score=True)
     t2 = sync()
-    crop = torch.nn.functional.interpolate(fg, size=(224, 224), mode="bilinear", align_corners=False)
+    crop = dino_px if args.device_inputs else torch.nn.functional.interpolate(fg, size=(224, 224), mode="bilinear", align_corners=False)
     feats = dino(crop).pooler_output.view(1, 1, -1)
     t3 = sync()
     ids = torch.from_numpy(rng.integers(0, 49408, size=(2, 1, 77)).astype(np.int64))
