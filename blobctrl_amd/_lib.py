@@ -247,6 +247,15 @@ EDIT_SIGNATURES = {
 }
 EDIT_MAX_DIM = 16384                  # largest H and W those entry points take (BC_EDIT_MAX_DIM)
 
+# Entry points of include/blobctrl_resample.h (Pillow's 8-bit resize on the device, blobctrl_amd/resample.py).  A table of its own, as for
+# the edit inputs: DIRECT launches on the caller's stream - no BC_OP_* code, in none of the op tables below, never recorded into a plan.
+RESAMPLE_SIGNATURES = {
+    "bc_resample_horizontal": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bc_resample_vertical": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+}
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -318,7 +327,7 @@ def load():
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
-            list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()):
+            list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -4,9 +4,10 @@ device tensors out.
 
 Every function here gives THE SAME BYTES as the host function of `blob_edit` / `image_processor` it stands for, and those stay what they
 were: they are the checkers (tests/test_edit_inputs_gpu.py).  The ellipse predicate is `blob_edit.ellipse_mask`'s arithmetic in fp64, one
-correctly rounded operation at a time on both sides; everything else is integer.  Two small copies do cross: `ellipses_from_masks` fetches
+correctly rounded operation at a time on both sides; everything else is integer.  One small copy does cross: `ellipses_from_masks` fetches
 the first / last set column of every mask row (n * H * 8 bytes) and fits the ellipses on the host, as `blob_edit.ellipses_from_image` does
-from the same points; and the pipeline hands DINOv2's PIL preprocessing the foreground canvas (3 * H * W bytes).
+from the same points.  The foreground canvas no longer does: the pipeline builds DINOv2's input from it on the device
+(`resample.dinov2_pixel_values`, Pillow's bicubic resize bit for bit), unless it was given a processor object that is not this package's.
 
 No CPU fallback: a CPU tensor raises `BlobCtrlHipError`.  This module raises it itself, before the library is called: the entry points take
 raw addresses, and a host pointer handed to a kernel would fault on the device instead of being refused.

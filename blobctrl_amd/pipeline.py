@@ -1386,8 +1386,14 @@ class StableDiffusionBlobNetPipeline:
     def encode_image_dinov2(self, image, device=None):
         if self.dinov2 is None:
             raise ValueError("this pipeline was built without dinov2: it cannot embed the foreground image")
-        if _is_device_image(image):
-            # the foreground canvas comes to the host (3 H W bytes) for the unchanged PIL preprocessing: `pixel_values` are the host path's
+        from .image_processor import Dinov2ImageProcessor
+        if _is_device_image(image) and image.is_cuda and type(self.dinov2_processor) is Dinov2ImageProcessor:
+            # this package's processor is Pillow's bicubic resize, a crop and a per-byte normalisation: `resample` does them where the pixels
+            # are, to the same bytes, and nothing comes to the host
+            from .resample import dinov2_pixel_values
+            image = dinov2_pixel_values(image, self.dinov2_processor)
+        elif _is_device_image(image):
+            # any other processor object: the foreground canvas comes to the host (3 H W bytes) for its own preprocessing
             image = image.cpu().numpy()
         if not torch.is_tensor(image):
             image = self.dinov2_processor.preprocess(images=image, do_resize=True, return_tensors="pt", do_convert_rgb=True)["pixel_values"]

@@ -722,10 +722,17 @@ class SamPredictor:
         self.original_size = self.input_size = None
 
     def set_image(self, image, image_format: str = "RGB"):
-        resized, x = preprocess_image(image, self.model.image_size, image_format)
+        """image uint8 [H][W][3]: a numpy array, preprocessed on the host (`preprocess_image`), or a device tensor, preprocessed where it is
+        (`resample.sam_pixel_values`: the same bytes, and the image never comes to the host)."""
+        if torch.is_tensor(image) and image.is_cuda:
+            from .resample import sam_pixel_values
+            input_size, x = sam_pixel_values(image, self.model.image_size, image_format)
+            original_size = tuple(int(v) for v in image.shape[:2])
+        else:
+            resized, x = preprocess_image(image, self.model.image_size, image_format)
+            original_size, input_size = tuple(np.asarray(image).shape[:2]), tuple(resized.shape[:2])
         self.reset_image()
-        self.original_size = tuple(np.asarray(image).shape[:2])
-        self.input_size = tuple(resized.shape[:2])
+        self.original_size, self.input_size = original_size, input_size
         self.features = self.model.encode(x)
         self.model._emb_owner = id(self)
         self.is_image_set = True
@@ -840,7 +847,7 @@ class SamAutomaticMaskGenerator:
 
     @torch.no_grad()
     def generate(self, image, min_mask_region_area=0):
-        """image uint8 [H][W][3] -> a list of dicts (segmentation, area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box) in NMS
+        """image uint8 [H][W][3] (a numpy array or a device tensor: it only goes to `set_image`) -> a list of dicts (segmentation, area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box) in NMS
         order, i.e. by descending predicted IoU.  A ragged last batch runs a decoder plan of its own size (recorded once, like the full one).
         `last_timing` holds HIP-event milliseconds of the call's phases (decode, resize, stats, regions) and the host time around them.
         `min_mask_region_area` > 0 is the package's post-processing of the kept masks, on the device before any mask crosses to the host

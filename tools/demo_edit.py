@@ -8,9 +8,10 @@ checkpoints exist offline), which exercises every kernel and prints per-stage ti
 With --sam DIR_OR_PTH --click X,Y the edit starts where the app's does: Segment-Anything turns the click on the foreground image into a
 mask and the mask into the blob's ellipse (DIR = a transformers directory, PTH = the original sam_vit_h_4b8939.pth, "synth" = seeded
 synthetic ViT-H weights).  With --sam ... --sam-auto K there is no click: SamAutomaticMaskGenerator segments everything in the image and
-the K-th largest mask gives the blob.  With --sam ... --click X,Y --device-inputs the mask never leaves the GPU: `predict_torch` -> `masks.clean_masks`
--> `edit_inputs.ellipses_from_masks` (the row extents come to the host, n * H * 8 bytes) -> `object_regions` / `build_edit_inputs_batch` ->
-`vae_input`, and the edit is a "move" of the clicked object; only the DINOv2 preprocessing sees the foreground on the host."""
+the K-th largest mask gives the blob.  With --sam ... --click X,Y --device-inputs the image is uploaded once and neither it nor the mask
+leaves the GPU: `set_image(device tensor)` (`resample.sam_pixel_values`) -> `predict_torch` -> `masks.clean_masks` ->
+`edit_inputs.ellipses_from_masks` (the row extents come to the host, n * H * 8 bytes) -> `object_regions` / `build_edit_inputs_batch` ->
+`vae_input`, DINOv2's input from `resample.dinov2_pixel_values`, and the edit is a "move" of the clicked object."""
 import argparse
 import os
 import sys
@@ -104,12 +105,13 @@ def main():
             print(f"SAM segment-everything: {len(blobs)} masks in {1e3 * (sync() - ts):.1f} ms (first call: planning + graph capture); mask "
                   f"{args.sam_auto}: area {ann['area']}, bbox {ann['bbox']}, predicted IoU {ann['predicted_iou']:.3f} -> ellipse {e}")
         elif args.device_inputs:
-            from blobctrl_amd import edit_inputs, masks as bc_masks
+            from blobctrl_amd import edit_inputs, masks as bc_masks, resample
             from blobctrl_amd.image_processor import Dinov2ImageProcessor
             click = [float(v) for v in (args.click or f"{R // 2},{R // 2}").split(",")]
+            image_dev = torch.from_numpy(image).cuda()        # the one upload: SAM, the cut-out and DINOv2 all read this tensor
             ts = sync()
             predictor = SamPredictor(sam)
-            predictor.set_image(image)
+            predictor.set_image(image_dev)
             pts = predictor.transform.apply_coords_torch(torch.tensor([[click]], dtype=torch.float32, device="cuda"), predictor.original_size)
             found, _, _ = predictor.predict_torch(pts, torch.ones(1, 1, dtype=torch.int32, device="cuda"), multimask_output=False)
             te = sync()
@@ -120,12 +122,11 @@ def main():
             if ells[0] is None:                           # (seeded synthetic SAM weights give masks that span the frame: nothing to fit)
                 print(f"no ellipse can be fitted to the mask of click {click} (box {boxes[0]}): the README's blob stands in for it")
                 ells = [((ellipse[0][0], ellipse[0][1]), (ellipse[1][0], ellipse[1][1]), ellipse[2])]
-            image_dev = torch.from_numpy(image).cuda()
-            target = ((ells[0][0][0] + 0.1 * R, ells[0][0][1]), ells[0][1], ells[0][2])          # the edit: move the object right
+            target =((ells[0][0][0] + 0.1 * R, ells[0][0][1]), ells[0][1], ells[0][2])          # the edit: move the object right
             fg_u8 = edit_inputs.object_regions(image_dev, clean, boxes)
             bg_u8, score, _ = edit_inputs.build_edit_inputs_batch(["move"], image_dev, ells, [target], [1.0])
             fg, bg = edit_inputs.vae_input(fg_u8), edit_inputs.vae_input(bg_u8)
-            dino_px = Dinov2ImageProcessor().preprocess(images=fg_u8[0].cpu().numpy())["pixel_values"]
+            dino_px = resample.dinov2_pixel_values(fg_u8[0], Dinov2ImageProcessor())
             print(f"SAM click {click} -> device mask in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); mask -> ellipse {ells[0]}, "
                   f"box {boxes[0]}, fg / bg / score on the device in {1e3 * (sync() - te):.1f} ms")
             e = target
