@@ -256,6 +256,14 @@ RESAMPLE_SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 
+# Entry point of include/blobctrl_ip.h (the IP-Adapter image cross-attention, accumulated onto attn2's text attention in place).  A table
+# of its own; a recordable plan op (IP_OPS below), in-process only like the SAM ops.
+IP_SIGNATURES = {
+    "bc_attention_ip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+}
+ATTENTION_IP_MAX_T = 64               # image tokens per launch (BC_ATTENTION_IP_MAX_T)
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -274,7 +282,9 @@ REQUEST_OPS = {"bc_scheduler_step_requests": 38, "bc_assemble_input_requests": 3
 SAM_OPS = {"bc_attention_relpos": 42, "bc_window_partition": 43, "bc_window_unpartition": 44, "bc_add_pos": 45, "bc_add_rows": 46,
            "bc_act_rows": 47, "bc_bilinear_resize_f32": 48, "bc_sam_tokens": 49, "bc_sam_masks": 50}
 SAM_BATCH_OPS = {"bc_sam_tokens_batch": 51, "bc_mask_stats": 52}
-_OP_TABLES = (OPS, REQUEST_OPS, SAM_OPS, SAM_BATCH_OPS)
+# ... and that of include/blobctrl_ip.h: extension headers continue from BC_OP_COUNT (53), the base header's enum is closed
+IP_OPS = {"bc_attention_ip": 53}
+_OP_TABLES = (OPS, REQUEST_OPS, SAM_OPS, SAM_BATCH_OPS, IP_OPS)
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
@@ -291,7 +301,8 @@ def op_code(name):
 
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
-    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES.get(name) or SAM_BATCH_SIGNATURES[name])[1][:-1]
+    args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES.get(name) or SAM_BATCH_SIGNATURES.get(name) or
+            IP_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -327,7 +338,8 @@ def load():
         raise BlobCtrlHipError(f"failed to load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
-            list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()):
+            list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
+            list(IP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -320,3 +320,26 @@ def load_blobnet(path: str):
     tc = TrunkConfig(in_channels=cin, block_out_channels=boc, num_heads=heads if isinstance(heads, int) else heads[0],
                      norm_num_groups=cfg.get("norm_num_groups", 32), cross_attention_dim=None, out_channels=0, is_blobnet=True)
     return sd, tc
+
+
+def load_ip_adapter(path_or_dict):
+    """IP-Adapter weights -> a list of {"image_proj": {...}, "ip_adapter": {...}}, one per adapter.  Takes the original layout as a dict, a
+    `.safetensors` file whose keys carry `image_proj.` / `ip_adapter.` prefixes (D/loaders/ip_adapter.py:166-176), or a list of either.
+    A `.bin` pickle is not read."""
+    if isinstance(path_or_dict, (list, tuple)):
+        return [load_ip_adapter(x)[0] for x in path_or_dict]
+    if isinstance(path_or_dict, dict):
+        if set(path_or_dict) != {"image_proj", "ip_adapter"}:
+            raise ValueError(f"an IP-Adapter state dict has the keys image_proj and ip_adapter, not {sorted(path_or_dict)[:4]}")
+        return [dict(image_proj=dict(path_or_dict["image_proj"]), ip_adapter=dict(path_or_dict["ip_adapter"]))]
+    path = os.fspath(path_or_dict)
+    if not path.endswith(".safetensors"):
+        raise NotImplementedError(f"{path}: only .safetensors IP-Adapter files are read (no .bin pickle)")
+    out = dict(image_proj={}, ip_adapter={})
+    for k, v in read_safetensors(path).items():
+        for part in out:
+            if k.startswith(part + "."):
+                out[part][k[len(part) + 1:]] = v
+    if not out["image_proj"] or not out["ip_adapter"]:
+        raise ValueError(f"{path}: no image_proj. / ip_adapter. tensors")
+    return [out]

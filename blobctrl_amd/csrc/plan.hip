@@ -22,6 +22,7 @@
 #include "plan_format.h"
 #include "../../include/blobctrl_requests.h"
 #include "../../include/blobctrl_sam.h"
+#include "../../include/blobctrl_ip.h"
 
 void bc_gemm_set_probe(hipEvent_t e);      // gemm.hip (timing probe between a split-K GEMM's main kernel and its reducer)
 bool bc_gemm_probe_hit();
@@ -58,6 +59,10 @@ struct BcPlan {
 };
 
 namespace {
+
+// The ops of extension headers that plan_format.h (the file format: closed at BC_OP_COUNT) does not know: in-process only.
+inline const char* plan_op_signature(int op) { return op == BC_OP_ATTENTION_IP ? "ppppiiiiiiiifp" : op_signature(op); }
+inline uint32_t plan_op_min_version(int op) { return op == BC_OP_ATTENTION_IP ? kNoFileVersion : op_min_version(op); }
 
 inline float as_float(uint64_t v) { uint32_t u = (uint32_t)v; float f; memcpy(&f, &u, 4); return f; }
 #define P(k) reinterpret_cast<void*>(r.a[k])
@@ -181,6 +186,9 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
         case BC_OP_FREEU:
             return bc_freeu(CP(bc_half, 0), I(1), CP(bc_half, 2), I(3), I(4), I(5), CP(float, 6), I(7), CP(float, 8), MP(bc_half, 9),
                             MP(bc_half, 10), MP(unsigned long long, 11), MP(unsigned long long, 12), s);
+        case BC_OP_ATTENTION_IP:
+            return bc_attention_ip(CP(bc_half, 0), CP(bc_half, 1), CP(bc_half, 2), MP(bc_half, 3), I(4), I(5), I(6), I(7), I(8), I(9), I(10), I(11),
+                                   F(12), CP(float, 13), s);
         case BC_OP_ROWCHAIN:
             return bc_rowchain(I(0), I(1), I(2), I(3), CP(bc_half, 4), CP(float, 5), CP(unsigned long long, 6), CP(float, 7), CP(float, 8), I(9),
                                F(10), CP(bc_half, 11), CP(bc_half, 12), CP(bc_half, 13), I(14), I(15), I(16), CP(bc_half, 17), CP(float, 18),
@@ -310,7 +318,7 @@ extern "C" int bc_plan_add_gemm(BcPlan* pl, int seg, int stream_id, const BcGemm
 extern "C" int bc_plan_add_op(BcPlan* pl, int seg, int stream_id, int op, const uint64_t* args, int nargs) {
     ADD_CHECK(pl != nullptr && seg >= 0 && seg < (int)pl->segs.size(), "bc_plan_add_op: bad segment id %d", seg);
     Seg& sg = pl->segs[seg];
-    const char* sig = op_signature(op);
+    const char* sig = plan_op_signature(op);
     ADD_CHECK(sig != nullptr && (int)strlen(sig) == nargs && args != nullptr, "bc_plan_add_op: op %d takes %d arguments, got %d", op,
               sig ? (int)strlen(sig) : -1, nargs);
     ADD_CHECK(stream_id >= 0 && stream_id < kMaxStreams, "bc_plan_add_op: stream id %d out of range", stream_id);
@@ -495,8 +503,8 @@ extern "C" int bc_plan_save(BcPlan* pl, const char* path, const BcPlanBuffer* bu
     }
     uint32_t version = op_min_version(BC_OP_GEMM);    // the lowest version that has every recorded op
     for (Seg& sg : pl->segs)
-        for (Rec& r : sg.recs) version = std::max(version, op_min_version(r.op));
-    BC_CHECK_ARG(version != kNoFileVersion, "bc_plan_save: the plan holds launches that exist in-process only (include/blobctrl_sam.h)");
+        for (Rec& r : sg.recs) version = std::max(version, plan_op_min_version(r.op));
+    BC_CHECK_ARG(version != kNoFileVersion, "bc_plan_save: the plan holds launches that exist in-process only (include/blobctrl_sam.h, blobctrl_ip.h)");
     FILE* f = fopen(path, "wb");
     BC_CHECK_ARG(f != nullptr, "bc_plan_save: cannot open %s", path);
     Writer w{f};
@@ -532,7 +540,7 @@ extern "C" int bc_plan_save(BcPlan* pl, const char* path, const BcPlanBuffer* bu
                     put_ptr(addr);
                 }
             } else {
-                const char* sig = op_signature(r.op);
+                const char* sig = plan_op_signature(r.op);
                 w.u32((uint32_t)r.a.size());
                 for (size_t k = 0; k < r.a.size(); ++k) {
                     if (sig[k] == 'p') put_ptr(r.a[k]);

@@ -80,6 +80,23 @@ def freeu_basis(H: int, W: int) -> torch.Tensor:
     return out
 
 
+class IpAdapter:
+    """One loaded IP-Adapter as the planner sees it (IPAdapterAttnProcessor2_0 in every attn2 + the base ImageProjection).
+    kv: {attn2 block prefix "<...>transformer_blocks.0.": (to_k_ip, to_v_ip)}, fp16 [C][ctx_dim] on the device, in attn_processors order.
+    scales: fp32 device table with one word per entry of `kv`, in that order: bc_attention_ip reads its weight there on every replay, so
+    set_ip_adapter_scale rewrites the table and no plan or graph is recorded again.
+    The image side is either `tokens` - fp16 [B][T][ctx_dim], already projected - or `embeds`, fp16 [B * n_images][embed_dim] (a per-edit
+    input buffer), with the projection (proj_w fp16 [num_tokens * ctx_dim][embed_dim], proj_b / norm_w / norm_b fp32): Linear, reshape
+    to [B][n_images * num_tokens][ctx_dim], LayerNorm (D/models/embeddings.py ImageProjection)."""
+
+    def __init__(self, kv, scales, tokens=None, embeds=None, n_images=1, num_tokens=4, proj_w=None, proj_b=None, norm_w=None, norm_b=None):
+        assert (tokens is None) != (embeds is None) and scales.dtype == torch.float32 and scales.numel() == len(kv)
+        self.kv, self.scales, self.tokens, self.embeds = dict(kv), scales, tokens, embeds
+        self.n_images, self.num_tokens = n_images, num_tokens
+        self.proj_w, self.proj_b, self.norm_w, self.norm_b = proj_w, proj_b, norm_w, norm_b
+        self.slot = {bp: i for i, bp in enumerate(self.kv)}
+
+
 class TrunkPlan:
     """Records one forward of a trunk into the recorder's current segment."""
 
@@ -88,6 +105,8 @@ class TrunkPlan:
         self.G = cfg.norm_num_groups
         self.heads = cfg.num_heads
         self.freeu_params = None          # UNet with FreeU on: the plan's fp32 (s1, s2, b1, b2) buffer, read by bc_freeu on the device
+        self.ip_adapters = ()             # UNet with IP-Adapters loaded (IpAdapter): record_context projects their K / V per attn2
+        self.ip_kv = {}                   # attn2 block prefix -> [(K_ip, V_ip, tokens per image, weight word)] per adapter
 
     # ------------------------------------------------------------------------------------------- helpers
     def _r2(self, res_t, H, W):
@@ -368,6 +387,7 @@ class TrunkPlan:
                 rec.rowchain(_lib.CHAIN_MID, Cc, M, HW, a, w, v, h1, out1=q2, res=h0)
                 a = rec.empty(M, Cc)
                 rec.attention(q2, ck, cvt, a, B, self.heads, d, HW, T, Cc, Cc, ldc_vt, Cc, HW * Cc, T * Cc, Cc * ldc_vt, HW * Cc, scale)
+                self.attention_ip(bp, q2, a, B, HW, Cc, d, scale)
             h = h1
         out = rec.empty(M, Cc)
         part = rec.new_tot(B, Cc)                            # GroupNorm statistics of the block output (the next ResBlock's norm1)
@@ -403,6 +423,12 @@ class TrunkPlan:
             rec.rowchain(_lib.CHAIN_OUT, Cc, M, HW, a, w, v, out, res=h, res2=x.t, gn_tot=part, **kw)
         rec.tots[out.data_ptr()] = part
         return Act(out, Cc, x.H, x.W), res_out
+
+    def attention_ip(self, bp, q, a, B, HW, Cc, d, scale):
+        """The image cross-attention of every loaded IP-Adapter behind attn2's text attention, on the same query rows `q` and accumulated
+        onto the same output rows `a` (attention_processor.py:3808-3868): one bc_attention_ip launch per adapter.  Nothing without one."""
+        for K_ip, V_ip, T_ip, w in self.ip_kv.get(bp, ()):
+            self.rec.attention_ip(q, K_ip, V_ip, a, B, HW, self.heads, d, T_ip, Cc, Cc, Cc, scale, w)
 
     def gw_tile(self, M, N, K, C1=0, prefer=None):
         """BC_TILE_GW* configuration for a projection of the low-resolution levels (csrc/gemm_wreg.hip), or 0 = the LDS-DMA tiles.
@@ -481,6 +507,7 @@ class TrunkPlan:
             ck, cvt, T, ldc_vt = self.ctx_kv[bp]
             a = rec.empty(M, Cc)
             rec.attention(q, ck, cvt, a, B, self.heads, d, HW, T, Cc, Cc, ldc_vt, Cc, HW * Cc, T * Cc, Cc * ldc_vt, HW * Cc, scale)
+            self.attention_ip(bp, q, a, B, HW, Cc, d, scale)
             h = proj(a, bp + "attn2.to_out.0", Cc, Cc, G128, R=h, ldr=Cc, kind="attn_out")
         # --- GEGLU feed-forward: LayerNorm3 folded into ff.net.0; ff.net.2 (K = 4C) stays on the LDS-DMA tiles with split-K
         # (64 x 128 workgroups everywhere: two fit a CU - 80 KiB of LDS each - and measure best at every shape of these levels, e.g.
@@ -546,6 +573,7 @@ class TrunkPlan:
             a = rec.empty(M, Cc)
             rec.attention(q, ck, cvt, a, B, self.heads, d, HW, T, Cc, Cc, ldc_vt, Cc, HW * Cc, T * Cc, Cc * ldc_vt,
                           HW * Cc, scale)
+            self.attention_ip(bp, q, a, B, HW, Cc, d, scale)
             h = self.dense(a, M, Cc, bp + "attn2.to_out.0", Cc, R=h, ldr=Cc, kind="attn_out")
         # --- GEGLU feed-forward
         ln = rec.layernorm(h, M, Cc, pw.f[bp + "norm3.weight"], pw.f[bp + "norm3.bias"], 1e-5)
@@ -581,6 +609,10 @@ class TrunkPlan:
             rec.gemm(A=ctx, W=pw.h[bp + "attn2.to_v.weight"], M=B * T, N=Cc, K=Dc, out=cvt, out_mode=_lib.OUT_F16_T,
                      ldc=ldvt, rows_per_batch=T, kind="ctx_kv")
             self.ctx_kv[bp] = (ck, cvt, T, ldvt)
+            if self.ip_adapters:
+                # the image attention needs attn2's query rows in memory: CHAIN_MIDX keeps them inside the workgroup and bc_ctx_fold never
+                # forms them, so with an adapter loaded attn2 takes the forms that store q (those of BC_PLAN midx=0 / ctx_fold=0)
+                continue
             # blocks the row-chain takes with 8 heads and <= 80 context tokens: K / V^T also as the fragment streams of CHAIN_MIDX
             if Cc in (320, 640) and self.heads == 8 and T <= 80 and opt("midx") and opt("rowchain"):
                 self.ctx_kvs[bp] = rec.rowchain_kv_stream(ck, cvt, B, T, Cc, ldvt)
@@ -589,6 +621,34 @@ class TrunkPlan:
             if self.ctx_fold_ok(Cc, T):
                 wq, bq, wo = pw.ctx_fold_weights(bp)
                 self.ctx_folded[bp] = rec.ctx_fold(ck, cvt, B, T, Cc, ldvt, self.heads, (Cc // self.heads) ** -0.5, wq, bq, wo)
+
+        self.record_ip_context()
+
+    def record_ip_context(self):
+        """The image side of the loaded IP-Adapters, once per edit with the launches the text side uses: the adapter's image tokens
+        (given, or ImageProjection of its embeddings: Linear -> [B][n_images * num_tokens][ctx_dim] -> LayerNorm), then per attn2 block
+        K_ip = tokens @ to_k_ip^T and V_ip = tokens @ to_v_ip^T, both row-major [B][T][C] as bc_attention_ip reads them."""
+        rec, B = self.rec, self.B
+        self.ip_kv = {}
+        for ad in self.ip_adapters:
+            if ad.tokens is not None:
+                tokens = ad.tokens
+            else:
+                rows, Dn = B * ad.n_images, ad.proj_w.shape[0]
+                lin = rec.empty(rows, Dn)
+                rec.gemm(A=ad.embeds, W=ad.proj_w, M=rows, N=Dn, K=ad.proj_w.shape[1], out=lin, bias=ad.proj_b, kind="ip_proj")
+                Dc = Dn // ad.num_tokens
+                tokens = rec.layernorm(lin, rows * ad.num_tokens, Dc, ad.norm_w, ad.norm_b, 1e-5).view(B, -1, Dc)
+            assert tokens.shape[0] == B, "IP-Adapter tokens: one set per UNet image"
+            T_ip, Dc = tokens.shape[1], tokens.shape[2]
+            if not 1 <= T_ip <= _lib.ATTENTION_IP_MAX_T:
+                raise ValueError(f"an IP-Adapter brings {T_ip} image tokens per UNet image; bc_attention_ip takes 1 .. {_lib.ATTENTION_IP_MAX_T}")
+            for bp, (wk, wv) in ad.kv.items():
+                Cc = wk.shape[0]
+                K_ip, V_ip = rec.empty(B, T_ip, Cc), rec.empty(B, T_ip, Cc)
+                rec.gemm(A=tokens, W=wk, M=B * T_ip, N=Cc, K=Dc, out=K_ip, kind="ip_kv")
+                rec.gemm(A=tokens, W=wv, M=B * T_ip, N=Cc, K=Dc, out=V_ip, kind="ip_kv")
+                self.ip_kv.setdefault(bp, []).append((K_ip, V_ip, T_ip, ad.scales[ad.slot[bp]:ad.slot[bp] + 1]))
 
     # ------------------------------------------------------------------------------------------- per-edit weight collapse
     def record_collapse(self, feat16: torch.Tensor, per_image: int = 0):

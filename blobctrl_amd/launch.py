@@ -645,6 +645,18 @@ class Recorder:
                  shape=(B, heads, d, Nq, Nkv), bytes_=2 * B * heads * d * (2 * Nq + 2 * Nkv))
         return out
 
+    def attention_ip(self, Q, K, V, out, B, rows_per_batch, heads, d, T, ldq, ldkv, ldo, scale, w, q_off=0):
+        """bc_attention_ip (include/blobctrl_ip.h): the image cross-attention of one IP-Adapter accumulated onto `out` - attn2's text
+        attention output - in place.  K / V [B][T][ldkv] row-major, `w` = the fp32 device word holding this (block, adapter)'s scale."""
+        Cc = heads * d
+        self.keep.append((Q, K, V, out, w))
+        for t in (Q, K, V, out, w):
+            self.register(t)
+        self._op("bc_attention_ip", (Q.data_ptr() + q_off * 2, K, V, out, B, rows_per_batch, heads, d, T, ldq, ldkv, ldo, scale, w),
+                 "attention_ip", flops=4 * B * rows_per_batch * T * Cc, variant=f"attention_ip_kernel<{d}>",
+                 shape=("attention_ip", B, heads, d, rows_per_batch, T), bytes_=2 * (3 * B * rows_per_batch * Cc + 2 * B * T * Cc))
+        return out
+
     # ------------------------------------------------------------------ row-chain (fused transformer-block glue, csrc/rowchain.hip)
     def rowchain(self, kind, Cc, M, rows_per_batch, x, wstream, vec, out0, out1=None, out2=None, ldvt=0, affine=None, gn_in=None, res=None, res2=None,
                  r2=None, r2_xmin=0, r2_bmod=1, out_w=0, gn_tot=None, ln_eps=1e-5, alpha=1.0, alpha_dev=None, alpha_idx=None,

@@ -15,7 +15,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import Residuals, TrunkConfig, TrunkPlan, freeu_enabled
+from .engine import IpAdapter, Residuals, TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder, run_graphed
 from .weights import LoraAdapters, PackedTrunk, lora_scale_of, pad8
 
@@ -70,7 +70,8 @@ class _TrunkModule(LoraAdapters, torch.nn.Module):
             conv_in_channels=config.in_channels, out_channels=config.out_channels, block_out_channels=tuple(config.block_out_channels),
             layers_per_block=config.layers_per_block, attention_head_dim=config.num_heads, norm_num_groups=config.norm_num_groups,
             cross_attention_dim=config.cross_attention_dim, time_cond_proj_dim=config.time_cond_proj_dim, sample_size=64,
-            conditioning_channels=(config.in_channels - latent) if config.is_blobnet else None)
+            conditioning_channels=(config.in_channels - latent) if config.is_blobnet else None,
+            encoder_hid_dim_type="ip_image_proj" if self.__dict__.get("ip_adapters") else None)
 
     # ---- weights: packed lazily from the host state dict + the active LoRA adapters
     def effective_state_dict(self, lora_scale: float = 1.0):
@@ -236,6 +237,7 @@ class UNet2DConditionModel(_TrunkModule):
         assert not config.is_blobnet
         super().__init__(state_dict, config, device, lazy)
         self.__dict__["freeu"] = None          # (s1, s2, b1, b2) after enable_freeu
+        self.__dict__.setdefault("ip_adapters", [])        # loaded IP-Adapters: device weights + the scale table of each
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, extra_in_channels=0, lora_path=None, lora_scale=1.0, device="cuda:0", **_ignored):
@@ -258,6 +260,73 @@ class UNet2DConditionModel(_TrunkModule):
     def disable_freeu(self):
         """Disables the FreeU mechanism."""
         self.__dict__["freeu"] = None
+
+    # ---- IP-Adapter (D/loaders/unet.py:823-853: IPAdapterAttnProcessor2_0 in every attn2, encoder_hid_proj = the image projections)
+    def load_ip_adapter_weights(self, state_dicts):
+        """`unet._load_ip_adapter_weights`: one adapter or a list, each the original {"image_proj", "ip_adapter"} dict or a .safetensors
+        file (checkpoint.load_ip_adapter).  Base adapters only; every scale starts at 1.0 as in the reference.  The weights live beside
+        the packed trunk: nothing is re-packed, and the adapter-less plans stay what they were."""
+        from .checkpoint import load_ip_adapter
+        from .weights import convert_ip_adapter, ip_adapter_on_device, ip_attn2_prefixes
+        if self._sd is None:
+            raise _lib.BlobCtrlHipError("this UNet was built from packed weights: IP-Adapter weights are laid out against its state dict")
+        prefixes = ip_attn2_prefixes(self._sd.keys())
+        host = [convert_ip_adapter(sd, prefixes, self.trunk_config.cross_attention_dim) for sd in load_ip_adapter(state_dicts)]
+        self._drop_ip_plans()
+        self.__dict__["ip_adapters"] = [ip_adapter_on_device(h, self._device) for h in host]
+        self._make_config()
+
+    def unload_ip_adapter(self):
+        """Back to the adapter-less UNet: config.encoder_hid_dim_type is None again and forward takes no image_embeds."""
+        self._drop_ip_plans()
+        self.__dict__["ip_adapters"] = []
+        self._make_config()
+
+    def set_ip_adapter_scale(self, scale):
+        """A float for every adapter, or one entry per adapter: a float, or a list with one value per attn2 processor in
+        `attn_processors` order.  Only the device scale tables are rewritten - recorded plans and their graphs read them on replay."""
+        ads = self.__dict__.get("ip_adapters") or []
+        if not ads:
+            raise ValueError("no IP-Adapter is loaded")
+        scales = [scale] * len(ads) if not isinstance(scale, (list, tuple)) else list(scale)
+        if len(scales) != len(ads):
+            raise ValueError(f"Cannot assign {len(scales)} scales to {len(ads)} IP-Adapter.")
+        for ad, s in zip(ads, scales):
+            n = ad["scales"].numel()
+            vals = [float(s)] * n if not isinstance(s, (list, tuple)) else [float(v) for v in s]
+            if len(vals) != n:
+                raise ValueError(f"a per-block scale list has one value per attn2 processor ({n}), got {len(vals)}")
+            ad["scales"].copy_(torch.tensor(vals, dtype=torch.float32))
+
+    def _drop_ip_plans(self):
+        """Plans recorded with adapters point at their weights and scale tables: they go with them."""
+        self.__dict__["_ip_version"] = self.__dict__.get("_ip_version", 0) + 1      # (the pipeline's loop engine follows: pipeline.engine)
+        drop = [k for k in self._plans if any(isinstance(x, tuple) and x[:1] == ("ip",) for x in k)]
+        if drop and self._device.type == "cuda":
+            torch.cuda.synchronize(self._device)
+        for k in drop:
+            self._plans.pop(k).rec.close()
+
+    def _check_image_embeds(self, added_cond_kwargs, B):
+        """unet_2d_condition.py process_encoder_hidden_states: with adapters loaded, `image_embeds` - a list with one [B][n_images][embed_dim]
+        tensor per adapter - is required; without one it is not taken."""
+        ads = self.__dict__.get("ip_adapters") or []
+        embeds = (added_cond_kwargs or {}).get("image_embeds")
+        if not ads:
+            if embeds is not None:
+                raise ValueError("image_embeds were passed in added_cond_kwargs, but no IP-Adapter is loaded (load_ip_adapter_weights)")
+            return None
+        if embeds is None:
+            raise ValueError(f"{type(self)} has the config param `encoder_hid_dim_type` set to 'ip_image_proj' which requires the keyword "
+                             "argument `image_embeds` to be passed in  `added_conditions`")
+        if torch.is_tensor(embeds):
+            embeds = [embeds.unsqueeze(1) if embeds.ndim == 2 else embeds]
+        if len(embeds) != len(ads):
+            raise ValueError(f"image_embeds holds {len(embeds)} tensors for {len(ads)} loaded IP-Adapters")
+        for e, ad in zip(embeds, ads):
+            if e.ndim != 3 or e.shape[0] != B or e.shape[2] != ad["proj_w"].shape[1]:
+                raise ValueError(f"image_embeds of an adapter must be [batch = {B}][images][{ad['proj_w'].shape[1]}], got {tuple(e.shape)}")
+        return list(embeds)
 
     # ---- `unet.conv_in` as the script uses it (inf:233-249): reads .weight / .bias / .out_channels, assigns a wider Conv2d
     @property
@@ -316,11 +385,11 @@ class UNet2DConditionModel(_TrunkModule):
                 up.append((rev[i],) + sizes[nb - 2 - i])
         return down, mid, up
 
-    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False):
+    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False, ip=()):
         """`cond`: the plan takes a `timestep_cond` (fp16 [B][pad8(time_cond_proj_dim)]) and adds cond_proj of it to the sinusoid; a
         plan of its own, so that calls without one keep the launches they always recorded.  `freeu`: likewise a plan of its own, with
         bc_freeu in up_blocks.0 / up_blocks.1 reading (s1, s2, b1, b2) from the plan buffer P.freeu."""
-        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ()) + (("freeu",) if freeu else ())
+        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ()) + (("freeu",) if freeu else ()) + ((("ip",) + tuple(ip),) if ip else ())
         if key not in self._plans:
             rec = Recorder(self.device)
             P = type("Plan", (), {})()
@@ -340,6 +409,14 @@ class UNet2DConditionModel(_TrunkModule):
             plan = TrunkPlan(rec, self.weights, self.trunk_config, B, H, W)
             if freeu:
                 P.freeu = plan.freeu_params = rec.zeros(4, dtype=torch.float32)
+            if ip:
+                # `ip` = images per adapter, the part of the adapter configuration a call can change; the adapter count and the embedding
+                # width are fixed by what is loaded, and load / unload drop every plan that carries an `ip` entry (_drop_ip_plans).  Scales
+                # are no part of the key: the launches read them from the adapters' device tables
+                ads = self.__dict__["ip_adapters"]
+                P.ip_embeds = [rec.zeros(B * n, ad["proj_w"].shape[1]) for n, ad in zip(ip, ads)]
+                plan.ip_adapters = [IpAdapter(ad["kv"], ad["scales"], embeds=e, n_images=n, proj_w=ad["proj_w"], proj_b=ad["proj_b"],
+                                              norm_w=ad["norm_w"], norm_b=ad["norm_b"]) for n, ad, e in zip(ip, ads, P.ip_embeds)]
             plan.record_context(P.ctx, T)
             if cond:
                 P.cond = rec.zeros(B, pad8(self.trunk_config.time_cond_proj_dim))
@@ -377,12 +454,17 @@ class UNet2DConditionModel(_TrunkModule):
             if tuple(timestep_cond.shape) != (B, dim):
                 raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
         self.set_lora_scale(lora_scale_of(cross_attention_kwargs))          # (a change of scale re-packs: the plans below are then new ones)
+        # the image embeddings reach the body beside the dispatcher's fixed schema, as module state of this one call
+        self.__dict__["_image_embeds"] = self._check_image_embeds(added_cond_kwargs, B)
         # through the dispatcher (torch.ops.blobctrl.unet_forward, ops.py); `timestep_cond` is the op's optional trailing argument
         from . import ops
         extra = () if timestep_cond is None else (timestep_cond,)
-        eps = torch.ops.blobctrl.unet_forward(sample, float(timestep), encoder_hidden_states,
-                                              list(down_block_add_samples) if is_blobnet else [], mid_block_add_sample if is_blobnet else None,
-                                              list(up_block_add_samples) if is_blobnet else [], ops.register(self), *extra)
+        try:
+            eps = torch.ops.blobctrl.unet_forward(sample, float(timestep), encoder_hidden_states,
+                                                  list(down_block_add_samples) if is_blobnet else [], mid_block_add_sample if is_blobnet else None,
+                                                  list(up_block_add_samples) if is_blobnet else [], ops.register(self), *extra)
+        finally:
+            self.__dict__["_image_embeds"] = None                       # (state of this one call: a later direct op call sees none)
         if is_blobnet:                                   # the reference consumes the two lists with pop(0) (:1217, 1230, 1313)
             del down_block_add_samples[:]
             del up_block_add_samples[:]
@@ -396,7 +478,11 @@ class UNet2DConditionModel(_TrunkModule):
         is_blobnet = mid_block_add_sample is not None
         T, Dc = encoder_hidden_states.shape[1:]
         freeu = self.__dict__.get("freeu")
-        P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None, freeu=freeu_enabled(freeu))
+        embeds = self.__dict__.get("_image_embeds")
+        P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None, freeu=freeu_enabled(freeu),
+                       ip=tuple(e.shape[1] for e in embeds) if embeds else ())
+        for buf, e in zip(getattr(P, "ip_embeds", ()), embeds or ()):
+            buf.copy_(e.to(self.device, torch.float16).reshape(buf.shape))
         if freeu_enabled(freeu):
             P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
         if timestep_cond is not None:

@@ -23,7 +23,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import _lib
-from .engine import TrunkConfig, TrunkPlan, freeu_enabled
+from .engine import IpAdapter, TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder
 from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, stack_request_tables, table_class
 from .weights import PackedTrunk, lora_scale_of, pad8
@@ -110,10 +110,47 @@ class BlobCtrlEngine:
         self.feat_dim = blobnet_config.in_channels - 5
         self.vae = vae                                                # optional blobctrl_amd.vae.AutoencoderKL
         self.text_encoder = text_encoder                              # optional blobctrl_amd.clip_text.CLIPTextModel
+        self.ip_adapters = []                                         # loaded IP-Adapters (set_ip_adapters): device weights + scale tables
+
+    # ------------------------------------------------------------------------------------------------ IP-Adapter
+    def set_ip_adapters(self, adapters):
+        """The loaded IP-Adapters, as UNet2DConditionModel.load_ip_adapter_weights lays them out on the device (proj_w, proj_b, norm_w,
+        norm_b, kv per attn2 block, the fp32 scale table); [] = none.  Plans recorded with adapters point at their weights and scale
+        tables and go with them; adapter-less plans stay.  Scales are device data: rewriting a table records nothing."""
+        drop = [k for k in self._plans if any(isinstance(x, tuple) and x[:1] == ("ip",) for x in k)]
+        if drop and self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        for k in drop:
+            self._plans.pop(k).rec.close()
+        self.ip_adapters = list(adapters or [])
+
+    def _ip_layout(self, embeds, Bu, B, duplicated):
+        """`ip_adapter_image_embeds` of a call -> (images per adapter, [fp16-able tensor [Bu][images][embed_dim]] per adapter).  One 3D
+        tensor per loaded adapter, batch = the UNet batch ([negative, positive] halves with classifier-free guidance); `duplicated`: the
+        plan runs the positive prompts in both halves, so B rows are taken twice."""
+        if embeds is None:
+            if self.ip_adapters:
+                raise ValueError(f"{len(self.ip_adapters)} IP-Adapter(s) are loaded: pass `ip_adapter_image_embeds` (one tensor per adapter), or unload them")
+            return (), []
+        if not self.ip_adapters:
+            raise ValueError("`ip_adapter_image_embeds` were passed, but no IP-Adapter is loaded (load_ip_adapter)")
+        if not isinstance(embeds, (list, tuple)) or len(embeds) != len(self.ip_adapters):
+            raise ValueError(f"`ip_adapter_image_embeds` must be a list with one tensor per loaded IP-Adapter ({len(self.ip_adapters)})")
+        out = []
+        for e, ad in zip(embeds, self.ip_adapters):
+            if e.ndim != 3 or e.shape[2] != ad["proj_w"].shape[1]:
+                raise ValueError(f"an adapter's image embeddings must be [batch][images][{ad['proj_w'].shape[1]}], got {tuple(e.shape)}")
+            if duplicated and e.shape[0] == B:
+                e = torch.cat([e, e], 0)
+            if e.shape[0] != Bu:
+                raise ValueError(f"`ip_adapter_image_embeds` hold {e.shape[0]} rows, the UNet batch of this call is {Bu} "
+                                 "(with classifier-free guidance: the negative and the positive halves)")
+            out.append(e)
+        return tuple(int(e.shape[1]) for e in out), out
 
     # ------------------------------------------------------------------------------------------------ planning
     def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-              freeu=False, requests=False):
+              freeu=False, requests=False, ip=()):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
@@ -135,6 +172,10 @@ class BlobCtrlEngine:
         image; no `t_table`) and `scale_table` [nsteps][B]; the time tables come from bc_timestep_embedding_rows, a scaling table
         assembles through the `_requests` entry points (a divisor per image) and both step segments end in
         bc_scheduler_step_requests.  The networks are what they are in every request batch.
+        ip: images per loaded IP-Adapter (empty: none).  The plan owns the named buffers `ip_embeds<i>` (fp16 [UNet batch * images][embed
+        dim], per-edit inputs like `ctx`); its prologue projects them to image tokens and to K_ip / V_ip per attn2 block, and every UNet
+        forward runs one bc_attention_ip per adapter behind each attn2 (16 per adapter).  The key holds the adapter configuration - count,
+        tokens each, embedding width - and never the scales, which the launches read from the adapters' device tables.  In-process only.
         `denoise` and `compile_plan` take every one of these switches from the EditSetup of their call (`_setup`) and fill the tables
         with `_write_tables`; a call without lists never asks for `requests`."""
         if requests and not per_request:
@@ -142,7 +183,8 @@ class BlobCtrlEngine:
         if stochastic and third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
         key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
-            (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ()) + (("requests",) if requests else ())
+            (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ()) + (("requests",) if requests else ()) + \
+            (((("ip", len(ip)) + tuple((4 * n, ad["proj_w"].shape[1]) for n, ad in zip(ip, self.ip_adapters))),) if ip else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -213,6 +255,9 @@ class BlobCtrlEngine:
         P.prologue = rec.begin("prologue")
         unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_a.freeu_params = P.freeu
+        P.ip_embeds = [rec.zeros(Bu * n, ad["proj_w"].shape[1], name=f"ip_embeds{i}") for i, (n, ad) in enumerate(zip(ip, self.ip_adapters))]
+        unet_a.ip_adapters = [IpAdapter(ad["kv"], ad["scales"], embeds=e, n_images=n, proj_w=ad["proj_w"], proj_b=ad["proj_b"],
+                                        norm_w=ad["norm_w"], norm_b=ad["norm_b"]) for n, ad, e in zip(ip, self.ip_adapters, P.ip_embeds)]
         unet_a.record_context(P.ctx, T)
         blob = TrunkPlan(rec, self.blob_w, self.blob_cfg, B, H, W)
         if P.collapse:
@@ -248,6 +293,7 @@ class BlobCtrlEngine:
             #  unfused MID + attention launches)
             hp.ctx_kvs = {bp: kvs.view(2 * B, -1)[b0:b0 + B].reshape(-1) for bp, kvs in getattr(unet_a, "ctx_kvs", {}).items()}
             hp.ctx_folded = {bp: tuple(t[b0:b0 + B] for t in f) for bp, f in getattr(unet_a, "ctx_folded", {}).items()}
+            hp.ip_kv = {bp: [(K[b0:b0 + B], V[b0:b0 + B], T_, w_) for K, V, T_, w_ in kv] for bp, kv in unet_a.ip_kv.items()}
             hp.tproj, hp.tproj_table = half_time.tproj, half_time.tproj_table
             return hp
 
@@ -320,6 +366,7 @@ class BlobCtrlEngine:
         unet_i = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_i.freeu_params = P.freeu
         unet_i.ctx_kv, unet_i.ctx_kvs, unet_i.ctx_folded = unet_a.ctx_kv, getattr(unet_a, "ctx_kvs", {}), getattr(unet_a, "ctx_folded", {})
+        unet_i.ip_kv = unet_a.ip_kv
         if not temb_per_step:
             unet_i.tproj, unet_i.tproj_table = unet_a.tproj, unet_a.tproj_table
         record_unet(unet_i, None)
@@ -747,7 +794,8 @@ class BlobCtrlEngine:
                  bg_image: Optional[torch.Tensor] = None, return_sample: bool = False, eta: float = 0.0,
                  do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
                  variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None,
-                 single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None, freeu=None):
+                 single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None, freeu=None,
+                 ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -775,6 +823,9 @@ class BlobCtrlEngine:
         `freeu` = (s1, s2, b1, b2) or None: FreeU (UNet2DConditionModel.enable_freeu) in up_blocks.0 / up_blocks.1 of the UNet.  As in the
         reference any value of 0.0 or None among the four runs the plain network - the plan every other call uses.  The values are
         per-edit data of the FreeU plan: other values replay the same graph.
+        `ip_adapter_image_embeds`: with IP-Adapters loaded (`set_ip_adapters`), one tensor [UNet batch][images][embed_dim] per adapter,
+        as the reference's prepare_ip_adapter_image_embeds returns them: the negative and the positive halves with classifier-free
+        guidance, one row per UNet image in a request batch too.  Per-edit data of the plan, like `prompt_embeds`.
         A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps (a list of
         lists): the requests of a request batch run their own schedules, on the `requests` plan form.  Both kinds of call are one
         set-up (`_setup` -> EditSetup; a call without lists is "one table, shared by every image"), one plan, one run; `self.timesteps`
@@ -818,8 +869,10 @@ class BlobCtrlEngine:
                         blobnet_control_guidance_start, blobnet_control_guidance_end, eta, guidance_off)
         self._check_timestep_cond(timestep_cond, B)
         self._check_variance_noise(S, variance_noise, (B, 4, h, w), generator)
+        Bu = B if single else 2 * B
+        ip, ip_embeds = self._ip_layout(ip_adapter_image_embeds, Bu, B, duplicated=not single and prompt_embeds.shape[0] == 2 * B and guidance_off)
         P = self._plan(B, h, w, T, Dc, S.n, per_request, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
-                       requests=S.requests)
+                       requests=S.requests, ip=ip)
         dev = self.device
         self.timesteps = [t.timesteps for t in S.tables] if S.requests else S.tables[0].timesteps
         if latents is None:                                                          # pipe:438-453
@@ -834,6 +887,8 @@ class BlobCtrlEngine:
             start = latents.to(dev, torch.float32) * sigma.view(-1, 1, 1, 1)
             self._fill_inputs(P, start, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond)
             self._write_tables(P, S, freeu)
+            for buf, e in zip(P.ip_embeds, ip_embeds):
+                buf.copy_(e.to(dev, torch.float16).reshape(buf.shape))
             if S.stochastic:
                 P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
             P.step_idx.zero_()
@@ -974,6 +1029,9 @@ class BlobCtrlEngine:
         (fg_lat, bg_lat, fg_score, bg_score, feat / feat16 with a leading B) it holds, saved with their contents, `coef` [B][nmax][16],
         `t_rows_unet` [nmax][2B or B], `t_rows_blob` [nmax][B] and `scale_table` [nmax][B] instead of `t_table` / `coef` [n][16] /
         `scale_table` [n]; `variance_noise` [nmax][B][4][h][w] as above; the segment names returned are those of the nmax steps."""
+        if self.ip_adapters:
+            raise NotImplementedError("a plan with IP-Adapters loaded is recorded and replayed in-process only (bc_attention_ip is not part of "
+                                      "the .bcplan format): unload them, or run `denoise`")
         listed = bool(self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                    blobnet_control_guidance_start=blobnet_control_guidance_start,
                                    blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps))
@@ -996,8 +1054,8 @@ class BlobCtrlEngine:
 
     # convenience for bench / tests ------------------------------------------------------------------
     def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-                 freeu=False, requests=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests)
+                 freeu=False, requests=False, ip=()):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip)
 
 
 def _is_device_image(image):
@@ -1120,6 +1178,10 @@ class StableDiffusionBlobNetPipeline:
             self._engine.unet_w = self._engine.blob_w = None
             self._engine.set_weights(self.unet.weights, self.blobnet.weights)
             self._engine_versions = versions
+        ip_version = self.unet.__dict__.get("_ip_version", 0)         # (the UNet's adapters were loaded or unloaded since: plans with them go)
+        if getattr(self._engine, "_ip_version", 0) != ip_version:
+            self._engine.set_ip_adapters(self.unet.__dict__.get("ip_adapters"))
+            self._engine._ip_version = ip_version
         if self._scheduler.kind is not None:
             self._engine.set_scheduler(self._scheduler.kind, self._scheduler.table_params()
                                        if hasattr(self._scheduler, "table_params") else None)
@@ -1231,6 +1293,95 @@ class StableDiffusionBlobNetPipeline:
             raise ValueError("The pipeline must have `unet` for using FreeU.")
         self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
 
+    # ---- IP-Adapter (IPAdapterMixin, D/loaders/ip_adapter.py: load_ip_adapter / set_ip_adapter_scale / unload_ip_adapter)
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None, weight_name=None, image_encoder_folder=None):
+        """One adapter or a list (of paths, of dicts, or of weight names under one path): the original {"image_proj", "ip_adapter"} dict
+        or a `.safetensors` file at path[/subfolder]/weight_name.  No image encoder is loaded (`image_encoder_folder` is accepted and
+        unused): the call takes `ip_adapter_image_embeds`.  Every scale starts at 1.0."""
+        import os
+        many = isinstance(weight_name, (list, tuple)) or isinstance(pretrained_model_name_or_path_or_dict, (list, tuple))
+        n = len(weight_name) if isinstance(weight_name, (list, tuple)) else len(pretrained_model_name_or_path_or_dict) if many else 1
+        as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        srcs = []
+        for src, sub, name in zip(as_list(pretrained_model_name_or_path_or_dict), as_list(subfolder), as_list(weight_name)):
+            if not isinstance(src, dict):
+                src = os.path.join(*[x for x in (os.fspath(src), sub, name) if x])
+            srcs.append(src)
+        self.unet.load_ip_adapter_weights(srcs)                       # (`engine` takes them over on its next use)
+
+    def ip_adapter_scale_lists(self, scale):
+        """What `set_ip_adapter_scale(scale)` assigns: one list per adapter with a value per attn2 processor in `attn_processors` order
+        (None where the argument leaves a processor as it is).  `scale`: a float or a per-block dict ({"down": {"block_2": [0.0, 1.0]},
+        "up": ..., "mid": ...}; what a dict does not name is 0.0), or a list of those with one entry per adapter (a single entry serves
+        every adapter) - D/loaders/ip_adapter.py:245-295 with _maybe_expand_lora_scales(default_scale=0.0)."""
+        from .weights import ip_attn2_prefixes
+        ads = self.unet.__dict__.get("ip_adapters") or []
+        configs = list(scale) if isinstance(scale, list) else [scale]
+        if len(configs) != len(ads):
+            raise ValueError(f"Cannot assign {len(configs)} scale_configs to {len(ads)} IP-Adapter.")
+        cfg = self.unet.trunk_config
+        nb, per = len(cfg.block_out_channels), {"down": cfg.layers_per_block, "up": cfg.layers_per_block + 1}
+        with_tf = {"down": list(range(nb - 1)), "up": list(range(1, nb))}             # SD layout: the last down / first up block has none
+        prefixes = ip_attn2_prefixes(self.unet._sd.keys()) if self.unet._sd is not None else list(ads[0]["kv"])
+        out = []
+        for c in configs:
+            if not isinstance(c, dict):
+                out.append([float(c)] * len(prefixes))
+                continue
+            names = {}
+            mid = c.get("mid", 0.0)
+            if isinstance(mid, list):
+                if len(mid) != 1:
+                    raise ValueError(f"Expected 1 scales for mid, got {len(mid)}.")
+                mid = mid[0]
+            names["mid_block.attentions.0."] = mid
+            for ud in ("up", "down"):
+                blocks = c.get(ud, 0.0)
+                if not isinstance(blocks, dict):
+                    blocks = {f"block_{i}": blocks for i in with_tf[ud]}
+                for i in with_tf[ud]:
+                    v = blocks.get(f"block_{i}", 0.0)
+                    v = [v] * per[ud] if not isinstance(v, list) else v * per[ud] if len(v) == 1 else v
+                    if len(v) != per[ud]:
+                        raise ValueError(f"Expected {per[ud]} scales for {ud}.block_{i}, got {len(v)}.")
+                    for j, x in enumerate(v):
+                        names[f"{ud}_blocks.{i}.attentions.{j}."] = x
+                extra = [k for k in blocks if k not in {f"block_{i}" for i in with_tf[ud]}]
+                if extra:
+                    raise ValueError(f"Can't set scale for layer {ud}.{extra[0]}: this UNet has no attention there.")
+            out.append([next((float(v) for k, v in names.items() if bp.startswith(k)), None) for bp in prefixes])
+        return out
+
+    def set_ip_adapter_scale(self, scale):
+        """The reference's set_ip_adapter_scale: see `ip_adapter_scale_lists`.  Only the adapters' device scale tables are rewritten -
+        recorded plans and whole-edit graphs read them on replay."""
+        ads = self.unet.__dict__.get("ip_adapters") or []
+        for ad, vals in zip(ads, self.ip_adapter_scale_lists(scale)):
+            old = ad["scales"].cpu().tolist()
+            ad["scales"].copy_(torch.tensor([o if v is None else v for o, v in zip(old, vals)], dtype=torch.float32))
+
+    def unload_ip_adapter(self):
+        self.unet.unload_ip_adapter()
+
+    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, ip_adapter_image_embeds, device, num_images_per_prompt,
+                                        do_classifier_free_guidance):
+        """D/pipelines/stable_diffusion/pipeline_stable_diffusion.py:508-552 for given embeddings: with classifier-free guidance each
+        tensor is chunked into its (negative, positive) halves, each half is repeated num_images_per_prompt times, and the halves are
+        concatenated again."""
+        if ip_adapter_image_embeds is None:
+            raise NotImplementedError("`ip_adapter_image` needs a CLIP vision tower, which this pipeline does not have: pass `ip_adapter_image_embeds`")
+        out = []
+        for e in ip_adapter_image_embeds:
+            if do_classifier_free_guidance:
+                if e.shape[0] % 2:
+                    raise ValueError(f"with classifier-free guidance `ip_adapter_image_embeds` hold the negative and the positive halves; got {e.shape[0]} rows")
+                neg, pos = e.chunk(2)
+                e = torch.cat([torch.cat([neg] * num_images_per_prompt, 0), torch.cat([pos] * num_images_per_prompt, 0)], 0)
+            else:
+                e = torch.cat([e] * num_images_per_prompt, 0)
+            out.append(e.to(device))
+        return out
+
     def disable_freeu(self):
         """Disables the FreeU mechanism if enabled."""
         self.unet.disable_freeu()
@@ -1313,8 +1464,20 @@ class StableDiffusionBlobNetPipeline:
                 raise ValueError(f"control guidance start: {start} can't be smaller than 0.")
             if end > 1.0:
                 raise ValueError(f"control guidance end: {end} can't be larger than 1.0.")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            raise NotImplementedError("IP-Adapter inputs are not part of the BlobCtrl path (the scripts never pass them)")
+        # pipe:422-436
+        if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
+            raise ValueError("Provide either `ip_adapter_image` or `ip_adapter_image_embeds`. Cannot leave both `ip_adapter_image` and "
+                             "`ip_adapter_image_embeds` defined.")
+        if ip_adapter_image_embeds is not None:
+            if not isinstance(ip_adapter_image_embeds, list):
+                raise ValueError(f"`ip_adapter_image_embeds` has to be of type `list` but is {type(ip_adapter_image_embeds)}")
+            elif ip_adapter_image_embeds[0].ndim not in [3, 4]:
+                raise ValueError(f"`ip_adapter_image_embeds` has to be a list of 3D or 4D tensors but is {ip_adapter_image_embeds[0].ndim}D")
+        if ip_adapter_image is not None:
+            # the reference pipeline registers no image_encoder (and its own __call__ fails on either IP input: pipe:925 calls a method
+            # the class never copied); the embeddings are the supported input
+            raise NotImplementedError("`ip_adapter_image` needs a CLIP vision tower, which this pipeline does not have: encode the image "
+                                      "yourself and pass `ip_adapter_image_embeds`")
 
     # ---- pipe:508-687
     def _tokenize(self, text, max_length):
@@ -1496,6 +1659,15 @@ class StableDiffusionBlobNetPipeline:
         if self.unet.config.time_cond_proj_dim is not None:
             w = torch.full((batch_size * num_images_per_prompt,), self.guidance_scale - 1, dtype=torch.float32)
             timestep_cond = get_guidance_scale_embedding(w, self.unet.config.time_cond_proj_dim)
+        # 3.1 the image embeddings of the loaded IP-Adapters (pipe:923-930)
+        ip_embeds = None
+        if ip_adapter_image_embeds is not None:
+            ip_embeds = self.prepare_ip_adapter_image_embeds(None, ip_adapter_image_embeds, self.device, batch_size * num_images_per_prompt, cfg)
+            want = batch_size * num_images_per_prompt * (2 if cfg else 1)
+            for e in ip_embeds:
+                if e.ndim != 3 or e.shape[0] != want:
+                    raise ValueError(f"`ip_adapter_image_embeds`: after the chunk and repeat of prepare_ip_adapter_image_embeds a tensor is "
+                                     f"{tuple(e.shape)}; the UNet batch of this call needs [{want}][images][embed_dim]")
         cb = None
         if callback_on_step_end is not None:
             def cb(_engine, i, t, kw):
@@ -1508,7 +1680,7 @@ class StableDiffusionBlobNetPipeline:
                                     blobnet_control_guidance_end=blobnet_control_guidance_end[0], output_type="latent",
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
                                     generator=generator, timesteps=timesteps, timestep_cond=timestep_cond,
-                                    freeu=getattr(self.unet, "freeu", None))
+                                    freeu=getattr(self.unet, "freeu", None), ip_adapter_image_embeds=ip_embeds)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

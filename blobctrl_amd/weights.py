@@ -571,3 +571,67 @@ def pack_rowchain(pw: "PackedTrunk", p: str, kind: int, zero_name: Optional[str]
             return torch.stack(slices).contiguous(), torch.cat([v.reshape(-1).float() for v in vec]).contiguous()
     pad = torch.zeros(nw, RC_RPAD, 64, 8, dtype=torch.float16, device=segs[0].device)
     return torch.cat(segs + [pad], 1).contiguous(), torch.cat([v.reshape(-1).float() for v in vec]).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------- IP-Adapter
+IP_NUM_TOKENS = 4                       # image tokens per image of the base ImageProjection (D/loaders/unet.py:783-785)
+
+
+def ip_attn2_prefixes(keys):
+    """The attn2 block prefixes ("<block>.attentions.<j>.transformer_blocks.0.") of a UNet state dict in `unet.attn_processors` order -
+    down_blocks, up_blocks, mid_block (the order the reference registers the modules in) - which is the order the key ids 1, 3, 5, ... of
+    an IP-Adapter file count through (D/loaders/unet.py:760-819)."""
+    end = "attn2.to_k.weight"
+    rank = {"down_blocks": 0, "up_blocks": 1, "mid_block": 2}
+
+    def order(bp):
+        parts = bp.split(".")
+        nums = [int(x) for x in parts if x.isdigit()]
+        return (rank[parts[0]], nums)
+    return sorted((k[: -len(end)] for k in keys if k.endswith(end)), key=order)
+
+
+def ip_adapter_layout(image_proj) -> str:
+    """Only the base projection is supported; the other layouts the reference tells apart (D/loaders/unet.py:783-797) are named."""
+    if "proj.weight" in image_proj:
+        return "base"
+    if "proj.3.weight" in image_proj:
+        what = "IP-Adapter Full Face (IPAdapterFullImageProjection)"
+    elif "perceiver_resampler.proj_in.weight" in image_proj:
+        what = "IP-Adapter FaceID Plus (IPAdapterFaceIDPlusImageProjection)"
+    elif "norm.weight" in image_proj:
+        what = "IP-Adapter FaceID (IPAdapterFaceIDImageProjection)"
+    elif "latents" in image_proj:
+        what = "IP-Adapter Plus (IPAdapterPlusImageProjection, a Resampler)"
+    else:
+        raise ValueError("not an IP-Adapter image projection: no proj.weight, proj.3.weight, perceiver_resampler, norm.weight or latents")
+    raise NotImplementedError(f"{what} is not supported: only the base IP-Adapter (ImageProjection: proj.weight + norm) is")
+
+
+def convert_ip_adapter(sd, prefixes, ctx_dim):
+    """One adapter {"image_proj": {...}, "ip_adapter": {"1.to_k_ip.weight", ...}} -> dict(proj_w [4 ctx_dim][embed_dim], proj_b, norm_w,
+    norm_b, kv={attn2 block prefix: (to_k_ip, to_v_ip)}) as fp32 host tensors; key id 1 + 2 i belongs to prefixes[i]."""
+    ip_adapter_layout(sd["image_proj"])
+    ip, proj = sd["ip_adapter"], sd["image_proj"]
+    if any("_lora." in k for k in ip):
+        raise NotImplementedError("IP-Adapter FaceID LoRA weights (to_k_lora / to_q_lora ...) are not supported")
+    if proj["proj.weight"].shape[0] != IP_NUM_TOKENS * ctx_dim:
+        raise ValueError(f"image_proj.proj.weight has {proj['proj.weight'].shape[0]} rows; {IP_NUM_TOKENS} tokens of this UNet's "
+                         f"cross_attention_dim {ctx_dim} need {IP_NUM_TOKENS * ctx_dim}")
+    want = {f"{1 + 2 * i}.to_{n}_ip.weight" for i in range(len(prefixes)) for n in "kv"}
+    if set(ip) != want:
+        raise ValueError(f"ip_adapter keys do not match this UNet's {len(prefixes)} attn2 processors: missing {sorted(want - set(ip))[:4]}, "
+                         f"unexpected {sorted(set(ip) - want)[:4]}")
+    kv = OrderedDict((bp, (ip[f"{1 + 2 * i}.to_k_ip.weight"].float(), ip[f"{1 + 2 * i}.to_v_ip.weight"].float())) for i, bp in enumerate(prefixes))
+    return dict(proj_w=proj["proj.weight"].float(), proj_b=proj["proj.bias"].float(), norm_w=proj["norm.weight"].float(),
+                norm_b=proj["norm.bias"].float(), kv=kv)
+
+
+def ip_adapter_on_device(host, device):
+    """convert_ip_adapter's host tensors as the plans read them: fp16 matrices, fp32 vectors, and the adapter's scale table - one fp32
+    word per attn2 block, 1.0 as in the reference - which bc_attention_ip reads on every replay."""
+    h16, f32 = torch.float16, torch.float32
+    return dict(proj_w=host["proj_w"].to(device, h16).contiguous(), proj_b=host["proj_b"].to(device, f32), norm_w=host["norm_w"].to(device, f32),
+                norm_b=host["norm_b"].to(device, f32),
+                kv=OrderedDict((bp, (wk.to(device, h16).contiguous(), wv.to(device, h16).contiguous())) for bp, (wk, wv) in host["kv"].items()),
+                scales=torch.ones(len(host["kv"]), dtype=f32, device=device))

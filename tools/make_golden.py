@@ -2256,6 +2256,149 @@ def golden_blocks():
     np.savez_compressed(os.path.join(OUT, "blocks.npz"), **out)
 
 
+def golden_ip_adapter():
+    """tests/golden/unet_tiny_ip.npz: the tiny UNet of build_tiny() after the reference's `unet._load_ip_adapter_weights` (D/loaders/
+    unet.py:823-853) with the synthetic base adapters of tests/ip_adapter_common.py tiny_ip_adapter, called with
+    added_cond_kwargs={"image_embeds": [...]} and BlobNet-style residual stand-ins (freeu_residuals).  Per case (IP_UNET_CASES: one
+    adapter with one image on the wide canvas, two adapters with two and one images on the square one): `eps` at the case's scales,
+    `eps_off` with every processor scale 0 - asserted bit-equal to the adapter-less UNet - and `eps_other_scale` at IP_OTHER_FACTOR times
+    the scales; plus the (key id -> processor name, shape) list the reference's loader walks.  The variants must lie at least 10 times
+    the GPU bar (1e-2 of eps' scale, tests/test_freeu_gpu.py) apart."""
+    from diffusers.models.attention_processor import IPAdapterAttnProcessor2_0
+    from tests.ip_adapter_common import (IP_GEOMETRIES, IP_OTHER_FACTOR, IP_RES_SCALE, IP_UNET_CASES, IP_UNET_SCALES, ip_unet_inputs,
+                                         tiny_ip_adapter)
+    out, t = {"timestep": np.array(981), "res_scale": np.array(IP_RES_SCALE), "other_factor": np.array(IP_OTHER_FACTOR)}, torch.tensor(981)
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    for case, (geo, images) in IP_UNET_CASES.items():
+        B, H, W = IP_GEOMETRIES[geo]
+        x_u, ehs, seed, embeds = ip_unet_inputs(case)
+        down, mid, up = _freeu_residual_shapes(H, W)
+        mk = lambda i, s: g(seed + i, B, *s) * IP_RES_SCALE
+        down, mid, up = [mk(i, s) for i, s in enumerate(down)], mk(100, mid), [mk(200 + i, s) for i, s in enumerate(up)]
+        res = lambda: dict(down_block_add_samples=[r.clone() for r in down], mid_block_add_sample=mid.clone(),
+                           up_block_add_samples=[r.clone() for r in up])
+        plain, _ = build_tiny()
+        with torch.no_grad():
+            eps_plain = plain(x_u, t, encoder_hidden_states=ehs, return_dict=False, **res())[0].numpy()
+        unet, _ = build_tiny()
+        unet._load_ip_adapter_weights([tiny_ip_adapter(i) for i in range(len(images))], low_cpu_mem_usage=False)
+        assert unet.config.encoder_hid_dim_type == "ip_image_proj"
+        procs = [(n, p) for n, p in unet.attn_processors.items() if isinstance(p, IPAdapterAttnProcessor2_0)]
+        assert len(procs) == 16 and all(p.scale == [1.0] * len(images) for _, p in procs)
+
+        def run(factor):
+            for _, p in procs:
+                p.scale = [factor * s_ for s_ in IP_UNET_SCALES[case]]
+            with torch.no_grad():
+                return unet(x_u, t, encoder_hidden_states=ehs, added_cond_kwargs={"image_embeds": embeds}, return_dict=False, **res())[0].numpy()
+        eps, eps_off, eps_other = run(1.0), run(0.0), run(IP_OTHER_FACTOR)
+        assert np.array_equal(eps_off, eps_plain), "scale 0 is the adapter-less UNet, bit for bit"
+        gaps = dict(on_off=rel(eps, eps_off) / 1e-2, on_other=rel(eps, eps_other) / 1e-2, other_off=rel(eps_other, eps_off) / 1e-2)
+        print(f"ip-adapter UNet {case}: eps std {eps.std():.4f}, variants apart by {gaps} bars")
+        assert min(gaps.values()) >= 10.0, (case, gaps)
+        out.update({f"{case}_eps": eps, f"{case}_eps_off": eps_off, f"{case}_eps_other_scale": eps_other})
+        out["key_names"] = np.array([n for n, _ in procs])
+        out["key_ids"] = np.array([1 + 2 * j for j in range(len(procs))])
+        out["key_shapes"] = np.array([tuple(p.to_k_ip[0].weight.shape) for _, p in procs])
+    np.savez_compressed(os.path.join(OUT, "unet_tiny_ip.npz"), **out)
+    print("unet_tiny_ip.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "unet_tiny_ip.npz")) / 1024))
+
+
+def golden_pipeline_call_ip():
+    """tests/golden/pipeline_call_ip.npz: the reference's own `__call__` (pipe:743-1166) with one synthetic base IP-Adapter loaded into its
+    UNet (`unet._load_ip_adapter_weights`, tiny_ip_adapter(0)) and `ip_adapter_image_embeds` given.  The reference class calls
+    `self.prepare_ip_adapter_image_embeds` (pipe:925) without having copied it, so the vendored function of D/pipelines/stable_diffusion/
+    pipeline_stable_diffusion.py:508 is bound onto the pipeline object (types.MethodType); with that the bound call runs.  DDIM, 3 steps,
+    the case `ddim_neg2` of pipeline_call.npz with seeds of its own.  Stores the final latents at IP_CALL_SCALE (`latents`), at
+    IP_CALL_SCALE_OTHER (`latents_other`), with the adapter-less UNet (`latents_off`: a pipeline that never loaded one, what unload
+    gives back), the per-processor scale lists the reference ends up with for a float, a list and a dict argument, and the embeddings.
+    The variants lie at least 10 times the GPU bar (1e-2 of the latents' scale) apart."""
+    from PIL import Image
+    from diffusers.loaders.ip_adapter import IPAdapterMixin
+    from diffusers.models.attention_processor import IPAdapterAttnProcessor2_0
+    from diffusers.pipelines.stable_diffusion.pipeline_stable_diffusion import StableDiffusionPipeline
+    from tests.common import FakeTokenizer, pipeline_cases
+    from tests.ip_adapter_common import IP_CALL_SCALE, IP_CALL_SCALE_DICT, IP_CALL_SCALE_OTHER, ip_call_embeds, tiny_ip_adapter
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"], seed=2041, rng_seed=41)
+    kw.pop("scheduler")
+    kw["num_inference_steps"] = 3
+    seed, rng_seed = kw.pop("seed"), kw.pop("rng_seed")
+    embeds = ip_call_embeds()
+
+    def make(adapter):
+        unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+        if adapter:
+            unet._load_ip_adapter_weights([tiny_ip_adapter(0)], low_cpu_mem_usage=False)
+        sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+        pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                              safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+        pipe.set_progress_bar_config(disable=True)
+        assert not hasattr(pipe, "prepare_ip_adapter_image_embeds")
+        pipe.prepare_ip_adapter_image_embeds = types.MethodType(StableDiffusionPipeline.prepare_ip_adapter_image_embeds, pipe)
+        return pipe
+
+    def call(pipe, **extra):
+        torch.manual_seed(rng_seed)
+        return pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                    height=64, width=64, generator=torch.Generator().manual_seed(seed), output_type="latent", **extra, **kw).images.numpy()
+    pipe = make(True)
+    procs = [p_ for p_ in pipe.unet.attn_processors.values() if isinstance(p_, IPAdapterAttnProcessor2_0)]
+    lists = {}
+    for tag, arg in (("float", IP_CALL_SCALE), ("list", [IP_CALL_SCALE_OTHER]), ("dict", IP_CALL_SCALE_DICT)):
+        IPAdapterMixin.set_ip_adapter_scale(pipe, arg)
+        lists[tag] = np.array([float(p_.scale[0]) for p_ in procs])
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(kw["num_inference_steps"]),
+           "embeds": embeds.numpy(), **{f"scales_{k}": v for k, v in lists.items()}}
+    IPAdapterMixin.set_ip_adapter_scale(pipe, IP_CALL_SCALE)
+    out["latents"] = call(pipe, ip_adapter_image_embeds=[embeds])
+    IPAdapterMixin.set_ip_adapter_scale(pipe, IP_CALL_SCALE_OTHER)
+    out["latents_other"] = call(pipe, ip_adapter_image_embeds=[embeds])
+    out["latents_off"] = call(make(False))
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    gaps = (rel(out["latents"], out["latents_off"]), rel(out["latents_other"], out["latents"]), rel(out["latents_other"], out["latents_off"]))
+    print("pipeline __call__ ip-adapter: latents std %.4f; on vs off %.3f, other vs on %.3f, other vs off %.3f (max-abs / scale)" %
+          ((out["latents"].std(),) + gaps))
+    assert min(gaps) >= 10 * 1e-2, gaps
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_ip.npz"), **out)
+    print("pipeline_call_ip.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "pipeline_call_ip.npz")) / 1024))
+
+
+def golden_blocks_ip():
+    """tests/golden/blocks_ip.npz: one Transformer2DModel at 320, 640 and 1280 channels with IPAdapterAttnProcessor2_0 on attn2
+    (D/models/attention_processor.py:3656-3883), called with encoder_hidden_states=(text, [tokens per adapter]) - what the UNet hands
+    its blocks once encoder_hid_proj has projected the image embeddings.  Per case (tests/ip_adapter_common.py IP_BLOCK_CASES): `<name>`
+    at the case's scales, `<name>_off` with every scale 0 (the reference skips the adapter) and `<name>_other` at half the scales.
+    Outputs only (fp32, every `sub`-th pixel); weights, inputs and tokens come from seeds on both sides.  The variants must lie at least
+    10 times the GPU bar of tests/test_blocks_gpu.py (1e-2 of the output's scale) apart, or the test could not tell them apart."""
+    from diffusers.models.attention_processor import IPAdapterAttnProcessor2_0
+    from diffusers.models.transformers.transformer_2d import Transformer2DModel
+    from tests.ip_adapter_common import IP_BLOCK_CASES, IP_BLOCK_SCALES, ip_block_inputs, ip_block_weights
+    out = {}
+    for name, p in IP_BLOCK_CASES.items():
+        x, ctx, tokens = ip_block_inputs(name)
+        m = Transformer2DModel(num_attention_heads=p["heads"], attention_head_dim=p["C"] // p["heads"], in_channels=p["C"], num_layers=1,
+                               cross_attention_dim=p["ctx"], norm_num_groups=32).eval()
+        sd, ip = ip_block_weights(name)
+        m.load_state_dict(sd, strict=True)
+        proc = IPAdapterAttnProcessor2_0(p["C"], p["ctx"], num_tokens=list(p["tokens"]), scale=list(IP_BLOCK_SCALES[name]))
+        for i, (wk, wv) in enumerate(ip):
+            proc.to_k_ip[i].weight.data.copy_(wk)
+            proc.to_v_ip[i].weight.data.copy_(wv)
+        m.transformer_blocks[0].attn2.set_processor(proc)
+        sub, res = p["sub"], {}
+        for tag, f in (("", 1.0), ("_off", 0.0), ("_other", 0.5)):
+            proc.scale = [f * s_ for s_ in IP_BLOCK_SCALES[name]]
+            with torch.no_grad():
+                y = m(x, encoder_hidden_states=(ctx, tokens), return_dict=False)[0]
+            res[tag] = out[name + tag] = y.numpy().astype(np.float32)[:, :, ::sub, ::sub]
+        bar = 1e-2 * np.abs(res[""]).max()
+        gaps = {a + "/" + b: float(np.abs(res[a] - res[b]).max() / bar) for a, b in (("", "_off"), ("", "_other"), ("_other", "_off"))}
+        print(f"block {name}: out std {res[''].std():.4f}, variants apart by {gaps} bars")
+        assert min(gaps.values()) >= 10.0, (name, gaps)
+    np.savez_compressed(os.path.join(OUT, "blocks_ip.npz"), **out)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -2299,6 +2442,9 @@ if __name__ == "__main__":
     golden_pipeline_call_lcm()
     golden_freeu()
     golden_pipeline_call_freeu()
+    golden_blocks_ip()
+    golden_ip_adapter()
+    golden_pipeline_call_ip()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
