@@ -263,6 +263,13 @@ IP_SIGNATURES = {
                                   C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
 }
 ATTENTION_IP_MAX_T = 64               # image tokens per launch (BC_ATTENTION_IP_MAX_T)
+# The two kernels behind bc_attention_ip by name (include/blobctrl_ip.h): which one the library picks for a shape, and a launch of a named
+# one.  Plain entry points for measurements and tests - no BC_OP_* code, in no op table, never recorded into a plan.
+IP_PATH_SIGNATURES = {
+    "bc_attention_ip_path": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bc_attention_ip_with": (C.c_int, [C.c_int] + IP_SIGNATURES["bc_attention_ip"][1]),
+}
+ATTENTION_IP_SCALAR, ATTENTION_IP_TILES = 0, 1
 
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
@@ -339,7 +346,7 @@ def load():
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
             list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
-            list(IP_SIGNATURES.items()):
+            list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -87,14 +87,34 @@ class IpAdapter:
     set_ip_adapter_scale rewrites the table and no plan or graph is recorded again.
     The image side is either `tokens` - fp16 [B][T][ctx_dim], already projected - or `embeds`, fp16 [B * n_images][embed_dim] (a per-edit
     input buffer), with the projection (proj_w fp16 [num_tokens * ctx_dim][embed_dim], proj_b / norm_w / norm_b fp32): Linear, reshape
-    to [B][n_images * num_tokens][ctx_dim], LayerNorm (D/models/embeddings.py ImageProjection)."""
+    to [B][n_images * num_tokens][ctx_dim], LayerNorm (D/models/embeddings.py ImageProjection).
+    IP-Adapter Plus: `hidden`, fp16 [B * n_images][S][embed_dims] (the image encoder's penultimate hidden states, a per-edit input buffer)
+    in place of `embeds`, and `plus` = the adapter's device dict (weights.ip_adapter_on_device: latents, proj_in, layers, proj_out,
+    norm_out); num_tokens = num_queries.  TrunkPlan.record_resampler turns them into the tokens."""
 
-    def __init__(self, kv, scales, tokens=None, embeds=None, n_images=1, num_tokens=4, proj_w=None, proj_b=None, norm_w=None, norm_b=None):
-        assert (tokens is None) != (embeds is None) and scales.dtype == torch.float32 and scales.numel() == len(kv)
+    def __init__(self, kv, scales, tokens=None, embeds=None, n_images=1, num_tokens=4, proj_w=None, proj_b=None, norm_w=None, norm_b=None,
+                 hidden=None, plus=None):
+        assert sum(x is not None for x in (tokens, embeds, hidden)) == 1 and scales.dtype == torch.float32 and scales.numel() == len(kv)
+        assert (hidden is None) == (plus is None)
         self.kv, self.scales, self.tokens, self.embeds = dict(kv), scales, tokens, embeds
         self.n_images, self.num_tokens = n_images, num_tokens
         self.proj_w, self.proj_b, self.norm_w, self.norm_b = proj_w, proj_b, norm_w, norm_b
+        self.hidden, self.plus = hidden, plus
         self.slot = {bp: i for i, bp in enumerate(self.kv)}
+
+    @classmethod
+    def for_plan(cls, rec, ad, B, entry, name=None):
+        """The adapter `ad` (weights.ip_adapter_on_device) in a plan of UNet batch B, with its per-edit input buffer allocated from the
+        recorder: `entry` = images per UNet image for a base adapter ([B * images][embed_dim]), (images, S) for a Plus adapter
+        ([B * images][S][embed_dims]).  Returns (IpAdapter, buffer)."""
+        from .weights import ip_adapter_embed_dim, ip_adapter_tokens
+        if ad.get("layout") == "plus":
+            n, S = entry
+            buf = rec.zeros(B * n, S, ip_adapter_embed_dim(ad), name=name)
+            return cls(ad["kv"], ad["scales"], hidden=buf, plus=ad, n_images=n, num_tokens=ip_adapter_tokens(ad)), buf
+        buf = rec.zeros(B * entry, ip_adapter_embed_dim(ad), name=name)
+        return cls(ad["kv"], ad["scales"], embeds=buf, n_images=entry, proj_w=ad["proj_w"], proj_b=ad["proj_b"], norm_w=ad["norm_w"],
+                   norm_b=ad["norm_b"]), buf
 
 
 class TrunkPlan:
@@ -633,6 +653,8 @@ class TrunkPlan:
         for ad in self.ip_adapters:
             if ad.tokens is not None:
                 tokens = ad.tokens
+            elif ad.plus is not None:
+                tokens = self.record_resampler(ad)
             else:
                 rows, Dn = B * ad.n_images, ad.proj_w.shape[0]
                 lin = rec.empty(rows, Dn)
@@ -649,6 +671,50 @@ class TrunkPlan:
                 rec.gemm(A=tokens, W=wk, M=B * T_ip, N=Cc, K=Dc, out=K_ip, kind="ip_kv")
                 rec.gemm(A=tokens, W=wv, M=B * T_ip, N=Cc, K=Dc, out=V_ip, kind="ip_kv")
                 self.ip_kv.setdefault(bp, []).append((K_ip, V_ip, T_ip, ad.scales[ad.slot[bp]:ad.slot[bp] + 1]))
+
+    def record_resampler(self, ad):
+        """IPAdapterPlusImageProjection (D/models/embeddings.py:1352-1441) on the adapter's hidden states, once per edit, with existing
+        launches: x = proj_in(hidden); four blocks { K, V over [ln0(x); ln1(latents)] (S + Q keys, heads of 64), Q from ln1(latents),
+        latents = to_out(attention) + latents, latents = ff(latents) + latents with ff = LayerNorm, Linear, GELU, Linear, no biases };
+        norm_out(proj_out(latents)) -> fp16 [B][n_images * Q][ctx_dim].
+        The two LayerNorms write one [images][S + Q][hidden] buffer (one launch per image and source: a plain row concatenation), so one
+        fused q | k GEMM and one V^T GEMM take all rows; bc_attention reads the Q rows - the last Q of each image - and the K columns
+        from that GEMM's output through its offsets and batch strides.  The q of the S image rows is computed and never read."""
+        rec, w = self.rec, ad.plus
+        Bi, S, E = ad.hidden.shape
+        Q, Hd = w["latents"].shape
+        heads, d = w["heads"], 64
+        inner, N = heads * d, S + Q
+        x = rec.empty(Bi * S, Hd)
+        rec.gemm(A=ad.hidden, W=w["proj_in_w"], M=Bi * S, N=Hd, K=E, out=x, bias=w["proj_in_b"], kind="ip_resampler")
+        lat = rec.register(w["latents"].repeat(Bi, 1).contiguous())                  # [Bi * Q][Hd]: the learned queries, per image
+        rec.keep.append(lat)
+        ldvt = (N + 63) // 64 * 64
+        for layer in w["layers"]:
+            cat = rec.empty(Bi, N, Hd)
+            for b in range(Bi):
+                rec.layernorm(x[b * S:(b + 1) * S], S, Hd, layer["ln0_w"], layer["ln0_b"], 1e-5, out=cat[b, :S])
+                rec.layernorm(lat[b * Q:(b + 1) * Q], Q, Hd, layer["ln1_w"], layer["ln1_b"], 1e-5, out=cat[b, S:])
+            qk = rec.empty(Bi * N, 2 * inner)
+            rec.gemm(A=cat, W=layer["qk"], M=Bi * N, N=2 * inner, K=Hd, out=qk, kind="ip_resampler")
+            vt = rec.zeros(Bi, inner, ldvt)
+            rec.gemm(A=cat, W=layer["to_v"], M=Bi * N, N=inner, K=Hd, out=vt, out_mode=_lib.OUT_F16_T, ldc=ldvt, rows_per_batch=N,
+                     kind="ip_resampler")
+            a = rec.empty(Bi * Q, inner)
+            rec.attention(qk, qk, vt, a, Bi, heads, d, Q, N, 2 * inner, 2 * inner, ldvt, inner, N * 2 * inner, N * 2 * inner, inner * ldvt,
+                          Q * inner, d ** -0.5, q_off=S * 2 * inner, k_off=inner)
+            lat2 = rec.empty(Bi * Q, Hd)
+            rec.gemm(A=a, W=layer["to_out"], M=Bi * Q, N=Hd, K=inner, out=lat2, R=lat, ldr=Hd, kind="ip_resampler")
+            ln = rec.layernorm(lat2, Bi * Q, Hd, layer["ff_ln_w"], layer["ff_ln_b"], 1e-5)
+            Hf = layer["ff1"].shape[0]
+            m1 = rec.empty(Bi * Q, Hf)
+            rec.gemm(A=ln, W=layer["ff1"], M=Bi * Q, N=Hf, K=Hd, out=m1, act=_lib.ACT_GELU, kind="ip_resampler")
+            lat = rec.empty(Bi * Q, Hd)
+            rec.gemm(A=m1, W=layer["ff2"], M=Bi * Q, N=Hd, K=Hf, out=lat, R=lat2, ldr=Hd, kind="ip_resampler")
+        Dc = w["proj_out_w"].shape[0]
+        out = rec.empty(Bi * Q, Dc)
+        rec.gemm(A=lat, W=w["proj_out_w"], M=Bi * Q, N=Dc, K=Hd, out=out, bias=w["proj_out_b"], kind="ip_resampler")
+        return rec.layernorm(out, Bi * Q, Dc, w["norm_w"], w["norm_b"], 1e-5).view(self.B, -1, Dc)
 
     # ------------------------------------------------------------------------------------------- per-edit weight collapse
     def record_collapse(self, feat16: torch.Tensor, per_image: int = 0):

@@ -136,6 +136,56 @@ class Dinov2ImageProcessor:
     __call__ = preprocess
 
 
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+
+
+class CLIPImageProcessor(Dinov2ImageProcessor):
+    """transformers' `CLIPImageProcessor(images=..., return_tensors="pt").pixel_values` with its Pillow backend, for an IP-Adapter's image
+    encoder: RGB, bicubic resize of the shortest edge to `size` (the long edge truncated by int(...)), centre crop, 1 / 255, CLIP mean /
+    std.  The geometry is Dinov2ImageProcessor's; the arithmetic differs in one rounding: the rescale multiplies in float64 and rounds
+    to float32 once (transformers' `rescale`), then (x - mean) / std in float32."""
+
+    def __init__(self, size=224, crop_size=224, image_mean=CLIP_MEAN, image_std=CLIP_STD, rescale_factor: float = 1 / 255):
+        super().__init__(self._edge(size, "shortest_edge"), self._edge(crop_size, "height"), image_mean, image_std, rescale_factor)
+
+    @staticmethod
+    def _edge(v, key):
+        """`size` / `crop_size` as a preprocessor_config.json spells them: a bare int or {"shortest_edge": n} / {"height": n, "width": n}."""
+        if isinstance(v, dict):
+            if key not in v or (key == "height" and v.get("width", v[key]) != v[key]):
+                raise ValueError(f"CLIPImageProcessor takes {{'{key}': n}} (a square crop), got {v}")
+            return int(v[key])
+        return int(v)
+
+    @property
+    def size(self):
+        return {"shortest_edge": self.shortest_edge}
+
+    @classmethod
+    def from_pretrained(cls, path, **_ignored):
+        import json
+        import os
+        with open(os.path.join(path, "preprocessor_config.json")) as f:
+            c = json.load(f)
+        return cls(c.get("size", 224), c.get("crop_size", 224), c.get("image_mean", CLIP_MEAN), c.get("image_std", CLIP_STD),
+                   c.get("rescale_factor", 1 / 255))
+
+    def normalise(self, arr_u8: np.ndarray) -> np.ndarray:
+        """uint8 [...][3] -> float32, channel last: the expression every pixel goes through after the crop (and resample.clip_lut's)."""
+        arr = (arr_u8.astype(np.float64) * self.rescale_factor).astype(np.float32)
+        return (arr - np.array(self.image_mean, np.float32)) / np.array(self.image_std, np.float32)
+
+    def _one(self, img) -> np.ndarray:
+        from .resample import dinov2_geometry
+        Image = _pil()
+        if isinstance(img, np.ndarray):
+            img = Image.fromarray(img)
+        img = img.convert("RGB")
+        (nh, nw), (top, left, ch, cw) = dinov2_geometry(img.size[1], img.size[0], self.shortest_edge, self.crop_size)
+        img = img.resize((nw, nh), resample=Image.BICUBIC)
+        return self.normalise(np.array(img)[top:top + ch, left:left + cw]).transpose(2, 0, 1)
+
+
 class _BatchFeature(dict):
     def __getattr__(self, k):
         try:

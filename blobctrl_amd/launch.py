@@ -652,8 +652,12 @@ class Recorder:
         self.keep.append((Q, K, V, out, w))
         for t in (Q, K, V, out, w):
             self.register(t)
+        # the library picks the kernel (bc_attention_ip_path: the scalar one, or MFMA tiles for measured classes at T = 16 .. 64); the
+        # same op is recorded either way, the listing names what will run
+        tiles = T % 16 == 0 and _lib.load().bc_attention_ip_path(d, T, rows_per_batch, heads) == _lib.ATTENTION_IP_TILES
+        variant = f"attention_ip_tiles_kernel<{d},{T // 16}>" if tiles else f"attention_ip_kernel<{d}>"
         self._op("bc_attention_ip", (Q.data_ptr() + q_off * 2, K, V, out, B, rows_per_batch, heads, d, T, ldq, ldkv, ldo, scale, w),
-                 "attention_ip", flops=4 * B * rows_per_batch * T * Cc, variant=f"attention_ip_kernel<{d}>",
+                 "attention_ip", flops=4 * B * rows_per_batch * T * Cc, variant=variant,
                  shape=("attention_ip", B, heads, d, rows_per_batch, T), bytes_=2 * (3 * B * rows_per_batch * Cc + 2 * B * T * Cc))
         return out
 

@@ -264,7 +264,7 @@ class UNet2DConditionModel(_TrunkModule):
     # ---- IP-Adapter (D/loaders/unet.py:823-853: IPAdapterAttnProcessor2_0 in every attn2, encoder_hid_proj = the image projections)
     def load_ip_adapter_weights(self, state_dicts):
         """`unet._load_ip_adapter_weights`: one adapter or a list, each the original {"image_proj", "ip_adapter"} dict or a .safetensors
-        file (checkpoint.load_ip_adapter).  Base adapters only; every scale starts at 1.0 as in the reference.  The weights live beside
+        file (checkpoint.load_ip_adapter).  Base adapters and IP-Adapter Plus (weights.ip_adapter_layout); every scale starts at 1.0 as in the reference.  The weights live beside
         the packed trunk: nothing is re-packed, and the adapter-less plans stay what they were."""
         from .checkpoint import load_ip_adapter
         from .weights import convert_ip_adapter, ip_adapter_on_device, ip_attn2_prefixes
@@ -323,9 +323,14 @@ class UNet2DConditionModel(_TrunkModule):
             embeds = [embeds.unsqueeze(1) if embeds.ndim == 2 else embeds]
         if len(embeds) != len(ads):
             raise ValueError(f"image_embeds holds {len(embeds)} tensors for {len(ads)} loaded IP-Adapters")
+        from .weights import ip_adapter_embed_dim
         for e, ad in zip(embeds, ads):
-            if e.ndim != 3 or e.shape[0] != B or e.shape[2] != ad["proj_w"].shape[1]:
-                raise ValueError(f"image_embeds of an adapter must be [batch = {B}][images][{ad['proj_w'].shape[1]}], got {tuple(e.shape)}")
+            width = ip_adapter_embed_dim(ad)
+            if ad.get("layout") == "plus":                 # hidden states: [batch][images][S][embed_dims]
+                if e.ndim != 4 or e.shape[0] != B or e.shape[3] != width:
+                    raise ValueError(f"image_embeds of an IP-Adapter Plus must be [batch = {B}][images][tokens][{width}], got {tuple(e.shape)}")
+            elif e.ndim != 3 or e.shape[0] != B or e.shape[2] != width:
+                raise ValueError(f"image_embeds of an adapter must be [batch = {B}][images][{width}], got {tuple(e.shape)}")
         return list(embeds)
 
     # ---- `unet.conv_in` as the script uses it (inf:233-249): reads .weight / .bias / .out_channels, assigns a wider Conv2d
@@ -414,9 +419,8 @@ class UNet2DConditionModel(_TrunkModule):
                 # width are fixed by what is loaded, and load / unload drop every plan that carries an `ip` entry (_drop_ip_plans).  Scales
                 # are no part of the key: the launches read them from the adapters' device tables
                 ads = self.__dict__["ip_adapters"]
-                P.ip_embeds = [rec.zeros(B * n, ad["proj_w"].shape[1]) for n, ad in zip(ip, ads)]
-                plan.ip_adapters = [IpAdapter(ad["kv"], ad["scales"], embeds=e, n_images=n, proj_w=ad["proj_w"], proj_b=ad["proj_b"],
-                                              norm_w=ad["norm_w"], norm_b=ad["norm_b"]) for n, ad, e in zip(ip, ads, P.ip_embeds)]
+                made = [IpAdapter.for_plan(rec, ad, B, entry) for entry, ad in zip(ip, ads)]      # (a Plus adapter's entry: (images, S))
+                plan.ip_adapters, P.ip_embeds = [m[0] for m in made], [m[1] for m in made]
             plan.record_context(P.ctx, T)
             if cond:
                 P.cond = rec.zeros(B, pad8(self.trunk_config.time_cond_proj_dim))
@@ -480,7 +484,7 @@ class UNet2DConditionModel(_TrunkModule):
         freeu = self.__dict__.get("freeu")
         embeds = self.__dict__.get("_image_embeds")
         P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None, freeu=freeu_enabled(freeu),
-                       ip=tuple(e.shape[1] for e in embeds) if embeds else ())
+                       ip=tuple(int(e.shape[1]) if e.ndim == 3 else (int(e.shape[1]), int(e.shape[2])) for e in embeds) if embeds else ())
         for buf, e in zip(getattr(P, "ip_embeds", ()), embeds or ()):
             buf.copy_(e.to(self.device, torch.float16).reshape(buf.shape))
         if freeu_enabled(freeu):

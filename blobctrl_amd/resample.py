@@ -328,6 +328,26 @@ def dinov2_pixel_values(images, processor):
     return _resize_to_planar(x, size, "bicubic", window, lut, window[2:], what)
 
 
+def clip_lut(processor):
+    """`CLIPImageProcessor.normalise` - the processor's own expression after the crop - for every byte value of every channel -> float32
+    [3][256]."""
+    arr = np.repeat(np.arange(256, dtype=np.uint8).reshape(256, 1, 1), 3, axis=2)
+    return np.ascontiguousarray(processor.normalise(arr).transpose(2, 0, 1).reshape(3, 256))
+
+
+@torch.no_grad()
+def clip_pixel_values(images, processor):
+    """`CLIPImageProcessor.preprocess(images)["pixel_values"]` (blobctrl_amd.image_processor) for uint8 device RGB images [n][H][W][3] or
+    [H][W][3] -> fp32 [n][3][crop][crop] on the device, bit for bit: the sibling of dinov2_pixel_values - the same resize kernels on the
+    centre crop's window, the processor's own normalisation looked up per byte."""
+    what = "clip_pixel_values"
+    x, _ = _device_images(images, what)
+    size, window = dinov2_geometry(x.shape[1], x.shape[2], processor.shortest_edge, processor.crop_size)
+    lut = _device_lut(("clip", float(processor.rescale_factor), tuple(processor.image_mean), tuple(processor.image_std)),
+                      lambda: torch.from_numpy(clip_lut(processor)), x.device)
+    return _resize_to_planar(x, size, "bicubic", window, lut, window[2:], what)
+
+
 def sam_lut():
     """`sam.preprocess_image`'s normalisation for every byte value of every channel -> float32 tensor [3][256] (host)."""
     from .sam import PIXEL_MEAN, PIXEL_STD

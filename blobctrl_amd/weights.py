@@ -591,10 +591,52 @@ def ip_attn2_prefixes(keys):
     return sorted((k[: -len(end)] for k in keys if k.endswith(end)), key=order)
 
 
+IP_PLUS_DEPTH, IP_PLUS_DIM_HEAD = 4, 64    # the Resampler of IP-Adapter Plus as the reference's loader builds it (D/loaders/unet.py:657-677)
+
+# per-layer tensors of a Plus projection: our name -> (the original spelling under "layers.{i}.", the converted one); `to_kv` is the
+# original file's fused K | V matrix (D/loaders/unet.py:691-697 splits it in halves)
+_PLUS_LAYER_KEYS = {
+    "ln0_w": ("0.norm1.weight", "ln0.weight"), "ln0_b": ("0.norm1.bias", "ln0.bias"),
+    "ln1_w": ("0.norm2.weight", "ln1.weight"), "ln1_b": ("0.norm2.bias", "ln1.bias"),
+    "to_q": ("0.to_q.weight", "attn.to_q.weight"), "to_kv": ("0.to_kv.weight", None),
+    "to_k": (None, "attn.to_k.weight"), "to_v": (None, "attn.to_v.weight"), "to_out": ("0.to_out.weight", "attn.to_out.0.weight"),
+    "ff_ln_w": ("1.0.weight", "ff.0.weight"), "ff_ln_b": ("1.0.bias", "ff.0.bias"),
+    "ff1": ("1.1.weight", "ff.1.net.0.proj.weight"), "ff2": ("1.3.weight", "ff.1.net.2.weight"),
+}
+_PLUS_TOP_KEYS = ("latents", "proj_in.weight", "proj_in.bias", "proj_out.weight", "proj_out.bias", "norm_out.weight", "norm_out.bias")
+
+
+def ip_plus_layers(image_proj):
+    """The IP_PLUS_DEPTH layers of a Plus projection as dicts of _PLUS_LAYER_KEYS' names (to_k / to_v split), from the original
+    `layers.{i}.0.* / layers.{i}.1.*` spelling or the converted `layers.{i}.ln0 / ln1 / attn.* / ff.*` one; None when a key is missing
+    or the file holds more layers than the reference builds."""
+    if any(k not in image_proj for k in _PLUS_TOP_KEYS) or any(k.startswith(f"layers.{IP_PLUS_DEPTH}.") for k in image_proj):
+        return None
+    layers = []
+    for i in range(IP_PLUS_DEPTH):
+        which = 1 if f"layers.{i}.attn.to_q.weight" in image_proj else 0
+        layer = {}
+        for name, spell in _PLUS_LAYER_KEYS.items():
+            if spell[which] is None:
+                continue
+            key = f"layers.{i}.{spell[which]}"
+            if key not in image_proj:
+                return None
+            layer[name] = image_proj[key]
+        if "to_kv" in layer:
+            layer["to_k"], layer["to_v"] = layer.pop("to_kv").chunk(2, dim=0)
+        layers.append(layer)
+    return layers
+
+
 def ip_adapter_layout(image_proj) -> str:
-    """Only the base projection is supported; the other layouts the reference tells apart (D/loaders/unet.py:783-797) are named."""
+    """"base" (ImageProjection) or "plus" (IPAdapterPlusImageProjection, complete, in either key spelling); the other layouts the
+    reference tells apart (D/loaders/unet.py:783-797) are named and refused."""
     if "proj.weight" in image_proj:
         return "base"
+    if "latents" in image_proj and "perceiver_resampler.proj_in.weight" not in image_proj and "proj.3.weight" not in image_proj and \
+            "norm.weight" not in image_proj and ip_plus_layers(image_proj) is not None:
+        return "plus"
     if "proj.3.weight" in image_proj:
         what = "IP-Adapter Full Face (IPAdapterFullImageProjection)"
     elif "perceiver_resampler.proj_in.weight" in image_proj:
@@ -602,36 +644,73 @@ def ip_adapter_layout(image_proj) -> str:
     elif "norm.weight" in image_proj:
         what = "IP-Adapter FaceID (IPAdapterFaceIDImageProjection)"
     elif "latents" in image_proj:
-        what = "IP-Adapter Plus (IPAdapterPlusImageProjection, a Resampler)"
+        what = "IP-Adapter Plus (IPAdapterPlusImageProjection, a Resampler) with an incomplete projection"
     else:
         raise ValueError("not an IP-Adapter image projection: no proj.weight, proj.3.weight, perceiver_resampler, norm.weight or latents")
-    raise NotImplementedError(f"{what} is not supported: only the base IP-Adapter (ImageProjection: proj.weight + norm) is")
+    raise NotImplementedError(f"{what} is not supported: only the base IP-Adapter (ImageProjection: proj.weight + norm) and a complete "
+                              "IP-Adapter Plus projection are")
+
+
+def ip_adapter_tokens(ad) -> int:
+    """Image tokens per image of a converted adapter (host or device dict): 4 for the base projection, num_queries for Plus."""
+    return int(ad["latents"].shape[0]) if ad.get("layout") == "plus" else IP_NUM_TOKENS
+
+
+def ip_adapter_embed_dim(ad) -> int:
+    """Width of what a call passes per image: the image embedding for the base projection, the hidden states' last dimension for Plus."""
+    return int(ad["proj_in_w"].shape[1]) if ad.get("layout") == "plus" else int(ad["proj_w"].shape[1])
 
 
 def convert_ip_adapter(sd, prefixes, ctx_dim):
-    """One adapter {"image_proj": {...}, "ip_adapter": {"1.to_k_ip.weight", ...}} -> dict(proj_w [4 ctx_dim][embed_dim], proj_b, norm_w,
-    norm_b, kv={attn2 block prefix: (to_k_ip, to_v_ip)}) as fp32 host tensors; key id 1 + 2 i belongs to prefixes[i]."""
-    ip_adapter_layout(sd["image_proj"])
+    """One adapter {"image_proj": {...}, "ip_adapter": {"1.to_k_ip.weight", ...}} as fp32 host tensors; key id 1 + 2 i belongs to prefixes[i].
+    Base: dict(proj_w [4 ctx_dim][embed_dim], proj_b, norm_w, norm_b, kv={attn2 block prefix: (to_k_ip, to_v_ip)}).
+    Plus: dict(layout="plus", latents [num_queries][hidden], proj_in_w / proj_in_b, layers=[IP_PLUS_DEPTH dicts: ln0_w, ln0_b, ln1_w, ln1_b,
+    qk (to_q over to_k, [2 heads * 64][hidden]), to_v, to_out, ff_ln_w, ff_ln_b, ff1, ff2], proj_out_w / proj_out_b, norm_w / norm_b =
+    norm_out, heads, kv) with the dimension rules of D/loaders/unet.py:657-677."""
+    layout = ip_adapter_layout(sd["image_proj"])
     ip, proj = sd["ip_adapter"], sd["image_proj"]
     if any("_lora." in k for k in ip):
         raise NotImplementedError("IP-Adapter FaceID LoRA weights (to_k_lora / to_q_lora ...) are not supported")
-    if proj["proj.weight"].shape[0] != IP_NUM_TOKENS * ctx_dim:
+    if layout == "base" and proj["proj.weight"].shape[0] != IP_NUM_TOKENS * ctx_dim:
         raise ValueError(f"image_proj.proj.weight has {proj['proj.weight'].shape[0]} rows; {IP_NUM_TOKENS} tokens of this UNet's "
                          f"cross_attention_dim {ctx_dim} need {IP_NUM_TOKENS * ctx_dim}")
+    if layout == "plus" and proj["proj_out.weight"].shape[0] != ctx_dim:
+        raise ValueError(f"image_proj.proj_out.weight has {proj['proj_out.weight'].shape[0]} rows; this UNet's cross_attention_dim is {ctx_dim}")
     want = {f"{1 + 2 * i}.to_{n}_ip.weight" for i in range(len(prefixes)) for n in "kv"}
     if set(ip) != want:
         raise ValueError(f"ip_adapter keys do not match this UNet's {len(prefixes)} attn2 processors: missing {sorted(want - set(ip))[:4]}, "
                          f"unexpected {sorted(set(ip) - want)[:4]}")
     kv = OrderedDict((bp, (ip[f"{1 + 2 * i}.to_k_ip.weight"].float(), ip[f"{1 + 2 * i}.to_v_ip.weight"].float())) for i, bp in enumerate(prefixes))
-    return dict(proj_w=proj["proj.weight"].float(), proj_b=proj["proj.bias"].float(), norm_w=proj["norm.weight"].float(),
-                norm_b=proj["norm.bias"].float(), kv=kv)
+    if layout == "base":
+        return dict(proj_w=proj["proj.weight"].float(), proj_b=proj["proj.bias"].float(), norm_w=proj["norm.weight"].float(),
+                    norm_b=proj["norm.bias"].float(), kv=kv)
+    hidden = proj["latents"].shape[2]
+    layers = []
+    for src in ip_plus_layers(proj):
+        inner = src["to_q"].shape[0]
+        if inner % IP_PLUS_DIM_HEAD or src["to_k"].shape != (inner, hidden) or src["to_out"].shape != (hidden, inner):
+            raise ValueError(f"a Resampler layer with to_q {tuple(src['to_q'].shape)}, to_k {tuple(src['to_k'].shape)}, to_out "
+                             f"{tuple(src['to_out'].shape)}: heads of {IP_PLUS_DIM_HEAD} over {hidden} hidden channels are expected")
+        layer = {k: src[k].float() for k in ("ln0_w", "ln0_b", "ln1_w", "ln1_b", "to_v", "to_out", "ff_ln_w", "ff_ln_b", "ff1", "ff2")}
+        layer["qk"] = torch.cat([src["to_q"].float(), src["to_k"].float()], 0)
+        layers.append(layer)
+    return dict(layout="plus", latents=proj["latents"].float().reshape(-1, hidden), proj_in_w=proj["proj_in.weight"].float(),
+                proj_in_b=proj["proj_in.bias"].float(), layers=layers, proj_out_w=proj["proj_out.weight"].float(),
+                proj_out_b=proj["proj_out.bias"].float(), norm_w=proj["norm_out.weight"].float(), norm_b=proj["norm_out.bias"].float(),
+                heads=layers[0]["qk"].shape[0] // 2 // IP_PLUS_DIM_HEAD, kv=kv)
 
 
 def ip_adapter_on_device(host, device):
     """convert_ip_adapter's host tensors as the plans read them: fp16 matrices, fp32 vectors, and the adapter's scale table - one fp32
     word per attn2 block, 1.0 as in the reference - which bc_attention_ip reads on every replay."""
     h16, f32 = torch.float16, torch.float32
-    return dict(proj_w=host["proj_w"].to(device, h16).contiguous(), proj_b=host["proj_b"].to(device, f32), norm_w=host["norm_w"].to(device, f32),
-                norm_b=host["norm_b"].to(device, f32),
-                kv=OrderedDict((bp, (wk.to(device, h16).contiguous(), wv.to(device, h16).contiguous())) for bp, (wk, wv) in host["kv"].items()),
-                scales=torch.ones(len(host["kv"]), dtype=f32, device=device))
+    mat, vec = (lambda t: t.to(device, h16).contiguous()), (lambda t: t.to(device, f32).contiguous())
+    out = dict(kv=OrderedDict((bp, (mat(wk), mat(wv))) for bp, (wk, wv) in host["kv"].items()),
+               scales=torch.ones(len(host["kv"]), dtype=f32, device=device), norm_w=vec(host["norm_w"]), norm_b=vec(host["norm_b"]))
+    if host.get("layout") == "plus":
+        out.update(layout="plus", heads=host["heads"], latents=mat(host["latents"]), proj_in_w=mat(host["proj_in_w"]),
+                   proj_in_b=vec(host["proj_in_b"]), proj_out_w=mat(host["proj_out_w"]), proj_out_b=vec(host["proj_out_b"]),
+                   layers=[{k: (vec(v) if v.ndim == 1 else mat(v)) for k, v in layer.items()} for layer in host["layers"]])
+    else:
+        out.update(proj_w=mat(host["proj_w"]), proj_b=vec(host["proj_b"]))
+    return out

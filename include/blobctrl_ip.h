@@ -27,6 +27,17 @@ enum { BC_OP_ATTENTION_IP = BC_OP_COUNT, BC_OP_IP_END };
 int bc_attention_ip(const bc_half* Q, const bc_half* K, const bc_half* V, bc_half* O, int B, int rows_per_batch, int heads, int d, int T,
                     int ldq, int ldkv, int ldo, float qk_scale, const float* w, bc_stream stream);
 
+/* Two kernels stand behind bc_attention_ip, with one contract (every word above holds for both):
+ *   path 0   the scalar kernel: lanes along channels, keys four at a time through shuffle reductions; any T.  Made for T = 4.
+ *   path 1   MFMA tiles: a wave owns 16 query rows of one head, scores and P.V by v_mfma; T = 16, 32, 48 or 64 only.
+ * bc_attention_ip_path names the path bc_attention_ip runs for a shape - a table of measured classes (profiles/ip_adapter_plus.md); it is 0
+ * for every T that is not a multiple of 16.  bc_attention_ip_with launches the named path: bc_attention_ip(...) is
+ * bc_attention_ip_with(bc_attention_ip_path(d, T, rows_per_batch, heads), ...).  Path 1 with another T, or a path other than 0 and 1, is an
+ * argument error before any launch.  Plain entry points for measurements and tests: NOT plan ops, no BC_OP_* code. */
+int bc_attention_ip_path(int d, int T, int rows_per_batch, int heads);
+int bc_attention_ip_with(int path, const bc_half* Q, const bc_half* K, const bc_half* V, bc_half* O, int B, int rows_per_batch, int heads, int d,
+                         int T, int ldq, int ldkv, int ldo, float qk_scale, const float* w, bc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

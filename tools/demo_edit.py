@@ -11,7 +11,12 @@ synthetic ViT-H weights).  With --sam ... --sam-auto K there is no click: SamAut
 the K-th largest mask gives the blob.  With --sam ... --click X,Y --device-inputs the image is uploaded once and neither it nor the mask
 leaves the GPU: `set_image(device tensor)` (`resample.sam_pixel_values`) -> `predict_torch` -> `masks.clean_masks` ->
 `edit_inputs.ellipses_from_masks` (the row extents come to the host, n * H * 8 bytes) -> `object_regions` / `build_edit_inputs_batch` ->
-`vae_input`, DINOv2's input from `resample.dinov2_pixel_values`, and the edit is a "move" of the clicked object."""
+`vae_input`, DINOv2's input from `resample.dinov2_pixel_values`, and the edit is a "move" of the clicked object.
+With --ip-adapter PATH --ip-image FILE the edit takes an image prompt: PATH is a local IP-Adapter .safetensors file (base or Plus) with its
+CLIP vision tower in the folder `image_encoder` beside it; the image goes through CLIPImageProcessor, the tower
+(blobctrl_amd.clip_vision) and - for a Plus adapter - the Resampler in the plan's prologue, and every attn2 runs bc_attention_ip on its
+tokens.  --ip-adapter synth uses a seeded tiny tower (320 wide, 4 layers) and a seeded Plus adapter of 16 queries; without --ip-image the
+image is seeded noise."""
 import argparse
 import os
 import sys
@@ -22,6 +27,60 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+
+def image_prompt(args, pipe, unet_keys):
+    """--ip-adapter / --ip-image: load the adapter into the engine, encode the image with the CLIP vision tower and return the keyword
+    the engine's call takes: `ip_adapter_image_embeds` = [[negative, positive]] - hidden_states[-2] of the image and of an all-zero image
+    for a Plus adapter, image_embeds and zeros for a base one."""
+    from blobctrl_amd import synth
+    from blobctrl_amd.checkpoint import load_ip_adapter
+    from blobctrl_amd.clip_vision import CLIPVisionModelWithProjection
+    from blobctrl_amd.image_processor import CLIPImageProcessor
+    from blobctrl_amd.weights import convert_ip_adapter, ip_adapter_on_device, ip_attn2_prefixes
+    prefixes = ip_attn2_prefixes(unet_keys)
+    ctx = pipe.unet_cfg.cross_attention_dim
+    if args.ip_adapter == "synth":
+        sys.path.insert(0, os.path.join(REPO, "tools"))
+        from ip_adapter_probe import plus_adapter_shapes
+        D, L, n = 320, 4, (224 // 14) ** 2 + 1
+        shapes = {"vision_model.embeddings.class_embedding": (D,), "vision_model.embeddings.patch_embedding.weight": (D, 3, 14, 14),
+                  "vision_model.embeddings.position_embedding.weight": (n, D), "vision_model.pre_layrnorm.weight": (D,),
+                  "vision_model.pre_layrnorm.bias": (D,), "vision_model.post_layernorm.weight": (D,), "vision_model.post_layernorm.bias": (D,),
+                  "visual_projection.weight": (1024, D)}
+        for i in range(L):
+            q = f"vision_model.encoder.layers.{i}."
+            for m in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                shapes[q + f"self_attn.{m}.weight"], shapes[q + f"self_attn.{m}.bias"] = (D, D), (D,)
+            shapes.update({q + "layer_norm1.weight": (D,), q + "layer_norm1.bias": (D,), q + "layer_norm2.weight": (D,), q + "layer_norm2.bias": (D,),
+                           q + "mlp.fc1.weight": (4 * D, D), q + "mlp.fc1.bias": (4 * D,), q + "mlp.fc2.weight": (D, 4 * D), q + "mlp.fc2.bias": (D,)})
+        tower = CLIPVisionModelWithProjection(synth.synth_state_dict(shapes, 171), num_heads=4, hidden_act="gelu")
+        kv = {f"{1 + 2 * j}.to_{m}_ip.weight": (c, ctx) for j, c in enumerate(pipe.unet_w.h[bp + "attn2.to_k.weight"].shape[0] for bp in prefixes)
+              for m in "kv"}
+        sd = {"image_proj": dict(synth.synth_state_dict(plus_adapter_shapes(embed=D, hidden=256, ctx=ctx), 172)),
+              "ip_adapter": dict(synth.synth_state_dict(kv, 173))}
+    else:
+        (sd,) = load_ip_adapter(args.ip_adapter)
+        tower = CLIPVisionModelWithProjection.from_pretrained(os.path.dirname(os.path.abspath(args.ip_adapter)), subfolder="image_encoder")
+    adapter = ip_adapter_on_device(convert_ip_adapter(sd, prefixes, ctx), pipe.device)
+    pipe.set_ip_adapters([adapter])
+    size = tower.config.image_size
+    if args.ip_image:
+        from PIL import Image
+        image = Image.open(args.ip_image)
+    else:
+        image = np.random.Generator(np.random.PCG64(7)).integers(0, 256, (300, 400, 3), dtype=np.uint8)
+    px = CLIPImageProcessor(size=size, crop_size=size)(image, return_tensors="pt").pixel_values
+    plus = adapter.get("layout") == "plus"
+    if plus:
+        pos = tower(px, output_hidden_states=True).hidden_states[-2]
+        neg = tower(torch.zeros_like(px), output_hidden_states=True).hidden_states[-2]
+    else:
+        pos = tower(px).image_embeds
+        neg = torch.zeros_like(pos)
+    embeds = torch.stack([neg, pos], 0).reshape(2, 1, *pos.shape[1:])
+    print(f"image prompt: {'Plus' if plus else 'base'} adapter, tower {tower.L} layers x {tower.D}, embeds {tuple(embeds.shape)}")
+    return dict(ip_adapter_image_embeds=[embeds])
 
 
 def main():
@@ -38,7 +97,11 @@ def main():
                     help="despeckle the SAM mask(s) on the GPU first: fill holes and remove islands of fewer than N pixels (with --sam)")
     ap.add_argument("--device-inputs", action="store_true",
                     help="build the edit's inputs on the GPU from the device mask (with --sam, click prompts): blobctrl_amd.edit_inputs")
+    ap.add_argument("--ip-adapter", default=None, help="an IP-Adapter .safetensors file with `image_encoder/` beside it, or 'synth'")
+    ap.add_argument("--ip-image", default=None, help="the image prompt (any file PIL opens); seeded noise without it")
     args = ap.parse_args()
+    if args.ip_image and not args.ip_adapter:
+        ap.error("--ip-image needs --ip-adapter")
     if args.device_inputs and (not args.sam or args.sam_auto is not None):
         ap.error("--device-inputs needs --sam and a click prompt")
     if (args.click or args.sam_auto is not None) and not args.sam:
@@ -75,6 +138,9 @@ def main():
         clip = CLIPTextModel(synth.synth_state_dict(synth.clip_text_param_shapes(), 88), num_heads=12)
         dino = Dinov2Model(synth.synth_state_dict(synth.dinov2_param_shapes(1024, 24, 4, 14, 37 * 37), 99), num_heads=16)
         pipe = BlobCtrlEngine(usd, bsd, ucfg, bcfg, scheduler="unipc", vae=vae, text_encoder=clip)
+    ip_kwargs = {}
+    if args.ip_adapter:
+        ip_kwargs = image_prompt(args, pipe, unet._sd.keys() if args.models else usd.keys())
     t1 = sync()
     R = args.res
     rng = np.random.Generator(np.random.PCG64(0))
@@ -151,14 +217,14 @@ def main():
     t4 = sync()
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,
-               fg_image=fg, bg_image=bg, output_type="np")
+               fg_image=fg, bg_image=bg, output_type="np", **ip_kwargs)
     t5 = sync()
     print(f"models {t1 - t0:.1f} s | splat {1e3 * (t2 - t1):.1f} ms | DINOv2 {1e3 * (t3 - t2):.1f} ms | CLIP {1e3 * (t4 - t3):.1f} ms | "
           f"VAE encode x2 + {args.steps}-step loop + VAE decode {1e3 * (t5 - t4):.1f} ms (first call: includes planning + graph capture)")
     t6 = sync()
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,
-               fg_image=fg, bg_image=bg, output_type="np")
+               fg_image=fg, bg_image=bg, output_type="np", **ip_kwargs)
     t7 = sync()
     print(f"second edit (plans cached): {1e3 * (t7 - t6):.1f} ms end to end; image {img.shape}, range [{img.min():.3f}, {img.max():.3f}]")
     if args.out:

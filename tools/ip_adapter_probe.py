@@ -8,6 +8,11 @@ attn2 on the forms that store q (no CHAIN_MIDX, no bc_ctx_fold) and 16 image-att
 
     python tools/ip_adapter_probe.py [--markdown profiles/ip_adapter.md] [--reps 20] [--steps 20] [--edits 4] [--no-step]
 
+With --paths-markdown profiles/ip_adapter_plus.md [--only-paths] [--rounds 7]: the two kernels behind bc_attention_ip by name
+(bc_attention_ip_with: the scalar kernel and the MFMA tiles) on the same eight shapes at T = 16, 32, 48 and 64 - the token counts of
+IP-Adapter Plus with one to four images - alternating in one process, the dispatch rule read off that table, and the step time without an
+adapter, with a base adapter and with a Plus adapter (ip-adapter-plus_sd15's shapes: 257 x 1280 hidden states, 16 queries).
+
 Bytes are the algorithmic ones of the launch (Q read once, O read and written once, K and V once): 2 * (3 M C + 2 B T C).  Every launch
 is replayed `reps` times in one segment behind a warm-up replay; the figure is the median of the per-launch event times.  Needs a GPU."""
 import argparse
@@ -56,8 +61,106 @@ def measure(dev, Cc, HW, B, reps):
         rec.close()
 
 
+PLUS_TOKENS = (16, 32, 48, 64)            # IP-Adapter Plus: 16 tokens per image; one to four images
+
+
+def measure_paths(dev, Cc, HW, B, T, reps, rounds):
+    """us per launch of both kernels behind bc_attention_ip (bc_attention_ip_with: path 0 scalar, path 1 MFMA tiles; T = 4 path 0 only) on
+    one shape.  `reps` launches of a path are captured into one graph; the two graphs are replayed in turn, `rounds` times each behind a
+    warm-up replay, in one process.  Returns {path: (median us, spread = max - min us over the rounds)} and the worst difference of the
+    two paths' outputs on the same inputs."""
+    from blobctrl_amd import _lib
+    lib = _lib.load()
+    d, M = Cc // HEADS, B * HW
+    q, a0 = torch.randn(M, Cc, device=dev).half(), torch.randn(M, Cc, device=dev).half()
+    k, v = torch.randn(B, T, Cc, device=dev).half(), torch.randn(B, T, Cc, device=dev).half()
+    w = torch.full((1,), 0.6, device=dev)
+    paths = (0, 1) if T % 16 == 0 else (0,)
+
+    def launch(path, out):
+        _lib.check(lib.bc_attention_ip_with(path, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, HW, HEADS, d, T, Cc, Cc, Cc,
+                                            d ** -0.5, w.data_ptr(), torch.cuda.current_stream().cuda_stream), f"path {path}")
+    outs = {}
+    for p in paths:                                                    # one launch each on the same inputs: the results must agree
+        outs[p] = a0.clone()
+        launch(p, outs[p])
+    torch.cuda.synchronize()
+    diff = (outs[0].float() - outs[1].float()).abs().max().item() if len(paths) == 2 else 0.0
+    graphs, bufs = {}, {}
+    side = torch.cuda.Stream()
+    for p in paths:
+        bufs[p] = a0.clone()
+        graphs[p] = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            launch(p, bufs[p])                                         # (warm: the code object is loaded before the capture)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graphs[p], stream=side):
+                for _ in range(reps):
+                    launch(p, bufs[p])
+    times = {p: [] for p in paths}
+    for r in range(rounds + 1):
+        for p in paths:
+            bufs[p].copy_(a0)                                          # (in place: keep the values where they started)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graphs[p].replay()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:
+                times[p].append(e0.elapsed_time(e1) * 1e3 / reps)
+    return {p: (statistics.median(t), max(t) - min(t)) for p, t in times.items()}, diff
+
+
+def paths_table(dev, reps, rounds):
+    """The two-path table and the dispatch rule read off it: [markdown lines], {(C, T): tiles win on both batch rows beyond the spread}."""
+    lines = ["# bc_attention_ip at 16 to 64 image tokens on an MI355X: the scalar kernel and the MFMA tiles", "",
+             f"HIP-event time per launch: {reps} launches of one path captured into one graph, the two paths' graphs replayed in turn,",
+             f"{rounds} replays each behind a warm-up, in one process.  us = median over the replays, +- = max - min over them (the run-to-run",
+             "spread).  Both paths through bc_attention_ip_with on the same inputs; `max diff` is the largest difference of their fp16 outputs",
+             "after one launch.  T = 4 is the base adapter on the scalar kernel: the anchor.", "",
+             "| C | tokens / image | UNet batch | T | scalar us | +- | tiles us | +- | tiles / scalar | max diff | tiles win |",
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    wins = {}
+    for B in (2, 16):
+        for Cc, HW in LEVELS:
+            for T in (T_IP,) + PLUS_TOKENS:
+                res, diff = measure_paths(dev, Cc, HW, B, T, reps, rounds)
+                (s_us, s_sp) = res[0]
+                if 1 in res:
+                    (t_us, t_sp) = res[1]
+                    win = s_us - t_us > max(s_sp, t_sp)
+                    wins.setdefault((Cc, T), []).append(win)
+                    lines.append(f"| {Cc} | {HW} | {B} | {T} | {s_us:.1f} | {s_sp:.1f} | {t_us:.1f} | {t_sp:.1f} | {t_us / s_us:.2f} | {diff:.4f} | "
+                                 f"{'yes' if win else 'no'} |")
+                else:
+                    lines.append(f"| {Cc} | {HW} | {B} | {T} | {s_us:.1f} | {s_sp:.1f} | - | - | - | - | - |")
+                print(lines[-1], flush=True)
+    rule = {key: all(v) for key, v in wins.items()}                    # (1280 channels: two levels x two batches = four rows)
+    lines += ["", "## Dispatch rule", "",
+              "A (channel width, T) class goes to the tiles only where they win on every row of that class above by more than the spread.  Every row has",
+              f"{HEADS} heads, so a class is the (heads, d) pair that was measured: another head split of the same width stays on the scalar kernel.", "",
+              "| C | " + " | ".join(f"T = {T}" for T in PLUS_TOKENS) + " |", "|---|" + "---|" * len(PLUS_TOKENS)]
+    for Cc in sorted({c for c, _ in LEVELS}):
+        lines.append(f"| {Cc} | " + " | ".join("tiles" if rule[(Cc, T)] else "scalar" for T in PLUS_TOKENS) + " |")
+    return lines, rule
+
+
+def plus_adapter_shapes(embed=1280, hidden=768, ctx=768, queries=16, depth=4):
+    """Parameter shapes of ip-adapter-plus_sd15's Resampler (ViT-H hidden states, 12 heads of 64) in the original key spelling."""
+    shapes = {"latents": (1, queries, hidden), "proj_in.weight": (hidden, embed), "proj_in.bias": (hidden,), "proj_out.weight": (ctx, hidden),
+              "proj_out.bias": (ctx,), "norm_out.weight": (ctx,), "norm_out.bias": (ctx,)}
+    for i in range(depth):
+        p = f"layers.{i}."
+        shapes.update({p + "0.norm1.weight": (hidden,), p + "0.norm1.bias": (hidden,), p + "0.norm2.weight": (hidden,), p + "0.norm2.bias": (hidden,),
+                       p + "0.to_q.weight": (hidden, hidden), p + "0.to_kv.weight": (2 * hidden, hidden), p + "0.to_out.weight": (hidden, hidden),
+                       p + "1.0.weight": (hidden,), p + "1.0.bias": (hidden,), p + "1.1.weight": (4 * hidden, hidden),
+                       p + "1.3.weight": (hidden, 4 * hidden)})
+    return shapes
+
+
 def step_times(dev, steps, edits):
-    """ms per denoise step of the flagship edit without and with one adapter, alternating edits in one process: ([plain], [adapter])."""
+    """ms per denoise step of the flagship edit without an adapter, with one base adapter and with one Plus adapter (one image each),
+    alternating edits in one process: ({name: [ms]}, {name: launches per active step})."""
     import time
     import bench
     from blobctrl_amd import synth
@@ -70,31 +173,55 @@ def step_times(dev, steps, edits):
     shapes = {f"{1 + 2 * j}.to_{n}_ip.weight": (usd[bp + "attn2.to_k.weight"].shape[0], 768) for j, bp in enumerate(prefixes) for n in "kv"}
     sd = {"image_proj": synth.synth_state_dict({"proj.weight": (4 * 768, 1024), "proj.bias": (4 * 768,), "norm.weight": (768,), "norm.bias": (768,)}, 51),
           "ip_adapter": synth.synth_state_dict(shapes, 52)}
-    adapter = ip_adapter_on_device(convert_ip_adapter(sd, prefixes, 768), dev)
+    sd_plus = {"image_proj": synth.synth_state_dict(plus_adapter_shapes(), 53), "ip_adapter": synth.synth_state_dict(shapes, 54)}
+    adapters = {"base": ip_adapter_on_device(convert_ip_adapter(sd, prefixes, 768), dev),
+                "plus": ip_adapter_on_device(convert_ip_adapter(sd_plus, prefixes, 768), dev)}
     eng = BlobCtrlEngine(PackedTrunk(usd, dev, ucfg.block_out_channels), PackedTrunk(bsd, dev, bcfg.block_out_channels), ucfg, bcfg,
                          device=str(dev), scheduler="ddim")
     del usd, bsd
     h = w = 64
     inp = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in bench.synth_inputs(h, w).items()}
     score = splat_features(**inp["blob"], score_size=(h, w), return_d_score=True, device=str(dev))
-    embeds = [torch.randn(2, 1, 1024, device=dev)]
+    embeds = {"base": [torch.randn(2, 1, 1024, device=dev)], "plus": [torch.randn(2, 1, 257, 1280, device=dev)]}
+    ip_key = {"none": (), "base": (1,), "plus": ((1, 257),)}
 
-    def edit(with_adapter):
-        eng.ip_adapters = [adapter] if with_adapter else []           # (both plans stay cached: nothing is dropped between edits)
-        extra = dict(ip_adapter_image_embeds=embeds) if with_adapter else {}
+    def edit(name):
+        # (the three plans have keys of their own - no adapter, 4 tokens of 1024, 16 tokens of 257 x 1280 - and stay cached: nothing is dropped)
+        eng.ip_adapters = [adapters[name]] if name != "none" else []
+        extra = dict(ip_adapter_image_embeds=embeds[name]) if name != "none" else {}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         eng(inp["prompt"], inp["fg"], inp["bg"], score, inp["dino"], num_inference_steps=steps, guidance_scale=7.5, latents=inp["latents"], **extra)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
-    for flag in (False, True, False, True):                            # record, capture, warm
-        edit(flag)
-    plain, ip = [], []
+    names = ("none", "base", "plus")
+    for n in names + names:                                            # record, capture, warm
+        edit(n)
+    times = {n: [] for n in names}
     for _ in range(edits):
-        plain.append(edit(False))
-        ip.append(edit(True))
-    launches = {flag: len(eng.plan_for(1, h, w, 77, 768, steps, ip=(1,) if flag else ()).step_active) for flag in (False, True)}
-    return plain, ip, launches
+        for n in names:
+            times[n].append(edit(n))
+    launches = {}
+    for n in names:
+        eng.ip_adapters = [adapters[n]] if n != "none" else []
+        launches[n] = len(eng.plan_for(1, h, w, 77, 768, steps, ip=ip_key[n]).step_active)
+    return times, launches
+
+
+def step_lines(dev, steps, edits):
+    times, launches = step_times(dev, steps, edits)
+    med = statistics.median
+    row = lambda label, n: f"| {label} | {med(times[n]):.3f} | {' '.join(f'{v:.3f}' for v in times[n])} | {launches[n]} |"
+    cost = lambda n: f"{med(times[n]) - med(times['none']):+.3f} ms per step ({100 * (med(times[n]) / med(times['none']) - 1):+.1f} %)"
+    return ["", f"## Step time, 512^2 edit, batch 1, DDIM, {steps} steps, whole-edit graph, alternating edits in one process", "",
+            "| | ms per step (median) | every edit | launches per active step |", "|---|---|---|---|",
+            row("no adapter", "none"), row("one base adapter, one image (T = 4)", "base"),
+            row("one Plus adapter, one image (T = 16, 257 x 1280 hidden states)", "plus"), "",
+            f"The base adapter costs {cost('base')}, the Plus adapter {cost('plus')}: 16 bc_attention_ip launches per UNet forward either",
+            "way, and attn2 on the forms that store q (no CHAIN_MIDX at 320 / 640 channels, no bc_ctx_fold at 1280).  The figure is the",
+            "whole edit over its steps, so the prologue - the Resampler, once per edit - is inside it.",
+            "The adapter-less step records the launch list it recorded before adapters existed (tests/test_ip_adapter_cpu.py compares the",
+            "listings): that is a statement about the listing, not a timing against the previous commit."]
 
 
 def main():
@@ -104,10 +231,24 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--edits", type=int, default=4)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--paths-markdown", help="time both kernels behind bc_attention_ip at T = 16, 32, 48, 64 and write the table there")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--only-paths", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ip_adapter_probe needs an MI355X: a timing taken elsewhere says nothing")
     dev = torch.device("cuda:0")
+    if args.paths_markdown:                                            # profiles/ip_adapter_plus.md: both kernels, the rule, the step cost
+        plines, _ = paths_table(dev, args.reps, args.rounds)
+        if not args.no_step:
+            plines += step_lines(dev, args.steps, args.edits)
+            for ln in plines[-12:]:
+                print(ln, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.paths_markdown)), exist_ok=True)
+        with open(args.paths_markdown, "w") as f:
+            f.write("\n".join(plines) + "\n")
+        if args.only_paths:
+            return
     lines = ["# bc_attention_ip on an MI355X", "",
              f"HIP-event time per launch (median of {args.reps} replays in one segment), T = {T_IP} image tokens, {HEADS} heads; GB/s over the",
              "launch's algorithmic bytes 2 (3 M C + 2 B T C).  The alternative: bc_attention at Nkv = 4 into a buffer of its own + bc_add_rows",
@@ -120,17 +261,8 @@ def main():
             lines.append(f"| {Cc} | {HW} | {B} | {us:.1f} | {gbs:.0f} | {alt_us:.1f} | {text_us:.1f} |")
             print(lines[-1], flush=True)
     if not args.no_step:
-        plain, ip, launches = step_times(dev, args.steps, args.edits)
-        med = statistics.median
-        lines += ["", f"## Step time, 512^2 edit, batch 1, DDIM, {args.steps} steps, whole-edit graph, alternating edits in one process", "",
-                  "| | ms per step (median) | every edit | launches per active step |", "|---|---|---|---|",
-                  f"| no adapter | {med(plain):.3f} | {' '.join(f'{v:.3f}' for v in plain)} | {launches[False]} |",
-                  f"| one adapter, one image | {med(ip):.3f} | {' '.join(f'{v:.3f}' for v in ip)} | {launches[True]} |", "",
-                  f"The adapter costs {med(ip) - med(plain):+.3f} ms per step ({100 * (med(ip) / med(plain) - 1):+.1f} %): 16 bc_attention_ip launches per UNet",
-                  "forward, and attn2 on the forms that store q (no CHAIN_MIDX at 320 / 640 channels, no bc_ctx_fold at 1280).",
-                  "The adapter-less step records the launch list it recorded before adapters existed (tests/test_ip_adapter_cpu.py compares the",
-                  "listings): that is a statement about the listing, not a timing against the previous commit."]
-        for ln in lines[-11:]:
+        lines += step_lines(dev, args.steps, args.edits)
+        for ln in lines[-12:]:
             print(ln, flush=True)
     if args.markdown:
         os.makedirs(os.path.dirname(os.path.abspath(args.markdown)), exist_ok=True)

@@ -2399,6 +2399,175 @@ def golden_blocks_ip():
     np.savez_compressed(os.path.join(OUT, "blocks_ip.npz"), **out)
 
 
+def golden_clip_vision():
+    """tests/golden/clip_vision_tiny.npz: transformers' CLIPVisionModelWithProjection at the two random tiny configurations of
+    tests/clip_vision_common.py CLIP_VISION_CONFIGS, the seeded state dict loaded after its key set is asserted equal to the model's (`position_ids` aside: the key names are the installed ones), batch 2:
+    `<name>_image_embeds`, `<name>_hidden` = hidden_states[-2], and both again for an all-zero input (`_zero`: what the reference's
+    encode_image feeds the negative branch of an IP-Adapter Plus).  Outputs only."""
+    from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection
+    from tests.clip_vision_common import CLIP_VISION_CONFIGS, clip_vision_pixels, clip_vision_weights
+    out = {}
+    for name, c in CLIP_VISION_CONFIGS.items():
+        model = CLIPVisionModelWithProjection(CLIPVisionConfig(**c)).eval()
+        have = {k for k in model.state_dict() if not k.endswith("position_ids")}
+        sd = clip_vision_weights(name, prefix="vision_model." if any(k.startswith("vision_model.") for k in have) else "")
+        assert set(sd) == have, (sorted(set(sd) ^ have))
+        model.load_state_dict(sd, strict=False)
+        px = clip_vision_pixels(name)
+        for tag, x in (("", px), ("_zero", torch.zeros_like(px))):
+            with torch.no_grad():
+                r = model(pixel_values=x, output_hidden_states=True)
+            assert len(r.hidden_states) == c["num_hidden_layers"] + 1
+            out[f"{name}_image_embeds{tag}"], out[f"{name}_hidden{tag}"] = r.image_embeds.numpy(), r.hidden_states[-2].numpy()
+        gap = float(np.abs(out[f"{name}_hidden"] - out[f"{name}_hidden_zero"]).max() / np.abs(out[f"{name}_hidden"]).max()) / 1e-2
+        print(f"clip vision {name}: image_embeds std {out[f'{name}_image_embeds'].std():.3f}, hidden std {out[f'{name}_hidden'].std():.3f}, "
+              f"seeded vs zero input {gap:.0f} bars")
+        assert gap >= 10.0, gap
+    np.savez_compressed(os.path.join(OUT, "clip_vision_tiny.npz"), **out)
+    print("clip_vision_tiny.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "clip_vision_tiny.npz")) / 1024))
+
+
+def golden_pipeline_call_ip_image():
+    """tests/golden/pipeline_call_ip_image.npz: the reference's own `__call__` with `ip_adapter_image=<PIL image>`.  The tiny CLIP tower
+    "a" of tests/clip_vision_common.py (transformers' CLIPVisionModelWithProjection, seeded weights) is set as `image_encoder`;
+    `clip_processor` and `feature_extractor` (CLIPImageProcessor at the tower's 42 pixels) are bound on the object because the class
+    forgets them, and `prepare_ip_adapter_image_embeds` is bound as golden_pipeline_call_ip does.  DDIM, 3 steps, the case `ddim_neg2`
+    of pipeline_call.npz; the Plus adapter (tiny_plus_adapter "q16") and the base adapter (tiny_ip_adapter(0)) in turn.  Stores the final
+    latents `<kind>_latents` for image A, `<kind>_latents_b` for image B and `latents_off` of a pipeline without an adapter; the variants
+    lie at least 10 GPU bars (1e-2 of the latents' scale) apart."""
+    from PIL import Image
+    from diffusers.pipelines.stable_diffusion.pipeline_stable_diffusion import StableDiffusionPipeline
+    from transformers import CLIPImageProcessor, CLIPVisionConfig, CLIPVisionModelWithProjection
+    from tests.clip_vision_common import (CLIP_VISION_CONFIGS, IP_IMAGE_CALL_IMAGES, IP_IMAGE_CALL_SEEDS, clip_processor_image,
+                                          clip_vision_weights, tiny_plus_adapter)
+    from tests.common import FakeTokenizer, pipeline_cases
+    from tests.ip_adapter_common import tiny_ip_adapter
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"])
+    for k in ("scheduler", "seed", "rng_seed"):
+        kw.pop(k)
+    kw["num_inference_steps"] = 3
+    seed, rng_seed = IP_IMAGE_CALL_SEEDS
+    c = CLIP_VISION_CONFIGS["a"]
+    tower = CLIPVisionModelWithProjection(CLIPVisionConfig(**c)).eval()
+    have = {k for k in tower.state_dict() if not k.endswith("position_ids")}
+    sd = clip_vision_weights("a", prefix="vision_model." if any(k.startswith("vision_model.") for k in have) else "")
+    assert set(sd) == have
+    tower.load_state_dict(sd, strict=False)
+    images = {k: Image.fromarray(clip_processor_image(v)) for k, v in IP_IMAGE_CALL_IMAGES.items()}
+
+    def make(adapter):
+        unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+        if adapter is not None:
+            unet._load_ip_adapter_weights([adapter], low_cpu_mem_usage=False)
+        sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+        pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                              safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+        pipe.set_progress_bar_config(disable=True)
+        pipe.image_encoder = tower
+        pipe.clip_processor = pipe.feature_extractor = CLIPImageProcessor(size=c["image_size"], crop_size=c["image_size"])
+        pipe.prepare_ip_adapter_image_embeds = types.MethodType(StableDiffusionPipeline.prepare_ip_adapter_image_embeds, pipe)
+        return pipe
+
+    def call(pipe, **extra):
+        torch.manual_seed(rng_seed)
+        return pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                    height=64, width=64, generator=torch.Generator().manual_seed(seed), output_type="latent", **extra, **kw).images.numpy()
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(3), "latents_off": call(make(None))}
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    for kind, adapter in (("plus", tiny_plus_adapter("q16")), ("base", tiny_ip_adapter(0))):
+        pipe = make(adapter)
+        out[f"{kind}_latents"] = call(pipe, ip_adapter_image=images["a"])
+        out[f"{kind}_latents_b"] = call(pipe, ip_adapter_image=images["b"])
+        gaps = (rel(out[f"{kind}_latents"], out["latents_off"]), rel(out[f"{kind}_latents_b"], out[f"{kind}_latents"]),
+                rel(out[f"{kind}_latents_b"], out["latents_off"]))
+        print("pipeline __call__ ip image %s: latents std %.4f; A vs off %.3f, B vs A %.3f, B vs off %.3f (max-abs / scale)" %
+              ((kind, out[f"{kind}_latents"].std()) + gaps))
+        assert min(gaps) >= 10 * 1e-2, (kind, gaps)
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_ip_image.npz"), **out)
+    print("pipeline_call_ip_image.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "pipeline_call_ip_image.npz")) / 1024))
+
+
+def golden_clip_processor():
+    """tests/golden/clip_processor.npz: the installed transformers CLIPImageProcessor - without torchvision it falls back to its Pillow
+    backend, the one to pin - on the seeded images of tests/clip_vision_common.py: `<image>_<size>` = pixel_values [3][size][size] at
+    size = crop = 224 and 56."""
+    from PIL import Image
+    from transformers import CLIPImageProcessor
+    from tests.clip_vision_common import CLIP_PROCESSOR_IMAGES, CLIP_PROCESSOR_SIZES, clip_processor_image
+    out = {}
+    for size in CLIP_PROCESSOR_SIZES:
+        proc = CLIPImageProcessor(size={"shortest_edge": size}, crop_size={"height": size, "width": size})
+        assert "Pil" in type(proc).__name__, type(proc).__name__
+        for name in CLIP_PROCESSOR_IMAGES:
+            px = proc(images=Image.fromarray(clip_processor_image(name)), return_tensors="pt").pixel_values
+            assert tuple(px.shape) == (1, 3, size, size) and px.dtype == torch.float32
+            out[f"{name}_{size}"] = px[0].numpy()
+    np.savez_compressed(os.path.join(OUT, "clip_processor.npz"), **out)
+    print("clip_processor.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "clip_processor.npz")) / 1024))
+
+
+def golden_ip_plus():
+    """tests/golden/ip_plus_tiny.npz: IP-Adapter Plus on the tiny UNet of build_tiny().  The synthetic Plus adapters of
+    tests/clip_vision_common.py (original key spelling: the reference's loader renames them, D/loaders/unet.py:657-724) go through
+    `unet._load_ip_adapter_weights`; stored are
+      tokens_<q16|q8>_<one|two>   encoder_hid_proj's IPAdapterPlusImageProjection on hidden states [2][1][10][64] / [2][2][10][64], as
+                                  MultiIPAdapterImageProjection lays them out: [2][images * queries][ctx]
+      <case>_eps / _eps_off / _eps_other_scale   the UNet of PLUS_UNET_CASES (one image, two images = 32 tokens, a Plus and a base adapter
+                                  together) as golden_ip_adapter stores its cases; eps_off is asserted bit-equal to the adapter-less UNet.
+    Variants a test must tell apart (on / off / other scale, one / two images' tokens) lie at least 10 GPU bars (1e-2 of the scale) apart."""
+    from diffusers.models.attention_processor import IPAdapterAttnProcessor2_0
+    from diffusers.models.embeddings import IPAdapterPlusImageProjection
+    from tests.clip_vision_common import (PLUS_QUERIES, PLUS_TOKEN_SHAPES, PLUS_UNET_CASES, PLUS_UNET_SCALES, plus_hidden, plus_unet_adapters,
+                                          plus_unet_inputs, tiny_plus_adapter)
+    from tests.ip_adapter_common import IP_GEOMETRIES, IP_OTHER_FACTOR, IP_RES_SCALE
+    out, t = {"timestep": np.array(981), "res_scale": np.array(IP_RES_SCALE), "other_factor": np.array(IP_OTHER_FACTOR)}, torch.tensor(981)
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    for kind in PLUS_QUERIES:
+        unet, _ = build_tiny()
+        unet._load_ip_adapter_weights([tiny_plus_adapter(kind)], low_cpu_mem_usage=False)
+        proj = unet.encoder_hid_proj.image_projection_layers[0]
+        assert isinstance(proj, IPAdapterPlusImageProjection) and proj.latents.shape[1] == PLUS_QUERIES[kind] and len(proj.layers) == 4
+        for name in PLUS_TOKEN_SHAPES:
+            with torch.no_grad():
+                tok = unet.encoder_hid_proj([plus_hidden(name)])[0]              # [2][images][queries][ctx]
+            tok = tok.reshape(tok.shape[0], -1, tok.shape[-1])
+            assert tok.shape[:2] ==(2, PLUS_TOKEN_SHAPES[name][1] * PLUS_QUERIES[kind])
+            out[f"tokens_{kind}_{name}"] = tok.numpy()
+        gap = rel(out[f"tokens_{kind}_two"][:, :PLUS_QUERIES[kind]], out[f"tokens_{kind}_one"]) / 1e-2
+        print(f"ip-adapter plus {kind}: tokens std {out[f'tokens_{kind}_one'].std():.3f}, first image of `two` vs `one` {gap:.0f} bars")
+        assert gap >= 10.0, gap
+    for case, (geo, adapters) in PLUS_UNET_CASES.items():
+        B, H, W = IP_GEOMETRIES[geo]
+        x_u, ehs, seed, ins = plus_unet_inputs(case)
+        down, mid, up = _freeu_residual_shapes(H, W)
+        mk = lambda i, s: g(seed + i, B, *s) * IP_RES_SCALE
+        down, mid, up = [mk(i, s) for i, s in enumerate(down)], mk(100, mid), [mk(200 + i, s) for i, s in enumerate(up)]
+        res = lambda: dict(down_block_add_samples=[r.clone() for r in down], mid_block_add_sample=mid.clone(),
+                           up_block_add_samples=[r.clone() for r in up])
+        plain, _ = build_tiny()
+        with torch.no_grad():
+            eps_plain = plain(x_u, t, encoder_hidden_states=ehs, return_dict=False, **res())[0].numpy()
+        unet, _ = build_tiny()
+        unet._load_ip_adapter_weights(plus_unet_adapters(case), low_cpu_mem_usage=False)
+        procs = [p for p in unet.attn_processors.values() if isinstance(p, IPAdapterAttnProcessor2_0)]
+        assert len(procs) == 16
+
+        def run(factor):
+            for p in procs:
+                p.scale = [factor * s_ for s_ in PLUS_UNET_SCALES[case]]
+            with torch.no_grad():
+                return unet(x_u, t, encoder_hidden_states=ehs, added_cond_kwargs={"image_embeds": ins}, return_dict=False, **res())[0].numpy()
+        eps, eps_off, eps_other = run(1.0), run(0.0), run(IP_OTHER_FACTOR)
+        assert np.array_equal(eps_off, eps_plain), "scale 0 is the adapter-less UNet, bit for bit"
+        gaps = dict(on_off=rel(eps, eps_off) / 1e-2, on_other=rel(eps, eps_other) / 1e-2, other_off=rel(eps_other, eps_off) / 1e-2)
+        print(f"ip-adapter plus UNet {case}: eps std {eps.std():.4f}, variants apart by {gaps} bars")
+        assert min(gaps.values()) >= 10.0, (case, gaps)
+        out.update({f"{case}_eps": eps, f"{case}_eps_off": eps_off, f"{case}_eps_other_scale": eps_other})
+    np.savez_compressed(os.path.join(OUT, "ip_plus_tiny.npz"), **out)
+    print("ip_plus_tiny.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "ip_plus_tiny.npz")) / 1024))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -2445,6 +2614,10 @@ if __name__ == "__main__":
     golden_blocks_ip()
     golden_ip_adapter()
     golden_pipeline_call_ip()
+    golden_ip_plus()
+    golden_clip_vision()
+    golden_clip_processor()
+    golden_pipeline_call_ip_image()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
