@@ -256,6 +256,18 @@ RESAMPLE_SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 
+# Entry points of include/blobctrl_overlay.h (zoomed edits: a mask's bounds, Pillow's Gaussian blur, the paste-back; blobctrl_amd/overlay.py).
+# A table of its own, as for the resize: DIRECT launches on the caller's stream - no BC_OP_* code, in no op table, never recorded.
+_BLUR_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+OVERLAY_SIGNATURES = {
+    "bc_box_blur3_rows": (C.c_int, _BLUR_ARGS),
+    "bc_box_blur3_cols": (C.c_int, _BLUR_ARGS),
+    "bc_mask_bounds": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bc_overlay_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+}
+BLUR_MAX_R = 63                       # largest integer box radius of the blur launches (BC_BLUR_MAX_R)
+
 # Entry point of include/blobctrl_ip.h (the IP-Adapter image cross-attention, accumulated onto attn2's text attention in place).  A table
 # of its own; a recordable plan op (IP_OPS below), in-process only like the SAM ops.
 IP_SIGNATURES = {
@@ -346,7 +358,7 @@ def load():
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
             list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
-            list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()):
+            list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()) + list(OVERLAY_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

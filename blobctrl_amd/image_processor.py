@@ -3,6 +3,8 @@
   * VaeImageProcessor      - D/image_processor.py:469-600 (preprocess) and :602-680 (postprocess) for the inputs the pipeline accepts:
                              PIL images (lanczos resize to (height, width) rounded down to a multiple of the VAE scale factor, THEN
                              RGB conversion, [0,1] -> [-1,1]), numpy arrays, tensors; outputs "latent" | "pt" | "np" | "pil".
+                             Also the four functions of a zoomed edit - blur, get_crop_region, resize(resize_mode) and apply_overlay
+                             (:184-407, :651-684) - for PIL images on the host and for uint8 device tensors through blobctrl_amd.overlay.
   * Dinov2ImageProcessor   - what `AutoImageProcessor.from_pretrained(dinov2_path)` resolves to for facebook/dinov2-* (transformers'
                              BitImageProcessor, called at pipeline_blobnet.py:696): RGB, bicubic resize of the SHORTEST edge to 256,
                              centre crop 224 x 224, 1/255, ImageNet mean / std.  Pinned against the installed BitImageProcessor
@@ -35,6 +37,87 @@ class VaeImageProcessor:
             width = image.width if isinstance(image, Image.Image) else (image.shape[3] if torch.is_tensor(image) else image.shape[2])
         f = self.config.vae_scale_factor
         return height - height % f, width - width % f
+
+    # ---- zoomed ("only masked") edits: D/image_processor.py:184-190, :193-280, :282-407 and :651-684.  A PIL image takes the host route,
+    #      which is Pillow's own calls (blobctrl_amd.overlay's numpy restatement is the tests' yardstick, not a route); a uint8 device tensor
+    #      takes that module's device half - the same bytes, on the GPU; a CPU tensor raises BlobCtrlHipError
+    @staticmethod
+    def blur(image, blur_factor: int = 4):
+        if torch.is_tensor(image):
+            from . import overlay
+            return overlay.blur(image, blur_factor)
+        from PIL import ImageFilter
+        return image.filter(ImageFilter.GaussianBlur(blur_factor))
+
+    @staticmethod
+    def get_crop_region(mask_image, width: int, height: int, pad=0):
+        from . import overlay
+        if torch.is_tensor(mask_image):
+            return overlay.crop_region(mask_image, width, height, pad)
+        box = mask_image.convert("L").getbbox()                   # (left, top, right, bottom) of the non-zero pixels, None without any
+        bounds = (-1, -1, -1, -1) if box is None else (box[0], box[2] - 1, box[1], box[3] - 1)
+        return overlay.crop_region_from_bounds(bounds, mask_image.width, mask_image.height, width, height, pad)
+
+    @staticmethod
+    def _fit(image, width: int, height: int, crop: bool):
+        """resize_mode "crop" (cover the frame, cut the excess) or "fill" (fit inside it, fill the bands from the image's edge lines)."""
+        from . import overlay
+        Image = _pil()
+        src_w, src_h, ox, oy, band = overlay.fill_geometry(image.width, image.height, width, height)
+        if crop:
+            src_w, src_h = overlay._fit_sizes(image.width, image.height, width, height, True)
+            ox, oy, band = width // 2 - src_w // 2, height // 2 - src_h // 2, None
+        resized = image.resize((src_w, src_h), resample=Image.LANCZOS)
+        res = Image.new("RGB", (width, height))
+        res.paste(resized, box=(ox, oy))
+        # a band is Image.resize of a box of zero extent on the edge it continues (overlay.band_tables says what Pillow makes of that)
+        if band == "rows":
+            for edge, y in ((0, 0), (src_h, oy + src_h)):
+                res.paste(resized.resize((width, oy), box=(0, edge, width, edge)), box=(0, y))
+        elif band == "cols":
+            for edge, x in ((0, 0), (src_w, ox + src_w)):
+                res.paste(resized.resize((ox, height), box=(edge, 0, edge, height)), box=(x, 0))
+        return res
+
+    def resize(self, image, height: int, width: int, resize_mode: str = "default"):
+        """PIL images and uint8 device images [n][H][W][3] / [H][W][3]; resize_mode "default" | "fill" | "crop".  (The float tensor and
+        numpy modes of the reference's `resize` are `preprocess`'s business here and are not taken.)"""
+        if resize_mode not in ("default", "fill", "crop"):
+            raise ValueError(f"resize_mode {resize_mode} is not supported")
+        if torch.is_tensor(image):
+            from . import overlay, resample
+            if resize_mode == "default":
+                if image.device.type != "cuda":
+                    raise overlay._no_cpu("resize")
+                return resample.resize_images(image, (height, width), self.config.resample)
+            return (overlay.resize_fill if resize_mode == "fill" else overlay.resize_fit)(image, width, height)
+        Image = _pil()
+        if not isinstance(image, Image.Image):
+            raise ValueError(f"Only PIL images and uint8 device tensors are supported for resize_mode {resize_mode}")
+        if resize_mode == "default":
+            rs = {"lanczos": Image.LANCZOS, "bilinear": Image.BILINEAR, "bicubic": Image.BICUBIC, "nearest": Image.NEAREST}
+            return image.resize((width, height), resample=rs[self.config.resample])
+        return self._fit(image, width, height, resize_mode == "crop")
+
+    def apply_overlay(self, mask, init_image, image, crop_coords=None):
+        """The edit's output laid over the original through the mask: the original where the mask is 0, Pillow's blend elsewhere.  The
+        frame is the image's; init and mask are resized to it."""
+        if torch.is_tensor(image):
+            from . import overlay
+            return overlay.apply_overlay(mask, init_image, image, crop_coords)
+        from PIL import Image, ImageOps
+        size = image.size
+        keep = ImageOps.invert(self.resize(mask, size[1], size[0]).convert("L"))            # alpha of the original: 255 where the mask is 0
+        original = Image.new("RGBa", size)                                                  # premultiplied, transparent black
+        original.paste(self.resize(init_image, size[1], size[0]).convert("RGBA").convert("RGBa"), mask=keep)
+        if crop_coords is not None:
+            x1, y1, x2, y2 = crop_coords
+            canvas = Image.new("RGBA", size)
+            canvas.paste(self.resize(image, y2 - y1, x2 - x1, resize_mode="crop"), (x1, y1))
+            image = canvas.convert("RGB")                                                   # black outside the box
+        out = image.convert("RGBA")
+        out.alpha_composite(original.convert("RGBA"))
+        return out.convert("RGB")
 
     def preprocess(self, image, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
         Image = _pil()

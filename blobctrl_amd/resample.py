@@ -261,6 +261,32 @@ def resize_images(images, size, resample="lanczos", window=None, out=None, tmp=N
     return out
 
 
+@torch.no_grad()
+def apply_axis_tables(images, axis, tables, lines, what="apply_axis_tables"):
+    """One pass with the caller's own tables, for a resampling `resample_tables` does not describe (a box other than the whole axis):
+    images uint8 device [n][H][W][3], axis 1 (rows) or 2 (columns), tables = (bounds int32 [out][2], coeffs int32 [out][ksize], ksize) as
+    DEVICE tensors, `lines` <= out the number of leading output lines wanted -> uint8 [n][lines][W][3] or [n][H][lines][3]: the device's
+    `apply_tables` along that axis."""
+    x, _ = _device_images(images, what)
+    if images.ndim != 4 or axis not in (1, 2):
+        raise ValueError(f"{what} takes a batch [n][H][W][3] and axis 1 or 2")
+    n, H, W, _ = x.shape
+    bounds, coeffs, ksize = tables
+    out_size = bounds.shape[0]
+    if not (1 <= lines <= out_size and tuple(coeffs.shape) == (out_size, ksize) and bounds.device == coeffs.device == x.device and
+            bounds.dtype == coeffs.dtype == torch.int32 and bounds.is_contiguous() and coeffs.is_contiguous()):
+        raise ValueError(f"{what}: tables must be contiguous int32 [out][2] and [out][{ksize}] on {x.device}, and lines within 1 .. out")
+    with torch.cuda.device(x.device):
+        lib = _lib.load()
+        if axis == 1:
+            out = torch.empty((n, lines, W, 3), dtype=torch.uint8, device=x.device)
+            _vertical(lib, x, n, H, W, 0, 0, tables, out_size, 0, lines, W, out, None, None, 0, 0, what)
+        else:
+            out = torch.empty((n, H, lines, 3), dtype=torch.uint8, device=x.device)
+            _horizontal(lib, x, 0, H, tables, out_size, 0, lines, out, what)
+    return out
+
+
 def _resize_to_planar(x, size, resample, window, lut, frame, what):
     """Resize + lookup: uint8 [n][H][W][3] -> fp32 [n][3][PH][PW] with lut[c][byte] in the window's rows and columns and 0.0 elsewhere.  The
     vertical launch carries the epilogue, so a pass whose side stays runs with the identity table."""

@@ -16,7 +16,11 @@ With --ip-adapter PATH --ip-image FILE the edit takes an image prompt: PATH is a
 CLIP vision tower in the folder `image_encoder` beside it; the image goes through CLIPImageProcessor, the tower
 (blobctrl_amd.clip_vision) and - for a Plus adapter - the Resampler in the plan's prologue, and every attn2 runs bc_attention_ip on its
 tokens.  --ip-adapter synth uses a seeded tiny tower (320 wide, 4 layers) and a seeded Plus adapter of 16 queries; without --ip-image the
-image is seeded noise."""
+image is seeded noise.
+With --device-inputs --zoom PAD the edit is a zoomed ("only masked") one (blobctrl_amd.overlay): the box around the start and
+target ellipses, padded by PAD and grown to the frame's ratio, is blown up to the model's resolution (`zoom_edit`), the model edits that
+frame, and the result is pasted back over the original through the ellipses' mask blurred with --blur F (`blur`, `apply_overlay`) - all
+on the device; pixels outside the blurred mask keep the original's bytes."""
 import argparse
 import os
 import sys
@@ -97,6 +101,9 @@ def main():
                     help="despeckle the SAM mask(s) on the GPU first: fill holes and remove islands of fewer than N pixels (with --sam)")
     ap.add_argument("--device-inputs", action="store_true",
                     help="build the edit's inputs on the GPU from the device mask (with --sam, click prompts): blobctrl_amd.edit_inputs")
+    ap.add_argument("--zoom", type=int, default=None, metavar="PAD",
+                    help="edit only the box around the blobs, padded by PAD pixels, at full model resolution, and paste it back (with --device-inputs)")
+    ap.add_argument("--blur", type=float, default=4, metavar="F", help="blur factor of the paste-back mask (with --zoom; the reference's default 4)")
     ap.add_argument("--ip-adapter", default=None, help="an IP-Adapter .safetensors file with `image_encoder/` beside it, or 'synth'")
     ap.add_argument("--ip-image", default=None, help="the image prompt (any file PIL opens); seeded noise without it")
     args = ap.parse_args()
@@ -104,6 +111,8 @@ def main():
         ap.error("--ip-image needs --ip-adapter")
     if args.device_inputs and (not args.sam or args.sam_auto is not None):
         ap.error("--device-inputs needs --sam and a click prompt")
+    if args.zoom is not None and not args.device_inputs:
+        ap.error("--zoom needs --device-inputs")
     if (args.click or args.sam_auto is not None) and not args.sam:
         ap.error("--click / --sam-auto need --sam")
     if args.click and args.sam_auto is not None:
@@ -190,7 +199,15 @@ def main():
                 ells = [((ellipse[0][0], ellipse[0][1]), (ellipse[1][0], ellipse[1][1]), ellipse[2])]
             target =((ells[0][0][0] + 0.1 * R, ells[0][0][1]), ells[0][1], ells[0][2])          # the edit: move the object right
             fg_u8 = edit_inputs.object_regions(image_dev, clean, boxes)
-            bg_u8, score, _ = edit_inputs.build_edit_inputs_batch(["move"], image_dev, ells, [target], [1.0])
+            frame, start = image_dev, ells[0]
+            # (the foreground stays what it was: the object cut out of the whole frame onto its own centred canvas, which is what DINOv2
+            # describes whatever frame the edit runs in; the background and both ellipses move into the zoomed frame)
+            if args.zoom is not None:                         # the model sees the padded box around both blobs at its full resolution
+                from blobctrl_amd import overlay
+                overlay.blur_params(args.blur)                # (an unsupported factor is refused here, not after the edit)
+                zoom_crop, frame, zoom_mask, start, target = overlay.zoom_edit(image_dev, ells[0], target, R, R, args.zoom)
+                print(f"zoom: box {zoom_crop} of the {R} x {R} frame edited at {R} x {R}")
+            bg_u8, score, _ = edit_inputs.build_edit_inputs_batch(["move"], frame, [start], [target], [1.0])
             fg, bg = edit_inputs.vae_input(fg_u8), edit_inputs.vae_input(bg_u8)
             dino_px = resample.dinov2_pixel_values(fg_u8[0], Dinov2ImageProcessor())
             print(f"SAM click {click} -> device mask in {1e3 * (te - ts):.1f} ms (first call: planning + graph capture); mask -> ellipse {ells[0]}, "
@@ -215,18 +232,26 @@ def main():
     ids = torch.from_numpy(rng.integers(0, 49408, size=(2, 1, 77)).astype(np.int64))
     prompt = pipe.encode_prompt(ids[1], ids[0])
     t4 = sync()
+    otype = "pt" if args.zoom is not None else "np"           # a zoomed edit's result stays on the device for the paste-back
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,
-               fg_image=fg, bg_image=bg, output_type="np", **ip_kwargs)
+               fg_image=fg, bg_image=bg, output_type=otype, **ip_kwargs)
     t5 = sync()
     print(f"models {t1 - t0:.1f} s | splat {1e3 * (t2 - t1):.1f} ms | DINOv2 {1e3 * (t3 - t2):.1f} ms | CLIP {1e3 * (t4 - t3):.1f} ms | "
           f"VAE encode x2 + {args.steps}-step loop + VAE decode {1e3 * (t5 - t4):.1f} ms (first call: includes planning + graph capture)")
     t6 = sync()
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,
-               fg_image=fg, bg_image=bg, output_type="np", **ip_kwargs)
+               fg_image=fg, bg_image=bg, output_type=otype, **ip_kwargs)
     t7 = sync()
-    print(f"second edit (plans cached): {1e3 * (t7 - t6):.1f} ms end to end; image {img.shape}, range [{img.min():.3f}, {img.max():.3f}]")
+    print(f"second edit (plans cached): {1e3 * (t7 - t6):.1f} ms end to end; image {tuple(img.shape)}, range [{img.min():.3f}, {img.max():.3f}]")
+    if args.zoom is not None:
+        t8 = sync()
+        pasted = overlay.apply_overlay(overlay.blur(zoom_mask, args.blur), image_dev, overlay.to_uint8(img, do_denormalize=False), zoom_crop)
+        t9 = sync()
+        kept = int((pasted[0] == image_dev).all(-1).sum())
+        print(f"zoom: blur + paste-back on the device {1e3 * (t9 - t8):.2f} ms; {kept} of {R * R} pixels keep the original's bytes")
+        img = pasted.float().div(255).cpu().numpy()
     if args.out:
         np.save(args.out, img[0])
 

@@ -2568,6 +2568,30 @@ def golden_ip_plus():
     print("ip_plus_tiny.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "ip_plus_tiny.npz")) / 1024))
 
 
+def golden_overlay():
+    """The vendored `VaeImageProcessor`'s own get_crop_region, apply_overlay, blur and resize("fill" | "crop") on the cases of
+    tests/overlay_common.py: ties blobctrl_amd.overlay's restatement to the reference, not only to Pillow."""
+    from PIL import Image
+    from diffusers.image_processor import VaeImageProcessor
+    from tests import overlay_common as oc
+    proc, out = VaeImageProcessor(), {}
+    for name, ((H, W), box, (width, height), pad) in oc.CROP_CASES.items():
+        out[f"crop_{name}"] = np.array(proc.get_crop_region(Image.fromarray(oc.box_mask(H, W, *box)), width, height, pad=pad), dtype=np.int64)
+    for name in oc.OVERLAY_CASES:
+        mask, init, image, crop = oc.overlay_inputs(name)
+        out[f"overlay_{name}"] = np.array(proc.apply_overlay(Image.fromarray(mask), Image.fromarray(init), Image.fromarray(image), crop))
+    mask, init, image = oc.overlay_resized_inputs()
+    out["overlay_resized"] = np.array(proc.apply_overlay(Image.fromarray(mask), Image.fromarray(init), Image.fromarray(image)))
+    for name, ((H, W), (width, height), seed) in oc.RESIZE_CASES.items():
+        img = Image.fromarray(oc.rgb_image(H, W, seed))
+        out[f"fill_{name}"] = np.array(proc.resize(img, height, width, resize_mode="fill"))
+        out[f"fit_{name}"] = np.array(proc.resize(img, height, width, resize_mode="crop"))
+    for name, ((H, W), factor, seed) in oc.BLUR_GOLDEN.items():
+        out[f"blur_{name}"] = np.array(proc.blur(Image.fromarray(oc.blob_mask(H, W, seed, hard="hard" in name)), factor))
+    np.savez_compressed(oc.GOLDEN, **out)
+    print("overlay.npz: %.1f KB, %d arrays" % (os.path.getsize(oc.GOLDEN) / 1024, len(out)))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -2618,6 +2642,7 @@ if __name__ == "__main__":
     golden_clip_vision()
     golden_clip_processor()
     golden_pipeline_call_ip_image()
+    golden_overlay()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
