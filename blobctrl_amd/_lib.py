@@ -283,6 +283,21 @@ IP_PATH_SIGNATURES = {
 }
 ATTENTION_IP_SCALAR, ATTENTION_IP_TILES = 0, 1
 
+# Entry points of include/blobctrl_ip_mask.h (ip_adapter_masks: one softmax per image, each weighted by its mask).  Tables of their own:
+# the masked attention is a recordable plan op (IP_MASK_OPS below), in-process only like bc_attention_ip ...
+IP_MASK_SIGNATURES = {
+    "bc_attention_ip_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+}
+# ... and the rest are DIRECT launches and plain entry points - no BC_OP_* code, in no op table, never recorded into a plan: the bicubic
+# downsampling of a mask to one attention level, and the masked kernels by name
+IP_MASK_DIRECT_SIGNATURES = {
+    "bc_ip_mask_downsample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_void_p]),
+    "bc_attention_ip_masked_path": (C.c_int, [C.c_int] * 5),
+    "bc_attention_ip_masked_with": (C.c_int, [C.c_int] + IP_MASK_SIGNATURES["bc_attention_ip_masked"][1]),
+}
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -303,7 +318,12 @@ SAM_OPS = {"bc_attention_relpos": 42, "bc_window_partition": 43, "bc_window_unpa
 SAM_BATCH_OPS = {"bc_sam_tokens_batch": 51, "bc_mask_stats": 52}
 # ... and that of include/blobctrl_ip.h: extension headers continue from BC_OP_COUNT (53), the base header's enum is closed
 IP_OPS = {"bc_attention_ip": 53}
+# ... and that of include/blobctrl_ip_mask.h, an enum of its own behind BC_OP_IP_END (54, which stays no op)
+IP_MASK_OPS = {"bc_attention_ip_masked": 55}
 _OP_TABLES = (OPS, REQUEST_OPS, SAM_OPS, SAM_BATCH_OPS, IP_OPS)
+# _OP_TABLES is the list up to BC_OP_IP_END and stays as it is; tables of headers that start an enum of their own behind it go here, and
+# `op_code` reads both
+_OP_TABLES_BEYOND = (IP_MASK_OPS,)
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
@@ -312,7 +332,7 @@ _KIND = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l", C.c_c
 
 def op_code(name):
     """BC_OP_* code of a recordable entry point."""
-    for table in _OP_TABLES:
+    for table in _OP_TABLES + _OP_TABLES_BEYOND:
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -321,7 +341,7 @@ def op_code(name):
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
     args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES.get(name) or SAM_BATCH_SIGNATURES.get(name) or
-            IP_SIGNATURES[name])[1][:-1]
+            IP_SIGNATURES.get(name) or IP_MASK_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -358,7 +378,8 @@ def load():
     for name, (res, args) in list(_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(REQUEST_SIGNATURES.items()) + \
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
             list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
-            list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()) + list(OVERLAY_SIGNATURES.items()):
+            list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()) + list(OVERLAY_SIGNATURES.items()) + \
+            list(IP_MASK_SIGNATURES.items()) + list(IP_MASK_DIRECT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -90,10 +90,13 @@ class IpAdapter:
     to [B][n_images * num_tokens][ctx_dim], LayerNorm (D/models/embeddings.py ImageProjection).
     IP-Adapter Plus: `hidden`, fp16 [B * n_images][S][embed_dims] (the image encoder's penultimate hidden states, a per-edit input buffer)
     in place of `embeds`, and `plus` = the adapter's device dict (weights.ip_adapter_on_device: latents, proj_in, layers, proj_out,
-    norm_out); num_tokens = num_queries.  TrunkPlan.record_resampler turns them into the tokens."""
+    norm_out); num_tokens = num_queries.  TrunkPlan.record_resampler turns them into the tokens.
+    masked: the plan was made for `ip_adapter_masks` - every attn2 runs bc_attention_ip_masked (one softmax per image, n_images x num_tokens
+    keys) and reads `mask_bufs[rows]`, fp16 [n_images][rows] per attention level, buffers the recorder allocates as `<mask_name>_<rows>` when
+    TrunkPlan.attention_ip first meets the level and blobctrl_amd.ip_masks.fill_plan_masks refills for every edit."""
 
     def __init__(self, kv, scales, tokens=None, embeds=None, n_images=1, num_tokens=4, proj_w=None, proj_b=None, norm_w=None, norm_b=None,
-                 hidden=None, plus=None):
+                 hidden=None, plus=None, masked=False, mask_name=None):
         assert sum(x is not None for x in (tokens, embeds, hidden)) == 1 and scales.dtype == torch.float32 and scales.numel() == len(kv)
         assert (hidden is None) == (plus is None)
         self.kv, self.scales, self.tokens, self.embeds = dict(kv), scales, tokens, embeds
@@ -101,9 +104,16 @@ class IpAdapter:
         self.proj_w, self.proj_b, self.norm_w, self.norm_b = proj_w, proj_b, norm_w, norm_b
         self.hidden, self.plus = hidden, plus
         self.slot = {bp: i for i, bp in enumerate(self.kv)}
+        self.masked, self.mask_name, self.mask_bufs = bool(masked), mask_name, {}
+
+    def mask_buffer(self, rec, rows):
+        """The fp16 [n_images][rows] mask of the attention level with `rows` query rows per UNet image, one buffer per level."""
+        if rows not in self.mask_bufs:
+            self.mask_bufs[rows] = rec.zeros(self.n_images, rows, name=None if self.mask_name is None else f"{self.mask_name}_{rows}")
+        return self.mask_bufs[rows]
 
     @classmethod
-    def for_plan(cls, rec, ad, B, entry, name=None):
+    def for_plan(cls, rec, ad, B, entry, name=None, masked=False, mask_name=None):
         """The adapter `ad` (weights.ip_adapter_on_device) in a plan of UNet batch B, with its per-edit input buffer allocated from the
         recorder: `entry` = images per UNet image for a base adapter ([B * images][embed_dim]), (images, S) for a Plus adapter
         ([B * images][S][embed_dims]).  Returns (IpAdapter, buffer)."""
@@ -111,10 +121,11 @@ class IpAdapter:
         if ad.get("layout") == "plus":
             n, S = entry
             buf = rec.zeros(B * n, S, ip_adapter_embed_dim(ad), name=name)
-            return cls(ad["kv"], ad["scales"], hidden=buf, plus=ad, n_images=n, num_tokens=ip_adapter_tokens(ad)), buf
+            return cls(ad["kv"], ad["scales"], hidden=buf, plus=ad, n_images=n, num_tokens=ip_adapter_tokens(ad), masked=masked,
+                       mask_name=mask_name), buf
         buf = rec.zeros(B * entry, ip_adapter_embed_dim(ad), name=name)
         return cls(ad["kv"], ad["scales"], embeds=buf, n_images=entry, proj_w=ad["proj_w"], proj_b=ad["proj_b"], norm_w=ad["norm_w"],
-                   norm_b=ad["norm_b"]), buf
+                   norm_b=ad["norm_b"], masked=masked, mask_name=mask_name), buf
 
 
 class TrunkPlan:
@@ -446,9 +457,16 @@ class TrunkPlan:
 
     def attention_ip(self, bp, q, a, B, HW, Cc, d, scale):
         """The image cross-attention of every loaded IP-Adapter behind attn2's text attention, on the same query rows `q` and accumulated
-        onto the same output rows `a` (attention_processor.py:3808-3868): one bc_attention_ip launch per adapter.  Nothing without one."""
-        for K_ip, V_ip, T_ip, w in self.ip_kv.get(bp, ()):
-            self.rec.attention_ip(q, K_ip, V_ip, a, B, HW, self.heads, d, T_ip, Cc, Cc, Cc, scale, w)
+        onto the same output rows `a` (attention_processor.py:3808-3868): one bc_attention_ip launch per adapter.  Nothing without one.
+        An adapter of a plan made for `ip_adapter_masks` (IpAdapter.masked) runs bc_attention_ip_masked in its place, on the level's mask."""
+        for K_ip, V_ip, T_ip, w, *rest in self.ip_kv.get(bp, ()):
+            ad = rest[0] if rest else None
+            if ad is not None and ad.masked:
+                mask = ad.mask_buffer(self.rec, HW)
+                self.rec.attention_ip_masked(q, K_ip, V_ip, a, B, HW, self.heads, d, ad.n_images, T_ip // ad.n_images, Cc, Cc, Cc, scale, w,
+                                             mask, mask.shape[1])
+            else:
+                self.rec.attention_ip(q, K_ip, V_ip, a, B, HW, self.heads, d, T_ip, Cc, Cc, Cc, scale, w)
 
     def gw_tile(self, M, N, K, C1=0, prefer=None):
         """BC_TILE_GW* configuration for a projection of the low-resolution levels (csrc/gemm_wreg.hip), or 0 = the LDS-DMA tiles.
@@ -670,7 +688,9 @@ class TrunkPlan:
                 K_ip, V_ip = rec.empty(B, T_ip, Cc), rec.empty(B, T_ip, Cc)
                 rec.gemm(A=tokens, W=wk, M=B * T_ip, N=Cc, K=Dc, out=K_ip, kind="ip_kv")
                 rec.gemm(A=tokens, W=wv, M=B * T_ip, N=Cc, K=Dc, out=V_ip, kind="ip_kv")
-                self.ip_kv.setdefault(bp, []).append((K_ip, V_ip, T_ip, ad.scales[ad.slot[bp]:ad.slot[bp] + 1]))
+                if ad.masked and T_ip % ad.n_images:
+                    raise ValueError(f"an IP-Adapter with masks brings {T_ip} image tokens for {ad.n_images} images: not the same number each")
+                self.ip_kv.setdefault(bp, []).append((K_ip, V_ip, T_ip, ad.scales[ad.slot[bp]:ad.slot[bp] + 1]) + ((ad,) if ad.masked else ()))
 
     def record_resampler(self, ad):
         """IPAdapterPlusImageProjection (D/models/embeddings.py:1352-1441) on the adapter's hidden states, once per edit, with existing

@@ -175,6 +175,67 @@ class VaeImageProcessor:
         return [Image.fromarray(a) for a in u8]
 
 
+class IPAdapterMaskProcessor(VaeImageProcessor):
+    """D/image_processor.py:928-1029: the masks of `cross_attention_kwargs={"ip_adapter_masks": ...}`.  `preprocess(mask, height, width)`:
+    lanczos resize to the call's height and width rounded down to multiples of `vae_scale_factor`, grayscale, binarised at 0.5, no
+    normalisation -> [n][1][H][W] with values 0 and 1; the caller stacks an adapter's masks to [1][images][H][W]
+    (`masks.reshape(1, masks.shape[0], masks.shape[2], masks.shape[3])`, as the reference's documentation does).
+    The host route takes PIL images and uint8 numpy arrays ([H][W] or [H][W][C]; taken as the PIL image `Image.fromarray` makes of them)
+    through Pillow and returns fp32 on the host.  The device route takes a uint8 device mask [H][W] or [n][H][W] (0 / 255, as
+    `edit_inputs.ellipse_masks` leaves them) through blobctrl_amd.resample - Pillow's bytes - and returns uint8 on the device.  Both give
+    the same values.  The downsampling to an attention level is no method here: blobctrl_amd.ip_masks does it into buffers a plan owns."""
+
+    def __init__(self, do_resize: bool = True, vae_scale_factor: int = 8, resample: str = "lanczos", do_normalize: bool = False,
+                 do_binarize: bool = True, do_convert_grayscale: bool = True):
+        super().__init__(vae_scale_factor=vae_scale_factor, do_resize=do_resize, resample=resample, do_normalize=do_normalize)
+        self.config.do_binarize, self.config.do_convert_grayscale = do_binarize, do_convert_grayscale
+
+    def preprocess(self, image, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
+        Image = _pil()
+        if torch.is_tensor(image) or (isinstance(image, list) and image and torch.is_tensor(image[0])):
+            return self._preprocess_device(torch.stack(list(image)) if isinstance(image, list) else image, height, width)
+        images = image if isinstance(image, list) else [image]
+        if not images or not all(isinstance(i, (Image.Image, np.ndarray)) for i in images):
+            raise ValueError("Input is in incorrect format. Currently, we only support PIL.Image.Image, np.ndarray, torch.Tensor")
+        pil = []
+        for i in images:
+            if isinstance(i, np.ndarray):
+                if i.dtype != np.uint8 or i.ndim not in (2, 3):
+                    raise ValueError(f"a numpy mask is uint8 [H][W] or [H][W][C], not {i.dtype} {i.shape}")
+                i = Image.fromarray(i[..., 0] if i.ndim == 3 and i.shape[-1] == 1 else i)
+            pil.append(i)
+        if self.config.do_resize:
+            height, width = self.get_default_height_width(pil[0], height, width)
+            pil = [self.resize(i, height, width) for i in pil]
+        if self.config.do_convert_grayscale:
+            pil = [i.convert("L") for i in pil]
+        arr = np.stack([np.array(i).astype(np.float32) / 255.0 for i in pil], axis=0)
+        x = torch.from_numpy(arr[..., None].transpose(0, 3, 1, 2) if arr.ndim == 3 else arr.transpose(0, 3, 1, 2))
+        if self.config.do_binarize:
+            x[x < 0.5] = 0
+            x[x >= 0.5] = 1
+        return x
+
+    def _preprocess_device(self, mask, height, width):
+        from . import resample
+        if mask.device.type != "cuda":
+            raise resample._no_cpu("IPAdapterMaskProcessor.preprocess")
+        if mask.dtype != torch.uint8 or mask.ndim not in (2, 3):
+            raise ValueError(f"a device mask is uint8 [H][W] or [n][H][W], not {mask.dtype} {tuple(mask.shape)}")
+        m = mask[None] if mask.ndim == 2 else mask
+        H, W = (m.shape[1] if height is None else height), (m.shape[2] if width is None else width)
+        f = self.config.vae_scale_factor
+        H, W = H - H % f, W - W % f
+        if self.config.do_resize and (H, W) != tuple(m.shape[1:]):
+            # a grayscale image resizes as each band of an RGB image does: the mask three times over, one band back
+            m = resample.resize_images(m[..., None].expand(-1, -1, -1, 3), (H, W), self.config.resample)[..., 0]
+        if self.config.do_binarize:
+            m = (m >= 128).to(torch.uint8)                        # v / 255 >= 0.5
+        else:
+            m = m.to(torch.float32) / 255.0
+        return m[:, None].contiguous()
+
+
 class Dinov2ImageProcessor:
     """`dinov2_processor.preprocess(images=..., do_resize=True, return_tensors="pt", do_convert_rgb=True)` (pipe:696) for the
     facebook/dinov2 preprocessor_config.json values; returns an object with `.pixel_values` that is also a mapping (`**inputs`)."""

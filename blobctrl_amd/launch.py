@@ -661,6 +661,24 @@ class Recorder:
                  shape=("attention_ip", B, heads, d, rows_per_batch, T), bytes_=2 * (3 * B * rows_per_batch * Cc + 2 * B * T * Cc))
         return out
 
+    def attention_ip_masked(self, Q, K, V, out, B, rows_per_batch, heads, d, images, tokens_per_image, ldq, ldkv, ldo, scale, w, mask, ldm, q_off=0):
+        """bc_attention_ip_masked (include/blobctrl_ip_mask.h): the image cross-attention of one IP-Adapter with `ip_adapter_masks` - one
+        softmax per image, each weighted row by row with `mask` (fp16 [images][ldm], a buffer the plan owns and every edit refills) -
+        accumulated onto `out` in place.  Stands where attention_ip stands in a plan made without masks."""
+        Cc, T = heads * d, images * tokens_per_image
+        self.keep.append((Q, K, V, out, w, mask))
+        for t in (Q, K, V, out, w, mask):
+            self.register(t)
+        # the library picks the kernel (bc_attention_ip_masked_path); the same op is recorded either way, the listing names what will run
+        tiles = _lib.load().bc_attention_ip_masked_path(d, images, tokens_per_image, rows_per_batch, heads) == _lib.ATTENTION_IP_TILES
+        variant = f"attention_ip_masked_tiles_kernel<{d},{T // 16}>" if tiles else f"attention_ip_masked_kernel<{d}>"
+        self._op("bc_attention_ip_masked", (Q.data_ptr() + q_off * 2, K, V, out, B, rows_per_batch, heads, d, images, tokens_per_image, ldq, ldkv,
+                                            ldo, scale, w, mask, ldm),
+                 "attention_ip_masked", flops=4 * B * rows_per_batch * T * Cc, variant=variant,
+                 shape=("attention_ip_masked", B, heads, d, rows_per_batch, images, tokens_per_image),
+                 bytes_=2 * (3 * B * rows_per_batch * Cc + 2 * B * T * Cc + images * rows_per_batch))
+        return out
+
     # ------------------------------------------------------------------ row-chain (fused transformer-block glue, csrc/rowchain.hip)
     def rowchain(self, kind, Cc, M, rows_per_batch, x, wstream, vec, out0, out1=None, out2=None, ldvt=0, affine=None, gn_in=None, res=None, res2=None,
                  r2=None, r2_xmin=0, r2_bmod=1, out_w=0, gn_tot=None, ln_eps=1e-5, alpha=1.0, alpha_dev=None, alpha_idx=None,

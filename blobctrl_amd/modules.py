@@ -390,11 +390,14 @@ class UNet2DConditionModel(_TrunkModule):
                 up.append((rev[i],) + sizes[nb - 2 - i])
         return down, mid, up
 
-    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False, ip=()):
+    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False, ip=(), ip_masked=False):
         """`cond`: the plan takes a `timestep_cond` (fp16 [B][pad8(time_cond_proj_dim)]) and adds cond_proj of it to the sinusoid; a
         plan of its own, so that calls without one keep the launches they always recorded.  `freeu`: likewise a plan of its own, with
-        bc_freeu in up_blocks.0 / up_blocks.1 reading (s1, s2, b1, b2) from the plan buffer P.freeu."""
-        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ()) + (("freeu",) if freeu else ()) + ((("ip",) + tuple(ip),) if ip else ())
+        bc_freeu in up_blocks.0 / up_blocks.1 reading (s1, s2, b1, b2) from the plan buffer P.freeu.  `ip_masked`: the call brings
+        `ip_adapter_masks` - a plan of its own again, with bc_attention_ip_masked behind every attn2 and one fp16 mask buffer per adapter
+        and attention level (P.ip_adapters[i].mask_bufs); the key says "masked", never what the masks hold."""
+        key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ()) + (("freeu",) if freeu else ()) + ((("ip",) + tuple(ip),) if ip else ()) + \
+            ((("ip", "masked"),) if ip and ip_masked else ())
         if key not in self._plans:
             rec = Recorder(self.device)
             P = type("Plan", (), {})()
@@ -419,8 +422,10 @@ class UNet2DConditionModel(_TrunkModule):
                 # width are fixed by what is loaded, and load / unload drop every plan that carries an `ip` entry (_drop_ip_plans).  Scales
                 # are no part of the key: the launches read them from the adapters' device tables
                 ads = self.__dict__["ip_adapters"]
-                made = [IpAdapter.for_plan(rec, ad, B, entry) for entry, ad in zip(ip, ads)]      # (a Plus adapter's entry: (images, S))
+                made = [IpAdapter.for_plan(rec, ad, B, entry, masked=bool(ip_masked), mask_name=f"ip_mask{i}")
+                        for i, (entry, ad) in enumerate(zip(ip, ads))]                            # (a Plus adapter's entry: (images, S))
                 plan.ip_adapters, P.ip_embeds = [m[0] for m in made], [m[1] for m in made]
+                P.ip_adapters = plan.ip_adapters
             plan.record_context(P.ctx, T)
             if cond:
                 P.cond = rec.zeros(B, pad8(self.trunk_config.time_cond_proj_dim))
@@ -457,9 +462,14 @@ class UNet2DConditionModel(_TrunkModule):
                 raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj (config.time_cond_proj_dim is None)")
             if tuple(timestep_cond.shape) != (B, dim):
                 raise ValueError(f"timestep_cond must have shape {(B, dim)} (batch, time_cond_proj_dim), got {tuple(timestep_cond.shape)}")
+        # "ip_adapter_masks" leaves the dict before the LoRA scale is read; without a loaded adapter nothing reads it (the reference's
+        # quiet_attn_parameters, attention_processor.py:480)
+        from . import ip_masks
+        cross_attention_kwargs, masks = ip_masks.split_kwargs(cross_attention_kwargs)
         self.set_lora_scale(lora_scale_of(cross_attention_kwargs))          # (a change of scale re-packs: the plans below are then new ones)
         # the image embeddings reach the body beside the dispatcher's fixed schema, as module state of this one call
-        self.__dict__["_image_embeds"] = self._check_image_embeds(added_cond_kwargs, B)
+        self.__dict__["_image_embeds"] = embeds = self._check_image_embeds(added_cond_kwargs, B)
+        self.__dict__["_ip_masks"] = ip_masks.check_masks(masks, [int(e.shape[1]) for e in embeds]) if embeds and masks is not None else None
         # through the dispatcher (torch.ops.blobctrl.unet_forward, ops.py); `timestep_cond` is the op's optional trailing argument
         from . import ops
         extra = () if timestep_cond is None else (timestep_cond,)
@@ -468,7 +478,7 @@ class UNet2DConditionModel(_TrunkModule):
                                                   list(down_block_add_samples) if is_blobnet else [], mid_block_add_sample if is_blobnet else None,
                                                   list(up_block_add_samples) if is_blobnet else [], ops.register(self), *extra)
         finally:
-            self.__dict__["_image_embeds"] = None                       # (state of this one call: a later direct op call sees none)
+            self.__dict__["_image_embeds"] = self.__dict__["_ip_masks"] = None      # (state of this one call: a later direct op call sees none)
         if is_blobnet:                                   # the reference consumes the two lists with pop(0) (:1217, 1230, 1313)
             del down_block_add_samples[:]
             del up_block_add_samples[:]
@@ -482,11 +492,15 @@ class UNet2DConditionModel(_TrunkModule):
         is_blobnet = mid_block_add_sample is not None
         T, Dc = encoder_hidden_states.shape[1:]
         freeu = self.__dict__.get("freeu")
-        embeds = self.__dict__.get("_image_embeds")
+        embeds, masks = self.__dict__.get("_image_embeds"), self.__dict__.get("_ip_masks")
         P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None, freeu=freeu_enabled(freeu),
-                       ip=tuple(int(e.shape[1]) if e.ndim == 3 else (int(e.shape[1]), int(e.shape[2])) for e in embeds) if embeds else ())
+                       ip=tuple(int(e.shape[1]) if e.ndim == 3 else (int(e.shape[1]), int(e.shape[2])) for e in embeds) if embeds else (),
+                       ip_masked=bool(embeds) and masks is not None)
         for buf, e in zip(getattr(P, "ip_embeds", ()), embeds or ()):
             buf.copy_(e.to(self.device, torch.float16).reshape(buf.shape))
+        if embeds and masks is not None:
+            from . import ip_masks
+            ip_masks.fill_plan_masks(P.ip_adapters, masks, self.device)
         if freeu_enabled(freeu):
             P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=torch.float32))
         if timestep_cond is not None:

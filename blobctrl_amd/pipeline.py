@@ -27,6 +27,7 @@ from .engine import IpAdapter, TrunkConfig, TrunkPlan, freeu_enabled
 from .launch import Recorder
 from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, stack_request_tables, table_class
 from .weights import PackedTrunk, lora_scale_of, pad8
+from . import ip_masks
 
 
 def get_guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -164,7 +165,7 @@ class BlobCtrlEngine:
 
     # ------------------------------------------------------------------------------------------------ planning
     def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-              freeu=False, requests=False, ip=()):
+              freeu=False, requests=False, ip=(), ip_masked=False):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
@@ -190,6 +191,10 @@ class BlobCtrlEngine:
         dim], per-edit inputs like `ctx`); its prologue projects them to image tokens and to K_ip / V_ip per attn2 block, and every UNet
         forward runs one bc_attention_ip per adapter behind each attn2 (16 per adapter).  The key holds the adapter configuration - count,
         tokens each, embedding width - and never the scales, which the launches read from the adapters' device tables.  In-process only.
+        ip_masked: the call brings `ip_adapter_masks` - every attn2 runs bc_attention_ip_masked in the place of bc_attention_ip (one softmax
+        per image, weighted by that image's mask), and the plan owns one named fp16 buffer `ip_mask<i>_<rows>` [images][rows] per adapter and
+        attention level, refilled per edit (ip_masks.fill_plan_masks).  A plan of its own; the key gains "masked" and the images per
+        adapter, never the masks: another mask of the same shape replays the same plan and the same whole-edit graph.
         `denoise` and `compile_plan` take every one of these switches from the EditSetup of their call (`_setup`) and fill the tables
         with `_write_tables`; a call without lists never asks for `requests`."""
         if requests and not per_request:
@@ -198,7 +203,8 @@ class BlobCtrlEngine:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
         key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
             (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ()) + (("requests",) if requests else ()) + \
-            (((("ip", len(ip)) + tuple(self._ip_key(entry, ad) for entry, ad in zip(ip, self.ip_adapters))),) if ip else ())
+            (((("ip", len(ip)) + tuple(self._ip_key(entry, ad) for entry, ad in zip(ip, self.ip_adapters))),) if ip else ()) + \
+            (((("ip", "masked") + tuple(e if isinstance(e, int) else e[0] for e in ip)),) if ip and ip_masked else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -269,8 +275,10 @@ class BlobCtrlEngine:
         P.prologue = rec.begin("prologue")
         unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_a.freeu_params = P.freeu
-        made = [IpAdapter.for_plan(rec, ad, Bu, entry, name=f"ip_embeds{i}") for i, (entry, ad) in enumerate(zip(ip, self.ip_adapters))]
+        made = [IpAdapter.for_plan(rec, ad, Bu, entry, name=f"ip_embeds{i}", masked=bool(ip_masked), mask_name=f"ip_mask{i}")
+                for i, (entry, ad) in enumerate(zip(ip, self.ip_adapters))]
         unet_a.ip_adapters, P.ip_embeds = [m[0] for m in made], [m[1] for m in made]
+        P.ip_adapters, P.ip_masked = unet_a.ip_adapters, bool(ip and ip_masked)     # (their mask_bufs fill up as the UNet forwards are recorded)
         unet_a.record_context(P.ctx, T)
         blob = TrunkPlan(rec, self.blob_w, self.blob_cfg, B, H, W)
         if P.collapse:
@@ -306,7 +314,7 @@ class BlobCtrlEngine:
             #  unfused MID + attention launches)
             hp.ctx_kvs = {bp: kvs.view(2 * B, -1)[b0:b0 + B].reshape(-1) for bp, kvs in getattr(unet_a, "ctx_kvs", {}).items()}
             hp.ctx_folded = {bp: tuple(t[b0:b0 + B] for t in f) for bp, f in getattr(unet_a, "ctx_folded", {}).items()}
-            hp.ip_kv = {bp: [(K[b0:b0 + B], V[b0:b0 + B], T_, w_) for K, V, T_, w_ in kv] for bp, kv in unet_a.ip_kv.items()}
+            hp.ip_kv = {bp: [(K[b0:b0 + B], V[b0:b0 + B], T_, w_, *ad_) for K, V, T_, w_, *ad_ in kv] for bp, kv in unet_a.ip_kv.items()}
             hp.tproj, hp.tproj_table = half_time.tproj, half_time.tproj_table
             return hp
 
@@ -808,7 +816,7 @@ class BlobCtrlEngine:
                  do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
                  variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None,
                  single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None, freeu=None,
-                 ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None):
+                 ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None, ip_adapter_masks: Optional[List[torch.Tensor]] = None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -839,6 +847,10 @@ class BlobCtrlEngine:
         `ip_adapter_image_embeds`: with IP-Adapters loaded (`set_ip_adapters`), one tensor [UNet batch][images][embed_dim] per adapter,
         as the reference's prepare_ip_adapter_image_embeds returns them: the negative and the positive halves with classifier-free
         guidance, one row per UNet image in a request batch too.  Per-edit data of the plan, like `prompt_embeds`.
+        `ip_adapter_masks`: one tensor [1][images][H][W] per adapter, float or uint8, on the device or the host (the reference's
+        cross_attention_kwargs["ip_adapter_masks"], checked as its processor checks them): the image prompt of image i acts where its mask
+        is set.  Every UNet image shares them, in a request batch too, as the reference repeats one mask over the batch.  Per-edit data of
+        the masked plan.  Ignored without a loaded adapter, as the reference's adapter-less processors ignore the key.
         A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps (a list of
         lists): the requests of a request batch run their own schedules, on the `requests` plan form.  Both kinds of call are one
         set-up (`_setup` -> EditSetup; a call without lists is "one table, shared by every image"), one plan, one run; `self.timesteps`
@@ -884,8 +896,10 @@ class BlobCtrlEngine:
         self._check_variance_noise(S, variance_noise, (B, 4, h, w), generator)
         Bu = B if single else 2 * B
         ip, ip_embeds = self._ip_layout(ip_adapter_image_embeds, Bu, B, duplicated=not single and prompt_embeds.shape[0] == 2 * B and guidance_off)
+        if ip and ip_adapter_masks is not None:
+            ip_adapter_masks = ip_masks.check_masks(ip_adapter_masks, [e if isinstance(e, int) else e[0] for e in ip])
         P = self._plan(B, h, w, T, Dc, S.n, per_request, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
-                       requests=S.requests, ip=ip)
+                       requests=S.requests, ip=ip, ip_masked=bool(ip) and ip_adapter_masks is not None)
         dev = self.device
         self.timesteps = [t.timesteps for t in S.tables] if S.requests else S.tables[0].timesteps
         if latents is None:                                                          # pipe:438-453
@@ -902,6 +916,8 @@ class BlobCtrlEngine:
             self._write_tables(P, S, freeu)
             for buf, e in zip(P.ip_embeds, ip_embeds):
                 buf.copy_(e.to(dev, torch.float16).reshape(buf.shape))
+            if P.ip_masked:
+                ip_masks.fill_plan_masks(P.ip_adapters, ip_adapter_masks, dev)
             if S.stochastic:
                 P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
             P.step_idx.zero_()
@@ -1067,8 +1083,8 @@ class BlobCtrlEngine:
 
     # convenience for bench / tests ------------------------------------------------------------------
     def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-                 freeu=False, requests=False, ip=()):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip)
+                 freeu=False, requests=False, ip=(), ip_masked=False):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip, ip_masked)
 
 
 def _is_device_image(image):
@@ -1692,6 +1708,12 @@ class StableDiffusionBlobNetPipeline:
         # pipe:934-945, 1084: {"scale": s} scales every active adapter for this call, in the text encoder when it encodes the prompt and in
         # the UNet (BlobNet has no LoRA and never sees it).  The UNet re-packs when the scale differs from the packed one, and `engine`
         # below is re-pointed exactly as after `set_adapters`.
+        # "ip_adapter_masks" (pipe:1084 -> IPAdapterAttnProcessor2_0) leaves the dict first: one tensor [1][images][H][W] per loaded adapter,
+        # checked as the processor checks them once the image embeddings are known (`engine.denoise`).  Without a loaded adapter nothing
+        # reads the key - in the reference it is one of `quiet_attn_parameters` - so it is dropped silently.
+        cross_attention_kwargs, ip_adapter_masks = ip_masks.split_kwargs(cross_attention_kwargs)
+        if not (self.unet.__dict__.get("ip_adapters") or []):
+            ip_adapter_masks = None
         lora_scale = lora_scale_of(cross_attention_kwargs)
         # 0.1 align the control-guidance format (pipe:884-893)
         if not isinstance(blobnet_control_guidance_start, list) and isinstance(blobnet_control_guidance_end, list):
@@ -1765,7 +1787,8 @@ class StableDiffusionBlobNetPipeline:
                                     blobnet_control_guidance_end=blobnet_control_guidance_end[0], output_type="latent",
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
                                     generator=generator, timesteps=timesteps, timestep_cond=timestep_cond,
-                                    freeu=getattr(self.unet, "freeu", None), ip_adapter_image_embeds=ip_embeds)
+                                    freeu=getattr(self.unet, "freeu", None), ip_adapter_image_embeds=ip_embeds,
+                                    ip_adapter_masks=ip_adapter_masks)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

@@ -124,7 +124,8 @@ class LoraAdapters:
 
 def lora_scale_of(cross_attention_kwargs) -> float:
     """`cross_attention_kwargs={"scale": s}` -> s (unet_2d_condition.py:1183-1191 pops it and scales every LoRA layer); None / {} -> 1.0.
-    No other key has a meaning here: the attention processors are the HIP kernels and take no arguments."""
+    The one other key with a meaning, "ip_adapter_masks", never arrives here: the pipeline's `__call__` and the UNet's `forward` take it
+    out first (ip_masks.split_kwargs).  Every key that does arrive beside "scale" is refused by name."""
     if not cross_attention_kwargs:
         return 1.0
     other = sorted(k for k in cross_attention_kwargs if k != "scale")

@@ -17,6 +17,10 @@ CLIP vision tower in the folder `image_encoder` beside it; the image goes throug
 (blobctrl_amd.clip_vision) and - for a Plus adapter - the Resampler in the plan's prologue, and every attn2 runs bc_attention_ip on its
 tokens.  --ip-adapter synth uses a seeded tiny tower (320 wide, 4 layers) and a seeded Plus adapter of 16 queries; without --ip-image the
 image is seeded noise.
+With --ip-adapter ... --ip-mask blob|FILE the image prompt is confined to a region (cross_attention_kwargs["ip_adapter_masks"] of the
+reference): `blob` is the edit's own target ellipse, filled on the device (edit_inputs.ellipse_masks); FILE is a mask image of the frame.
+Either goes through IPAdapterMaskProcessor.preprocess and ip_masks.canvas_masks (the UNet's canvas is the background frame beside the
+edited one), and every attn2 runs bc_attention_ip_masked on the mask downsampled to its level.
 With --device-inputs --zoom PAD the edit is a zoomed ("only masked") one (blobctrl_amd.overlay): the box around the start and
 target ellipses, padded by PAD and grown to the frame's ratio, is blown up to the model's resolution (`zoom_edit`), the model edits that
 frame, and the result is pasted back over the original through the ellipses' mask blurred with --blur F (`blur`, `apply_overlay`) - all
@@ -106,9 +110,13 @@ def main():
     ap.add_argument("--blur", type=float, default=4, metavar="F", help="blur factor of the paste-back mask (with --zoom; the reference's default 4)")
     ap.add_argument("--ip-adapter", default=None, help="an IP-Adapter .safetensors file with `image_encoder/` beside it, or 'synth'")
     ap.add_argument("--ip-image", default=None, help="the image prompt (any file PIL opens); seeded noise without it")
+    ap.add_argument("--ip-mask", default=None, metavar="blob|FILE",
+                    help="confine the image prompt (with --ip-adapter): 'blob' = the edit's target ellipse, or a mask image of the frame")
     args = ap.parse_args()
     if args.ip_image and not args.ip_adapter:
         ap.error("--ip-image needs --ip-adapter")
+    if args.ip_mask and not args.ip_adapter:
+        ap.error("--ip-mask needs --ip-adapter")
     if args.device_inputs and (not args.sam or args.sam_auto is not None):
         ap.error("--device-inputs needs --sam and a click prompt")
     if args.zoom is not None and not args.device_inputs:
@@ -232,6 +240,17 @@ def main():
     ids = torch.from_numpy(rng.integers(0, 49408, size=(2, 1, 77)).astype(np.int64))
     prompt = pipe.encode_prompt(ids[1], ids[0])
     t4 = sync()
+    if args.ip_mask:
+        from blobctrl_amd import edit_inputs as ei, ip_masks
+        from blobctrl_amd.image_processor import IPAdapterMaskProcessor
+        if args.ip_mask == "blob":                            # the blob says where, the image prompt says what: uint8 255 / 0, on the device
+            frame_mask = ei.ellipse_masks([(tuple(ellipse[0]), tuple(ellipse[1]), ellipse[2])], R, R)[0]
+        else:
+            from PIL import Image
+            frame_mask = Image.open(args.ip_mask)
+        m = IPAdapterMaskProcessor().preprocess(frame_mask, height=R, width=R)
+        ip_kwargs["ip_adapter_masks"] = [ip_masks.canvas_masks(m.reshape(1, m.shape[0], m.shape[2], m.shape[3]))]
+        print(f"--ip-mask {args.ip_mask}: {100 * float(m.float().mean()):.1f} % of the frame takes the image prompt")
     otype = "pt" if args.zoom is not None else "np"           # a zoomed edit's result stays on the device for the paste-back
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,

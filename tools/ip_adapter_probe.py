@@ -13,6 +13,12 @@ With --paths-markdown profiles/ip_adapter_plus.md [--only-paths] [--rounds 7]: t
 IP-Adapter Plus with one to four images - alternating in one process, the dispatch rule read off that table, and the step time without an
 adapter, with a base adapter and with a Plus adapter (ip-adapter-plus_sd15's shapes: 257 x 1280 hidden states, 16 queries).
 
+With --masks-markdown profiles/ip_adapter_masks.md [--only-masks]: bc_attention_ip_masked (include/blobctrl_ip_mask.h) beside
+bc_attention_ip at the four levels, UNet batch 2, for (images, tokens per image) = (1, 4), (2, 4), (1, 16), (4, 16), with a full mask and
+with a blob-sized one (an ellipse over about a tenth of the canvas), every kernel by name and alternating in one process; the dispatch
+rule of the masked kernels read off that table; the step time without an adapter, with a base adapter, and with the base adapter masked
+by the blob; and what the bc_ip_mask_downsample launches of one edit cost.
+
 Bytes are the algorithmic ones of the launch (Q read once, O read and written once, K and V once): 2 * (3 M C + 2 B T C).  Every launch
 is replayed `reps` times in one segment behind a warm-up replay; the figure is the median of the per-launch event times.  Needs a GPU."""
 import argparse
@@ -145,6 +151,203 @@ def paths_table(dev, reps, rounds):
     return lines, rule
 
 
+MASK_CASES = ((1, 4), (2, 4), (1, 16), (4, 16))      # (images, tokens per image)
+
+
+def blob_mask(h, w, images, dev):
+    """fp16 [images][h * w]: an ellipse over about a tenth of the h x w canvas, bicubic-downsampled from a 0 / 1 mask at 8 x the size (so
+    its rim holds the small non-zero values a real mask has); every image gets the same blob."""
+    from blobctrl_amd import ip_masks
+    y, x = torch.meshgrid(torch.arange(8 * h, device=dev), torch.arange(8 * w, device=dev), indexing="ij")
+    inside = (((y + 0.5) / (8 * h) - 0.5) / 0.25) ** 2 + (((x + 0.5) / (8 * w) - 0.7) / 0.127) ** 2 <= 1.0      # pi * .25 * .127 = 0.0997
+    m = inside.to(torch.float32)[None].expand(images, -1, -1).contiguous()
+    return ip_masks.downsample(m, h * w), float(inside.float().mean())
+
+
+def replay_in_turn(launchers, a0, reps, rounds):
+    """{name: launcher(out)} -> {name: (median us per launch, max - min us over the rounds)}: `reps` launches of a launcher captured into
+    one graph, the graphs replayed in turn, `rounds` times each behind a warm-up replay, in one process."""
+    graphs, bufs = {}, {}
+    side = torch.cuda.Stream()
+    for n, fn in launchers.items():
+        bufs[n] = a0.clone()
+        graphs[n] = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            fn(bufs[n])                                                # (warm: the code object is loaded before the capture)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graphs[n], stream=side):
+                for _ in range(reps):
+                    fn(bufs[n])
+    times = {n: [] for n in launchers}
+    for r in range(rounds + 1):
+        for n in launchers:
+            bufs[n].copy_(a0)                                          # (in place: keep the values where they started)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graphs[n].replay()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:
+                times[n].append(e0.elapsed_time(e1) * 1e3 / reps)
+    return {n: (statistics.median(t), max(t) - min(t)) for n, t in times.items()}
+
+
+def measure_masked(dev, Cc, h, wd, B, images, Tp, reps, rounds):
+    """One shape: the unmasked launch (the dispatcher's kernel) and every masked kernel by name under a full and under a blob mask."""
+    from blobctrl_amd import _lib
+    lib = _lib.load()
+    HW, T = h * wd, images * Tp
+    d, M = Cc // HEADS, B * HW
+    q, a0 = torch.randn(M, Cc, device=dev).half(), torch.randn(M, Cc, device=dev).half()
+    k, v = torch.randn(B, T, Cc, device=dev).half(), torch.randn(B, T, Cc, device=dev).half()
+    w = torch.full((1,), 0.6, device=dev)
+    blob, share = blob_mask(h, wd, images, dev)
+    masks = {"full": torch.ones(images, HW, device=dev).half(), "blob": blob}
+    stream = lambda: torch.cuda.current_stream().cuda_stream
+
+    def plain(out):
+        _lib.check(lib.bc_attention_ip(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, HW, HEADS, d, T, Cc, Cc, Cc, d ** -0.5,
+                                       w.data_ptr(), stream()), "bc_attention_ip")
+
+    def masked(path, m):
+        def fn(out):
+            _lib.check(lib.bc_attention_ip_masked_with(path, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, HW, HEADS, d, images, Tp,
+                                                       Cc, Cc, Cc, d ** -0.5, w.data_ptr(), m.data_ptr(), HW, stream()), f"masked path {path}")
+        return fn
+    launchers = {"unmasked": plain}
+    for path in ((0, 1) if Tp % 16 == 0 else (0,)):
+        for name, m in masks.items():
+            launchers[(path, name)] = masked(path, m)
+    rows = float((blob != 0).any(0).float().mean())
+    return replay_in_turn(launchers, a0, reps, rounds), share, rows
+
+
+def masks_table(dev, reps, rounds):
+    B = 2
+    lines = ["# bc_attention_ip_masked on an MI355X: ip_adapter_masks beside the unmasked launch", "",
+             f"HIP-event time per launch: {reps} launches of one kernel captured into one graph, the graphs of a shape replayed in turn, {rounds}",
+             "replays each behind a warm-up, in one process.  us = median over the replays, +- = max - min over them (the run-to-run spread).",
+             f"UNet batch {B}, {HEADS} heads.  `unmasked` is bc_attention_ip at images x Tp keys (the kernel its dispatcher picks); the masked kernels",
+             "go through bc_attention_ip_masked_with by name: path 0 the scalar kernel, path 1 the MFMA tiles (Tp a multiple of 16).  `full`: a mask",
+             "of ones; `blob`: an ellipse over a tenth of the canvas, bicubic-downsampled to the level (rows with a non-zero mask: last column).", "",
+             "| C | rows / image | images x Tp | unmasked us | +- | scalar full us | +- | scalar blob us | +- | tiles full us | +- | tiles blob us | +- | "
+             "blob rows |", "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    wins, blob_cheaper = {}, []
+    for Cc, HW in LEVELS:
+        h = int(round((HW // 2) ** 0.5))
+        for images, Tp in MASK_CASES:
+            res, share, rows = measure_masked(dev, Cc, h, 2 * h, B, images, Tp, reps, rounds)
+            cell = lambda key: f"{res[key][0]:.1f} | {res[key][1]:.1f}" if key in res else "- | -"
+            lines.append(f"| {Cc} | {HW} | {images} x {Tp} | {cell('unmasked')} | {cell((0, 'full'))} | {cell((0, 'blob'))} | {cell((1, 'full'))} | "
+                         f"{cell((1, 'blob'))} | {rows:.3f} |")
+            print(lines[-1], flush=True)
+            if (1, "full") in res:
+                wins.setdefault((Cc, images * Tp), []).append(all(
+                    res[(0, m)][0] - res[(1, m)][0] > max(res[(0, m)][1], res[(1, m)][1]) for m in ("full", "blob")))
+            best = min(res[(p, "blob")][0] for p in (0, 1) if (p, "blob") in res)
+            blob_cheaper.append((Cc, HW, images, Tp, best, res["unmasked"][0]))
+    lines += ["", "## Dispatch rule of the masked kernels", "",
+              "A (channel width, images x Tp) class with Tp a multiple of 16 goes to the tiles where they beat the masked scalar kernel on every",
+              "measured row of the class, under the full and under the blob mask, by more than the spread.  Measured classes:", ""]
+    for (Cc, T), v in sorted(wins.items()):
+        lines.append(f"- C = {Cc}, {T} keys: {'tiles' if all(v) else 'scalar'} ({sum(v)} of {len(v)} rows won by the tiles)")
+    lines += ["", "## A blob-sized mask against the unmasked launch", "",
+              "| C | rows / image | images x Tp | best masked kernel, blob us | unmasked us | blob / unmasked |", "|---|---|---|---|---|---|"]
+    for Cc, HW, images, Tp, best, un in blob_cheaper:
+        lines.append(f"| {Cc} | {HW} | {images} x {Tp} | {best:.1f} | {un:.1f} | {best / un:.2f} |")
+    return lines
+
+
+def downsample_lines(dev, reps, rounds):
+    """What the four bc_ip_mask_downsample launches of one edit and adapter cost: a 512 x 1024 mask (the canvas of a 512^2 edit) to the
+    four levels, one image, from fp32 and from uint8."""
+    from blobctrl_amd import ip_masks
+    lines = ["", "## The downsampling launches of one edit (once per edit and adapter, outside the captured graph)", "",
+             "| mask | dtype | four levels, us (median) | +- |", "|---|---|---|---|"]
+    for dtype in (torch.float32, torch.uint8):
+        m = (torch.rand(1, 512, 1024, device=dev) > 0.5).to(dtype)
+        outs = [torch.empty(1, HW, device=dev).half() for _, HW in LEVELS]
+
+        def run():
+            for (_, HW), o in zip(LEVELS, outs):
+                ip_masks.downsample(m, HW, out=o)
+        run()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(rounds + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3 / reps)
+        ts = ts[1:]
+        lines.append(f"| 512 x 1024, 1 image | {str(dtype).replace('torch.', '')} | {statistics.median(ts):.1f} | {max(ts) - min(ts):.1f} |")
+        print(lines[-1], flush=True)
+    lines += ["", "(host-launched, not captured: the figure includes the four launches' host time.)"]
+    return lines
+
+
+def masked_step_setup(dev):
+    """The flagship edit's engine with one base adapter at hand: (engine, adapter, inputs, score, {name: extra keywords of the call})."""
+    import bench
+    from blobctrl_amd import synth
+    from blobctrl_amd.pipeline import BlobCtrlEngine
+    from blobctrl_amd.splat import splat_features
+    from blobctrl_amd.weights import PackedTrunk, convert_ip_adapter, ip_adapter_on_device, ip_attn2_prefixes
+    ucfg, bcfg = bench.full_configs()
+    usd, bsd = bench.synth_weights()
+    prefixes = ip_attn2_prefixes(usd.keys())
+    shapes = {f"{1 + 2 * j}.to_{n}_ip.weight": (usd[bp + "attn2.to_k.weight"].shape[0], 768) for j, bp in enumerate(prefixes) for n in "kv"}
+    sd = {"image_proj": synth.synth_state_dict({"proj.weight": (4 * 768, 1024), "proj.bias": (4 * 768,), "norm.weight": (768,), "norm.bias": (768,)}, 51),
+          "ip_adapter": synth.synth_state_dict(shapes, 52)}
+    adapter = ip_adapter_on_device(convert_ip_adapter(sd, prefixes, 768), dev)
+    eng = BlobCtrlEngine(PackedTrunk(usd, dev, ucfg.block_out_channels), PackedTrunk(bsd, dev, bcfg.block_out_channels), ucfg, bcfg,
+                         device=str(dev), scheduler="ddim")
+    del usd, bsd
+    h = w = 64
+    inp = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in bench.synth_inputs(h, w).items()}
+    score = splat_features(**inp["blob"], score_size=(h, w), return_d_score=True, device=str(dev))
+    embeds = [torch.randn(2, 1, 1024, device=dev)]
+    y, x = torch.meshgrid(torch.arange(512, device=dev), torch.arange(1024, device=dev), indexing="ij")
+    blob = ((((y + 0.5) / 512 - 0.5) / 0.25) ** 2 + (((x + 0.5) / 1024 - 0.7) / 0.127) ** 2 <= 1.0).to(torch.uint8)[None, None]
+    extras = {"none": {}, "base": dict(ip_adapter_image_embeds=embeds), "masked": dict(ip_adapter_image_embeds=embeds, ip_adapter_masks=[blob])}
+    return eng, adapter, inp, score, extras
+
+
+def masked_step_lines(dev, steps, edits):
+    """ms per denoise step of the flagship edit without an adapter, with one base adapter, and with the base adapter masked by a blob."""
+    import time
+    eng, adapter, inp, score, extras = masked_step_setup(dev)
+
+    def edit(name):
+        eng.ip_adapters = [adapter] if name != "none" else []          # (the three plans have keys of their own and stay cached)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng(inp["prompt"], inp["fg"], inp["bg"], score, inp["dino"], num_inference_steps=steps, guidance_scale=7.5, latents=inp["latents"],
+            **extras[name])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / steps
+    names = ("none", "base", "masked")
+    for n in names + names:                                            # record, capture, warm
+        edit(n)
+    times = {n: [] for n in names}
+    for _ in range(edits):
+        for n in names:
+            times[n].append(edit(n))
+    med = statistics.median
+    row = lambda label, n: f"| {label} | {med(times[n]):.3f} | {' '.join(f'{v:.3f}' for v in times[n])} |"
+    cost = lambda n, ref: f"{med(times[n]) - med(times[ref]):+.3f} ms per step ({100 * (med(times[n]) / med(times[ref]) - 1):+.1f} %)"
+    return ["", f"## Step time, 512^2 edit, batch 1, DDIM, {steps} steps, whole-edit graph, alternating edits in one process", "",
+            "| | ms per step (median) | every edit |", "|---|---|---|",
+            row("no adapter", "none"), row("one base adapter, one image (T = 4), no mask", "base"),
+            row("the same adapter, masked by a blob (a tenth of the 512 x 1024 canvas, uint8 on the device)", "masked"), "",
+            f"Against no adapter the unmasked adapter costs {cost('base', 'none')}, the masked one {cost('masked', 'none')}; the mask changes the",
+            f"adapter's step by {cost('masked', 'base')}.  The figure is the whole edit over its steps: the four downsampling launches of the",
+            "masked edit, outside the graph, are inside it."]
+
+
 def plus_adapter_shapes(embed=1280, hidden=768, ctx=768, queries=16, depth=4):
     """Parameter shapes of ip-adapter-plus_sd15's Resampler (ViT-H hidden states, 12 heads of 64) in the original key spelling."""
     shapes = {"latents": (1, queries, hidden), "proj_in.weight": (hidden, embed), "proj_in.bias": (hidden,), "proj_out.weight": (ctx, hidden),
@@ -234,10 +437,23 @@ def main():
     ap.add_argument("--paths-markdown", help="time both kernels behind bc_attention_ip at T = 16, 32, 48, 64 and write the table there")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--only-paths", action="store_true")
+    ap.add_argument("--masks-markdown", help="time bc_attention_ip_masked beside bc_attention_ip, full and blob masks, and write the table there")
+    ap.add_argument("--only-masks", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ip_adapter_probe needs an MI355X: a timing taken elsewhere says nothing")
     dev = torch.device("cuda:0")
+    if args.masks_markdown:                                            # profiles/ip_adapter_masks.md: the masked kernels, the rule, step and set-up cost
+        mlines = masks_table(dev, args.reps, args.rounds) + downsample_lines(dev, args.reps, args.rounds)
+        if not args.no_step:
+            mlines += masked_step_lines(dev, args.steps, args.edits)
+            for ln in mlines[-10:]:
+                print(ln, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.masks_markdown)), exist_ok=True)
+        with open(args.masks_markdown, "w") as f:
+            f.write("\n".join(mlines) + "\n")
+        if args.only_masks:
+            return
     if args.paths_markdown:                                            # profiles/ip_adapter_plus.md: both kernels, the rule, the step cost
         plines, _ = paths_table(dev, args.reps, args.rounds)
         if not args.no_step:

@@ -2592,6 +2592,180 @@ def golden_overlay():
     print("overlay.npz: %.1f KB, %d arrays" % (os.path.getsize(oc.GOLDEN) / 1024, len(out)))
 
 
+def golden_ip_mask_downsample():
+    """tests/golden/ip_mask_downsample.npz: IPAdapterMaskProcessor.downsample (D/image_processor.py:969-1029) of the two 0 / 1 masks of
+    tests/ip_masks_common.py downsample_masks for every (H, W, rows) of DOWNSAMPLE_CASES, batch 1, one value per row (value_embed_dim 1):
+    `<H>x<W>_<rows>` fp32 [2][rows], and `<H>x<W>_<rows>_warned` whether the reference warned about the aspect ratio.  The grids must be
+    those the formula predicts (DOWNSAMPLE_GRIDS) and exactly the padded cases warn."""
+    import warnings
+    from diffusers.image_processor import IPAdapterMaskProcessor
+    from tests.ip_masks_common import DOWNSAMPLE_CASES, DOWNSAMPLE_GRIDS, DOWNSAMPLE_PADDED, downsample_masks
+    out = {}
+    for H, W, rows in DOWNSAMPLE_CASES:
+        m = torch.from_numpy(downsample_masks(H, W).astype(np.float32))
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            y = torch.stack([IPAdapterMaskProcessor.downsample(m[i:i + 1], 1, rows, 1)[0, :, 0] for i in range(m.shape[0])]).numpy()
+        warned = any(issubclass(c.category, UserWarning) and "aspect ratio" in str(c.message) for c in caught)
+        mh, mw = DOWNSAMPLE_GRIDS[(H, W, rows)]
+        assert y.shape == (2, rows) and warned == ((H, W, rows) in DOWNSAMPLE_PADDED) == (mh * mw < rows), (H, W, rows, warned)
+        assert not y[:, mh * mw:].any() and (mh * mw == rows or y[:, :mh * mw].any())
+        print(f"ip mask downsample {H} x {W} -> {rows} rows ({mh} x {mw}): range [{y.min():.3f}, {y.max():.3f}], warned {warned}")
+        out[f"{H}x{W}_{rows}"], out[f"{H}x{W}_{rows}_warned"] = y.astype(np.float32), np.array(warned)
+    np.savez_compressed(os.path.join(OUT, "ip_mask_downsample.npz"), **out)
+    print("ip_mask_downsample.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "ip_mask_downsample.npz")) / 1024))
+
+
+def golden_blocks_ip_masks():
+    """tests/golden/blocks_ip_masks.npz: the blocks of golden_blocks_ip called with cross_attention_kwargs={"ip_adapter_masks": [...]}
+    (D/models/attention_processor.py:3776-3849), every adapter's tokens handed over as [B][images][4][ctx] and the masks of
+    tests/ip_masks_common.py block_masks.  Per case: `<name>_masked`, `<name>_unmasked` (no masks: one softmax over all images) and, where
+    an adapter has two images, `<name>_swapped` (their masks exchanged).  The variants must lie at least 10 times the GPU bar of
+    tests/test_blocks_gpu.py (1e-2 of the output's scale) apart: otherwise the test could not tell a mask applied to the wrong image, or a
+    shared softmax, from the truth."""
+    import warnings
+    from diffusers.models.attention_processor import IPAdapterAttnProcessor2_0
+    from diffusers.models.transformers.transformer_2d import Transformer2DModel
+    from tests.ip_adapter_common import IP_BLOCK_CASES, IP_BLOCK_SCALES, ip_block_inputs, ip_block_weights
+    from tests.ip_masks_common import block_has_swap, block_masks, images_of, swap_images
+    out = {}
+    for name, p in IP_BLOCK_CASES.items():
+        x, ctx, tokens = ip_block_inputs(name)
+        m = Transformer2DModel(num_attention_heads=p["heads"], attention_head_dim=p["C"] // p["heads"], in_channels=p["C"], num_layers=1,
+                               cross_attention_dim=p["ctx"], norm_num_groups=32).eval()
+        sd, ip = ip_block_weights(name)
+        m.load_state_dict(sd, strict=True)
+        proc = IPAdapterAttnProcessor2_0(p["C"], p["ctx"], num_tokens=list(p["tokens"]), scale=list(IP_BLOCK_SCALES[name]))
+        for i, (wk, wv) in enumerate(ip):
+            proc.to_k_ip[i].weight.data.copy_(wk)
+            proc.to_v_ip[i].weight.data.copy_(wv)
+        m.transformer_blocks[0].attn2.set_processor(proc)
+        per_image = [t.reshape(t.shape[0], n, 4, t.shape[2]) for t, n in zip(tokens, images_of(p["tokens"]))]
+        masks = block_masks(name)
+        sub, res = p["sub"], {}
+        variants = [("_masked", per_image, masks), ("_unmasked", tokens, None)] + ([("_swapped", per_image, swap_images(masks))] if block_has_swap(name) else [])
+        for tag, toks, mk in variants:
+            with torch.no_grad(), warnings.catch_warnings():
+                warnings.simplefilter("error")                            # (the masks have the canvas' aspect ratio: nothing is padded)
+                y = m(x, encoder_hidden_states=(ctx, toks), return_dict=False,
+                      **({} if mk is None else dict(cross_attention_kwargs={"ip_adapter_masks": mk})))[0]
+            res[tag] = out[name + tag] = y.numpy().astype(np.float32)[:, :, ::sub, ::sub]
+        bar = 1e-2 * np.abs(res["_masked"]).max()
+        tags = [t for t, _, _ in variants]
+        gaps = {a + "/" + b: float(np.abs(res[a] - res[b]).max() / bar) for i, a in enumerate(tags) for b in tags[i + 1:]}
+        print(f"block {name} with masks: out std {res['_masked'].std():.4f}, variants apart by {gaps} bars")
+        assert min(gaps.values()) >= 10.0, (name, gaps)
+    np.savez_compressed(os.path.join(OUT, "blocks_ip_masks.npz"), **out)
+    print("blocks_ip_masks.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "blocks_ip_masks.npz")) / 1024))
+
+
+def golden_unet_ip_masks():
+    """tests/golden/unet_tiny_ip_masks.npz: the cases of golden_ip_adapter (same UNet, adapters, inputs and residual stand-ins, the
+    case's scales) called with cross_attention_kwargs={"ip_adapter_masks": [...]}, masks at the image resolution
+    (tests/ip_masks_common.py unet_masks).  Per case `<case>_eps_masked`, and `<case>_eps_swapped` where an adapter has two images; the
+    unmasked `eps` is that of unet_tiny_ip.npz.  The variants lie at least 10 GPU bars (1e-2 of eps' scale) apart."""
+    from diffusers.models.attention_processor import IPAdapterAttnProcessor2_0
+    from tests.ip_adapter_common import IP_GEOMETRIES, IP_RES_SCALE, IP_UNET_CASES, IP_UNET_SCALES, ip_unet_inputs, tiny_ip_adapter
+    from tests.ip_masks_common import swap_images, unet_masks
+    base = np.load(os.path.join(OUT, "unet_tiny_ip.npz"))
+    out, t = {}, torch.tensor(int(base["timestep"]))
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    for case, (geo, images) in IP_UNET_CASES.items():
+        B, H, W = IP_GEOMETRIES[geo]
+        x_u, ehs, seed, embeds = ip_unet_inputs(case)
+        down, mid, up = _freeu_residual_shapes(H, W)
+        mk = lambda i, s: g(seed + i, B, *s) * IP_RES_SCALE
+        down, mid, up = [mk(i, s) for i, s in enumerate(down)], mk(100, mid), [mk(200 + i, s) for i, s in enumerate(up)]
+        res = lambda: dict(down_block_add_samples=[r.clone() for r in down], mid_block_add_sample=mid.clone(),
+                           up_block_add_samples=[r.clone() for r in up])
+        unet, _ = build_tiny()
+        unet._load_ip_adapter_weights([tiny_ip_adapter(i) for i in range(len(images))], low_cpu_mem_usage=False)
+        for p in unet.attn_processors.values():
+            if isinstance(p, IPAdapterAttnProcessor2_0):
+                p.scale = list(IP_UNET_SCALES[case])
+
+        def run(masks):
+            with torch.no_grad():
+                return unet(x_u, t, encoder_hidden_states=ehs, added_cond_kwargs={"image_embeds": embeds}, return_dict=False,
+                            **({} if masks is None else dict(cross_attention_kwargs={"ip_adapter_masks": masks})), **res())[0].numpy()
+        masks = unet_masks(case)
+        eps = run(None)
+        assert np.array_equal(eps, base[f"{case}_eps"]), "without masks: the eps of unet_tiny_ip.npz, bit for bit"
+        got = {"eps": eps, "eps_masked": run(masks)}
+        if any(n > 1 for n in images):
+            got["eps_swapped"] = run(swap_images(masks))
+        tags = list(got)
+        gaps = {a + "/" + b: rel(got[a], got[b]) / 1e-2 for i, a in enumerate(tags) for b in tags[i + 1:]}
+        print(f"ip-adapter masks UNet {case}: eps std {got['eps_masked'].std():.4f}, variants apart by {gaps} bars")
+        assert min(gaps.values()) >= 10.0, (case, gaps)
+        out.update({f"{case}_{k}": v for k, v in got.items() if k != "eps"})
+    np.savez_compressed(os.path.join(OUT, "unet_tiny_ip_masks.npz"), **out)
+    print("unet_tiny_ip_masks.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "unet_tiny_ip_masks.npz")) / 1024))
+
+
+def golden_pipeline_call_ip_masks():
+    """tests/golden/pipeline_call_ip_masks.npz: the call of golden_pipeline_call_ip (same seeds, adapter, scale IP_CALL_SCALE and
+    embeddings) with cross_attention_kwargs={"ip_adapter_masks": [...]} (pipe:1084).  The stored uint8 mask images (`mask_A`, `mask_B`,
+    tests/ip_masks_common.py call_mask_images; 64 x 128, the aspect ratio of the canvas the UNet runs on) go through the reference's
+    IPAdapterMaskProcessor.preprocess(mask, 64, 128); the preprocessed masks are stored too (`pre_A`, `pre_B`, fp32 [1][1][64][128]),
+    with the preprocessed masks of the same images at half the size (`pre_A_32x64`: lanczos, then binarised).  Latents for mask A, for
+    mask B and - asserted equal to pipeline_call_ip.npz's - without masks; at least 10 GPU bars (1e-2 of the latents' scale) apart."""
+    import warnings
+    from PIL import Image
+    from diffusers.image_processor import IPAdapterMaskProcessor
+    from diffusers.loaders.ip_adapter import IPAdapterMixin
+    from diffusers.pipelines.stable_diffusion.pipeline_stable_diffusion import StableDiffusionPipeline
+    from tests.common import FakeTokenizer, pipeline_cases
+    from tests.ip_adapter_common import IP_CALL_SCALE, ip_call_embeds, tiny_ip_adapter
+    from tests.ip_masks_common import call_mask_images
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    zi = np.load(os.path.join(OUT, "pipeline_call_ip.npz"))
+    kw = dict(pipeline_cases()["ddim_neg2"])
+    for k in ("scheduler", "seed", "rng_seed"):
+        kw.pop(k)
+    kw["num_inference_steps"] = int(zi["num_inference_steps"])
+    seed, rng_seed = int(zi["seed"]), int(zi["rng_seed"])
+    embeds = ip_call_embeds()
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    unet._load_ip_adapter_weights([tiny_ip_adapter(0)], low_cpu_mem_usage=False)
+    sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+    pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                          safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+    pipe.set_progress_bar_config(disable=True)
+    pipe.prepare_ip_adapter_image_embeds = types.MethodType(StableDiffusionPipeline.prepare_ip_adapter_image_embeds, pipe)
+    IPAdapterMixin.set_ip_adapter_scale(pipe, IP_CALL_SCALE)
+    mp = IPAdapterMaskProcessor()
+    images = call_mask_images()
+    out = {}
+    for tag, im in images.items():
+        out[f"mask_{tag}"] = im.astype(np.uint8)
+        pre = mp.preprocess(Image.fromarray(out[f"mask_{tag}"]), height=64, width=128)
+        out[f"pre_{tag}"] = pre.reshape(1, pre.shape[0], pre.shape[2], pre.shape[3]).numpy()
+        half = mp.preprocess(Image.fromarray(out[f"mask_{tag}"]), height=32, width=64)
+        out[f"pre_{tag}_32x64"] = half.reshape(1, half.shape[0], half.shape[2], half.shape[3]).numpy()
+        assert set(np.unique(out[f"pre_{tag}"])) == {0.0, 1.0} and out[f"pre_{tag}"].shape == (1, 1, 64, 128)
+
+    def call(masks):
+        torch.manual_seed(rng_seed)
+        with warnings.catch_warnings():
+            warnings.simplefilter("error", UserWarning)                   # (no level pads: the masks have the canvas' aspect ratio)
+            return pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                        height=64, width=64, generator=torch.Generator().manual_seed(seed), output_type="latent",
+                        ip_adapter_image_embeds=[embeds], **({} if masks is None else dict(cross_attention_kwargs={"ip_adapter_masks": masks})),
+                        **kw).images.numpy()
+    out["latents_none"] = call(None)
+    assert np.array_equal(out["latents_none"], zi["latents"]), "without masks: the latents of pipeline_call_ip.npz, bit for bit"
+    for tag in images:
+        out[f"latents_{tag}"] = call([torch.from_numpy(out[f"pre_{tag}"])])
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    gaps = (rel(out["latents_A"], out["latents_B"]), rel(out["latents_A"], out["latents_none"]), rel(out["latents_B"], out["latents_none"]))
+    print("pipeline __call__ ip-adapter masks: latents std %.4f; A vs B %.3f, A vs none %.3f, B vs none %.3f (max-abs / scale)" %
+          ((out["latents_A"].std(),) + gaps))
+    assert min(gaps) >= 10 * 1e-2, gaps
+    np.savez_compressed(os.path.join(OUT, "pipeline_call_ip_masks.npz"), **out)
+    print("pipeline_call_ip_masks.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "pipeline_call_ip_masks.npz")) / 1024))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -2643,6 +2817,10 @@ if __name__ == "__main__":
     golden_clip_processor()
     golden_pipeline_call_ip_image()
     golden_overlay()
+    golden_ip_mask_downsample()
+    golden_blocks_ip_masks()
+    golden_unet_ip_masks()
+    golden_pipeline_call_ip_masks()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
