@@ -298,6 +298,22 @@ IP_MASK_DIRECT_SIGNATURES = {
     "bc_attention_ip_masked_with": (C.c_int, [C.c_int] + IP_MASK_SIGNATURES["bc_attention_ip_masked"][1]),
 }
 
+# Entry points of include/blobctrl_tiny_vae.h (the AutoencoderTiny decoder, blobctrl_amd/tiny_vae.py).  bc_tiny_conv3x3 takes the struct
+# below; the recordable plan ops (TINY_VAE_OPS below, in-process only) are its flat form and the latent prologue.
+class BcTinyConvArgs(C.Structure):
+    """Mirror of `struct bc_tiny_conv_args` (include/blobctrl_tiny_vae.h) - keep field order identical."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("skip", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Ci", C.c_int), ("Co", C.c_int),
+                ("up", C.c_int), ("relu", C.c_int), ("out_mode", C.c_int)]
+
+
+TINY_VAE_SIGNATURES = {
+    "bc_tiny_conv3x3_flat": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
+    "bc_tiny_latents_in": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+TINY_VAE_DIRECT_SIGNATURES = {"bc_tiny_conv3x3": (C.c_int, [C.POINTER(BcTinyConvArgs), C.c_void_p])}
+TINY_OUT_F16, TINY_OUT_IMAGE, TINY_OUT_U8 = 0, 1, 2
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -324,6 +340,9 @@ _OP_TABLES = (OPS, REQUEST_OPS, SAM_OPS, SAM_BATCH_OPS, IP_OPS)
 # _OP_TABLES is the list up to BC_OP_IP_END and stays as it is; tables of headers that start an enum of their own behind it go here, and
 # `op_code` reads both
 _OP_TABLES_BEYOND = (IP_MASK_OPS,)
+# ... and those of include/blobctrl_tiny_vae.h, again an enum of its own behind BC_OP_IP_MASK_END (56, which stays no op)
+TINY_VAE_OPS = {"bc_tiny_conv3x3_flat": 57, "bc_tiny_latents_in": 58}
+_OP_TABLES_TINY_VAE = (TINY_VAE_OPS,)
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
@@ -332,7 +351,7 @@ _KIND = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l", C.c_c
 
 def op_code(name):
     """BC_OP_* code of a recordable entry point."""
-    for table in _OP_TABLES + _OP_TABLES_BEYOND:
+    for table in _OP_TABLES + _OP_TABLES_BEYOND + _OP_TABLES_TINY_VAE:
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -341,7 +360,7 @@ def op_code(name):
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
     args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES.get(name) or SAM_BATCH_SIGNATURES.get(name) or
-            IP_SIGNATURES.get(name) or IP_MASK_SIGNATURES[name])[1][:-1]
+            IP_SIGNATURES.get(name) or IP_MASK_SIGNATURES.get(name) or TINY_VAE_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -379,7 +398,8 @@ def load():
             list(SAM_SIGNATURES.items()) + list(SAM_BATCH_SIGNATURES.items()) + list(SAM_HOST_SIGNATURES.items()) + \
             list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
             list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()) + list(OVERLAY_SIGNATURES.items()) + \
-            list(IP_MASK_SIGNATURES.items()) + list(IP_MASK_DIRECT_SIGNATURES.items()):
+            list(IP_MASK_SIGNATURES.items()) + list(IP_MASK_DIRECT_SIGNATURES.items()) + list(TINY_VAE_SIGNATURES.items()) + \
+            list(TINY_VAE_DIRECT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -24,6 +24,7 @@
 #include "../../include/blobctrl_sam.h"
 #include "../../include/blobctrl_ip.h"
 #include "../../include/blobctrl_ip_mask.h"
+#include "../../include/blobctrl_tiny_vae.h"
 
 void bc_gemm_set_probe(hipEvent_t e);      // gemm.hip (timing probe between a split-K GEMM's main kernel and its reducer)
 bool bc_gemm_probe_hit();
@@ -63,10 +64,12 @@ namespace {
 
 // The ops of extension headers that plan_format.h (the file format: closed at BC_OP_COUNT) does not know: in-process only.
 inline const char* plan_op_signature(int op) {
-    return op == BC_OP_ATTENTION_IP ? "ppppiiiiiiiifp" : op == BC_OP_ATTENTION_IP_MASKED ? "ppppiiiiiiiiifppi" : op_signature(op);
+    return op == BC_OP_ATTENTION_IP ? "ppppiiiiiiiifp" : op == BC_OP_ATTENTION_IP_MASKED ? "ppppiiiiiiiiifppi" :
+           op == BC_OP_TINY_CONV3X3 ? "pppppiiiiiiii" : op == BC_OP_TINY_LATENTS_IN ? "piiip" : op_signature(op);
 }
 inline uint32_t plan_op_min_version(int op) {
-    return op == BC_OP_ATTENTION_IP || op == BC_OP_ATTENTION_IP_MASKED ? kNoFileVersion : op_min_version(op);
+    return op == BC_OP_ATTENTION_IP || op == BC_OP_ATTENTION_IP_MASKED || op == BC_OP_TINY_CONV3X3 || op == BC_OP_TINY_LATENTS_IN
+               ? kNoFileVersion : op_min_version(op);
 }
 
 inline float as_float(uint64_t v) { uint32_t u = (uint32_t)v; float f; memcpy(&f, &u, 4); return f; }
@@ -197,6 +200,10 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
         case BC_OP_ATTENTION_IP_MASKED:
             return bc_attention_ip_masked(CP(bc_half, 0), CP(bc_half, 1), CP(bc_half, 2), MP(bc_half, 3), I(4), I(5), I(6), I(7), I(8), I(9), I(10),
                                           I(11), I(12), F(13), CP(float, 14), CP(bc_half, 15), I(16), s);
+        case BC_OP_TINY_CONV3X3:
+            return bc_tiny_conv3x3_flat(CP(bc_half, 0), CP(bc_half, 1), CP(float, 2), CP(bc_half, 3), P(4), I(5), I(6), I(7), I(8), I(9), I(10), I(11),
+                                        I(12), s);
+        case BC_OP_TINY_LATENTS_IN: return bc_tiny_latents_in(CP(float, 0), I(1), I(2), I(3), MP(bc_half, 4), s);
         case BC_OP_ROWCHAIN:
             return bc_rowchain(I(0), I(1), I(2), I(3), CP(bc_half, 4), CP(float, 5), CP(unsigned long long, 6), CP(float, 7), CP(float, 8), I(9),
                                F(10), CP(bc_half, 11), CP(bc_half, 12), CP(bc_half, 13), I(14), I(15), I(16), CP(bc_half, 17), CP(float, 18),

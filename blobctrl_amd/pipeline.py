@@ -69,7 +69,54 @@ class EditSetup(namedtuple("EditSetup", "requests tables n stochastic third_orde
         return ["step_active" if a else "step_inactive" for a in self.active]
 
 
-class BlobCtrlEngine:
+class _PreviewVAE:
+    """Per-step previews with a tiny decoder held next to the pipeline (what diffusers users do with `AutoencoderTiny` inside
+    `callback_on_step_end`): `load_preview_vae` / `unload_preview_vae` / `preview`, shared by the engine and the pipeline.  Additive: no edit,
+    plan or launch of the loop changes."""
+    preview_vae = None                                                # blobctrl_amd.tiny_vae.AutoencoderTiny, or None
+
+    def load_preview_vae(self, path_or_state_dict):
+        """A TAESD checkpoint folder (config.json + diffusion_pytorch_model.safetensors) or a state dict -> `self.preview_vae`."""
+        from .tiny_vae import AutoencoderTiny
+        if isinstance(path_or_state_dict, (str, os.PathLike)):
+            self.preview_vae = AutoencoderTiny.from_pretrained(os.fspath(path_or_state_dict), device=str(self.device))
+        else:
+            self.preview_vae = AutoencoderTiny(path_or_state_dict, device=str(self.device))
+        return self.preview_vae
+
+    def unload_preview_vae(self):
+        self.preview_vae = None
+
+    def _preview_loop_streams(self):
+        return ()
+
+    def preview(self, latents: torch.Tensor, output_type: str = "pil"):
+        """The image of the latents a `callback_on_step_end` receives (already scaled; TAESD's scaling factor is 1).  "uint8": the device
+        tensor [B][8h][8w][3] of AutoencoderTiny.preview; "pt" / "np" / "pil": AutoencoderTiny.decode through
+        VaeImageProcessor.postprocess.  Enqueued on the caller's current stream with no host synchronisation; the loop's streams are made to
+        wait for the READ of `latents` (not for the decoder), so a callback may hand over the loop's own latent buffer and return."""
+        if self.preview_vae is None:
+            raise ValueError("no preview VAE is loaded: call load_preview_vae(path_or_state_dict) first")
+        if output_type not in ("pil", "np", "pt", "uint8"):
+            raise ValueError(f"preview: output_type {output_type!r} (pil, np, pt or uint8)")
+        tiny = self.preview_vae
+        if output_type == "uint8":
+            out = tiny.preview(latents)
+        else:
+            out = tiny.decode(latents, return_dict=False)[0]
+        if tiny.input_read is not None:
+            for st in self._preview_loop_streams():
+                st.wait_event(tiny.input_read)
+        if output_type == "uint8":
+            return out
+        proc = getattr(self, "image_processor", None)
+        if proc is None:
+            from .image_processor import VaeImageProcessor
+            proc = VaeImageProcessor(vae_scale_factor=8, do_convert_rgb=True)
+        return proc.postprocess(out, output_type=output_type, do_denormalize=[True] * out.shape[0])
+
+
+class BlobCtrlEngine(_PreviewVAE):
     """The denoising hot path on MI355X at tensor level (prompt embeddings, image latents, scores, DINO feature in; latents out):
     static launch plans per (batch, canvas, steps), hipGraph replay, two streams.  `StableDiffusionBlobNetPipeline` below wraps it
     with the reference pipeline's constructor and `__call__` signature."""
@@ -515,6 +562,9 @@ class BlobCtrlEngine:
 
     def _extra(self):
         return (self.side_stream2.cuda_stream if self.two_streams else self.stream.cuda_stream,)
+
+    def _preview_loop_streams(self):
+        return (self.stream, self.side_stream, self.side_stream2) if self.device.type == "cuda" else ()
 
     # ------------------------------------------------------------------------------------------------ call
     def check_inputs(self, blobnet_conditioning_scale, start, end, num_inference_steps):
@@ -1109,7 +1159,7 @@ class StableDiffusionBlobNetPipelineOutput:
         return (self.images, self.nsfw_content_detected)[i]
 
 
-class StableDiffusionBlobNetPipeline:
+class StableDiffusionBlobNetPipeline(_PreviewVAE):
     """Drop-in for blobctrl/pipelines/pipeline_blobnet.py:StableDiffusionBlobNetPipeline on MI355X.
 
     Components (pipe:206-243): `vae` = blobctrl_amd.vae.AutoencoderKL, `unet` / `blobnet` = blobctrl_amd.modules shells (any LoRA is
@@ -1221,6 +1271,9 @@ class StableDiffusionBlobNetPipeline:
             self._engine.set_scheduler(self._scheduler.kind, self._scheduler.table_params()
                                        if hasattr(self._scheduler, "table_params") else None)
         return self._engine
+
+    def _preview_loop_streams(self):
+        return self._engine._preview_loop_streams() if self._engine is not None else ()
 
     # ---- attribute plumbing the scripts touch (inf:276-279)
     @property

@@ -319,6 +319,29 @@ def vae_param_shapes(block_out_channels=(128, 256, 512, 512), layers_per_block=2
     return s
 
 
+def tiny_vae_param_shapes(num_decoder_blocks=(3, 3, 3, 1), channels=64, latent_channels=4, out_channels=3) -> "OrderedDict[str, tuple]":
+    """The decoder half of `AutoencoderTiny.state_dict()` (D/models/autoencoders/vae.py:931-957 DecoderTiny, D/models/unets/unet_2d_blocks.py:
+    568-583 AutoencoderTinyBlock): a Sequential of conv_in, ReLU, then per stage its blocks (convolutions at .conv.0 / .2 / .4), an Upsample
+    (no parameters) and a convolution that has a bias only in the last stage."""
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    c = channels
+    s["decoder.layers.0.weight"] = (c, latent_channels, 3, 3); s["decoder.layers.0.bias"] = (c,)
+    i = 2
+    for st, n in enumerate(num_decoder_blocks):
+        for _ in range(n):
+            for j in (0, 2, 4):
+                s[f"decoder.layers.{i}.conv.{j}.weight"] = (c, c, 3, 3); s[f"decoder.layers.{i}.conv.{j}.bias"] = (c,)
+            i += 1
+        last = st == len(num_decoder_blocks) - 1
+        if not last:
+            i += 1
+        s[f"decoder.layers.{i}.weight"] = (out_channels if last else c, c, 3, 3)
+        if last:
+            s[f"decoder.layers.{i}.bias"] = (out_channels,)
+        i += 1
+    return s
+
+
 def synth_tensor(name: str, shape: tuple, seed: int) -> np.ndarray:
     """One parameter, float32, from a PCG64 stream keyed by (seed, crc32(name)).
 

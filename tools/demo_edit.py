@@ -112,7 +112,12 @@ def main():
     ap.add_argument("--ip-image", default=None, help="the image prompt (any file PIL opens); seeded noise without it")
     ap.add_argument("--ip-mask", default=None, metavar="blob|FILE",
                     help="confine the image prompt (with --ip-adapter): 'blob' = the edit's target ellipse, or a mask image of the frame")
+    ap.add_argument("--preview-vae", default=None, metavar="PATH|synth", help="a TAESD folder (config.json + diffusion_pytorch_model.safetensors), or 'synth'")
+    ap.add_argument("--preview-every", type=int, default=5, metavar="N", help="preview every N-th step (with --preview-vae)")
+    ap.add_argument("--preview-dir", default="previews", metavar="DIR", help="where the step_<i>.png files go (with --preview-vae)")
     args = ap.parse_args()
+    if args.preview_vae and args.preview_every < 1:
+        ap.error("--preview-every needs N >= 1")
     if args.ip_image and not args.ip_adapter:
         ap.error("--ip-image needs --ip-adapter")
     if args.ip_mask and not args.ip_adapter:
@@ -251,6 +256,16 @@ def main():
         m = IPAdapterMaskProcessor().preprocess(frame_mask, height=R, width=R)
         ip_kwargs["ip_adapter_masks"] = [ip_masks.canvas_masks(m.reshape(1, m.shape[0], m.shape[2], m.shape[3]))]
         print(f"--ip-mask {args.ip_mask}: {100 * float(m.float().mean()):.1f} % of the frame takes the image prompt")
+    if args.preview_vae:
+        pipe.load_preview_vae(synth.synth_state_dict(synth.tiny_vae_param_shapes(), 33) if args.preview_vae == "synth" else args.preview_vae)
+        os.makedirs(args.preview_dir, exist_ok=True)
+
+        def show(p, i, t, kw):
+            if i % args.preview_every == 0:
+                p.preview(kw["latents"], "pil")[0].save(os.path.join(args.preview_dir, f"step_{i:03d}.png"))
+            return {}
+        ip_kwargs["callback_on_step_end"] = show
+        print(f"--preview-vae {args.preview_vae}: a PNG every {args.preview_every} steps into {args.preview_dir} (a callback runs the loop step by step)")
     otype = "pt" if args.zoom is not None else "np"           # a zoomed edit's result stays on the device for the paste-back
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,

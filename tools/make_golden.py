@@ -2766,6 +2766,59 @@ def golden_pipeline_call_ip_masks():
     print("pipeline_call_ip_masks.npz: %.1f KB" % (os.path.getsize(os.path.join(OUT, "pipeline_call_ip_masks.npz")) / 1024))
 
 
+TINY_VAE_CASES = {"a": (2, 5, 7), "b": (1, 1, 1), "c": (3, 9, 3)}      # tag -> (batch, latent h, w); seeds 331 ... in this order
+
+
+def golden_tiny_vae():
+    """tests/golden/autoencoder_tiny.npz: the reference's AutoencoderTiny (default architecture) with synth weights, seed 33, on z = 2 N(0, 1):
+    `<tag>_z`, `<tag>_sample` = decode(z).sample, `<tag>_preview` = the bytes round(clamp(sample / 2 + 0.5, 0, 1) * 255) as [B][H][W][3]; `schema`
+    = the (name, shape) list of the reference's decoder state dict; `meta` (JSON) = the per-layer output stds of case a, the share of
+    saturated preview bytes, and the error of an fp16-storage emulation of the reference (weights, inputs and every Conv2d / ReLU output
+    rounded to fp16, arithmetic in fp32 on the CPU) per case.  synth's N(0, 1 / fan_in) weights, NOT the framework's default initialisation:
+    with that the image's std falls to 0.04 and an error in a layer no longer reaches the output."""
+    from diffusers import AutoencoderTiny
+    vae = AutoencoderTiny().eval()
+    sh = synth.tiny_vae_param_shapes()
+    dec = {"decoder." + k: tuple(v.shape) for k, v in vae.decoder.state_dict().items()}
+    assert list(dec) == list(sh) and all(dec[k] == tuple(sh[k]) for k in dec), "AutoencoderTiny decoder schema mismatch"
+    sd = synth.synth_state_dict(sh, 33)
+    vae.decoder.load_state_dict({k[len("decoder."):]: v for k, v in sd.items()}, strict=True)
+    out = {"schema": np.array(json.dumps([[k, list(v)] for k, v in dec.items()]))}
+    mods = [m for m in vae.decoder.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.ReLU))]
+    stds, hooks = [], [m.register_forward_hook(lambda _m, _i, o: stds.append(float(o.std()))) for m in mods if isinstance(m, torch.nn.Conv2d)]
+    meta = {"cases": {}, "seed": 33}
+    for n, (tag, (B, h, w)) in enumerate(TINY_VAE_CASES.items()):
+        z = 2.0 * g(331 + n, B, 4, h, w)
+        del stds[:]
+        sample = vae.decode(z).sample
+        if tag == "a":
+            meta["layer_output_std"] = list(stds)
+        by = ((sample / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        out[f"{tag}_z"], out[f"{tag}_sample"], out[f"{tag}_preview"] = z.numpy(), sample.numpy(), by.numpy()
+        meta["cases"][tag] = dict(shape=[B, h, w], sample_std=float(sample.std()), sample_max_abs=float(sample.abs().max()),
+                                  saturated_bytes=float(((by == 0) | (by == 255)).float().mean()))
+    for hk in hooks:
+        hk.remove()
+    # fp16-storage emulation
+    keep = {k: v.clone() for k, v in vae.decoder.state_dict().items()}
+    vae.decoder.load_state_dict({k: (v.half().float() if k.endswith("weight") else v) for k, v in keep.items()}, strict=True)
+    hooks = [m.register_forward_hook(lambda _m, _i, o: o.half().float()) for m in mods]
+    hooks.append(vae.decoder.layers.register_forward_pre_hook(lambda _m, i: (i[0].half().float(),)))
+    for tag in TINY_VAE_CASES:
+        emu = vae.decode(torch.from_numpy(out[f"{tag}_z"])).sample.numpy()
+        ref = out[f"{tag}_sample"]
+        meta["cases"][tag]["fp16_storage_emulation_max_abs_over_scale"] = float(np.abs(emu - ref).max() / np.abs(ref).max())
+    for hk in hooks:
+        hk.remove()
+    vae.decoder.load_state_dict(keep, strict=True)
+    out["meta"] = np.array(json.dumps(meta))
+    path = os.path.join(OUT, "autoencoder_tiny.npz")
+    np.savez_compressed(path, **out)
+    lo, hi = min(meta["layer_output_std"]), max(meta["layer_output_std"])
+    print("autoencoder_tiny.npz: %.1f KB; layer stds %.3f .. %.3f; %s" % (os.path.getsize(path) / 1024, lo, hi, json.dumps(meta["cases"])))
+    assert 0.2 < lo and hi < 1.6, "a decoder layer's output has left the O(1) range: an error there would not reach the image"
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -2821,6 +2874,7 @@ if __name__ == "__main__":
     golden_blocks_ip_masks()
     golden_unet_ip_masks()
     golden_pipeline_call_ip_masks()
+    golden_tiny_vae()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
