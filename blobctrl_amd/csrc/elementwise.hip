@@ -2,6 +2,7 @@
 // timestep embedding, CFG + scheduler step, layout conversion at the nn.Module boundary, DINOv2 embedding glue.
 #include "bc_common.h"
 #include "bc_splat.h"
+#include "bc_cfg_step.h"
 #include "../../include/blobctrl_requests.h"
 
 namespace {
@@ -172,66 +173,8 @@ __global__ void silu_kernel(const h16* __restrict__ x, h16* __restrict__ y, long
         y[i] = (h16)bc_silu_f((float)x[i]);
 }
 
-// Crop (right half) + classifier-free guidance + scheduler step: ONE body behind the three bc_cfg_scheduler_step* entry points,
-// specialised at compile time.  cf = coef row *step_idx (16 floats; the full column table is at the top of blobctrl_amd/schedulers.py).
-//   NOISE: x_next += cf[12] * noise[step][i], the variance noise of stochastic DDIM (scheduling_ddim.py:438-466) and SDE-DPM-Solver++;
-//          noise fp32 [nsteps][B][4][h][w]
-//   THIRD: x_next += cf[13] * x0_{i-2}, third-order DPM-Solver++ (scheduling_dpmsolver_multistep.py:804-887), read from the hist slot
-//          m1 that every instantiation already loads
-//   GUARD: a step index outside [0, nsteps) (the capture warm-ups advance the counter) has no table row and no noise slice: the
-//          launch then leaves every buffer as it is.  The plain entry point has no nsteps in its ABI, hence no guard.
-//   SINGLE: a guidance-free (single-pass) plan: eps holds B images, not 2B, and e is the right half of image b as it is - no second
-//          read, no guidance arithmetic, `guidance` and column 11 are not read (pipe:1031, 1095: do_classifier_free_guidance False).
-//   REQ:   a batch of edit requests with their own tables: coef is [B][nsteps][16] and image b applies ITS row, guidance (column 11)
-//          included.  Column 15 != 0 marks a request that has finished: its elements are left alone - nothing of image b is loaded from
-//          eps and nothing is stored, eps_out included - whatever the networks put out for it (a non-finite value included).
-// `noise` / `nsteps` are not read by an instantiation without NOISE / GUARD.
-template <bool SINGLE, bool NOISE, bool THIRD, bool GUARD, bool REQ = false>
-__device__ __forceinline__ void cfg_step_body(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
-                                              const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h,
-                                              int w, const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
-    const int n = B * 4 * h * w;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int step = *step_idx;
-    if (i >= n) return;
-    if (GUARD && (step < 0 || step >= nsteps)) return;
-    const float* cf = coef + (size_t)step * 16;
-    const int xx = i % w;
-    const int yy = (i / w) % h;
-    const int c = (i / (w * h)) % 4;
-    const int b = i / (4 * w * h);
-    if (REQ) {
-        cf = coef + ((size_t)b * nsteps + step) * 16;
-        if (cf[15] != 0.f) return;
-    }
-    // eps token-major [2B][h][2w][4]; right half, uncond = batch b, cond = batch B + b   (pipe:1092-1098)
-    const size_t pu = (((size_t)b * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-    float e;
-    if (SINGLE) {
-        e = eps[pu];                                              // eps token-major [B][h][2w][4]
-    } else {
-        const size_t pc = (((size_t)(B + b) * h + yy) * (2 * w) + (w + xx)) * 4 + c;
-        const float eu = eps[pu], ec = eps[pc];
-        const float gscale = guidance >= 0.f ? guidance : cf[11];     // < 0: read from the coefficient table (graph-replay safe)
-        e = eu + gscale * (ec - eu);
-    }
-    if (eps_out) eps_out[i] = e;
-    const float x = latents[i];
-    float* m0 = hist, *m1 = hist + n, *last = hist + 2 * (size_t)n;
-    const float x0 = x * cf[0] - e * cf[1];
-    float xc = x;
-    const float pm0 = m0[i], pm1 = m1[i];
-    if (cf[2] != 0.f) xc = cf[3] * last[i] + cf[4] * pm0 + cf[5] * pm1 + cf[6] * x0;
-    float xn = cf[7] * xc + cf[8] * x0 + cf[9] * pm0 + cf[10] * e;
-    m1[i] = pm0;
-    m0[i] = x0;
-    last[i] = xc;
-    // the optional terms come last, after the history stores: every instantiation is the plain step up to here
-    if (NOISE) xn = xn + cf[12] * noise[(size_t)step * n + i];
-    if (THIRD) xn = xn + cf[13] * pm1;
-    latents[i] = xn;
-}
-
+// Crop (right half) + classifier-free guidance + scheduler step: ONE body (cfg_step_body, bc_cfg_step.h) behind the bc_cfg_scheduler_step*
+// entry points and their single-pass and request forms, specialised at compile time.
 template <bool NOISE, bool THIRD, bool GUARD>
 __global__ void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
                                 const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h, int w,
@@ -254,8 +197,6 @@ __global__ void step_requests_kernel(const float* __restrict__ eps, float* __res
                                      const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out) {
     cfg_step_body<SINGLE, NOISE, THIRD, true, true>(eps, latents, coef, step_idx, hist, -1.f, B, h, w, noise, nsteps, eps_out);
 }
-
-__global__ void advance_kernel(int* step_idx) { *step_idx += 1; }
 
 __global__ void nchw_to_nhwc_kernel(const void* __restrict__ src, int src_f32, int B, int C, int HW, int Cpad,
                                     h16* __restrict__ dst) {
@@ -514,22 +455,6 @@ extern "C" int bc_silu(const bc_half* x, bc_half* y, long long n, bc_stream stre
     return 0;
 }
 
-// The host side of every step entry point: `ok` is the entry point's argument check (`name` = its own name for the error text), then
-// the launch of its kernel instance over the B * 4 * h * w latent elements and, with `advance`, of the step counter's increment.
-template <typename... Params, typename... Args>
-static int step_launch(const char* name, bool ok, void (*kernel)(Params...), int B, int h, int w, int* step_idx, int advance,
-                       bc_stream stream_, Args... args) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BC_CHECK_ARG(ok, "%s: bad args", name);
-    hipLaunchKernelGGL(kernel, dim3(bc_ceil_div(B * 4 * h * w, 256)), dim3(256), 0, stream, args...);
-    BC_CHECK_LAUNCH();
-    if (advance) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, step_idx);
-        BC_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
 // The three CFG entry points are one instance each; one without NOISE / GUARD passes noise = nullptr / nsteps = 0, which its
 // instantiation never reads.
 template <bool NOISE, bool THIRD, bool GUARD>
@@ -571,8 +496,6 @@ static const GuardedStep request_steps[8] = {
     step_requests_kernel<false, false, false>, step_requests_kernel<false, false, true>, step_requests_kernel<false, true, false>,
     step_requests_kernel<false, true, true>,   step_requests_kernel<true, false, false>, step_requests_kernel<true, false, true>,
     step_requests_kernel<true, true, false>,   step_requests_kernel<true, true, true>};
-
-static int step_form(bool single, bool noise, bool third) { return (single ? 4 : 0) | (noise ? 2 : 0) | (third ? 1 : 0); }
 
 // The step of a guidance-free (single-pass) plan: eps [B][h][2w][4], e = its right half.  noise != NULL adds cf[12] * noise[step],
 // third != 0 adds cf[13] * x0_{i-2}; a step index outside [0, nsteps) leaves every buffer as it is.

@@ -138,6 +138,8 @@ class TrunkPlan:
         self.freeu_params = None          # UNet with FreeU on: the plan's fp32 (s1, s2, b1, b2) buffer, read by bc_freeu on the device
         self.ip_adapters = ()             # UNet with IP-Adapters loaded (IpAdapter): record_context projects their K / V per attn2
         self.ip_kv = {}                   # attn2 block prefix -> [(K_ip, V_ip, tokens per image, weight word)] per adapter
+        self.pag_layers = frozenset()     # UNet of a PAG plan: the prefixes "<...>attentions.<j>." of the blocks whose attn1 is perturbed ...
+        self.pag_images = 0               # ... for the last `pag_images` images of the batch (PAGIdentitySelfAttnProcessor2_0: their own V)
 
     # ------------------------------------------------------------------------------------------- helpers
     def _r2(self, res_t, H, W):
@@ -394,8 +396,7 @@ class TrunkPlan:
         w, v = packed(_lib.CHAIN_IN)
         rec.rowchain(_lib.CHAIN_IN, Cc, M, HW, x.t, w, v, h0, out1=qk, out2=vt, ldvt=ldvt, **gnkw)
         a = a_all[:M]
-        rec.attention(qk, qk, vt, a, B, self.heads, d, HW, HW, 2 * Cc, 2 * Cc, ldvt, Cc, HW * 2 * Cc, HW * 2 * Cc, Cc * ldvt, HW * Cc,
-                      scale, q_off=0, k_off=Cc)
+        self.self_attention(p, qk, vt, a, B, d, HW, Cc, ldvt, scale)
         if fan_out is not None:
             x_full, extra = fan_out
             half = M * Cc * 2
@@ -454,6 +455,19 @@ class TrunkPlan:
             rec.rowchain(_lib.CHAIN_OUT, Cc, M, HW, a, w, v, out, res=h, res2=x.t, gn_tot=part, **kw)
         rec.tots[out.data_ptr()] = part
         return Act(out, Cc, x.H, x.W), res_out
+
+    def self_attention(self, p, qk, vt, a, B, d, HW, Cc, ldvt, scale):
+        """attn1 of block `p` on the fused q | k rows and V^T: one bc_attention launch over the batch.  In a PAG layer (self.pag_layers) the
+        last self.pag_images images skip Q, K and the softmax - their attention output is their own to_v output (attention_processor.py
+        PAGIdentitySelfAttnProcessor2_0 / PAGCFGIdentitySelfAttnProcessor2_0) - so the same launch runs on the images in front of them and
+        bc_attention_identity fills the rest of `a` from V^T."""
+        rec = self.rec
+        n_ptb = self.pag_images if p in self.pag_layers else 0
+        assert 0 <= n_ptb < B and (n_ptb == 0 or B == self.B), "PAG: the perturbed images are the last ones of the whole UNet batch"
+        rec.attention(qk, qk, vt, a, B - n_ptb, self.heads, d, HW, HW, 2 * Cc, 2 * Cc, ldvt, Cc, HW * 2 * Cc, HW * 2 * Cc, Cc * ldvt, HW * Cc,
+                      scale, q_off=0, k_off=Cc)
+        if n_ptb:
+            rec.attention_identity(vt, a, B, B - n_ptb, HW, Cc, ldvt, Cc)
 
     def attention_ip(self, bp, q, a, B, HW, Cc, d, scale):
         """The image cross-attention of every loaded IP-Adapter behind attn2's text attention, on the same query rows `q` and accumulated
@@ -523,8 +537,7 @@ class TrunkPlan:
         qk = proj(h, bp + "attn1.to_qk", 3 * Cc, Cc, G128, ln=bp + "norm1", bias=False, extra=(bp + "attn1.to_v.weight",), C_t=vt, ldc_t=ldvt,
                   n_t0=2 * Cc, rows_per_batch=HW, kind="qkv")
         a = rec.empty(M, Cc)
-        rec.attention(qk, qk, vt, a, B, self.heads, d, HW, HW, 2 * Cc, 2 * Cc, ldvt, Cc, HW * 2 * Cc, HW * 2 * Cc, Cc * ldvt, HW * Cc,
-                      scale, q_off=0, k_off=Cc)
+        self.self_attention(p, qk, vt, a, B, d, HW, Cc, ldvt, scale)
         h = proj(a, bp + "attn1.to_out.0", Cc, Cc, G128, R=h, ldr=Cc, kind="attn_out")
         folded = getattr(self, "ctx_folded", {}).get(bp) if pw.has_cross else None
         if folded is not None and rec.lib.bc_gemm_wreg_eligible(M, 128 * self.heads, Cc, 0, G128) and rec.lib.bc_gemm_wreg_eligible(M, Cc, 80 * self.heads, 0, G128):
@@ -600,8 +613,7 @@ class TrunkPlan:
             self.dense(ln, M, Cc, None, Cc, bias=False, wkey=bp + "attn1.to_v.weight", out=vt, out_mode=_lib.OUT_F16_T,
                        ldc=ldvt, rows_per_batch=HW, kind="qkv")
         a = rec.empty(M, Cc)
-        rec.attention(qk, qk, vt, a, B, self.heads, d, HW, HW, 2 * Cc, 2 * Cc, ldvt, Cc, HW * 2 * Cc, HW * 2 * Cc,
-                      Cc * ldvt, HW * Cc, scale, q_off=0, k_off=Cc)
+        self.self_attention(p, qk, vt, a, B, d, HW, Cc, ldvt, scale)
         h = self.dense(a, M, Cc, bp + "attn1.to_out.0", Cc, R=h, ldr=Cc, kind="attn_out")
         # --- cross attention (UNet only)
         if pw.has_cross:

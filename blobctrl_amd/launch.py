@@ -645,6 +645,16 @@ class Recorder:
                  shape=(B, heads, d, Nq, Nkv), bytes_=2 * B * heads * d * (2 * Nq + 2 * Nkv))
         return out
 
+    def attention_identity(self, Vt, out, B, b0, HW, Cc, ldvt, ldo):
+        """bc_attention_identity (include/blobctrl_pag.h): the self-attention of the perturbed images [b0, B) of a PAG layer - their rows
+        of `out` are their own V, transposed out of `Vt` [B][Cc][ldvt].  Stands behind the bc_attention launch of the first b0 images."""
+        self.keep.append((Vt, out))
+        for t in (Vt, out):
+            self.register(t)
+        self._op("bc_attention_identity", (Vt, out, B, b0, HW, Cc, ldvt, ldo), "attention_identity", variant="attention_identity_kernel",
+                 shape=("attention_identity", B - b0, HW, Cc), bytes_=2 * 2 * (B - b0) * HW * Cc)
+        return out
+
     def attention_ip(self, Q, K, V, out, B, rows_per_batch, heads, d, T, ldq, ldkv, ldo, scale, w, q_off=0):
         """bc_attention_ip (include/blobctrl_ip.h): the image cross-attention of one IP-Adapter accumulated onto `out` - attn2's text
         attention output - in place.  K / V [B][T][ldkv] row-major, `w` = the fp32 device word holding this (block, adapter)'s scale."""

@@ -238,6 +238,7 @@ class UNet2DConditionModel(_TrunkModule):
         super().__init__(state_dict, config, device, lazy)
         self.__dict__["freeu"] = None          # (s1, s2, b1, b2) after enable_freeu
         self.__dict__.setdefault("ip_adapters", [])        # loaded IP-Adapters: device weights + the scale table of each
+        self.__dict__["pag"] = None            # (chunks of the batch, block prefixes) after set_pag_attn_processors
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, extra_in_channels=0, lora_path=None, lora_scale=1.0, device="cuda:0", **_ignored):
@@ -260,6 +261,19 @@ class UNet2DConditionModel(_TrunkModule):
     def disable_freeu(self):
         """Disables the FreeU mechanism."""
         self.__dict__["freeu"] = None
+
+    # ---- PAG (D/pipelines/pag/pag_utils.py `_set_pag_attn_processor`): the reference puts PAGCFGIdentitySelfAttnProcessor2_0 (batch = [uncond |
+    # cond | perturbed]) or PAGIdentitySelfAttnProcessor2_0 ([cond | perturbed]) on the named attn1 modules; here it is module state that the plans read
+    def set_pag_attn_processors(self, pag_applied_layers, do_classifier_free_guidance: bool = True):
+        """Perturb the self-attentions `pag_applied_layers` names (a string or a list of strings, matched as PAGMixin matches them; ValueError
+        for an id that matches nothing): in those blocks the last third of the batch - the last half with do_classifier_free_guidance False
+        - takes its own V as attention output.  forward then needs a batch that divides by 3 (by 2)."""
+        from . import pag
+        self.__dict__["pag"] = (3 if do_classifier_free_guidance else 2, pag.resolve_layers(self.trunk_config, pag_applied_layers))
+
+    def unset_pag_attn_processors(self):
+        """Back to the plain self-attention everywhere: the plans every other call uses."""
+        self.__dict__["pag"] = None
 
     # ---- IP-Adapter (D/loaders/unet.py:823-853: IPAdapterAttnProcessor2_0 in every attn2, encoder_hid_proj = the image projections)
     def load_ip_adapter_weights(self, state_dicts):
@@ -390,14 +404,15 @@ class UNet2DConditionModel(_TrunkModule):
                 up.append((rev[i],) + sizes[nb - 2 - i])
         return down, mid, up
 
-    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False, ip=(), ip_masked=False):
+    def _plan(self, B, H, W, T, Dc, with_res, cond=False, freeu=False, ip=(), ip_masked=False, pag=None):
         """`cond`: the plan takes a `timestep_cond` (fp16 [B][pad8(time_cond_proj_dim)]) and adds cond_proj of it to the sinusoid; a
         plan of its own, so that calls without one keep the launches they always recorded.  `freeu`: likewise a plan of its own, with
         bc_freeu in up_blocks.0 / up_blocks.1 reading (s1, s2, b1, b2) from the plan buffer P.freeu.  `ip_masked`: the call brings
         `ip_adapter_masks` - a plan of its own again, with bc_attention_ip_masked behind every attn2 and one fp16 mask buffer per adapter
-        and attention level (P.ip_adapters[i].mask_bufs); the key says "masked", never what the masks hold."""
+        and attention level (P.ip_adapters[i].mask_bufs); the key says "masked", never what the masks hold.  `pag` = (chunks, block
+        prefixes): a plan of its own whose attn1 in those blocks is the identity on V for the last B / chunks images."""
         key = (B, H, W, T, Dc, with_res) + (("cond",) if cond else ()) + (("freeu",) if freeu else ()) + ((("ip",) + tuple(ip),) if ip else ()) + \
-            ((("ip", "masked"),) if ip and ip_masked else ())
+            ((("ip", "masked"),) if ip and ip_masked else ()) + ((("pag", pag[0]) + tuple(pag[1]),) if pag else ())
         if key not in self._plans:
             rec = Recorder(self.device)
             P = type("Plan", (), {})()
@@ -415,6 +430,10 @@ class UNet2DConditionModel(_TrunkModule):
             P.residuals = residuals
             P.seg = rec.begin("unet")
             plan = TrunkPlan(rec, self.weights, self.trunk_config, B, H, W)
+            if pag:
+                if B % pag[0]:
+                    raise ValueError(f"PAG attention processors are set for a batch of {pag[0]} chunks; this batch is {B}")
+                plan.pag_layers, plan.pag_images = frozenset(pag[1]), B // pag[0]
             if freeu:
                 P.freeu = plan.freeu_params = rec.zeros(4, dtype=torch.float32)
             if ip:
@@ -495,7 +514,7 @@ class UNet2DConditionModel(_TrunkModule):
         embeds, masks = self.__dict__.get("_image_embeds"), self.__dict__.get("_ip_masks")
         P = self._plan(B, H, W, T, Dc, is_blobnet, cond=timestep_cond is not None, freeu=freeu_enabled(freeu),
                        ip=tuple(int(e.shape[1]) if e.ndim == 3 else (int(e.shape[1]), int(e.shape[2])) for e in embeds) if embeds else (),
-                       ip_masked=bool(embeds) and masks is not None)
+                       ip_masked=bool(embeds) and masks is not None, pag=self.__dict__.get("pag"))
         for buf, e in zip(getattr(P, "ip_embeds", ()), embeds or ()):
             buf.copy_(e.to(self.device, torch.float16).reshape(buf.shape))
         if embeds and masks is not None:

@@ -28,6 +28,7 @@ from .launch import Recorder
 from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, stack_request_tables, table_class
 from .weights import PackedTrunk, lora_scale_of, pad8
 from . import ip_masks
+from . import pag as pag_mod
 
 
 def get_guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -172,11 +173,12 @@ class BlobCtrlEngine(_PreviewVAE):
             self._plans.pop(k).rec.close()
         self.ip_adapters = list(adapters or [])
 
-    def _ip_layout(self, embeds, Bu, B, duplicated):
+    def _ip_layout(self, embeds, Bu, B, duplicated, pag=False):
         """`ip_adapter_image_embeds` of a call -> (plan entry per adapter, [fp16-able tensor] per adapter).  One tensor per loaded adapter,
         batch = the UNet batch ([negative, positive] halves with classifier-free guidance): 3D [Bu][images][embed_dim] for a base adapter
         (entry: images), 4D [Bu][images][S][embed_dims] - the image encoder's hidden states - for an IP-Adapter Plus (entry: (images, S)).
-        `duplicated`: the plan runs the positive prompts in both halves, so B rows are taken twice."""
+        `duplicated`: the plan runs the positive prompts in both halves, so B rows are taken twice.  `pag`: a PAG plan runs B perturbed
+        images behind the `Bu` the call brings; they take the rows of the positive chunk again (_prepare_perturbed_attention_guidance)."""
         if embeds is None:
             if self.ip_adapters:
                 raise ValueError(f"{len(self.ip_adapters)} IP-Adapter(s) are loaded: pass `ip_adapter_image_embeds` (one tensor per adapter), or unload them")
@@ -199,7 +201,7 @@ class BlobCtrlEngine(_PreviewVAE):
             if e.shape[0] != Bu:
                 raise ValueError(f"`ip_adapter_image_embeds` hold {e.shape[0]} rows, the UNet batch of this call is {Bu} "
                                  "(with classifier-free guidance: the negative and the positive halves)")
-            out.append(e)
+            out.append(torch.cat([e, e[-B:]], 0) if pag else e)
         return tuple(int(e.shape[1]) if e.ndim == 3 else (int(e.shape[1]), int(e.shape[2])) for e in out), out
 
     @staticmethod
@@ -212,7 +214,7 @@ class BlobCtrlEngine(_PreviewVAE):
 
     # ------------------------------------------------------------------------------------------------ planning
     def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-              freeu=False, requests=False, ip=(), ip_masked=False):
+              freeu=False, requests=False, ip=(), ip_masked=False, pag=()):
         """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
         conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
         named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
@@ -242,16 +244,29 @@ class BlobCtrlEngine(_PreviewVAE):
         per image, weighted by that image's mask), and the plan owns one named fp16 buffer `ip_mask<i>_<rows>` [images][rows] per adapter and
         attention level, refilled per edit (ip_masks.fill_plan_masks).  A plan of its own; the key gains "masked" and the images per
         adapter, never the masks: another mask of the same shape replays the same plan and the same whole-edit graph.
+        pag: perturbed-attention guidance - the sorted tuple of block prefixes ("mid_block.attentions.0.", ...) whose attn1 is perturbed
+        (pag.resolve_layers).  The UNet runs B more images, the perturbed ones, behind the others: [uncond | cond | perturbed] (3B), or
+        with `single` [cond | perturbed] (2B); `ctx`, `timestep_cond` and every `ip_embeds<i>` are sized for that batch and the last chunk
+        is filled with a copy of the cond chunk.  In the named blocks bc_attention runs on the images in front and bc_attention_identity
+        gives the perturbed ones their own V; both step segments end in bc_pag_scheduler_step, which reads the scale of the step from the
+        named buffer `pag_table` (fp32 [nsteps], refilled per edit).  The key holds the prefixes and never the scales: another pag_scale
+        or pag_adaptive_scale replays the same plan and the same whole-edit graph.  No CFG-prefix sharing (it pairs images b and b + Bu /
+        2) and no BC_SPLIT_CFG; not with `requests`.  In-process only.
         `denoise` and `compile_plan` take every one of these switches from the EditSetup of their call (`_setup`) and fill the tables
         with `_write_tables`; a call without lists never asks for `requests`."""
         if requests and not per_request:
             raise ValueError("per-request schedules need a request batch (per_request)")
+        pag = tuple(pag or ())
+        if pag and requests:
+            raise NotImplementedError("perturbed-attention guidance with per-request schedules: bc_pag_scheduler_step reads ONE coefficient "
+                                      "table and ONE pag_table; run the requests with shared steps, guidance scale, window and eta")
         if stochastic and third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
         key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
             (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ()) + (("requests",) if requests else ()) + \
             (((("ip", len(ip)) + tuple(self._ip_key(entry, ad) for entry, ad in zip(ip, self.ip_adapters))),) if ip else ()) + \
-            (((("ip", "masked") + tuple(e if isinstance(e, int) else e[0] for e in ip)),) if ip and ip_masked else ())
+            (((("ip", "masked") + tuple(e if isinstance(e, int) else e[0] for e in ip)),) if ip and ip_masked else ()) + \
+            (((("pag",) + pag),) if pag else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -278,7 +293,10 @@ class BlobCtrlEngine(_PreviewVAE):
         P.bg_score = rec.zeros(Bi, h, w, dtype=f32, name="bg_score")
         P.feat = rec.zeros(Bi, max(F, 1), dtype=f32, name="feat")
         Bu = B if single else 2 * B                          # images the UNet runs: the CFG pair of every sample, or the sample alone
-        P.single = bool(single)
+        if pag:
+            Bu += B                                          # ... and behind them the perturbed copy of the (conditional) sample
+        P.single, P.pag = bool(single), pag
+        P.pag_table = rec.zeros(nsteps, dtype=f32, name="pag_table") if pag else None
         P.ctx = rec.zeros(Bu, T, ctx_dim, name="ctx")
         # a UNet with time_cond_proj_dim (a distilled LCM UNet): the guidance-scale embedding of every UNet image, replay-time data like
         # the guidance scale itself - zero when the caller gives none (cond_proj has no bias: the add is then + 0)
@@ -322,6 +340,7 @@ class BlobCtrlEngine(_PreviewVAE):
         P.prologue = rec.begin("prologue")
         unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_a.freeu_params = P.freeu
+        unet_a.pag_layers, unet_a.pag_images = frozenset(pag), B if pag else 0
         made = [IpAdapter.for_plan(rec, ad, Bu, entry, name=f"ip_embeds{i}", masked=bool(ip_masked), mask_name=f"ip_mask{i}")
                 for i, (entry, ad) in enumerate(zip(ip, self.ip_adapters))]
         unet_a.ip_adapters, P.ip_embeds = [m[0] for m in made], [m[1] for m in made]
@@ -341,7 +360,7 @@ class BlobCtrlEngine(_PreviewVAE):
             blob.record_time_table(P.t_table, nsteps, P.step_idx)          # (BlobNet never has a cond_proj: pipe:1063 passes no timestep_cond)
 
         # CFG halves on two streams (opt-in, BC_SPLIT_CFG=1; single edits only - larger batches fill the GPU with the batch-2B UNet)
-        split_cfg = B == 1 and self.two_streams and not temb_per_step and bool(os.environ.get("BC_SPLIT_CFG")) and not single
+        split_cfg = B == 1 and self.two_streams and not temb_per_step and bool(os.environ.get("BC_SPLIT_CFG")) and not single and not pag
         P.split_cfg = split_cfg
         if split_cfg:
             # the uncond / cond halves of the UNet batch as two batch-B plans on their own streams (ids 0 and 2): more concurrent
@@ -391,8 +410,13 @@ class BlobCtrlEngine(_PreviewVAE):
                 rec.wait(joined)
                 eps = P.eps_all
             else:
-                eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=not single)   # (images b and b + B: the CFG pair)
+                # (images b and b + B: the CFG pair; a PAG batch is no batch of pairs - cfg_prefix_ok would pair b with b + Bu / 2)
+                eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=not single and not pag)
             P.eps = eps
+            if pag:                                               # one entry point, every step form: noise (or NULL), nsteps, third, single
+                rec.call("bc_pag_scheduler_step", eps, P.latents, P.coef, P.step_idx, P.hist, P.pag_table, B, h, w, P.variance_noise, nsteps,
+                         int(P.third_order), int(single), P.eps_guided, 1, kind="cfg_step")
+                return
             if requests:                                          # one entry point, every step form: noise (or NULL), nsteps, third, single
                 rec.call("bc_scheduler_step_requests", eps, P.latents, P.coef, P.step_idx, P.hist, B, h, w, P.variance_noise, nsteps,
                          int(P.third_order), int(single), P.eps_guided, 1, kind="cfg_step")
@@ -433,6 +457,7 @@ class BlobCtrlEngine(_PreviewVAE):
         P.step_inactive = rec.begin("step_inactive")
         unet_i = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
         unet_i.freeu_params = P.freeu
+        unet_i.pag_layers, unet_i.pag_images = unet_a.pag_layers, unet_a.pag_images
         unet_i.ctx_kv, unet_i.ctx_kvs, unet_i.ctx_folded = unet_a.ctx_kv, getattr(unet_a, "ctx_kvs", {}), getattr(unet_a, "ctx_folded", {})
         unet_i.ip_kv = unet_a.ip_kv
         if not temb_per_step:
@@ -758,8 +783,9 @@ class BlobCtrlEngine(_PreviewVAE):
         return self.variance_noise(S.n, B, h, w, generator, device, [any(d[i] for d in draws) for i in range(S.n)])
 
     @staticmethod
-    def _write_tables(P, S, freeu):
-        """The tables of an edit into the plan's buffers; returns the buffers written (what `compile_plan` saves with their contents)."""
+    def _write_tables(P, S, freeu, pag_scales=(0.0, 0.0)):
+        """The tables of an edit into the plan's buffers; returns the buffers written (what `compile_plan` saves with their contents).
+        `pag_scales` = (pag_scale, pag_adaptive_scale) of a PAG plan: `pag_table` takes _get_pag_scale of every evaluation's timestep."""
         f32 = torch.float32
         if S.requests:
             P.t_rows_blob.copy_(S.t_rows)
@@ -770,8 +796,10 @@ class BlobCtrlEngine(_PreviewVAE):
         P.scale_table.copy_(torch.tensor(S.scale_rows, dtype=f32).reshape(-1))
         if P.freeu is not None:
             P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=f32))
+        if getattr(P, "pag_table", None) is not None:
+            P.pag_table.copy_(torch.tensor(pag_mod.pag_table(S.t_rows[:, 0].tolist(), *pag_scales), dtype=f32))
         return ([P.t_rows_blob, P.t_rows_unet] if S.requests else [P.t_table]) + [P.coef, P.scale_table] + \
-            ([P.freeu] if P.freeu is not None else [])
+            ([P.freeu] if P.freeu is not None else []) + ([P.pag_table] if getattr(P, "pag_table", None) is not None else [])
 
     @staticmethod
     def _mark_stored(P, tables, variance_noise):
@@ -788,9 +816,12 @@ class BlobCtrlEngine(_PreviewVAE):
                 P.variance_noise.zero_()
                 P.rec._workspace.add(key)
 
-    def _prompt_layout(self, prompt_embeds, latents, guidance_on, do_classifier_free_guidance, single_pass):
+    def _prompt_layout(self, prompt_embeds, latents, guidance_on, do_classifier_free_guidance, single_pass, pag=False):
         """The layout of `prompt_embeds` and the plan form it asks for: (prompt_embeds as the plan's `ctx` takes them, B, T, ctx_dim,
-        single, guidance_off).  `guidance_on`: the call's guidance scale (any of them, in a request batch with its own) is above 1."""
+        single, guidance_off).  `guidance_on`: the call's guidance scale (any of them, in a request batch with its own) is above 1.
+        `pag`: the call runs perturbed-attention guidance - with guidance off the UNet batch is [cond | perturbed] whatever `single_pass`
+        says (the `single` form of a PAG plan; the duplicated form would be [cond | cond | perturbed] at scale 1), and the prompts of the
+        perturbed chunk, a copy of the conditional ones, go behind the others."""
         if do_classifier_free_guidance is None:
             do_classifier_free_guidance = guidance_on and self.unet_cfg.time_cond_proj_dim is None      # (pipe:497)
             if not do_classifier_free_guidance:
@@ -799,7 +830,7 @@ class BlobCtrlEngine(_PreviewVAE):
                                      "positive prompts only) or =True (negative and positive halves) - the layout cannot be inferred")
                 do_classifier_free_guidance = prompt_embeds.shape[0] != latents.shape[0]
         guidance_off = not guidance_on or not do_classifier_free_guidance
-        single = self._single_pass(single_pass, guidance_off)
+        single = True if (pag and guidance_off) else self._single_pass(single_pass, guidance_off)
         if not do_classifier_free_guidance and not single:
             prompt_embeds = torch.cat([prompt_embeds, prompt_embeds], 0)
         B2, T, Dc = prompt_embeds.shape
@@ -811,6 +842,8 @@ class BlobCtrlEngine(_PreviewVAE):
             B = B2 // 2
             if single:
                 prompt_embeds = prompt_embeds[B:]                    # (both halves given, scale <= 1: eps is the positive half's)
+        if pag:
+            prompt_embeds = torch.cat([prompt_embeds, prompt_embeds[-B:]], 0)
         return prompt_embeds, B, T, Dc, single, guidance_off
 
     @staticmethod
@@ -852,7 +885,28 @@ class BlobCtrlEngine(_PreviewVAE):
             P.timestep_cond.zero_()
             if timestep_cond is not None:                # (both CFG halves of a sample take the sample's embedding)
                 tc = timestep_cond.to(dev, torch.float16)
-                P.timestep_cond[:, : tc.shape[1]].copy_(tc if P.single else torch.cat([tc, tc], 0))
+                P.timestep_cond[:, : tc.shape[1]].copy_(torch.cat([tc] * (P.timestep_cond.shape[0] // tc.shape[0]), 0))
+
+    def _pag_layers(self, pag_scale, pag_adaptive_scale, pag_applied_layers, listed=False):
+        """The PAG part of a call's plan key: the sorted block prefixes when perturbed-attention guidance is active, else ()."""
+        for name, v in (("pag_scale", pag_scale), ("pag_adaptive_scale", pag_adaptive_scale)):
+            if isinstance(v, (list, tuple)):
+                raise NotImplementedError(f"{name}: a list of per-request values is not supported - a PAG plan reads one `pag_table`, shared by "
+                                          "every request of the batch")
+        if isinstance(pag_applied_layers, str):
+            pag_applied_layers = (pag_applied_layers,)
+        if not pag_mod.is_active(pag_scale, pag_applied_layers):
+            return ()
+        if listed:
+            raise NotImplementedError("perturbed-attention guidance with per-request schedules (a list for num_inference_steps, guidance_scale, "
+                                      "the control window, eta or timesteps): bc_pag_scheduler_step reads one coefficient table and one pag_table")
+        known = {n[: -len("transformer_blocks.0.attn1")] for n in pag_mod.self_attention_names(self.unet_cfg)}
+        layers = tuple(sorted(set(pag_applied_layers)))
+        for p in layers:
+            if p not in known:
+                raise ValueError(f"pag_applied_layers: {p!r} is no self-attention block prefix of this UNet (pag.resolve_layers turns layer ids "
+                                 f"such as 'mid' into prefixes such as 'mid_block.attentions.0.')")
+        return layers
 
     @torch.no_grad()
     def denoise(self, prompt_embeds: torch.Tensor, fg_image_latents: Optional[torch.Tensor] = None,
@@ -866,7 +920,8 @@ class BlobCtrlEngine(_PreviewVAE):
                  do_classifier_free_guidance: Optional[bool] = None, callback_self=None,
                  variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None,
                  single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None, freeu=None,
-                 ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None, ip_adapter_masks: Optional[List[torch.Tensor]] = None):
+                 ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None, ip_adapter_masks: Optional[List[torch.Tensor]] = None,
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -901,6 +956,13 @@ class BlobCtrlEngine(_PreviewVAE):
         cross_attention_kwargs["ip_adapter_masks"], checked as its processor checks them): the image prompt of image i acts where its mask
         is set.  Every UNet image shares them, in a request batch too, as the reference repeats one mask over the batch.  Per-edit data of
         the masked plan.  Ignored without a loaded adapter, as the reference's adapter-less processors ignore the key.
+        `pag_scale`, `pag_adaptive_scale`, `pag_applied_layers`: perturbed-attention guidance (pag_utils.py PAGMixin).  The layers are block
+        prefixes already resolved (pag.resolve_layers), e.g. ("mid_block.attentions.0.",).  Active when pag_scale > 0 and there is a layer
+        (`do_perturbed_attention_guidance`): the UNet then runs a perturbed copy of every conditional image whose attn1 in those blocks is
+        the identity on V, and eps gains pag_scale * (eps_cond - eps_perturbed) - with guidance off it is the only guidance, on the batch
+        [cond | perturbed].  pag_adaptive_scale > 0: the scale of a step at timestep t is max(0, pag_scale - pag_adaptive_scale * (1000 -
+        t)).  The scales are per-edit data of the PAG plan.  One setting per call, in a request batch too (per-request schedules and
+        lists for these arguments are refused); inactive, the call is the call without these arguments.
         A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps (a list of
         lists): the requests of a request batch run their own schedules, on the `requests` plan form.  Both kinds of call are one
         set-up (`_setup` -> EditSetup; a call without lists is "one table, shared by every image"), one plan, one run; `self.timesteps`
@@ -911,6 +973,7 @@ class BlobCtrlEngine(_PreviewVAE):
         listed = self._listed(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                               blobnet_control_guidance_start=blobnet_control_guidance_start,
                               blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps)
+        pag = self._pag_layers(pag_scale, pag_adaptive_scale, pag_applied_layers, bool(listed))
         if not listed:                                           # (a call without lists refuses its eta before anything else)
             self._check_eta(float(eta))
         if output_type not in ("latent", "pt", "np"):
@@ -936,7 +999,7 @@ class BlobCtrlEngine(_PreviewVAE):
         # `do_classifier_free_guidance=False` (what the reference derives from guidance_scale <= 1) says explicitly that prompt_embeds
         # holds the positive prompts only; without the flag the layout is inferred from `latents` and refused when ambiguous.
         prompt_embeds, B, T, Dc, single, guidance_off = self._prompt_layout(prompt_embeds, latents, self._guidance_on(guidance_scale),
-                                                                            do_classifier_free_guidance, single_pass)
+                                                                            do_classifier_free_guidance, single_pass, pag=bool(pag))
         h, w = fg_image_latents.shape[-2:]
         per_request, Bi, req_scales = self._request_batch(B, fg_image_latents, bg_image_latents, gs_score, dino_feats,
                                                           blobnet_conditioning_scale, generator)
@@ -945,11 +1008,12 @@ class BlobCtrlEngine(_PreviewVAE):
         self._check_timestep_cond(timestep_cond, B)
         self._check_variance_noise(S, variance_noise, (B, 4, h, w), generator)
         Bu = B if single else 2 * B
-        ip, ip_embeds = self._ip_layout(ip_adapter_image_embeds, Bu, B, duplicated=not single and prompt_embeds.shape[0] == 2 * B and guidance_off)
+        ip, ip_embeds = self._ip_layout(ip_adapter_image_embeds, Bu, B, duplicated=not single and not pag and prompt_embeds.shape[0] == 2 * B and guidance_off,
+                                             pag=bool(pag))
         if ip and ip_adapter_masks is not None:
             ip_adapter_masks = ip_masks.check_masks(ip_adapter_masks, [e if isinstance(e, int) else e[0] for e in ip])
         P = self._plan(B, h, w, T, Dc, S.n, per_request, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
-                       requests=S.requests, ip=ip, ip_masked=bool(ip) and ip_adapter_masks is not None)
+                       requests=S.requests, ip=ip, ip_masked=bool(ip) and ip_adapter_masks is not None, pag=pag)
         dev = self.device
         self.timesteps = [t.timesteps for t in S.tables] if S.requests else S.tables[0].timesteps
         if latents is None:                                                          # pipe:438-453
@@ -963,7 +1027,7 @@ class BlobCtrlEngine(_PreviewVAE):
             sigma = torch.tensor([t.init_noise_sigma for t in S.tables], dtype=torch.float32, device=dev)    # (one, or one per request)
             start = latents.to(dev, torch.float32) * sigma.view(-1, 1, 1, 1)
             self._fill_inputs(P, start, fg_image_latents, bg_image_latents, fg, bg, dino_feats, prompt_embeds, timestep_cond)
-            self._write_tables(P, S, freeu)
+            self._write_tables(P, S, freeu, (float(pag_scale), float(pag_adaptive_scale)))
             for buf, e in zip(P.ip_embeds, ip_embeds):
                 buf.copy_(e.to(dev, torch.float16).reshape(buf.shape))
             if P.ip_masked:
@@ -1051,6 +1115,8 @@ class BlobCtrlEngine(_PreviewVAE):
         the dispatcher as torch.ops.blobctrl.denoise (ops.py), everything else calls `denoise` directly."""
         plain = {"num_inference_steps", "guidance_scale", "latents", "blobnet_conditioning_scale", "blobnet_control_guidance_start",
                  "blobnet_control_guidance_end", "eta", "variance_noise"}
+        if not self._pag_layers(kw.get("pag_scale", 0.0), kw.get("pag_adaptive_scale", 0.0), kw.get("pag_applied_layers")):
+            kw = {k: v for k, v in kw.items() if k not in ("pag_scale", "pag_adaptive_scale", "pag_applied_layers")}   # (inactive: today's call)
         sc = kw.get("blobnet_conditioning_scale", 1.0)
         # (ints and anything else take `denoise` directly, which raises the reference's TypeError for them)
         is_list = isinstance(sc, (list, tuple))
@@ -1084,7 +1150,7 @@ class BlobCtrlEngine(_PreviewVAE):
 
     def compile_plan(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale=7.5, blobnet_conditioning_scale=1.0,
                      blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None, timesteps=None,
-                     single_pass=None, freeu=None):
+                     single_pass=None, freeu=None, pag_scale=0.0, pag_adaptive_scale=0.0, pag_applied_layers=None):
         """Write the launch plan of one edit configuration as a relocatable `.bcplan` file for the C plan runtime
         (include/blobctrl_hip.h: bc_plan_load / bc_plan_buffer / bc_step / bc_plan_capture_loop): segments "prologue",
         "step_active", "step_inactive"; packed weights and the scheduler / guidance tables stored with their contents; the per-edit
@@ -1108,6 +1174,10 @@ class BlobCtrlEngine(_PreviewVAE):
         (fg_lat, bg_lat, fg_score, bg_score, feat / feat16 with a leading B) it holds, saved with their contents, `coef` [B][nmax][16],
         `t_rows_unet` [nmax][2B or B], `t_rows_blob` [nmax][B] and `scale_table` [nmax][B] instead of `t_table` / `coef` [n][16] /
         `scale_table` [n]; `variance_noise` [nmax][B][4][h][w] as above; the segment names returned are those of the nmax steps."""
+        # (the three PAG arguments of `denoise`, taken so that a caller's keywords carry over: active PAG is refused, inactive is no PAG)
+        if self._pag_layers(pag_scale, pag_adaptive_scale, pag_applied_layers):
+            raise NotImplementedError("a plan with perturbed-attention guidance is recorded and replayed in-process only (bc_attention_identity "
+                                      "and bc_pag_scheduler_step are not part of the .bcplan format): run `denoise`")
         if self.ip_adapters:
             raise NotImplementedError("a plan with IP-Adapters loaded is recorded and replayed in-process only (bc_attention_ip is not part of "
                                       "the .bcplan format): unload them, or run `denoise`")
@@ -1133,8 +1203,8 @@ class BlobCtrlEngine(_PreviewVAE):
 
     # convenience for bench / tests ------------------------------------------------------------------
     def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-                 freeu=False, requests=False, ip=(), ip_masked=False):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip, ip_masked)
+                 freeu=False, requests=False, ip=(), ip_masked=False, pag=()):
+        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip, ip_masked, pag)
 
 
 def _is_device_image(image):
@@ -1172,7 +1242,8 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
     _callback_tensor_inputs = ["latents", "image_embeds", "negative_image_embeds"]
 
     def __init__(self, vae, unet, tokenizer, text_encoder, blobnet, scheduler, safety_checker=None, dinov2_processor=None,
-                 dinov2=None, requires_safety_checker: bool = False, use_graphs: bool = True, image_encoder=None, feature_extractor=None):
+                 dinov2=None, requires_safety_checker: bool = False, use_graphs: bool = True, image_encoder=None, feature_extractor=None,
+                 pag_applied_layers: Union[str, List[str]] = "mid"):
         from .image_processor import Dinov2ImageProcessor, VaeImageProcessor
         from .schedulers import TableScheduler
         if safety_checker is not None:
@@ -1197,12 +1268,36 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
         self.vae_scale_factor = 2 ** (nblocks - 1)                                                  # pipe:241
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_convert_rgb=True)    # pipe:242
         self._guidance_scale, self._clip_skip, self._num_timesteps = 7.5, None, 0
+        self._pag_scale, self._pag_adaptive_scale = 0.0, 0.0
+        self.set_pag_applied_layers(pag_applied_layers)               # (the PAG pipelines' constructor argument and default: "mid")
+
+    # ---- perturbed-attention guidance (D/pipelines/pag/pag_utils.py PAGMixin: the same names, defaults and errors)
+    def set_pag_applied_layers(self, pag_applied_layers: Union[str, List[str]]):
+        """The self-attention layers PAG perturbs: a layer name, a block name ("mid", "down_blocks.1"), a regex ("up_blocks.(1|2)") or a
+        list of them; ValueError for anything that is no string.  Names are matched against the UNet when a call uses them."""
+        self.pag_applied_layers = pag_mod.normalize_layers(pag_applied_layers)
+
+    @property
+    def pag_scale(self) -> float:
+        return self._pag_scale
+
+    @property
+    def pag_adaptive_scale(self) -> float:
+        return self._pag_adaptive_scale
+
+    @property
+    def do_pag_adaptive_scaling(self) -> bool:
+        return self._pag_adaptive_scale > 0 and self._pag_scale > 0 and len(self.pag_applied_layers) > 0
+
+    @property
+    def do_perturbed_attention_guidance(self) -> bool:
+        return self._pag_scale > 0 and len(self.pag_applied_layers) > 0
 
     # ---- construction as the scripts do it (inf:260-279)
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, unet=None, blobnet=None, dinov2_processor=None, dinov2=None,
                         vae=None, text_encoder=None, tokenizer=None, scheduler=None, safety_checker=None, torch_dtype=None,
-                        device="cuda:0", image_encoder=None, feature_extractor=None, **_ignored):
+                        device="cuda:0", image_encoder=None, feature_extractor=None, pag_applied_layers="mid", **_ignored):
         """`StableDiffusionBlobNetPipeline.from_pretrained(sd15_path, unet=, blobnet=, torch_dtype=, dinov2_processor=, dinov2=)`
         (inf:260-267; D/pipelines/pipeline_utils.py from_pretrained): components that are not passed are built from the sub-folders
         of the model directory - `vae/`, `text_encoder/`, `tokenizer/` (vocab.json + merges.txt), `scheduler/scheduler_config.json`,
@@ -1233,7 +1328,7 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
             scheduler = scheduler_from_config_dir(os.path.join(root, "scheduler"))
         return cls(vae=vae, unet=unet, tokenizer=tokenizer, text_encoder=text_encoder, blobnet=blobnet, scheduler=scheduler,
                    safety_checker=None, dinov2_processor=dinov2_processor, dinov2=dinov2, image_encoder=image_encoder,
-                   feature_extractor=feature_extractor)
+                   feature_extractor=feature_extractor, pag_applied_layers=pag_applied_layers)
 
     def splat_features_from_scores(self, scores: torch.Tensor, features: torch.Tensor, size: Optional[int],
                                    channels_last: bool = True) -> torch.Tensor:
@@ -1745,11 +1840,13 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
                  blobnet_control_guidance_start: Union[float, List[float]] = 0.0,
                  blobnet_control_guidance_end: Union[float, List[float]] = 1.0, clip_skip: Optional[int] = None,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: List[str] = ["latents"], return_sample: bool = False,
-                 **kwargs):
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
         """pipeline_blobnet.py:743-1166 with the same keyword names, defaults and error behaviour.  Returns
         StableDiffusionBlobNetPipelineOutput(images=..., nsfw_content_detected=None) or `(images, None)` for return_dict=False;
         `output_type` "pil" | "np" | "pt" | "latent".  Beyond the reference: `fg_image` / `bg_image` may be uint8 DEVICE tensors [H][W][3] of
-        exactly (height, width), as `blobctrl_amd.edit_inputs` builds them; they give the latents the same pixels give as PIL images."""
+        exactly (height, width), as `blobctrl_amd.edit_inputs` builds them; they give the latents the same pixels give as PIL images.
+        `pag_scale` / `pag_adaptive_scale`: perturbed-attention guidance as in the reference's PAG pipelines, on the layers of
+        `set_pag_applied_layers` (default "mid"); pag_scale = 0, the default, is the call without it."""
         callback_steps = kwargs.pop("callback_steps", None)
         if kwargs.pop("callback", None) is not None:
             raise NotImplementedError("`callback` is deprecated in the reference (pipe:868-875): use callback_on_step_end")
@@ -1789,6 +1886,13 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
         else:
             batch_size = prompt_embeds.shape[0]
         self._guidance_scale, self._clip_skip = guidance_scale, clip_skip
+        if isinstance(pag_scale, (list, tuple)) or isinstance(pag_adaptive_scale, (list, tuple)):
+            raise NotImplementedError("pag_scale / pag_adaptive_scale: one value per call (a PAG plan reads one pag_table, shared by the batch)")
+        self._pag_scale, self._pag_adaptive_scale = pag_scale, pag_adaptive_scale
+        pag_kw = {}
+        if self.do_perturbed_attention_guidance:                     # (else: the call the pipeline always made)
+            pag_kw = dict(pag_scale=float(pag_scale), pag_adaptive_scale=float(pag_adaptive_scale),
+                          pag_applied_layers=pag_mod.resolve_layers(self.unet.trunk_config, self.pag_applied_layers))
         cfg = self.do_classifier_free_guidance
         self.unet.set_lora_scale(lora_scale)
         # 3. prompt (pipe:937-949)
@@ -1841,7 +1945,7 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
                                     generator=generator, timesteps=timesteps, timestep_cond=timestep_cond,
                                     freeu=getattr(self.unet, "freeu", None), ip_adapter_image_embeds=ip_embeds,
-                                    ip_adapter_masks=ip_adapter_masks)
+                                    ip_adapter_masks=ip_adapter_masks, **pag_kw)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

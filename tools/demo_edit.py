@@ -24,7 +24,9 @@ edited one), and every attn2 runs bc_attention_ip_masked on the mask downsampled
 With --device-inputs --zoom PAD the edit is a zoomed ("only masked") one (blobctrl_amd.overlay): the box around the start and
 target ellipses, padded by PAD and grown to the frame's ratio, is blown up to the model's resolution (`zoom_edit`), the model edits that
 frame, and the result is pasted back over the original through the ellipses' mask blurred with --blur F (`blur`, `apply_overlay`) - all
-on the device; pixels outside the blurred mask keep the original's bytes."""
+on the device; pixels outside the blurred mask keep the original's bytes.
+With --pag-scale S [--pag-layers mid,up_blocks.1] [--pag-adaptive-scale A] the edit runs perturbed-attention guidance (blobctrl_amd.pag): the
+UNet takes a third copy of the sample whose self-attention in the named layers is the identity on V, and eps gains S (eps_cond - eps_perturbed)."""
 import argparse
 import os
 import sys
@@ -112,6 +114,9 @@ def main():
     ap.add_argument("--ip-image", default=None, help="the image prompt (any file PIL opens); seeded noise without it")
     ap.add_argument("--ip-mask", default=None, metavar="blob|FILE",
                     help="confine the image prompt (with --ip-adapter): 'blob' = the edit's target ellipse, or a mask image of the frame")
+    ap.add_argument("--pag-scale", type=float, default=0.0, metavar="S", help="perturbed-attention guidance scale (0 = off; the PAG pipelines use 3.0)")
+    ap.add_argument("--pag-layers", default="mid", metavar="IDS", help="comma-separated layer ids as diffusers' set_pag_applied_layers takes them (with --pag-scale)")
+    ap.add_argument("--pag-adaptive-scale", type=float, default=0.0, metavar="A", help="the scale falls by A per timestep below 1000 (with --pag-scale)")
     ap.add_argument("--preview-vae", default=None, metavar="PATH|synth", help="a TAESD folder (config.json + diffusion_pytorch_model.safetensors), or 'synth'")
     ap.add_argument("--preview-every", type=int, default=5, metavar="N", help="preview every N-th step (with --preview-vae)")
     ap.add_argument("--preview-dir", default="previews", metavar="DIR", help="where the step_<i>.png files go (with --preview-vae)")
@@ -266,6 +271,11 @@ def main():
             return {}
         ip_kwargs["callback_on_step_end"] = show
         print(f"--preview-vae {args.preview_vae}: a PNG every {args.preview_every} steps into {args.preview_dir} (a callback runs the loop step by step)")
+    if args.pag_scale > 0:
+        from blobctrl_amd import pag
+        layers = pag.resolve_layers(pipe.unet_cfg, args.pag_layers.split(","))
+        ip_kwargs.update(pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale, pag_applied_layers=layers)
+        print(f"--pag-scale {args.pag_scale}: {len(layers)} self-attention layers perturbed, UNet batch 3")
     otype = "pt" if args.zoom is not None else "np"           # a zoomed edit's result stays on the device for the paste-back
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,

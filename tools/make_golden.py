@@ -2819,6 +2819,183 @@ def golden_tiny_vae():
     assert 0.2 < lo and hi < 1.6, "a decoder layer's output has left the O(1) range: an error there would not reach the image"
 
 
+# ------------------------------------------------------------------------------------------------ perturbed-attention guidance (PAG)
+def _pag_shim(unet, layers, pag_scale=3.0, pag_adaptive_scale=0.0):
+    """A PAGMixin object around `unet`, as the reference's PAG pipelines are one: set_pag_applied_layers has run."""
+    from diffusers.pipelines.pag.pag_utils import PAGMixin
+    shim = type("PagShim", (PAGMixin,), {})()
+    shim.unet, shim._pag_scale, shim._pag_adaptive_scale = unet, pag_scale, pag_adaptive_scale
+    shim.set_pag_applied_layers(layers)
+    return shim
+
+
+def _pag_gain(unet):
+    """The one changed weight of the PAG fixtures (tests/pag_common.py pag_tiny_unet_weights) on a reference UNet; returns it."""
+    from tests.pag_common import PAG_MID_VALUE_GAIN, PAG_MID_VALUE_KEY
+    sd = unet.state_dict()
+    sd[PAG_MID_VALUE_KEY] = sd[PAG_MID_VALUE_KEY] * PAG_MID_VALUE_GAIN
+    unet.load_state_dict(sd, strict=True)
+    return unet
+
+
+def _pag_names(unet):
+    from diffusers.models.attention_processor import PAGCFGIdentitySelfAttnProcessor2_0, PAGIdentitySelfAttnProcessor2_0
+    return [n for n, m in unet.named_modules() if isinstance(getattr(m, "processor", None), (PAGCFGIdentitySelfAttnProcessor2_0, PAGIdentitySelfAttnProcessor2_0))]
+
+
+def golden_blocks_pag():
+    """tests/golden/blocks_pag.npz: one Transformer2DModel at 320, 640 and 1280 channels with PAGCFGIdentitySelfAttnProcessor2_0 on attn1
+    (batch [uncond | cond | perturbed]) and one case with PAGIdentitySelfAttnProcessor2_0 ([cond | perturbed]) - tests/pag_common.py
+    PAG_BLOCK_CASES.  The cond and perturbed chunks get identical inputs; their outputs must lie at least 10 times the GPU bar of
+    tests/test_blocks_gpu.py (1e-2 of the output's max-abs) apart, or the fixture could not see a missing perturbation.  Outputs only
+    (fp32, every `sub`-th pixel); weights and inputs come from seeds on both sides."""
+    from diffusers.models.attention_processor import PAGCFGIdentitySelfAttnProcessor2_0, PAGIdentitySelfAttnProcessor2_0
+    from diffusers.models.transformers.transformer_2d import Transformer2DModel
+    from tests.pag_common import PAG_BLOCK_CASES, pag_block_inputs, pag_block_weights
+    out = {}
+    for name, p in PAG_BLOCK_CASES.items():
+        x, ctx = pag_block_inputs(name)
+        m = Transformer2DModel(num_attention_heads=p["heads"], attention_head_dim=p["C"] // p["heads"], in_channels=p["C"], num_layers=1,
+                               cross_attention_dim=p["ctx"], norm_num_groups=32).eval()
+        m.load_state_dict(pag_block_weights(name), strict=True)
+        m.transformer_blocks[0].attn1.set_processor(PAGCFGIdentitySelfAttnProcessor2_0() if p["chunks"] == 3 else PAGIdentitySelfAttnProcessor2_0())
+        with torch.no_grad():
+            y = m(x, encoder_hidden_states=ctx, return_dict=False)[0].numpy().astype(np.float32)
+        n = p["B"] // p["chunks"]
+        gap = float(np.abs(y[-n:] - y[-2 * n:-n]).max() / (1e-2 * np.abs(y).max()))
+        print(f"block {name}: out std {y.std():.4f}, perturbed vs cond chunk {gap:.1f} bars apart")
+        assert gap >= 10.0, (name, gap)
+        out[name] = y[:, :, ::p["sub"], ::p["sub"]]
+    path = os.path.join(OUT, "blocks_pag.npz")
+    np.savez_compressed(path, **out)
+    print("blocks_pag.npz: %.1f KB" % (os.path.getsize(path) / 1024))
+
+
+def golden_unet_pag():
+    """tests/golden/unet_tiny_pag.npz: the tiny UNet of build_tiny() at batch 3 = [uncond | cond | perturbed] (tests/pag_common.py
+    pag_unet_inputs, residual stand-ins pag_residual) with the processors PAGMixin._set_pag_attn_processor sets for PAG_UNET_LAYERS:
+    `eps_<case>` and `eps_off` (no PAG processor), at least 10 times the GPU bar (1e-2 of eps' scale, tests/test_freeu_gpu.py) apart.
+    The UNet carries the one changed weight of pag_tiny_unet_weights (see there).
+    Also the module names the reference matches for every id of PAG_MATCH_IDS (`match_<i>`: a JSON list, empty where it raises
+    ValueError) and `_get_pag_scale` over PAG_SCALE_TIMESTEPS for PAG_SCALE_CASES (`scale_<case>`)."""
+    from tests.pag_common import (PAG_MATCH_IDS, PAG_SCALE_CASES, PAG_SCALE_TIMESTEPS, PAG_UNET_GEOMETRY, PAG_UNET_LAYERS, pag_residual,
+                                  pag_unet_inputs)
+    _, H, W = PAG_UNET_GEOMETRY
+    x, ehs, seed = pag_unet_inputs()
+    t = torch.tensor(981)
+    down, mid, up = _freeu_residual_shapes(H, W)
+    down, mid, up = [pag_residual(seed + i, s) for i, s in enumerate(down)], pag_residual(seed + 100, mid), [pag_residual(seed + 200 + i, s) for i, s in enumerate(up)]
+    res = lambda: dict(down_block_add_samples=[r.clone() for r in down], mid_block_add_sample=mid.clone(), up_block_add_samples=[r.clone() for r in up])
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    run = lambda u: u(x, t, encoder_hidden_states=ehs, return_dict=False, **res())[0].numpy()
+    out = {"timestep": np.array(981), "eps_off": run(_pag_gain(build_tiny()[0]))}
+    assert np.array_equal(out["eps_off"][1], out["eps_off"][2]), "cond and perturbed images are identical without PAG"
+    for case, layers in PAG_UNET_LAYERS.items():
+        unet = _pag_gain(build_tiny()[0])
+        shim = _pag_shim(unet, layers)
+        shim._set_pag_attn_processor(shim.pag_applied_layers, True)
+        out[f"eps_{case}"] = eps = run(unet)
+        out[f"names_{case}"] = np.array(json.dumps(_pag_names(unet)))
+        gap = rel(eps, out["eps_off"]) / 1e-2
+        print(f"PAG UNet {case}: {len(_pag_names(unet))} layers, eps std {eps.std():.4f}, on vs off {gap:.1f} bars; uncond / cond rows equal off: "
+              f"{np.array_equal(eps[:2], out['eps_off'][:2])}")
+        assert gap >= 10.0 and np.array_equal(eps[:2], out["eps_off"][:2]), (case, gap)
+    for i, layer_id in enumerate(PAG_MATCH_IDS):
+        unet, _ = build_tiny()
+        shim = _pag_shim(unet, layer_id)
+        try:
+            shim._set_pag_attn_processor(shim.pag_applied_layers, True)
+            names = _pag_names(unet)
+            assert names
+        except ValueError:
+            names = []
+        out[f"match_{i}"] = np.array(json.dumps(names))
+        print(f"PAG layer id {layer_id!r}: {len(names)} modules")
+    out["match_ids"] = np.array(json.dumps(list(PAG_MATCH_IDS)))
+    for case, (s, a) in PAG_SCALE_CASES.items():
+        shim = _pag_shim(build_tiny()[0], "mid", s, a)
+        out[f"scale_{case}"] = np.array([float(shim._get_pag_scale(torch.tensor(ts))) for ts in PAG_SCALE_TIMESTEPS], dtype=np.float64)
+    assert out["scale_clamped"].min() == 0.0 and out["scale_clamped"].max() > 0.0
+    path = os.path.join(OUT, "unet_tiny_pag.npz")
+    np.savez_compressed(path, **out)
+    print("unet_tiny_pag.npz: %.1f KB" % (os.path.getsize(path) / 1024))
+
+
+def _pag_wrap_unet(unet, shim, guidance_scale, do_cfg):
+    """Make the reference pipeline's own loop compute PAG: `unet.forward` of this instance takes the call's batch - [uncond | cond], or
+    [cond] without classifier-free guidance - runs the real forward with the PAG processors on [uncond | cond | cond] ([cond | cond]),
+    every per-image argument and BlobNet add-sample duplicated the way _prepare_perturbed_attention_guidance duplicates `cond`, and hands
+    back [e_u | e_c + (s / g) (e_c - e_p)], so that the pipeline's e_u + g (e'_c - e_u) is e_u + g (e_c - e_u) + s (e_c - e_p); without
+    CFG it hands back e_c + s (e_c - e_p).  s = _get_pag_scale(t)."""
+    shim._set_pag_attn_processor(shim.pag_applied_layers, do_cfg)
+    inner = type(unet).forward
+
+    def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, cross_attention_kwargs=None, down_block_add_samples=None,
+                mid_block_add_sample=None, up_block_add_samples=None, added_cond_kwargs=None, return_dict=False, **kw):
+        assert not kw and not return_dict
+        n = sample.shape[0] // (2 if do_cfg else 1)
+        dup = lambda v: None if v is None else torch.cat([v, v[-n:]], 0)
+        added = None if added_cond_kwargs is None else {k: [dup(e) for e in v] if isinstance(v, list) else dup(v) for k, v in added_cond_kwargs.items()}
+        eps = inner(self, dup(sample), timestep, dup(encoder_hidden_states), timestep_cond=dup(timestep_cond),
+                    cross_attention_kwargs=cross_attention_kwargs, down_block_add_samples=[dup(r) for r in down_block_add_samples],
+                    mid_block_add_sample=dup(mid_block_add_sample), up_block_add_samples=[dup(r) for r in up_block_add_samples],
+                    added_cond_kwargs=added, return_dict=False)[0]
+        s = float(shim._get_pag_scale(timestep))
+        if do_cfg:
+            eu, ec, ep = eps.chunk(3)
+            return (torch.cat([eu, ec + (s / guidance_scale) * (ec - ep)], 0),)
+        ec, ep = eps.chunk(2)
+        return (ec + s * (ec - ep),)
+    unet.forward = types.MethodType(forward, unet)
+
+
+def golden_pipeline_call_pag():
+    """tests/golden/pipeline_call_pag.npz: the reference's own `__call__` (pipe:743-1166) on the tiny pipeline of pipeline_call_ip.npz
+    (case `ddim_neg2` of pipeline_call.npz, 3 steps, seeds of its own; the UNet with the one changed weight of pag_tiny_unet_weights) with its UNet wrapped by _pag_wrap_unet - the loop is the
+    reference's, only the UNet call computes the PAG batch.  Cases (tests/pag_common.py PAG_CALL_CASES): DDIM with PAG on
+    "mid", with an adaptive scale, with half the scale, PAG off, guidance-free (guidance_scale 1.0) with and without PAG, and
+    EulerDiscreteScheduler (a table that scales the model input) with and without PAG.  The pairs of PAG_CALL_PAIRS lie at least 10 times
+    the GPU bar (1e-2 of the latents' scale) apart."""
+    from PIL import Image
+    from diffusers import EulerDiscreteScheduler
+    from tests.common import FakeTokenizer, pipeline_cases
+    from tests.pag_common import PAG_CALL_CASES, PAG_CALL_LAYERS, PAG_CALL_PAIRS, PAG_CALL_SEEDS
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw0 = dict(pipeline_cases()["ddim_neg2"])
+    for k in ("scheduler", "seed", "rng_seed"):
+        kw0.pop(k)
+    kw0["num_inference_steps"] = 3
+    seed, rng_seed = PAG_CALL_SEEDS["seed"], PAG_CALL_SEEDS["rng_seed"]
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(3)}
+    for case, extra in PAG_CALL_CASES.items():
+        kw = dict(kw0)
+        kw["guidance_scale"] = extra.get("guidance_scale", kw0["guidance_scale"])
+        unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+        _pag_gain(unet)
+        sch = DDIMScheduler(**SD_SCHED, clip_sample=False, set_alpha_to_one=False)
+        if case.startswith("euler"):
+            sch = EulerDiscreteScheduler.from_config(sch.config)
+        pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob, scheduler=sch,
+                                              safety_checker=None, dinov2_processor=proc, dinov2=dino, requires_safety_checker=False)
+        pipe.set_progress_bar_config(disable=True)
+        if extra.get("pag_scale", 0.0) > 0:
+            shim = _pag_shim(unet, PAG_CALL_LAYERS, extra["pag_scale"], extra.get("pag_adaptive_scale", 0.0))
+            _pag_wrap_unet(unet, shim, kw["guidance_scale"], kw["guidance_scale"] > 1.0)
+        torch.manual_seed(rng_seed)
+        out[f"{case}_latents"] = pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]),
+                                      gs_score=torch.from_numpy(base["gs_score"]), height=64, width=64,
+                                      generator=torch.Generator().manual_seed(seed), output_type="latent", **kw).images.numpy()
+        out[f"{case}_timesteps"] = pipe.scheduler.timesteps.numpy()
+        print(f"pipeline __call__ PAG {case}: latents std {out[f'{case}_latents'].std():.4f}")
+    rel = lambda a, b: float(np.abs(out[f"{a}_latents"] - out[f"{b}_latents"]).max() / np.abs(out[f"{b}_latents"]).max())
+    gaps = {f"{a}/{b}": rel(a, b) / 1e-2 for a, b in PAG_CALL_PAIRS}
+    print("pipeline __call__ PAG: variants apart by (bars)", {k: round(v, 1) for k, v in gaps.items()})
+    assert min(gaps.values()) >= 10.0, gaps
+    path = os.path.join(OUT, "pipeline_call_pag.npz")
+    np.savez_compressed(path, **out)
+    print("pipeline_call_pag.npz: %.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -2875,6 +3052,9 @@ if __name__ == "__main__":
     golden_unet_ip_masks()
     golden_pipeline_call_ip_masks()
     golden_tiny_vae()
+    golden_blocks_pag()
+    golden_unet_pag()
+    golden_pipeline_call_pag()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
