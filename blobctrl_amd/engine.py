@@ -140,6 +140,36 @@ class TrunkPlan:
         self.ip_kv = {}                   # attn2 block prefix -> [(K_ip, V_ip, tokens per image, weight word)] per adapter
         self.pag_layers = frozenset()     # UNet of a PAG plan: the prefixes "<...>attentions.<j>." of the blocks whose attn1 is perturbed ...
         self.pag_images = 0               # ... for the last `pag_images` images of the batch (PAGIdentitySelfAttnProcessor2_0: their own V)
+        self.ctx_kv = {}                  # attn2 block prefix -> (K, V^T, prompt tokens, ld of V^T) of the prompt (record_context)
+        self.ctx_kvs = {}                 # ... -> the K / V^T fragment streams of CHAIN_MIDX, where the row-chain takes the block
+        self.ctx_folded = {}              # ... -> the prompt folded into attn2's weights (bc_ctx_fold), on the 1280-channel levels
+        self.tproj = None                 # time_emb_proj of every ResBlock: [B][temb_total] (record_time), or of every step ...
+        self.tproj_table = ()             # ... (device step counter, row stride) behind the row vector's address (record_time_table)
+        self.w8_img = None                # BlobNet of a request batch: the collapsed conv_in weight of every image (record_collapse)
+        self.res_events = None            # residual address -> event the BlobNet branch signals (record_forward sets both per forward)
+        self.res_bmod = 1
+
+    def share_from(self, other, images=None, time=None):
+        """Make this forward another forward of `other`'s plan: it reads what `other` recorded once per edit - FreeU parameters, PAG layers,
+        adapters, prompt and image K / V, the time table - and records none of it again.  `images` = (b0, b1): this forward runs images
+        b0 .. b1 - 1 of `other`'s batch and takes their part of the per-image state; the time table, rows [step][other.B], is then that of
+        `time`, a forward of this batch size that recorded one.  Returns self."""
+        assert (images is None) == (time is None), "a forward of part of the batch needs a time table of its own batch size, and only it"
+        time = time or other
+        self.freeu_params, self.ip_adapters = other.freeu_params, other.ip_adapters
+        self.pag_layers, self.pag_images = other.pag_layers, other.pag_images
+        self.tproj, self.tproj_table = time.tproj, time.tproj_table
+        if images is None:
+            self.ctx_kv, self.ctx_kvs, self.ctx_folded, self.ip_kv = other.ctx_kv, other.ctx_kvs, other.ctx_folded, other.ip_kv
+            return self
+        b0, b1 = images
+        self.ctx_kv = {bp: (ck[b0 * T:b1 * T], cvt[b0:b1], T, ld) for bp, (ck, cvt, T, ld) in other.ctx_kv.items()}
+        # (the K / V^T fragment streams of CHAIN_MIDX are laid out per image too: without the slice both halves fell back to the
+        #  unfused MID + attention launches, ADVICE r4)
+        self.ctx_kvs = {bp: kvs.view(other.B, -1)[b0:b1].reshape(-1) for bp, kvs in other.ctx_kvs.items()}
+        self.ctx_folded = {bp: tuple(t[b0:b1] for t in f) for bp, f in other.ctx_folded.items()}
+        self.ip_kv = {bp: [(K[b0:b1], V[b0:b1], *rest) for K, V, *rest in kv] for bp, kv in other.ip_kv.items()}
+        return self
 
     # ------------------------------------------------------------------------------------------- helpers
     def _r2(self, res_t, H, W):
@@ -293,7 +323,7 @@ class TrunkPlan:
         Cin = x.C + (skip.C if skip is not None else 0)
         off, n = pw.temb_slices[p]
         assert n == Cout
-        rowvec = (self.tproj.data_ptr() + off * 2, pw.temb_total) + getattr(self, "tproj_table", ())
+        rowvec = (self.tproj.data_ptr() + off * 2, pw.temb_total) + self.tproj_table
         h = self.gn_conv(x, skip, p + "norm1", 1e-5, p + "conv1", Cout, rowvec=rowvec)
         M = self.B * x.H * x.W
         if (p + "conv_shortcut.weight") in pw.h and self.sc_fold_ok(Cout, Cout, x.H, x.W, Cin, x.C if skip is not None else 0):
@@ -408,7 +438,7 @@ class TrunkPlan:
             h1 = rec.empty(M, Cc)
             w, v = packed(_lib.CHAIN_MID)
             ck, cvt, T, ldc_vt = self.ctx_kv[bp]
-            kvs = getattr(self, "ctx_kvs", {}).get(bp)
+            kvs = self.ctx_kvs.get(bp)
             if kvs is not None:
                 # the cross-attention runs inside the MID launch: q never leaves the workgroup, K / V^T come as fragment streams
                 a2 = rec.empty(M, Cc)
@@ -539,7 +569,7 @@ class TrunkPlan:
         a = rec.empty(M, Cc)
         self.self_attention(p, qk, vt, a, B, d, HW, Cc, ldvt, scale)
         h = proj(a, bp + "attn1.to_out.0", Cc, Cc, G128, R=h, ldr=Cc, kind="attn_out")
-        folded = getattr(self, "ctx_folded", {}).get(bp) if pw.has_cross else None
+        folded = self.ctx_folded.get(bp) if pw.has_cross else None
         if folded is not None and rec.lib.bc_gemm_wreg_eligible(M, 128 * self.heads, Cc, 0, G128) and rec.lib.bc_gemm_wreg_eligible(M, Cc, 80 * self.heads, 0, G128):
             # cross-attention with the prompt folded into per-image weights, once per edit: softmax(LN2(h) QK^T) in one launch (a 64 x 128
             # workgroup = one head's keys, padded; the scores never leave it), then the 80 kept probabilities per head x VO + bias + residual
@@ -905,7 +935,7 @@ class TrunkPlan:
         conv_in_name = "conv_in"
         if not im2col and x_in.shape[-1] == 8 and pad8(cfg.in_channels) > 8:
             raise ValueError("the rank-1-collapsed BlobNet input is consumed in its im2col form (bc_assemble_input_im2col, im2col=True)")
-        if im2col and getattr(self, "w8_img", None) is not None:
+        if im2col and self.w8_img is not None:
             # per-request batch (record_collapse per_image): one launch per image with that image's collapsed weight; the statistics totals
             # of the output are one table over the batch, every launch adding to its own image's rows
             def conv_in(r2=None):

@@ -23,10 +23,10 @@ from typing import List, Optional, Union
 import torch
 
 from . import _lib
-from .engine import IpAdapter, TrunkConfig, TrunkPlan, freeu_enabled
-from .launch import Recorder
+from .edit_plan import PlanSpec, record_plan
+from .engine import TrunkConfig, freeu_enabled
 from .schedulers import OPTION_KINDS, draw_variance_noise, randn_tensor, stack_request_tables, table_class
-from .weights import PackedTrunk, lora_scale_of, pad8
+from .weights import PackedTrunk, lora_scale_of
 from . import ip_masks
 from . import pag as pag_mod
 
@@ -56,7 +56,7 @@ class EditSetup(namedtuple("EditSetup", "requests tables n stochastic third_orde
     """What the arguments of an edit come to (`BlobCtrlEngine._setup`), for `denoise` to run and `compile_plan` to save.  A call without
     lists is the case "one table, shared by every image" of a call with lists, which has a table per request:
     requests: whether any argument was a list - the plan form; tables: the table objects, one or B; n: the loop length (the longest
-    table's evaluations); stochastic, third_order, scaled: the step form and input scaling of the plan (`_plan`);
+    table's evaluations); stochastic, third_order, scaled: the step form and input scaling of the plan (`PlanSpec`);
     coef: [n][16] with the guidance scale in column 11, or [B][n][16] (`stack_request_tables`); t_rows: [n][1 or B] fp32, the timestep of
     every step and table; scale_rows: [n][Bi], conditioning scale * keep of every step and image; evals: evaluations per table."""
 
@@ -68,6 +68,12 @@ class EditSetup(namedtuple("EditSetup", "requests tables n stochastic third_orde
     @property
     def segments(self):
         return ["step_active" if a else "step_inactive" for a in self.active]
+
+    def plan_spec(self, B, h, w, T, ctx_dim, *, per_request, single, freeu=False, ip=(), ip_masked=False, pag=()):
+        """The PlanSpec of this set-up: the loop length, the step form, the input scaling and the request form are the set-up's, the rest
+        is the call's."""
+        return PlanSpec(B, h, w, T, ctx_dim, self.n, per_request, self.stochastic, self.third_order, self.scaled, single, freeu,
+                        self.requests, ip, ip_masked, pag)
 
 
 class _PreviewVAE:
@@ -204,69 +210,11 @@ class BlobCtrlEngine(_PreviewVAE):
             out.append(torch.cat([e, e[-B:]], 0) if pag else e)
         return tuple(int(e.shape[1]) if e.ndim == 3 else (int(e.shape[1]), int(e.shape[2])) for e in out), out
 
-    @staticmethod
-    def _ip_key(entry, ad):
-        """An adapter's part of a plan key: (image tokens per UNet image, width of its input[, tokens of a Plus adapter's hidden states])."""
-        from .weights import ip_adapter_embed_dim, ip_adapter_tokens
-        if ad.get("layout") == "plus":
-            return (ip_adapter_tokens(ad) * entry[0], ip_adapter_embed_dim(ad), entry[1])
-        return (ip_adapter_tokens(ad) * entry, ip_adapter_embed_dim(ad))
-
     # ------------------------------------------------------------------------------------------------ planning
-    def _plan(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
-              freeu=False, requests=False, ip=(), ip_masked=False, pag=()):
-        """per_request: the B samples are B independent edit requests (own fg / bg latents, scores, DINO features and
-        conditioning scales) instead of B variations of one edit.  stochastic: DDIM with eta > 0 or SDE-DPM-Solver++ - the plan owns the
-        named buffer `variance_noise` [nsteps][B][4][h][w] and its steps end in bc_cfg_scheduler_step_noise (eta and the noise itself are
-        per-call contents of the coefficient table and of that buffer, so one plan and its graphs serve every eta > 0 and every seed).
-        third_order: a table with third-order DPM-Solver++ rows (column 13) - the steps end in bc_cfg_scheduler_step3.  Every other
-        table (UniPC, DDIM, DPM-Solver++ of order 1 / 2) runs on the same plan: only the tables differ.
-        scaled: a table that scales the model input (Euler, Euler-ancestral, Heun: `scheduler.scale_model_input`, pipe:1032) - the BlobNet
-        and UNet inputs are assembled by the `_scaled` entry points, which divide the noisy latents by column 14 of the current row.  A
-        plan of its own (and with it graphs of its own): no other table ever replays these launches.
-        single: a guidance-free (single-pass) plan, pipe:1031 / 1095 with do_classifier_free_guidance False: `ctx` holds the B positive
-        prompts, the UNet runs once per request at batch B (no CFG pair, so no CFG-prefix sharing and no BC_SPLIT_CFG) and the step ends
-        in bc_scheduler_step_single, which takes the right half of image b as eps.  BlobNet is what it is in every plan: batch B.
-        freeu: FreeU is on (UNet2DConditionModel.enable_freeu) - every UNet forward runs bc_freeu in front of the six channel concats of
-        up_blocks.0 / up_blocks.1, reading (s1, s2, b1, b2) from the named buffer `freeu` (fp32 [4], refilled per edit: one plan and its
-        graphs serve every setting).  A plan of its own; BlobNet's up blocks never run it.
-        requests: a request batch (per_request) whose requests run their OWN schedules - step count, guidance scale, control window,
-        eta, timesteps.  The loop has nsteps = the longest request's evaluations; the plan owns `coef` [B][nsteps][16] (a table per
-        request, finished rows marked in column 15), `t_rows_unet` [nsteps][Bu] / `t_rows_blob` [nsteps][B] (a timestep per step and
-        image; no `t_table`) and `scale_table` [nsteps][B]; the time tables come from bc_timestep_embedding_rows, a scaling table
-        assembles through the `_requests` entry points (a divisor per image) and both step segments end in
-        bc_scheduler_step_requests.  The networks are what they are in every request batch.
-        ip: images per loaded IP-Adapter (empty: none).  The plan owns the named buffers `ip_embeds<i>` (fp16 [UNet batch * images][embed
-        dim], per-edit inputs like `ctx`); its prologue projects them to image tokens and to K_ip / V_ip per attn2 block, and every UNet
-        forward runs one bc_attention_ip per adapter behind each attn2 (16 per adapter).  The key holds the adapter configuration - count,
-        tokens each, embedding width - and never the scales, which the launches read from the adapters' device tables.  In-process only.
-        ip_masked: the call brings `ip_adapter_masks` - every attn2 runs bc_attention_ip_masked in the place of bc_attention_ip (one softmax
-        per image, weighted by that image's mask), and the plan owns one named fp16 buffer `ip_mask<i>_<rows>` [images][rows] per adapter and
-        attention level, refilled per edit (ip_masks.fill_plan_masks).  A plan of its own; the key gains "masked" and the images per
-        adapter, never the masks: another mask of the same shape replays the same plan and the same whole-edit graph.
-        pag: perturbed-attention guidance - the sorted tuple of block prefixes ("mid_block.attentions.0.", ...) whose attn1 is perturbed
-        (pag.resolve_layers).  The UNet runs B more images, the perturbed ones, behind the others: [uncond | cond | perturbed] (3B), or
-        with `single` [cond | perturbed] (2B); `ctx`, `timestep_cond` and every `ip_embeds<i>` are sized for that batch and the last chunk
-        is filled with a copy of the cond chunk.  In the named blocks bc_attention runs on the images in front and bc_attention_identity
-        gives the perturbed ones their own V; both step segments end in bc_pag_scheduler_step, which reads the scale of the step from the
-        named buffer `pag_table` (fp32 [nsteps], refilled per edit).  The key holds the prefixes and never the scales: another pag_scale
-        or pag_adaptive_scale replays the same plan and the same whole-edit graph.  No CFG-prefix sharing (it pairs images b and b + Bu /
-        2) and no BC_SPLIT_CFG; not with `requests`.  In-process only.
-        `denoise` and `compile_plan` take every one of these switches from the EditSetup of their call (`_setup`) and fill the tables
-        with `_write_tables`; a call without lists never asks for `requests`."""
-        if requests and not per_request:
-            raise ValueError("per-request schedules need a request batch (per_request)")
-        pag = tuple(pag or ())
-        if pag and requests:
-            raise NotImplementedError("perturbed-attention guidance with per-request schedules: bc_pag_scheduler_step reads ONE coefficient "
-                                      "table and ONE pag_table; run the requests with shared steps, guidance scale, window and eta")
-        if stochastic and third_order:
-            raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
-        key = (B, h, w, T, ctx_dim, nsteps, per_request, bool(stochastic)) + (("step3",) if third_order else ()) + \
-            (("scaled",) if scaled else ()) + (("single",) if single else ()) + (("freeu",) if freeu else ()) + (("requests",) if requests else ()) + \
-            (((("ip", len(ip)) + tuple(self._ip_key(entry, ad) for entry, ad in zip(ip, self.ip_adapters))),) if ip else ()) + \
-            (((("ip", "masked") + tuple(e if isinstance(e, int) else e[0] for e in ip)),) if ip and ip_masked else ()) + \
-            (((("pag",) + pag),) if pag else ())
+    def _plan(self, spec):
+        """The plan of a PlanSpec (edit_plan.py): the cached one, or recorded now - the least recently used plan then makes room."""
+        spec.validate()
+        key = spec.key(self.ip_adapters)
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)                   # mark as most recently used
             self.cache_stats["plan_hits"] += 1
@@ -277,198 +225,7 @@ class BlobCtrlEngine(_PreviewVAE):
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             old.rec.close()                                           # graphs and events of the evicted plan
-        dev = self.device
-        rec = Recorder(dev)
-        P = type("Plan", (), {})()
-        P.rec = rec
-        H, W = h, 2 * w
-        F = self.feat_dim
-        f32 = torch.float32
-        Bi = B if per_request else 1                         # images (fg / bg / score / feature sets) behind the batch
-        P.Bi = Bi
-        P.latents = rec.zeros(B, 4, h, w, dtype=f32, name="latents")
-        P.fg_lat = rec.zeros(Bi, 4, h, w, dtype=f32, name="fg_lat")
-        P.bg_lat = rec.zeros(Bi, 4, h, w, dtype=f32, name="bg_lat")
-        P.fg_score = rec.zeros(Bi, h, w, dtype=f32, name="fg_score")
-        P.bg_score = rec.zeros(Bi, h, w, dtype=f32, name="bg_score")
-        P.feat = rec.zeros(Bi, max(F, 1), dtype=f32, name="feat")
-        Bu = B if single else 2 * B                          # images the UNet runs: the CFG pair of every sample, or the sample alone
-        if pag:
-            Bu += B                                          # ... and behind them the perturbed copy of the (conditional) sample
-        P.single, P.pag = bool(single), pag
-        P.pag_table = rec.zeros(nsteps, dtype=f32, name="pag_table") if pag else None
-        P.ctx = rec.zeros(Bu, T, ctx_dim, name="ctx")
-        # a UNet with time_cond_proj_dim (a distilled LCM UNet): the guidance-scale embedding of every UNet image, replay-time data like
-        # the guidance scale itself - zero when the caller gives none (cond_proj has no bias: the add is then + 0)
-        cond_dim = self.unet_cfg.time_cond_proj_dim
-        P.timestep_cond = rec.zeros(Bu, pad8(cond_dim), name="timestep_cond") if cond_dim is not None else None
-        P.step_idx = rec.zeros(1, dtype=torch.int32, name="step_idx")
-        P.requests = bool(requests)
-        if requests:
-            P.t_table = None
-            P.t_rows_unet = rec.zeros(nsteps, Bu, dtype=f32, name="t_rows_unet")
-            P.t_rows_blob = rec.zeros(nsteps, B, dtype=f32, name="t_rows_blob")
-            P.coef = rec.zeros(B, nsteps, 16, dtype=f32, name="coef")
-        else:
-            P.t_table = rec.zeros(nsteps, dtype=f32, name="t_table")
-            P.coef = rec.zeros(nsteps, 16, dtype=f32, name="coef")
-        P.scale_table = rec.zeros(nsteps * Bi, dtype=f32, name="scale_table")   # [step][image] conditioning_scale * keep
-        P.hist = rec.zeros(3, B * 4 * h * w, dtype=f32, name="hist")
-        P.eps_guided = rec.zeros(B, 4, h, w, dtype=f32, name="eps_guided")
-        P.stochastic = bool(stochastic)
-        P.third_order = bool(third_order)
-        P.scaled = bool(scaled)
-        P.variance_noise = rec.zeros(nsteps, B, 4, h, w, dtype=f32, name="variance_noise") if stochastic else None
-        P.guidance = [7.5]
-        P.freeu = rec.zeros(4, dtype=f32, name="freeu") if freeu else None
-
-        # rank-1 collapse of the BlobNet feature channels (per-edit weight; round 6: per-IMAGE weights for a batch of independent requests -
-        # conv_in then runs as one launch per image, engine.record_collapse)
-        no_im2col = False
-        P.collapse = F > 3 and "conv_in.featmat" in self.blob_w.h and not no_im2col
-        unet_cin = pad8(self.unet_cfg.in_channels)
-        blob_cin = 8 if P.collapse else pad8(self.blob_cfg.in_channels)
-        # 8-channel inputs (the UNet's 4 latents + score; BlobNet's rank-1-collapsed 4 latents + 2 x score) are assembled directly as
-        # the 3x3 im2col operand [rows][128] of conv_in, which then runs as a dense GEMM on the LDS-DMA fast path (K = 72 does not)
-        P.unet_im2col = unet_cin == 8 and not no_im2col
-        P.blob_im2col = P.collapse
-        P.feat16 = rec.zeros(Bi, pad8(max(F, 1)), name="feat16")
-        P.blob_in = rec.zeros(B, H * W, 128 if P.blob_im2col else blob_cin)
-        P.unet_in = rec.zeros(Bu, H * W, 128 if P.unet_im2col else unet_cin)
-
-        # ---- prologue: prompt K/V
-        P.prologue = rec.begin("prologue")
-        unet_a = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
-        unet_a.freeu_params = P.freeu
-        unet_a.pag_layers, unet_a.pag_images = frozenset(pag), B if pag else 0
-        made = [IpAdapter.for_plan(rec, ad, Bu, entry, name=f"ip_embeds{i}", masked=bool(ip_masked), mask_name=f"ip_mask{i}")
-                for i, (entry, ad) in enumerate(zip(ip, self.ip_adapters))]
-        unet_a.ip_adapters, P.ip_embeds = [m[0] for m in made], [m[1] for m in made]
-        P.ip_adapters, P.ip_masked = unet_a.ip_adapters, bool(ip and ip_masked)     # (their mask_bufs fill up as the UNet forwards are recorded)
-        unet_a.record_context(P.ctx, T)
-        blob = TrunkPlan(rec, self.blob_w, self.blob_cfg, B, H, W)
-        if P.collapse:
-            blob.record_collapse(P.feat16, per_image=B if per_request else 0)
-        # time-embedding path of every step, once per edit (read in the step through the device step counter)
-        temb_per_step = False                                # (the per-edit table replaced the four launches per net inside every step)
-        if requests:
-            unet_a.record_time_table(P.t_rows_unet, nsteps, P.step_idx, per_image=True,
-                                     **({} if P.timestep_cond is None else dict(cond=P.timestep_cond)))
-            blob.record_time_table(P.t_rows_blob, nsteps, P.step_idx, per_image=True)
-        elif not temb_per_step:
-            unet_a.record_time_table(P.t_table, nsteps, P.step_idx, **({} if P.timestep_cond is None else dict(cond=P.timestep_cond)))
-            blob.record_time_table(P.t_table, nsteps, P.step_idx)          # (BlobNet never has a cond_proj: pipe:1063 passes no timestep_cond)
-
-        # CFG halves on two streams (opt-in, BC_SPLIT_CFG=1; single edits only - larger batches fill the GPU with the batch-2B UNet)
-        split_cfg = B == 1 and self.two_streams and not temb_per_step and bool(os.environ.get("BC_SPLIT_CFG")) and not single and not pag
-        P.split_cfg = split_cfg
-        if split_cfg:
-            # the uncond / cond halves of the UNet batch as two batch-B plans on their own streams (ids 0 and 2): more concurrent
-            # kernels for a GPU that one batch-2 UNet does not fill, at the price of reading the UNet weights twice per step
-            # (measured, same box, interleaved: 11.56 vs 11.73 ms per active step, +2-3 % edits/s; 1108 instead of 725 launches.
-            #  Not the default: it trades per-kernel efficiency - every self-attention then runs at batch 1, the 64x64-tile GEMM
-            #  becomes the largest kernel of the step - for concurrency, a gain inside the box-to-box spread)
-            half_time = TrunkPlan(rec, self.unet_w, self.unet_cfg, B, H, W)
-            half_time.record_time_table(P.t_table, nsteps, P.step_idx, **({} if P.timestep_cond is None else dict(cond=P.timestep_cond[:B])))
-            P.eps_all = rec.zeros(2 * B, H * W, self.unet_cfg.out_channels, dtype=f32)
-
-        def half_plan(b0):
-            hp = TrunkPlan(rec, self.unet_w, self.unet_cfg, B, H, W)
-            hp.freeu_params = P.freeu
-            hp.ctx_kv = {bp: (ck[b0 * T:(b0 + B) * T], cvt[b0:b0 + B], T_, ld) for bp, (ck, cvt, T_, ld) in unet_a.ctx_kv.items()}
-            # (the K / V^T fragment streams of CHAIN_MIDX are laid out per image too: without the slice both halves fell back to the
-            #  unfused MID + attention launches)
-            hp.ctx_kvs = {bp: kvs.view(2 * B, -1)[b0:b0 + B].reshape(-1) for bp, kvs in getattr(unet_a, "ctx_kvs", {}).items()}
-            hp.ctx_folded = {bp: tuple(t[b0:b0 + B] for t in f) for bp, f in getattr(unet_a, "ctx_folded", {}).items()}
-            hp.ip_kv = {bp: [(K[b0:b0 + B], V[b0:b0 + B], T_, w_, *ad_) for K, V, T_, w_, *ad_ in kv] for bp, kv in unet_a.ip_kv.items()}
-            hp.tproj, hp.tproj_table = half_time.tproj, half_time.tproj_table
-            return hp
-
-        # the input assembly of a net: the entry point's `_scaled` form, with (coef, step_idx, nsteps) in front of the output, when the
-        # table scales the model input (`_requests`: the same with a table, hence a divisor, per request)
-        divisor = (P.coef.data_ptr(), P.step_idx.data_ptr(), nsteps) if P.scaled else ()
-        suffix = ("_requests" if requests else "_scaled") if P.scaled else ""
-
-        def record_unet(plan, residuals):
-            if P.unet_im2col:
-                rec.call("bc_assemble_input_im2col" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), Bi, Bu,
-                         h, w, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
-            else:
-                rec.call("bc_assemble_input" + suffix, P.latents.data_ptr(), B, P.bg_lat.data_ptr(), P.bg_score.data_ptr(), None, Bi, 0,
-                         Bu, h, w, unet_cin, 0, *divisor, P.unet_in.data_ptr(), kind="assemble")
-            if temb_per_step:
-                plan.record_time(P.t_table, P.step_idx)
-            if split_cfg:
-                ready, joined = rec.new_event(), rec.new_event()
-                rec.signal(ready)                                   # unet_in assembled (stream 0)
-                rec.sid = 2
-                rec.wait(ready)
-                half_plan(B).record_forward(P.unet_in[B:], residuals, eps_out=P.eps_all[B:], im2col=P.unet_im2col)   # cond half
-                rec.signal(joined)
-                rec.sid = 0
-                half_plan(0).record_forward(P.unet_in[:B], residuals, eps_out=P.eps_all[:B], im2col=P.unet_im2col)   # uncond half
-                rec.wait(joined)
-                eps = P.eps_all
-            else:
-                # (images b and b + B: the CFG pair; a PAG batch is no batch of pairs - cfg_prefix_ok would pair b with b + Bu / 2)
-                eps = plan.record_forward(P.unet_in, residuals, im2col=P.unet_im2col, cfg_pairs=not single and not pag)
-            P.eps = eps
-            if pag:                                               # one entry point, every step form: noise (or NULL), nsteps, third, single
-                rec.call("bc_pag_scheduler_step", eps, P.latents, P.coef, P.step_idx, P.hist, P.pag_table, B, h, w, P.variance_noise, nsteps,
-                         int(P.third_order), int(single), P.eps_guided, 1, kind="cfg_step")
-                return
-            if requests:                                          # one entry point, every step form: noise (or NULL), nsteps, third, single
-                rec.call("bc_scheduler_step_requests", eps, P.latents, P.coef, P.step_idx, P.hist, B, h, w, P.variance_noise, nsteps,
-                         int(P.third_order), int(single), P.eps_guided, 1, kind="cfg_step")
-                return
-            if single:                                            # one entry point, every step form: noise (or NULL), nsteps, third
-                rec.call("bc_scheduler_step_single", eps, P.latents, P.coef, P.step_idx, P.hist, B, h, w, P.variance_noise, nsteps,
-                         int(P.third_order), P.eps_guided, 1, kind="cfg_step")
-                return
-            # the plan's step form: the entry point and what it takes between `w` and `eps_out`
-            name, extra = ("bc_cfg_scheduler_step_noise", (P.variance_noise, nsteps)) if P.stochastic else \
-                ("bc_cfg_scheduler_step3", (nsteps,)) if P.third_order else ("bc_cfg_scheduler_step", ())
-            rec.call(name, eps, P.latents, P.coef, P.step_idx, P.hist, -1.0, B, h, w, *extra, P.eps_guided, 1, kind="cfg_step")
-
-        # ---- step A: BlobNet + UNet
-        # The BlobNet branch is recorded for the side stream: fork (side waits for the start of the step on main), every
-        # residual is signalled when its zero-conv finishes, the UNet waits right before the GEMM whose epilogue adds it.
-        P.step_active = rec.begin("step_active")
-        fork = rec.new_event()
-        rec.signal(fork)
-        rec.sid = 1
-        rec.wait(fork)
-        if P.blob_im2col:
-            rec.call("bc_assemble_input_im2col" + suffix, P.latents.data_ptr(), B, P.fg_lat.data_ptr(), P.fg_score.data_ptr(), Bi, B, h, w,
-                     1, *divisor, P.blob_in.data_ptr(), kind="assemble")
-        else:
-            rec.call("bc_assemble_input" + suffix, P.latents.data_ptr(), B, P.fg_lat.data_ptr(), P.fg_score.data_ptr(),
-                     P.feat.data_ptr() if F > 0 else None, Bi, F, B, h, w, blob_cin, 0, *divisor, P.blob_in.data_ptr(), kind="assemble")
-        if temb_per_step:
-            blob.record_time(P.t_table, P.step_idx)
-        residuals = blob.record_forward(P.blob_in, None, zero_scale=(1.0, P.scale_table, P.step_idx, B if per_request else 0),
-                                        signal_residuals=True, im2col=P.blob_im2col)
-        rec.sid = 0
-        P.residuals = residuals
-        record_unet(unet_a, residuals)
-        P.eps_active = P.eps
-
-        # ---- step I: UNet only (cond_scale == 0: BlobNet output is multiplied by 0, bn:936-938)
-        P.step_inactive = rec.begin("step_inactive")
-        unet_i = TrunkPlan(rec, self.unet_w, self.unet_cfg, Bu, H, W)
-        unet_i.freeu_params = P.freeu
-        unet_i.pag_layers, unet_i.pag_images = unet_a.pag_layers, unet_a.pag_images
-        unet_i.ctx_kv, unet_i.ctx_kvs, unet_i.ctx_folded = unet_a.ctx_kv, getattr(unet_a, "ctx_kvs", {}), getattr(unet_a, "ctx_folded", {})
-        unet_i.ip_kv = unet_a.ip_kv
-        if not temb_per_step:
-            unet_i.tproj, unet_i.tproj_table = unet_a.tproj, unet_a.tproj_table
-        record_unet(unet_i, None)
-        P.eps_inactive = P.eps
-        P.loop_graphs = {}
-        P.captured = False
-        from . import options
-        P.options, P.options_non_default = options.effective(), options.non_default()     # (what BC_PLAN said while this plan was recorded)
-        self._plans[key] = P
+        P = self._plans[key] = record_plan(self, spec)
         return P
 
     def set_scheduler(self, kind, params=None):
@@ -796,10 +553,9 @@ class BlobCtrlEngine(_PreviewVAE):
         P.scale_table.copy_(torch.tensor(S.scale_rows, dtype=f32).reshape(-1))
         if P.freeu is not None:
             P.freeu.copy_(torch.tensor([float(v) for v in freeu], dtype=f32))
-        if getattr(P, "pag_table", None) is not None:
+        if P.pag_table is not None:
             P.pag_table.copy_(torch.tensor(pag_mod.pag_table(S.t_rows[:, 0].tolist(), *pag_scales), dtype=f32))
-        return ([P.t_rows_blob, P.t_rows_unet] if S.requests else [P.t_table]) + [P.coef, P.scale_table] + \
-            ([P.freeu] if P.freeu is not None else []) + ([P.pag_table] if getattr(P, "pag_table", None) is not None else [])
+        return [t for t in (P.t_rows_blob, P.t_rows_unet, P.t_table, P.coef, P.scale_table, P.freeu, P.pag_table) if t is not None]
 
     @staticmethod
     def _mark_stored(P, tables, variance_noise):
@@ -1012,8 +768,8 @@ class BlobCtrlEngine(_PreviewVAE):
                                              pag=bool(pag))
         if ip and ip_adapter_masks is not None:
             ip_adapter_masks = ip_masks.check_masks(ip_adapter_masks, [e if isinstance(e, int) else e[0] for e in ip])
-        P = self._plan(B, h, w, T, Dc, S.n, per_request, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
-                       requests=S.requests, ip=ip, ip_masked=bool(ip) and ip_adapter_masks is not None, pag=pag)
+        P = self._plan(S.plan_spec(B, h, w, T, Dc, per_request=per_request, single=single, freeu=freeu_enabled(freeu), ip=ip,
+                                   ip_masked=ip_adapter_masks is not None, pag=pag))
         dev = self.device
         self.timesteps = [t.timesteps for t in S.tables] if S.requests else S.tables[0].timesteps
         if latents is None:                                                          # pipe:438-453
@@ -1195,8 +951,7 @@ class BlobCtrlEngine(_PreviewVAE):
         S = self._setup(B, listed and B > 1, blobnet_conditioning_scale, req_scales, num_inference_steps, timesteps, guidance_scale,
                         blobnet_control_guidance_start, blobnet_control_guidance_end, eta, guidance_off and listed)
         self._check_variance_noise(S, variance_noise, (B, 4, h, w), compiling=True)
-        P = self._plan(B, h, w, T, ctx_dim, S.n, S.requests, S.stochastic, S.third_order, S.scaled, single, freeu_enabled(freeu),
-                       requests=S.requests)
+        P = self._plan(S.plan_spec(B, h, w, T, ctx_dim, per_request=S.requests, single=single, freeu=freeu_enabled(freeu)))
         self._mark_stored(P, self._write_tables(P, S, freeu), variance_noise)
         P.rec.save(path)
         return S.segments
@@ -1204,7 +959,7 @@ class BlobCtrlEngine(_PreviewVAE):
     # convenience for bench / tests ------------------------------------------------------------------
     def plan_for(self, B, h, w, T, ctx_dim, nsteps, per_request=False, stochastic=False, third_order=False, scaled=False, single=False,
                  freeu=False, requests=False, ip=(), ip_masked=False, pag=()):
-        return self._plan(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip, ip_masked, pag)
+        return self._plan(PlanSpec(B, h, w, T, ctx_dim, nsteps, per_request, stochastic, third_order, scaled, single, freeu, requests, ip, ip_masked, pag))
 
 
 def _is_device_image(image):
