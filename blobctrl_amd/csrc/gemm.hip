@@ -591,7 +591,8 @@ int resolve(GemmArgs& g, BcGemmInfo& info, bool choose_split) {
         bool fast_ok = (p.K % BK == 0);
         if (p.a_mode == BC_A_CONV3X3) {
             bool ups = (p.Hv != p.Hin) || (p.Wv != p.Win);
-            fast_ok = fast_ok && (p.Cin % BK == 0) && (!ups || (p.Hv == 2 * p.Hin && p.Wv == 2 * p.Win && p.stride == 1));
+            // (gemm_fast's upsample gather has the window origin of pad 1 built in: with conv_nopad_lo it goes to the generic gather)
+            fast_ok = fast_ok && (p.Cin % BK == 0) && (!ups || (p.Hv == 2 * p.Hin && p.Wv == 2 * p.Win && p.stride == 1 && !p.conv_nopad_lo));
         } else if (p.A2) {
             fast_ok = fast_ok && (p.C1 % BK == 0);
         }

@@ -193,6 +193,18 @@ class AutoencoderKL:
             sc = x
         return self._conv(rec, B, h, p + "conv2", Cout, R=sc)
 
+    @staticmethod
+    def _attend(rec, qk, vt, s, o, B, N, Cc):
+        """The mid-block attention of B images over packed buffers: qk [B N][2 Cc] (q | k), vt [B Cc][pad8(N)] (V transposed, pad columns
+        zero), s [N][pad8(N)] (the scores, then the probabilities, of ONE image), o [B N][Cc]."""
+        Np = pad8(N)
+        for b in range(B):                                 # heads = 1, head_dim = C: plain GEMMs per image
+            rec.gemm(A=qk, a_offset=b * N * 2 * Cc, lda=2 * Cc, W=qk, w_offset=b * N * 2 * Cc + Cc, M=N, N=N, K=Cc, out=s,
+                     ldc=Np, alpha=Cc ** -0.5, kind="vae_attn", ldw=2 * Cc)
+            rec.call("bc_softmax_rows", s.data_ptr(), N, N, Np, kind="softmax", keep=(s,))
+            rec.gemm(A=s, lda=Np, W=vt, w_offset=b * Cc * Np, M=N, N=Cc, K=Np, out=o, out_offset=b * N * Cc, kind="vae_attn",
+                     ldw=Np)
+
     def _mid(self, rec, B, p, x: _Act):
         x = self._res(rec, B, p + "resnets.0.", x, x.C)
         a = p + "attentions.0."
@@ -208,12 +220,7 @@ class AutoencoderKL:
         o = rec.empty(M, Cc)
         Np = pad8(N)
         s = rec.zeros(N, Np)                               # scores of ONE image (images run back to back on the stream)
-        for b in range(B):                                 # heads = 1, head_dim = C: plain GEMMs per image
-            rec.gemm(A=qk, a_offset=b * N * 2 * Cc, lda=2 * Cc, W=qk, w_offset=b * N * 2 * Cc + Cc, M=N, N=N, K=Cc, out=s,
-                     ldc=Np, alpha=Cc ** -0.5, kind="vae_attn", ldw=2 * Cc)
-            rec.call("bc_softmax_rows", s.data_ptr(), N, N, Np, kind="softmax", keep=(s,))
-            rec.gemm(A=s, lda=Np, W=vt, w_offset=b * Cc * Np, M=N, N=Cc, K=Np, out=o, out_offset=b * N * Cc, kind="vae_attn",
-                     ldw=Np)
+        self._attend(rec, qk, vt, s, o, B, N, Cc)
         out = self._dense(rec, o, M, Cc, a + "to_out.0.weight", a + "to_out.0.bias", Cc, rows_per_batch=N, R=x.t, ldr=Cc,
                           want_gn=True)
         return self._res(rec, B, p + "resnets.1.", _Act(out, Cc, x.H, x.W), Cc)

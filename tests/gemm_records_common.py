@@ -79,16 +79,19 @@ def capture(plan_opts=None):
 
 
 # ---------------------------------------------------------------------------------------------------- sources
-def view_cases():
+def view_cases(front_end=False):
+    """The cases of the view tables that were frozen (tests/golden/gemm_records_before_resolve.json); front_end: the front ends' launch forms
+    added since (Case.front_end) as well."""
     from tests import gemm_views_common as gv
     cases = gv.generic_cases() + [gv.fast_case(cfg, mode) for cfg in range(1, 8) for mode in gv.FAST_MODES]
-    return cases + gv.gw_cases() + gv.g256_cases() + gv.halo_cases("halo") + gv.halo_cases("wreg")
+    cases += gv.gw_cases() + gv.g256_cases() + gv.halo_cases("halo") + gv.halo_cases("wreg")
+    return [c for c in cases if front_end or not c.front_end]
 
 
-def view_problems():
+def view_problems(front_end=False):
     """Every (case, flavour) problem of the view tables, built on the CPU."""
     from tests import gemm_views_common as gv
-    for case in view_cases():
+    for case in view_cases(front_end):
         for flavour in gv.FLAVOURS:
             yield gv.build(case, flavour, CPU)
 

@@ -8,7 +8,12 @@ pattern 0x7E5A (fp32: 0x7FC5A5A5), row stride > width, guard rows in front and b
 256-row tile; after the launch every element of the view differs from the sentinel and is finite, every other element of the parent is
 bit-equal to the sentinel.  The float64 reference is computed from the fp16-rounded valid sub-tensors only; the bars are the project's own,
 through tests.common.close.  Nothing here needs a device: `emulate` is a torch statement of the kernel (with the mistakes a kernel can make)
-that tests/test_gemm_views_cpu.py drives the same harness with."""
+that tests/test_gemm_views_cpu.py drives the same harness with.
+The launch forms of the VAE / CLIP / DINOv2 / SAM front ends (Case.front_end): convolutions on the generic gather (Cin % 64 != 0), the VAE
+encoder's pad = (0, 1, 0, 1) stride-2 convolution - whose last output row reads input row H: the next image's first row, or the guard pixels -,
+an upsample to an explicit size, the fp32 convolution output at N = 3, the epilogue chain act -> colscale -> alpha -> alpha_dev[...] with GELU /
+quick-GELU / SiLU, a scalar, a device scalar and a per-image table behind a device step counter (the table between NaN lanes, its other rows
+9.0), and the three launches per image of the VAE mid-block attention through the model's own recording (vae_attention_problem)."""
 import math
 from collections import namedtuple
 
@@ -24,6 +29,12 @@ NAN16, NAN32 = 0x7F33, 0x7FD12345       # what the input parents are filled with
 PAD = 8                                 # pad columns behind every input row
 FRONT = 16                              # guard rows in front of row 0 of an input
 FLAVOURS = ("vec", "scalar")            # 16-byte aligned view (offset % 8 == 0, ld % 8 == 0) / ld = width + 4 at an odd offset
+
+
+# activation -> (its BC_ACT_* name in blobctrl_amd._lib, the float64 statement: GELU is the erf form, quick-GELU x sigmoid(1.702 x))
+ACTS = {"gelu": ("ACT_GELU", lambda t: 0.5 * t * (1 + torch.erf(t / math.sqrt(2.0)))),
+        "quick_gelu": ("ACT_QUICK_GELU", lambda t: t * torch.sigmoid(1.702 * t)),
+        "silu": ("ACT_SILU", lambda t: t * torch.sigmoid(t))}
 
 
 def _filled(n, device, f32=False, bits=None):
@@ -66,6 +77,13 @@ class View:
         assert _elems_behind(self.t) >= (self.rows + self.back - 1) * self.ld + self.cols + PAD
         assert (self.parent.data_ptr() + self.offset * self.parent.element_size()) % 16 == 0 or self.dtype == torch.float32
 
+    def guards_intact(self):
+        """Every element of the parent outside the view still holds the NaN it was filled with (an input nobody may write)."""
+        bits = self.parent.view(torch.int32 if self.dtype == torch.float32 else torch.int16).cpu()
+        outside = torch.ones(bits.numel(), dtype=torch.bool)
+        outside[(self.offset + torch.arange(self.rows)[:, None] * self.ld + torch.arange(self.cols)[None, :]).flatten()] = False
+        return bool((bits[outside] == (NAN32 if self.dtype == torch.float32 else NAN16)).all())
+
 
 class Out:
     """`rows` x `width` output at FRONT rows + `extra` elements inside a sentinel-filled parent, row stride `ld` (a transposed output
@@ -97,11 +115,12 @@ class Out:
     def _where(self, i):
         return divmod(int(i) - self.offset, self.ld)
 
-    def check(self, what):
+    def check(self, what, rows=None):
         """(values [rows][width] float64, count of sentinel elements checked).  Fails when an element outside the view was written, when
-        one inside was not, or when one inside is not finite - with the count and the first offending (row, col) of the view's grid."""
+        one inside was not, or when one inside is not finite - with the count and the first offending (row, col) of the view's grid.
+        rows: the view's first `rows` rows are the view (a launch that fills a buffer image by image: the rest is still sentinel)."""
         bits = self.bits.cpu()
-        idx = self.offset + torch.arange(self.rows)[:, None] * self.ld + torch.arange(self.width)[None, :]
+        idx = self.offset + torch.arange(self.rows if rows is None else rows)[:, None] * self.ld + torch.arange(self.width)[None, :]
         inside = torch.zeros(bits.numel(), dtype=torch.bool)
         inside[idx.flatten()] = True
         wrote = bits != self.sentinel
@@ -188,9 +207,11 @@ def _vec(x, device):
 # ---------------------------------------------------------------------------------------------------- dense problems
 def dense_problem(name, device, flavour, M, N, K, family="fast", tile_cfg=0, splitk=None, C1=0, colscale=False, R=False, r2=None, out_mode="f16",
                   rpb=0, ldc=None, extra=None, geglu=False, gw_nt=0, ln=False, n_t0=0, softmax=None, gn_groups=0, want_gn=False, bias=True,
-                  refused=None):
+                  refused=None, act=None, alpha=1.0, alpha_table=None):
     """A (strided, one or two sources) x W^T (strided row-major, or the packed stream of a BC_TILE_GW* configuration) + the epilogue modes of
-    bc_gemm.  r2 = (out_w, xmin); softmax = (group, keep, valid); out_mode f16 / f16t / f32."""
+    bc_gemm.  r2 = (out_w, xmin); softmax = (group, keep, valid); out_mode f16 / f16t / f32; act gelu / quick_gelu / silu; alpha: the scalar;
+    alpha_table = (steps, step, per_image): the device table [steps] or [steps][M / rpb] behind a device step counter.  The reference follows
+    the chain of include/blobctrl_hip.h: (acc + bias) -> act -> colscale -> alpha -> alpha_dev[...] -> + R -> + R2."""
     from blobctrl_amd import _lib
     from blobctrl_amd.weights import fold_layernorm, pack_gemm_wreg
     A, W, b = g(1, M, K), g(2, N, K) / math.sqrt(K), g(3, N)
@@ -244,11 +265,26 @@ def dense_problem(name, device, flavour, M, N, K, family="fast", tile_cfg=0, spl
         acc, n_out = p.reshape(M, -1), N // group * keep
         zero_cols = (torch.arange(n_out) % keep) >= valid
         kw.update(sm_group=group, sm_keep=keep, sm_valid=valid)
+    if act:
+        acc = ACTS[act][1](acc)
+        kw.update(act=getattr(_lib, ACTS[act][0]))
     if colscale:
-        cs_ = 1 + 0.5 * g(5, n_out)
+        cs_ = 0.5 + torch.rand(n_out, generator=torch.Generator().manual_seed(5))        # (0.5 .. 1.5: where it stands in the chain matters)
         acc = acc * cs_.double()
         views["colscale"] = _vec(cs_, device)
         kw.update(colscale=views["colscale"].t)
+    if alpha != 1.0:
+        acc = acc * float(torch.tensor(alpha, dtype=torch.float32))                     # (the struct's float)
+        kw.update(alpha=alpha)
+    if alpha_table:
+        # the table as a producer leaves it: one row per step, the launch reads the row a device counter names; every other row holds 9.0
+        steps, step, per_image = alpha_table
+        nb = M // rpb if per_image else 1
+        tab = torch.full((steps, nb), 9.0)
+        tab[step] = 0.5 + torch.rand(nb, generator=torch.Generator().manual_seed(11))
+        acc = (acc.view(nb, -1, n_out) * tab[step].double()[:, None, None]).reshape(M, n_out)
+        views["alpha"] = _vec(tab.flatten(), device)
+        kw.update(alpha_dev=views["alpha"].t, alpha_idx=torch.tensor([step], dtype=torch.int32, device=device), alpha_bstride=nb if per_image else 0)
     if R:
         Rh = g(4, M, n_out).half()
         acc = acc + Rh.double()
@@ -293,16 +329,19 @@ def dense_problem(name, device, flavour, M, N, K, family="fast", tile_cfg=0, spl
     variant = {"generic": "gemm_kernel<", "gw": "gemm_wreg_kernel<", "g256": "gemm256_kernel<"}.get(family) or f"gemm_fast_kernel<{_lib.TILE_NAMES[tile_cfg]},"
     if family in ("gw", "g256"):
         variant += _lib.TILE_NAMES[tile_cfg] + ","
-    spec = dict(kind="dense", M=M, N=N, K=K, n_out=n_out)
+    spec = dict(kind="dense", M=M, N=N, K=K, n_out=n_out, act=act, alpha=alpha, alpha_table=alpha_table, rpb=rpb or M, f32=out_mode == "f32")
     return Prob(name, kw, views, outs, variant, sk=splitk, refused=refused, spec=spec, gn_in=gn_in, gn_out=gn_out, zero_cols=zero_cols)
 
 
 # ---------------------------------------------------------------------------------------------------- convolutions
 def conv_problem(name, device, flavour, B, H, W, Cin, Cout, family="fast", tile_cfg=0, stride=1, ups=False, C1=0, splitk=None, sk=None, gn=False,
-                 resblock=False, want_gn=False, lda_pad=PAD, refused=None):
+                 resblock=False, want_gn=False, lda_pad=PAD, refused=None, nopad_lo=False, size=None, out_mode="f16", R=False):
     """3x3 convolution, pad 1, over NHWC pixels [B][H W][lda] with guard pixels (>= W + 1 and one 256-row tile) in front of image 0 and behind
     image B - 1.  gn: GroupNorm + SiLU in front (finalize in the kernel's prologue, statistics totals of the valid channels from the host);
-    resblock: + time-embedding row through a step table + R + R2 from r2_xmin on."""
+    resblock: + time-embedding row through a step table + R + R2 from r2_xmin on.  nopad_lo: no padding on top and left, F.pad(x, (0, 1, 0, 1))
+    in front of the convolution (the VAE encoder's downsampler): at an even H and stride 2 the last output row reads input row H - the bottom
+    pad, which in memory is the first row of the next image or the guard pixels behind the last one.  ups / size: nearest upsample to twice
+    the size / to an explicit size in front.  out_mode f16 / f32; R: + a residual."""
     from blobctrl_amd import _lib
     from blobctrl_amd.weights import pack_conv3x3, pack_conv_wreg
     x = g(1, B, Cin, H, W)
@@ -319,11 +358,13 @@ def conv_problem(name, device, flavour, B, H, W, Cin, Cout, family="fast", tile_
         views["A2"] = View(pix[:, C1:], device, ld=Cin - C1 + lda_pad, front=guard, back=guard)
     else:
         views["A"] = View(pix, device, ld=Cin + lda_pad, front=guard, back=guard)
-    Hv, Wv = (2 * H, 2 * W) if ups else (H, W)
-    Ho, Wo = (Hv - 1) // stride + 1, (Wv - 1) // stride + 1
+    assert not (ups and size)
+    Hv, Wv = size if size else ((2 * H, 2 * W) if ups else (H, W))
+    pads = 1 if nopad_lo else 2                                  # (bc_gemm's geometry check: Hout = (Hv + pads - 3) / stride + 1)
+    Ho, Wo = (Hv + pads - 3) // stride + 1, (Wv + pads - 3) // stride + 1
     M, HWo = B * Ho * Wo, Ho * Wo
     kw = dict(M=M, N=Cout, K=9 * Cin, tile_cfg=tile_cfg, splitk=splitk, A=views["A"].parent, a_offset=views["A"].offset, lda=views["A"].ld,
-              conv=dict(Cin=Cin, Hin=H, Win=W, Hv=Hv, Wv=Wv, Hout=Ho, Wout=Wo, stride=stride), rows_per_batch=HWo)
+              conv=dict(Cin=Cin, Hin=H, Win=W, Hv=Hv, Wv=Wv, Hout=Ho, Wout=Wo, stride=stride, nopad_lo=nopad_lo), rows_per_batch=HWo)
     if C1:
         kw.update(A2=views["A2"].t, C1=C1, lda2=views["A2"].ld)
     if gn:
@@ -337,8 +378,16 @@ def conv_problem(name, device, flavour, B, H, W, Cin, Cout, family="fast", tile_
         kw.update(a_act=_lib.ACT_SILU)
     if ups:
         src = F.interpolate(src, scale_factor=2.0, mode="nearest")
-    wp = pack_conv3x3(w).half()
-    ref = F.conv2d(src, w.half().double(), b.double(), stride=stride, padding=1)
+    if size:
+        src0, src = src, F.interpolate(src, size=size, mode="nearest")
+        # (the reference's float scale and the kernel's integer floor(dst * in / out) name the same source pixels at this size)
+        assert torch.equal(src, src0[:, :, torch.arange(Hv) * H // Hv][:, :, :, torch.arange(Wv) * W // Wv])
+    wp =pack_conv3x3(w).half()
+    if nopad_lo:
+        ref = F.conv2d(F.pad(src, (0, 1, 0, 1)), w.half().double(), b.double(), stride=stride)
+    else:
+        ref = F.conv2d(src, w.half().double(), b.double(), stride=stride, padding=1)
+    assert tuple(ref.shape[2:]) == (Ho, Wo)
     if family == "wreg":
         kw.update(W=pack_conv_wreg(wp).to(device))              # (the packed stream as it is)
     else:
@@ -358,9 +407,17 @@ def conv_problem(name, device, flavour, B, H, W, Cin, Cout, family="fast", tile_
                   R=views["R"].t, ldr=views["R"].ld, R2=views["R2"].t, ldr2=views["R2"].ld, r2_xmin=xmin, r2_bmod=1, out_w=Wo)
         ref = ref + temb.double().view(steps, B, Cout)[step][:, :, None, None] + Rh.double()
         ref[..., xmin:] += R2h.double()[..., xmin:]
+    if R:
+        assert not resblock
+        Rh = g(8, B, Cout, Ho, Wo).half()
+        views["R"] = View(Rh.permute(0, 2, 3, 1).reshape(M, Cout), device)
+        kw.update(R=views["R"].t, ldr=views["R"].ld)
+        ref = ref + Rh.double()
     ld, ex = out_layout(flavour, Cout)
-    o = Out(M, Cout, ld, device, ex)
+    o = Out(M, Cout, ld, device, ex, f32=out_mode == "f32")
     kw.update(out=o.parent, out_offset=o.offset, ldc=o.ld)
+    if out_mode == "f32":
+        kw.update(out_mode=_lib.OUT_F32)
     gn_out = None
     if want_gn:
         kw.update(want_gn=True)
@@ -368,20 +425,138 @@ def conv_problem(name, device, flavour, B, H, W, Cin, Cout, family="fast", tile_
     halo = family in ("halo", "wreg")
     if refused is None:
         refused = flavour == "scalar" and halo                 # bc_gemm: the halo convolutions store 16 bytes at a time
-    variant = {"halo": "conv_halo_kernel<", "wreg": "conv_wreg_kernel<"}.get(family) or f"gemm_fast_kernel<{_lib.TILE_NAMES[tile_cfg]},"
+    variant = {"halo": "conv_halo_kernel<", "wreg": "conv_wreg_kernel<", "generic": "gemm_kernel<"}.get(family) or \
+        f"gemm_fast_kernel<{_lib.TILE_NAMES[tile_cfg]},"
     if gn:
         variant += _lib.TILE_NAMES[tile_cfg] + ",halo_gnfin"
-    spec = dict(kind="conv", B=B, H=H, W=W, Cin=Cin, N=Cout, M=M, n_out=Cout)
-    outs = [("C", o, ref.permute(0, 2, 3, 1).reshape(M, Cout), 4e-3 if gn else 2e-3, None)]
+    spec = dict(kind="conv", B=B, H=H, W=W, Cin=Cin, N=Cout, M=M, n_out=Cout, stride=stride, nopad_lo=nopad_lo, Hv=Hv, Wv=Wv, Ho=Ho, Wo=Wo,
+                f32=out_mode == "f32")
+    ref = ref.permute(0, 2, 3, 1).reshape(M, Cout)
+    outs = [("C fp32", o, ref, 1e-4, 1e-4)] if out_mode == "f32" else [("C", o, ref, 4e-3 if gn else 2e-3, None)]
     return Prob(name, kw, views, outs, variant, sk=sk if sk is not None else splitk, refused=refused, spec=spec, gn_in=gn_in, gn_out=gn_out)
 
 
+# ---------------------------------------------------------------------------------------------------- the VAE mid-block attention
+def pad8(n):
+    return (n + 7) // 8 * 8
+
+
+ATTN_STAGES = ("scores", "probs", "o")
+ATTN_SHAPES = [(2, 72, 64), (1, 64, 128)]          # (B, N, C): N = 72 is a ragged second 64-tile and 8-aligned, as vae.py requires; K = 72
+                                                   # sends P V to the generic kernel, every other launch is gemm_fast
+
+
+class AttnProb(Prob):
+    """The three launches per image of AutoencoderKL._attend - Q K^T with the scale as alpha, bc_softmax_rows in place, P V against V^T - on
+    fenced buffers: `check(b, stage)` after each launch, `verify()` after the last.  The score buffer holds ONE image: it is reset to the
+    sentinel in front of each image's Q K^T, so that what is checked is what that launch wrote."""
+
+    def __init__(self, name, views, s, o, refs, B, N, C):
+        from tests.attention_common import BAR_ATOL, BAR_RTOL
+        super().__init__(name, None, views, [("o", o, refs["o"], BAR_RTOL, BAR_ATOL)], None, spec=dict(kind="vae_attn", B=B, N=N, C=C))
+        self.s, self.o, self.refs = s, o, refs
+        # the scores are a dense GEMM's output: the dense bar; probabilities and the product: the attention bar (tests/attention_common.py)
+        self.bars = dict(scores=(2e-3, None), probs=(BAR_RTOL, BAR_ATOL), o=(BAR_RTOL, BAR_ATOL))
+        # kind and variant of the launches `_attend` records per image
+        fast = lambda k: "gemm_fast_kernel<" if k % 64 == 0 else "gemm_kernel<"
+        self.launches = [("vae_attn", fast(C)), ("softmax", ""), ("vae_attn", fast(pad8(N)))]
+        self.worst, self.checked = {}, 0
+
+    def assert_inside(self):
+        super().assert_inside()
+        self.s.assert_inside()
+
+    def reset(self):
+        self.s.reset()
+        self.o.reset()
+        self.worst, self.checked = {}, 0
+
+    def untouched(self):
+        return self.s.untouched() and self.o.untouched()
+
+    def check(self, b, stage):
+        """After launch `stage` of image b: the score buffer (or the rows of o written so far) is written, finite and inside its bar, every
+        sentinel around it is unchanged.  Prints the figure before it asserts."""
+        N = self.spec["N"]
+        what = f"{self.name} [image {b}: {stage}]"
+        if stage == "o":
+            vals, n = self.o.check(what, rows=(b + 1) * N)
+            ref = self.refs["o"][:(b + 1) * N]
+        else:
+            vals, n = self.s.check(what)
+            ref = self.refs[stage][b]
+        rtol, atol = self.bars[stage]
+        e = err_over_bar(vals, ref, rtol, atol)
+        print(f"{what}: max err/bar {e:.3f}, {n} sentinel elements checked")
+        close(vals, ref, rtol=rtol, atol=atol, what=what)
+        self.worst[stage] = max(self.worst.get(stage, 0.0), e)
+        self.checked += n
+        return e
+
+    def verify(self):
+        assert sorted(self.worst) == sorted(ATTN_STAGES), f"{self.name}: not every stage was checked"
+        for name, v in self.views.items():
+            assert v.guards_intact(), f"{self.name}: the NaN guards around {name} were written"
+        return max(self.worst.values()), self.checked
+
+
+def vae_attention_problem(device, B, N, C, qk_scale=1.0):
+    """The buffers of the VAE mid-block attention (blobctrl_amd/vae.py: _mid, _attend) as the producers leave them, fenced: qk [B N][2 C]
+    (q | k; the weight operand of Q K^T is columns C .. 2 C of the same rows, image b at a per-image offset) and vt [B C][pad8(N)] (V
+    transposed, pad columns zero) inside NaN parents - packed rows, as `_attend` addresses them: NaN guard rows in front and behind -, the
+    score buffer s [N][pad8(N)] of one image and o [B N][C] inside sentinel parents.  The float64 references - scaled scores, softmax,
+    product - are computed from the fp16-rounded operands, nothing rounded in between."""
+    assert N % 8 == 0, "VAE attention needs a token count that is a multiple of 8"
+    Np = pad8(N)
+    qkh = (g(1, B * N, 2 * C) * qk_scale).half()
+    vh = g(2, B, N, C).half()
+    vth = torch.zeros(B, C, Np, dtype=torch.float16)
+    vth[:, :, :N] = vh.permute(0, 2, 1)
+    views = dict(qk=View(qkh, device, ld=2 * C), vt=View(vth.reshape(B * C, Np), device, ld=Np))
+    q, k = qkh.double().view(B, N, 2 * C)[..., :C], qkh.double().view(B, N, 2 * C)[..., C:]
+    scores = q @ k.transpose(1, 2) * float(torch.tensor(C ** -0.5, dtype=torch.float32))          # (alpha is the struct's float)
+    probs = torch.softmax(scores, -1)
+    refs = dict(scores=scores, probs=probs, o=(probs @ vh.double()).reshape(B * N, C))
+    s, o = Out(N, N, Np, device, 8), Out(B * N, C, C, device, 8)
+    return AttnProb(f"vae-attention-B{B}-N{N}-C{C}", views, s, o, refs, B, N, C)
+
+
+def emulate_attention(prob, mutation=None):
+    """`_attend` in torch, float64 arithmetic, rounded to fp16 exactly where the three launches store (scores, probabilities, product), checked
+    after each launch.  Against the float64 references this is the floor the storage formats leave of each bar.  w_image0: image 0's K rows
+    used for every image."""
+    assert mutation in (None, "w_image0")
+    B, N, C = (prob.spec[k] for k in "BNC")
+    Np, qk, vt, s, o = pad8(N), prob.views["qk"], prob.views["vt"], prob.s, prob.o
+    alpha = float(torch.tensor(C ** -0.5, dtype=torch.float32))
+    sv = s.parent.as_strided((N, N), (s.ld, 1), s.offset)
+    for b in range(B):
+        s.reset()
+        bw = 0 if mutation == "w_image0" else b
+        A = qk.parent.as_strided((N, C), (qk.ld, 1), qk.offset + b * N * 2 * C).double()
+        Wm = qk.parent.as_strided((N, C), (qk.ld, 1), qk.offset + bw * N * 2 * C + C).double()
+        sv.copy_((A @ Wm.t() * alpha).half())
+        prob.check(b, "scores")
+        sv.copy_(torch.softmax(sv.double(), -1).half())
+        prob.check(b, "probs")
+        P = s.parent.as_strided((N, Np), (s.ld, 1), s.offset).double()
+        Vt = vt.parent.as_strided((C, Np), (vt.ld, 1), vt.offset + b * C * Np).double()
+        o.parent.as_strided((N, C), (o.ld, 1), o.offset + b * N * C).copy_((P @ Vt.t()).half())
+        prob.check(b, "o")
+
+
 # ---------------------------------------------------------------------------------------------------- the case tables
-Case = namedtuple("Case", "id fn args")
+# front_end: a launch form of the VAE / CLIP / DINOv2 / SAM front ends, added after tests/golden/gemm_records_before_resolve.json was frozen
+# (tests/gemm_records_common.py records the cases that file knows)
+Case = namedtuple("Case", "id fn args front_end", defaults=(False,))
 
 
 def build(case, flavour, device):
     return case.fn(f"{case.id}/{flavour}", device, flavour, **case.args)
+
+
+def _front_end(id_, fn, args):
+    return Case(id_, fn, args, True)
 
 
 def _tiles():
@@ -394,11 +569,39 @@ def generic_cases():
     one column of an 8-wide weight matrix, columns 0-4 and 6-7 of every row must survive)."""
     return [Case("generic-130x72x200", dense_problem, dict(M=130, N=72, K=200, family="generic", colscale=True, R=True)),
             Case("generic-33x8x8", dense_problem, dict(M=33, N=8, K=8, family="generic")),
-            Case("generic-rank1-collapse", dense_problem, dict(M=128, N=1, K=1032, family="generic", bias=False, ldc=8, extra=5))]
+            Case("generic-rank1-collapse", dense_problem, dict(M=128, N=1, K=1032, family="generic", bias=False, ldc=8, extra=5))] + \
+        generic_front_end_cases()
+
+
+def generic_front_end_cases():
+    """Convolutions on the generic kernel (Cin % 64 != 0: the tap is computed per 16-byte chunk, one 64-wide K tile spans several taps; the
+    VAE's conv_in at Cin = 8, K = 72): stride 1 and 2, the VAE encoder's pad = (0, 1, 0, 1) downsampler at an even size (the last output row
+    and column read the bottom / right pad: row H is the next image's first row, or the guard pixels) and at an odd one, the upsample gather at
+    an explicit size and at twice the size, the fp32 output at N = 3 (decoder.conv_out), N = 8 with a residual, and Cin = 24, where a K tile
+    ends inside a tap (three row tiles at B = 3).  At 5 x 6 -> 9 x 11 floor(i * 5 / 9) equals i >> 1 for every i: 8 x 9 is the size at which
+    a gather that shifts where it should scale reads other pixels.  And the scalar epilogue at n_out % 8 != 0 through GELU, LayerScale and
+    the per-image table."""
+    c = dict(B=2, H=9, W=11, Cin=8, Cout=40, family="generic", lda_pad=0)                             # (the gather reads packed pixels)
+    return [_front_end("generic-conv-9x11-s1-N72", conv_problem, dict(c, Cout=72)),
+            _front_end("generic-conv-10x12-s2", conv_problem, dict(c, H=10, W=12, stride=2)),
+            _front_end("generic-conv-10x12-s2-nopad_lo", conv_problem, dict(c, H=10, W=12, stride=2, nopad_lo=True)),
+            _front_end("generic-conv-9x11-s2-nopad_lo", conv_problem, dict(c, stride=2, nopad_lo=True)),
+            _front_end("generic-conv-5x6-size9x11", conv_problem, dict(c, H=5, W=6, size=(9, 11))),
+            _front_end("generic-conv-5x6-size8x9", conv_problem, dict(c, H=5, W=6, size=(8, 9))),
+            _front_end("generic-conv-5x6-ups", conv_problem, dict(c, H=5, W=6, ups=True)),
+            # Cin % 64 == 0 and twice the size, yet not gemm_fast's: its upsample gather has the window origin of pad 1 built in
+            _front_end("generic-conv-5x6-ups-nopad_lo-Cin64", conv_problem, dict(c, H=5, W=6, Cin=64, ups=True, nopad_lo=True)),
+            _front_end("generic-conv-N3-f32", conv_problem, dict(c, Cout=3, out_mode="f32")),
+            _front_end("generic-conv-N8-R", conv_problem, dict(c, Cout=8, R=True)),
+            _front_end("generic-conv-Cin24-B3", conv_problem, dict(c, B=3, Cin=24)),
+            _front_end("generic-130x20x72-gelu-colscale-alpha_per_image", dense_problem,
+                       dict(M=130, N=20, K=72, family="generic", act="gelu", colscale=True, rpb=65, alpha_table=(2, 1, True)))]
 
 
 FAST_MODES = ("dense", "two_source", "splitk3_R", "t100_ldc104", "t100_ldc112", "t77_ldc80", "t96_ldc104", "f32", "geglu", "geglu_sk2",
-              "conv1", "conv2", "ups", "conv1_strided_pixels")
+              "conv1", "conv2", "ups", "conv1_strided_pixels",
+              "conv2_nopad", "conv2_nopad_odd", "act_gelu", "act_quick_gelu", "act_silu", "alpha_per_image", "alpha_scalar_sk3")
+FAST_FRONT_END_MODES = FAST_MODES[14:]
 
 
 def fast_case(cfg, mode):
@@ -423,12 +626,22 @@ def fast_case(cfg, mode):
         "ups": (conv_problem, dict(conv, ups=True)),
         # refused by design: the gather kernels address pixel * Cin, a wider pixel stride would be ignored
         "conv1_strided_pixels": (conv_problem, dict(conv, lda_pad=PAD, refused=True)),
+        # the VAE encoder's downsampler: at 10 x 12 output row 4 and column 5 read the bottom / right pad (input row 10, column 12)
+        "conv2_nopad": (conv_problem, dict(conv, H=10, W=12, stride=2, nopad_lo=True)),
+        "conv2_nopad_odd": (conv_problem, dict(conv, stride=2, nopad_lo=True)),
+        # act -> colscale -> alpha (DINOv2 / SAM: GELU; CLIP: quick-GELU)
+        "act_gelu": (dense_problem, dict(d, M=300, N=200, K=192, act="gelu", colscale=True, alpha=0.5)),
+        "act_quick_gelu": (dense_problem, dict(d, M=300, N=200, K=192, act="quick_gelu", colscale=True, alpha=0.5)),
+        "act_silu": (dense_problem, dict(d, M=300, N=200, K=192, act="silu", colscale=True, alpha=0.5)),
+        # BlobNet's zero-convs: step 1 of a [2][3] table (the other row holds 9.0), one scalar per image of 100 rows
+        "alpha_per_image": (dense_problem, dict(d, M=300, N=200, K=192, rpb=100, alpha_table=(2, 1, True))),
+        "alpha_scalar_sk3": (dense_problem, dict(d, M=300, N=200, K=640, splitk=3, alpha_table=(2, 1, False))),
     }
     fn, args = table[mode]
-    return Case(f"fast{cfg}-{mode}", fn, args)
+    return Case(f"fast{cfg}-{mode}", fn, args, mode in FAST_FRONT_END_MODES)
 
 
-GW_MODES = ("plain_bias_R", "ln", "two_source", "C_t", "softmax", "gn_rows")
+GW_MODES = ("plain_bias_R", "ln", "two_source", "C_t", "softmax", "gn_rows", "alpha")
 
 
 def gw_case(cfg, M, mode):
@@ -448,8 +661,9 @@ def gw_case(cfg, M, mode):
         "C_t_two_tiles": dict(d, N=2 * bn, n_t0=bn, rpb=64),
         "softmax": dict(d, softmax=(128, 80, 77), refused=True if nt != 2 else None),
         "gn_rows": dict(d, gn_groups=32, rpb=64),
+        "alpha": dict(d, alpha=0.5),
     }
-    return Case(f"{lib.TILE_NAMES[cfg]}-M{M}-{mode}", dense_problem, table[mode])
+    return Case(f"{lib.TILE_NAMES[cfg]}-M{M}-{mode}", dense_problem, table[mode], mode == "alpha")
 
 
 def gw_cases():
@@ -471,7 +685,8 @@ def g256_cases():
             Case("g256-C_t", dense_problem, dict(d, M=512, N=512, K=256, n_t0=256, rpb=256)),
             Case("g256-transposed", dense_problem, dict(d, M=512, N=256, K=128, out_mode="f16t", rpb=256, ldc=264)),
             Case("g256-geglu", dense_problem, dict(d, M=256, N=256, K=128, geglu=True)),
-            Case("g256-R_R2_gn", dense_problem, dict(d, M=512, N=512, K=256, R=True, r2=(16, 8), rpb=256, want_gn=True))]
+            Case("g256-R_R2_gn", dense_problem, dict(d, M=512, N=512, K=256, R=True, r2=(16, 8), rpb=256, want_gn=True)),
+            _front_end("g256-gelu-alpha", dense_problem, dict(d, M=256, N=256, K=128, act="gelu", alpha=0.5))]
 
 
 def halo_cases(family):
@@ -492,23 +707,33 @@ def halo_cases(family):
              Case(f"{family}-resblock-epilogue-sk2", conv_problem, dict(d, Cin=192, splitk=2, resblock=True, want_gn=True))]
     if family == "wreg":
         cases.append(Case("wreg-upsample-4x8", conv_problem, dict(d, H=4, W=8, ups=True)))
+    # refused by design (bc_conv_halo_ok): the LDS-resident halo tile is staged for pad 1 on every side
+    cases.append(_front_end(f"{family}-nopad_lo-refused", conv_problem, dict(d, nopad_lo=True, refused=True)))
     return cases
 
 
 # ---------------------------------------------------------------------------------------------------- a torch statement of the kernel
-MUTATIONS = ("store_vec8", "rows_round64", "skip_one", "k_round64", "row_M", "bias_lane", "halo_unchecked")
+MUTATIONS = ("store_vec8", "rows_round64", "skip_one", "k_round64", "row_M", "bias_lane", "halo_unchecked",
+             "pad_lo_kept", "pad_hi_unchecked", "ups_shift", "act_swapped", "scale_before_act", "alpha_image0", "alpha_next_step", "w_image0")
 
 
 def emulate(prob, mutation=None):
-    """What the kernel does, in torch: reads the views it is given, computes in float64, stores fp16 into the output view.  Dense: A W^T + bias
-    (+ R); conv: 3x3, stride 1, pad 1, + bias.  `mutation` makes one of the mistakes a kernel can make:
+    """What the kernel does, in torch: reads the views it is given, computes in float64, stores fp16 (fp32) into the output view.  Dense: A W^T;
+    conv: the 3x3 gather at the problem's stride, padding (nopad_lo) and virtual size (Hv x Wv); then the epilogue chain + bias -> act ->
+    colscale -> alpha -> table entry -> + R.  The VAE attention problem: emulate_attention.  `mutation` makes one of the mistakes a kernel can
+    make:
     store_vec8 (a full 8-wide vector stored at the last column), rows_round64 (M rounded up to 64 rows stored), skip_one (one element left
     unwritten), k_round64 (K rounded up to 64 read from A), row_M (row M of A added into row M - 1), bias_lane (bias lane n_out added into
-    column n_out - 1), halo_unchecked (conv: the halo row -1 of image 0 fetched without the bounds test)."""
+    column n_out - 1), halo_unchecked (conv: the halo row -1 of image 0 fetched without the bounds test), pad_lo_kept (conv: nopad_lo ignored
+    in the gather origin), pad_hi_unchecked (conv: an index equal to Hv or Wv fetched without the bounds test), ups_shift (conv: >> 1 in place
+    of * Hin / Hv at an explicit upsample size), act_swapped (quick-GELU where GELU was asked for), scale_before_act (colscale applied
+    before the activation), alpha_image0 (image 0's table entry for every image), alpha_next_step (the table row of step + 1), w_image0 (VAE
+    attention: image 0's K rows for every image)."""
     assert mutation is None or mutation in MUTATIONS
     s, v = prob.spec, prob.views
+    if s["kind"] == "vae_attn":
+        return emulate_attention(prob, mutation)
     M, N = s["M"], s["N"]
-    bias_p, bias_o = v["bias"].parent.double(), v["bias"].offset
     Wv = v["W"]
     if s["kind"] == "dense":
         K, a = s["K"], v["A"]
@@ -522,31 +747,57 @@ def emulate(prob, mutation=None):
             acc[M - 1] += a.parent.as_strided((K,), (1,), a.offset + M * a.ld).double() @ Wm.t()
     else:
         B, H, W, Cin, a = s["B"], s["H"], s["W"], s["Cin"], v["A"]
+        Hv, Wv_, Ho, Wo, stride = s["Hv"], s["Wv"], s["Ho"], s["Wo"], s["stride"]
+        pad_lo = 0 if s["nopad_lo"] and mutation != "pad_lo_kept" else 1
         Wm = Wv.parent.as_strided((N, 9, Cin), (Wv.ld, Cin, 1), Wv.offset).double()
         flat = a.parent.double()
-        bb, oy, ox = torch.meshgrid(torch.arange(B), torch.arange(H), torch.arange(W), indexing="ij")
-        acc = torch.zeros(B, H, W, N, dtype=torch.float64)
+        bb, oy, ox = torch.meshgrid(torch.arange(B), torch.arange(Ho), torch.arange(Wo), indexing="ij")
+        acc = torch.zeros(B, Ho, Wo, N, dtype=torch.float64)
+        hi = 1 if mutation == "pad_hi_unchecked" else 0
         for tap in range(9):
-            iy, ix = oy + tap // 3 - 1, ox + tap % 3 - 1
-            ok = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
+            iy, ix = oy * stride - pad_lo + tap // 3, ox * stride - pad_lo + tap % 3          # (on the virtual Hv x Wv grid)
+            ok = (iy >= 0) & (iy < Hv + hi) & (ix >= 0) & (ix < Wv_ + hi)
             if mutation == "halo_unchecked":
                 ok = ok | ((bb == 0) & (iy == -1))
+            if (Hv, Wv_) != (H, W):                                                # nearest: src = floor(dst * in / out)
+                if mutation == "ups_shift":
+                    iy, ix = iy >> 1, ix >> 1
+                else:
+                    iy, ix = torch.div(iy * H, Hv, rounding_mode="floor"), torch.div(ix * W, Wv_, rounding_mode="floor")
             pix = (bb * H + iy) * W + ix                                           # (negative in front of image 0)
             idx = a.offset + pix[..., None] * a.ld + torch.arange(Cin)
             val = torch.where(ok[..., None], flat[idx.clamp(0, flat.numel() - 1)], torch.zeros((), dtype=torch.float64))
             acc += val @ Wm[:, tap].t()
         acc = acc.reshape(M, N)
-    acc = acc + bias_p[bias_o:bias_o + N]
-    if mutation == "bias_lane":
-        acc[:, N - 1] += bias_p[bias_o + N]
+    if "bias" in v:
+        bias_p, bias_o = v["bias"].parent.double(), v["bias"].offset
+        acc = acc + bias_p[bias_o:bias_o + N]
+        if mutation == "bias_lane":
+            acc[:, N - 1] += bias_p[bias_o + N]
+    cs = 1.0
+    if "colscale" in v:
+        cs = v["colscale"].parent.double()[v["colscale"].offset:v["colscale"].offset + N]
+    if mutation == "scale_before_act":
+        acc, cs = acc * cs, 1.0
+    act = s.get("act")
+    if act:
+        acc = ACTS["quick_gelu" if mutation == "act_swapped" and act == "gelu" else act][1](acc)
+    acc = acc * cs
+    acc = acc * float(torch.tensor(s.get("alpha", 1.0), dtype=torch.float32))
+    if s.get("alpha_table"):
+        steps, step, per_image = s["alpha_table"]
+        nb = M // s["rpb"] if per_image else 1
+        tab, row = v["alpha"], step + (1 if mutation == "alpha_next_step" else 0)
+        img = torch.arange(M) // s["rpb"] if per_image and mutation != "alpha_image0" else torch.zeros(M, dtype=torch.long)
+        acc = acc * tab.parent.double()[tab.offset + row * nb + img][:, None]
     if "R" in v:
         r = v["R"]
         acc = acc + r.parent.as_strided((M, N), (r.ld, 1), r.offset).double()
     _, o, _, _, _ = prob.outs[0]
     dst = o.parent
     rows = M if mutation != "rows_round64" else (M + 63) // 64 * 64
-    val = torch.zeros(rows, N, dtype=torch.float16)
-    val[:M] = acc.half()
+    val = torch.zeros(rows, N, dtype=dst.dtype)
+    val[:M] = acc.to(dst.dtype)
     dst.as_strided((rows, N), (o.ld, 1), o.offset).copy_(val)
     if mutation == "store_vec8":
         dst.as_strided((M, 8), (o.ld, 1), o.offset + N - 1).copy_(val[:M, N - 1:].expand(M, 8))

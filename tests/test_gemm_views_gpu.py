@@ -3,7 +3,8 @@ operands that are views inside hostile parents (tests/gemm_views_common.py): NaN
 read outside a view shows as a non-finite output, a store outside one as a changed sentinel; inside, the float64 reference holds at the
 project's bars.  Every case runs in a 16-byte aligned flavour (the vector epilogues) and in one that forces the scalar epilogue - or asserts
 that bc_gemm refuses that (family, flavour) pair -, asserts the kernel family the recorder names for it, and prints its margin
-(profiles/gemm_views_margins.txt is a copy of one run)."""
+(profiles/gemm_views_margins.txt is a copy of one run).  The VAE mid-block attention runs through the model's own recording, launch by
+launch, on the same kind of buffers."""
 import pytest
 import torch
 
@@ -117,3 +118,36 @@ def test_gemm256_views(rec, case):
 @pytest.mark.parametrize("case", gv.halo_cases("halo") + gv.halo_cases("wreg"), ids=_ids(gv.halo_cases("halo") + gv.halo_cases("wreg")))
 def test_halo_and_wreg_convolution_views(rec, case):
     run_case(rec, case)
+
+
+@pytest.mark.parametrize("B,N,C", gv.ATTN_SHAPES)
+def test_vae_attention_launches_in_fenced_buffers(rec, B, N, C):
+    """The VAE mid-block attention through the model's own recording (AutoencoderKL._attend), one launch at a time: per image Q K^T whose
+    weight operand is columns C .. 2 C of the rows that hold A (image b at a per-image offset, the scale as alpha), bc_softmax_rows in place,
+    P V at K = pad8(N) against V^T.  After each launch the buffer it wrote is written, finite and inside its bar (scores: the dense bar;
+    probabilities and product: the attention bar) with every sentinel around it unchanged; at the end every NaN guard of qk and vt is intact."""
+    from blobctrl_amd.vae import AutoencoderKL
+    prob = gv.vae_attention_problem(DEV, B, N, C)
+    prob.assert_inside()
+    prob.reset()
+    seg = rec.begin("vae_attention")
+    AutoencoderKL._attend(rec, prob.views["qk"].t, prob.views["vt"].t, prob.s.t, prob.o.t, B, N, C)
+    assert len(seg.meta) == 3 * B
+    for i in range(len(seg.meta)):
+        seg.enable(i, False)
+    stream = torch.cuda.current_stream().cuda_stream
+    for i, m in enumerate(seg.meta):
+        b, st = divmod(i, 3)
+        kind, variant = prob.launches[st]
+        assert m["kind"] == kind and m["variant"].startswith(variant), (prob.name, i, m["kind"], m["variant"])
+        if st == 0:
+            prob.s.reset()                                      # (the score buffer holds one image: what is checked is what this image wrote)
+        seg.enable(i, True)
+        seg.run(stream)
+        torch.cuda.synchronize()
+        seg.enable(i, False)
+        prob.check(b, gv.ATTN_STAGES[st])
+    worst, checked = prob.verify()
+    names = " / ".join(seg.meta[i]["variant"] or seg.meta[i]["kind"] for i in range(3))
+    print(f"MARGIN {prob.name}: {names} | max err/bar " + ", ".join(f"{st} {prob.worst[st]:.3f}" for st in gv.ATTN_STAGES) +
+          f" | {checked} sentinel elements checked")
