@@ -22,13 +22,15 @@ from tests.common import g
 B, ROWS = ipc.B, ipc.ROWS               # 2 x 72 rows: the ragged count of the unmasked test
 HEADS_D = ((2, 8), (8, 40), (8, 80), (8, 160))
 IMAGES_TP = ((1, 4), (2, 4), (3, 5), (1, 16), (2, 16), (4, 16), (2, 32))
+HEADS_D_MORE = ((2, 16), (2, 32), (2, 64))                              # the other head sizes the masked kernels are built for,
+IMAGES_TP_MORE = ((3, 5), (2, 16))                                      # ... at a ragged Tp and at one both kernels take (block_rows = 32)
 WEIGHTS = ipc.WEIGHTS
 MASK_LO, MASK_HI = -0.4, 1.3
 
 
 def block_rows(heads, d):
-    """Rows of one image a workgroup of the scalar kernel takes (csrc/attention_ip_masked.hip: about 5 items per lane group, at most 32
-    rows, all heads in one slab at these sizes): 32, 30, 15 and 7 rows for HEADS_D."""
+    """Rows of one image a workgroup of the scalar kernel takes (csrc/bc_attention_ip.h ip_scalar_geometry: about 5 items per lane group,
+    at most 32 rows, all heads in one slab at these sizes): 32, 30, 15 and 7 rows for HEADS_D, 32 for HEADS_D_MORE."""
     per_pass = 4 * (64 // (d // 8))
     return max(1, min(32, 5 * per_pass // heads))
 

@@ -56,12 +56,13 @@ def _paths(prob):
     return (0, 1) if prob.Tp % 16 == 0 else (0,)
 
 
-@pytest.mark.parametrize("images,Tp", mc.IMAGES_TP)
-@pytest.mark.parametrize("heads,d", mc.HEADS_D)
+@pytest.mark.parametrize("heads,d,images,Tp", [hd + it for it in mc.IMAGES_TP for hd in mc.HEADS_D] +
+                         [hd + it for it in mc.IMAGES_TP_MORE for hd in mc.HEADS_D_MORE])
 def test_masked_attention_against_float64(heads, d, images, Tp):
-    """Every (heads, d) x (images, Tp) at B = 2 x 72 rows, ldq = 2 C, for w = 1, 0.35 and -0.5, by the dispatcher and by every path that
-    takes the shape: within the attention bar, no non-finite element in the view, every bit outside the view as it was; rows whose mask
-    is zero for every image - a whole row block, and all but one row of the last block - come back bit-identical."""
+    """Every (heads, d) x (images, Tp), and the head sizes 16, 32 and 64 at (3, 5) and (2, 16), at B = 2 x 72 rows, ldq = 2 C, for
+    w = 1, 0.35 and -0.5, by the dispatcher and by every path that takes the shape: within the attention bar, no non-finite element in
+    the view, every bit outside the view as it was; rows whose mask is zero for every image - a whole row block, and all but one row of
+    the last block - come back bit-identical."""
     for w in mc.WEIGHTS:
         for path in (None,) + _paths(mc.Problem("cpu", heads, d, images, Tp, w)):
             prob = mc.Problem(DEV, heads, d, images, Tp, w)

@@ -92,29 +92,7 @@ def measure_paths(dev, Cc, HW, B, T, reps, rounds):
         launch(p, outs[p])
     torch.cuda.synchronize()
     diff = (outs[0].float() - outs[1].float()).abs().max().item() if len(paths) == 2 else 0.0
-    graphs, bufs = {}, {}
-    side = torch.cuda.Stream()
-    for p in paths:
-        bufs[p] = a0.clone()
-        graphs[p] = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side):
-            launch(p, bufs[p])                                         # (warm: the code object is loaded before the capture)
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graphs[p], stream=side):
-                for _ in range(reps):
-                    launch(p, bufs[p])
-    times = {p: [] for p in paths}
-    for r in range(rounds + 1):
-        for p in paths:
-            bufs[p].copy_(a0)                                          # (in place: keep the values where they started)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            graphs[p].replay()
-            e1.record()
-            torch.cuda.synchronize()
-            if r:
-                times[p].append(e0.elapsed_time(e1) * 1e3 / reps)
-    return {p: (statistics.median(t), max(t) - min(t)) for p, t in times.items()}, diff
+    return replay_in_turn({p: (lambda out, p=p: launch(p, out)) for p in paths}, a0, reps, rounds), diff
 
 
 def paths_table(dev, reps, rounds):
