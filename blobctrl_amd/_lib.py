@@ -321,6 +321,13 @@ PAG_SIGNATURES = {
     "bc_pag_scheduler_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# Entry points of include/blobctrl_blend.h (masked edits: the step of a blend plan and the mask at latent resolution).  A table of its
+# own; both are recordable plan ops (BLEND_OPS below), in-process only like the PAG ops.
+BLEND_SIGNATURES = {
+    "bc_blend_scheduler_step": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "bc_blend_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
+
 # Recordable entry points of the plan runtime: name -> BC_OP_* code (include/blobctrl_hip.h).  The argument kinds of an op are derived
 # from its ctypes signature above (stream excluded): p pointer, i int, f float, l long long - the same strings plan.hip checks.
 OPS = {"bc_gemm": 0, "bc_gn_stats": 1, "bc_gn_finalize": 2, "bc_gn_apply_fused": 3, "bc_gn_apply": 4, "bc_layernorm": 5,
@@ -353,6 +360,9 @@ _OP_TABLES_TINY_VAE = (TINY_VAE_OPS,)
 # ... and those of include/blobctrl_pag.h, again an enum of its own behind BC_OP_TINY_VAE_END (59, which stays no op)
 PAG_OPS = {"bc_attention_identity": 60, "bc_pag_scheduler_step": 61}
 _OP_TABLES_PAG = (PAG_OPS,)
+# ... and those of include/blobctrl_blend.h, again an enum of its own behind BC_OP_PAG_END (62, which stays no op)
+BLEND_OPS = {"bc_blend_scheduler_step": 63, "bc_blend_mask": 64}
+_OP_TABLES_BLEND = (BLEND_OPS,)
 OP_SIGNAL, OP_WAIT = 20, 21
 CHAIN_IN, CHAIN_MID, CHAIN_OUT, CHAIN_OUT_FF, CHAIN_OUT_TAIL, CHAIN_MIDX, CHAIN_OUT_FFP = 0, 1, 2, 3, 4, 5, 6
 GN_TOT_WORDS = 6                      # 64-bit words per (image, channel) of a GroupNorm statistics table (include/blobctrl_hip.h)
@@ -361,7 +371,7 @@ _KIND = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l", C.c_c
 
 def op_code(name):
     """BC_OP_* code of a recordable entry point."""
-    for table in _OP_TABLES + _OP_TABLES_BEYOND + _OP_TABLES_TINY_VAE + _OP_TABLES_PAG:
+    for table in _OP_TABLES + _OP_TABLES_BEYOND + _OP_TABLES_TINY_VAE + _OP_TABLES_PAG + _OP_TABLES_BLEND:
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -370,7 +380,8 @@ def op_code(name):
 def op_signature(name):
     """Argument kinds of a recordable entry point without its trailing stream argument."""
     args = (_SIGNATURES.get(name) or REQUEST_SIGNATURES.get(name) or SAM_SIGNATURES.get(name) or SAM_BATCH_SIGNATURES.get(name) or
-            IP_SIGNATURES.get(name) or IP_MASK_SIGNATURES.get(name) or TINY_VAE_SIGNATURES.get(name) or PAG_SIGNATURES[name])[1][:-1]
+            IP_SIGNATURES.get(name) or IP_MASK_SIGNATURES.get(name) or TINY_VAE_SIGNATURES.get(name) or PAG_SIGNATURES.get(name) or
+            BLEND_SIGNATURES[name])[1][:-1]
     return "".join("p" if (a not in _KIND) else _KIND[a] for a in args)
 
 
@@ -409,7 +420,7 @@ def load():
             list(MASK_SIGNATURES.items()) + list(EDIT_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
             list(IP_SIGNATURES.items()) + list(IP_PATH_SIGNATURES.items()) + list(OVERLAY_SIGNATURES.items()) + \
             list(IP_MASK_SIGNATURES.items()) + list(IP_MASK_DIRECT_SIGNATURES.items()) + list(TINY_VAE_SIGNATURES.items()) + \
-            list(TINY_VAE_DIRECT_SIGNATURES.items()) + list(PAG_SIGNATURES.items()):
+            list(TINY_VAE_DIRECT_SIGNATURES.items()) + list(PAG_SIGNATURES.items()) + list(BLEND_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => symbol missing from the build
         fn.restype = res
         fn.argtypes = args

@@ -1,9 +1,19 @@
 // Crop + guidance + scheduler step: the ONE body behind every step entry point (elementwise.hip: bc_cfg_scheduler_step*,
-// bc_scheduler_step_single, bc_scheduler_step_requests; pag.hip: bc_pag_scheduler_step) and the host side they share.
+// bc_scheduler_step_single, bc_scheduler_step_requests; pag.hip: bc_pag_scheduler_step; blend.hip: bc_blend_scheduler_step) and the host side they share.
 #pragma once
 #include "bc_common.h"
 
 namespace {
+
+// The BLEND term of cfg_step_body and the store of latents[i]: *dst = (1 - m) * (a * image + s * bnoise) + m * xn, compiled without
+// contraction - one rounding per written operation - and never inlined (see the call).
+__device__ __noinline__ void blend_store(float* dst, float xn, float a, float s, float image, float bnoise, float m) {
+#pragma clang fp contract(off)
+    const float pa = a * image, ps = s * bnoise;
+    const float p = pa + ps;
+    const float keep = (1.f - m) * p, repaint = m * xn;
+    *dst = keep + repaint;
+}
 
 // Crop (right half) + classifier-free guidance + scheduler step, specialised at compile time.  cf = coef row *step_idx (16 floats; the
 // full column table is at the top of blobctrl_amd/schedulers.py).
@@ -21,12 +31,19 @@ namespace {
 //   PAG:   perturbed-attention guidance (pag_utils.py:_apply_perturbed_attention_guidance): eps holds B more images behind the others,
 //          the perturbed ones, and e += s * (e_cond - e_perturbed) with s = pag_table[step] (fp32 [nsteps]) - with SINGLE on
 //          [cond | perturbed], e = e_c + s * (e_c - e_p); else on [uncond | cond | perturbed], e = e_u + g * (e_c - e_u) + s * (e_c - e_p).
-// `noise` / `nsteps` are not read by an instantiation without NOISE / GUARD, `pag_table` by none without PAG.
-template <bool SINGLE, bool NOISE, bool THIRD, bool GUARD, bool REQ = false, bool PAG = false>
+//   BLEND: a masked edit (the reference stack's pipeline_stable_diffusion_inpaint.py:1272-1285): after the step, noise and third-order
+//          terms included, x_next = (1 - m) * (a * image[i] + s * bnoise[i]) + m * x_next with (a, s) = blend_table[step] (fp32
+//          [nsteps][2]: add_noise to the NEXT timestep) and m = mask[b][yy][xx], one value for the 4 channels.  Rounded operation by
+//          operation as written (no contraction), so m == 0 stores exactly a * image + s * bnoise and m == 1 exactly the step's result.
+// `noise` / `nsteps` are not read by an instantiation without NOISE / GUARD, `pag_table` by none without PAG, the four blend operands by
+// none without BLEND.
+template <bool SINGLE, bool NOISE, bool THIRD, bool GUARD, bool REQ = false, bool PAG = false, bool BLEND = false>
 __device__ __forceinline__ void cfg_step_body(const float* __restrict__ eps, float* __restrict__ latents, const float* __restrict__ coef,
                                               const int* __restrict__ step_idx, float* __restrict__ hist, float guidance, int B, int h,
                                               int w, const float* __restrict__ noise, int nsteps, float* __restrict__ eps_out,
-                                              const float* __restrict__ pag_table = nullptr) {
+                                              const float* __restrict__ pag_table = nullptr, const float* __restrict__ bl_image = nullptr,
+                                              const float* __restrict__ bl_noise = nullptr, const float* __restrict__ bl_mask = nullptr,
+                                              const float* __restrict__ bl_table = nullptr) {
     const int n = B * 4 * h * w;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int step = *step_idx;
@@ -69,6 +86,14 @@ __device__ __forceinline__ void cfg_step_body(const float* __restrict__ eps, flo
     // the optional terms come last, after the history stores: every instantiation is the plain step up to here
     if (NOISE) xn = xn + cf[12] * noise[(size_t)step * n + i];
     if (THIRD) xn = xn + cf[13] * pm1;
+    if (BLEND) {
+        // xn is a finished value here, where the other instantiations store it.  The blend and the store are a call of their own: to
+        // the compiler the step's arithmetic ends in one use of xn, as it does in their store, so it compiles to the same operations
+        // and the m == 1 bits are theirs (inlined, the blend's products regroup the step's and its roundings change)
+        blend_store(latents + i, xn, bl_table[2 * step], bl_table[2 * step + 1], bl_image[i], bl_noise[i],
+                    bl_mask[((size_t)b * h + yy) * w + xx]);
+        return;
+    }
     latents[i] = xn;
 }
 

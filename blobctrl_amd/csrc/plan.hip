@@ -26,6 +26,7 @@
 #include "../../include/blobctrl_ip_mask.h"
 #include "../../include/blobctrl_tiny_vae.h"
 #include "../../include/blobctrl_pag.h"
+#include "../../include/blobctrl_blend.h"
 
 void bc_gemm_set_probe(hipEvent_t e);      // gemm.hip (timing probe between a split-K GEMM's main kernel and its reducer)
 bool bc_gemm_probe_hit();
@@ -67,11 +68,12 @@ namespace {
 inline const char* plan_op_signature(int op) {
     return op == BC_OP_ATTENTION_IP ? "ppppiiiiiiiifp" : op == BC_OP_ATTENTION_IP_MASKED ? "ppppiiiiiiiiifppi" :
            op == BC_OP_TINY_CONV3X3 ? "pppppiiiiiiii" : op == BC_OP_TINY_LATENTS_IN ? "piiip" :
-           op == BC_OP_ATTENTION_IDENTITY ? "ppiiiiii" : op == BC_OP_PAG_SCHEDULER_STEP ? "ppppppiiipiiipi" : op_signature(op);
+           op == BC_OP_ATTENTION_IDENTITY ? "ppiiiiii" : op == BC_OP_PAG_SCHEDULER_STEP ? "ppppppiiipiiipi" :
+           op == BC_OP_BLEND_SCHEDULER_STEP ? "ppppppppppiiipiiipi" : op == BC_OP_BLEND_MASK ? "ppiii" : op_signature(op);
 }
 inline uint32_t plan_op_min_version(int op) {
     return op == BC_OP_ATTENTION_IP || op == BC_OP_ATTENTION_IP_MASKED || op == BC_OP_TINY_CONV3X3 || op == BC_OP_TINY_LATENTS_IN ||
-                   op == BC_OP_ATTENTION_IDENTITY || op == BC_OP_PAG_SCHEDULER_STEP
+                   op == BC_OP_ATTENTION_IDENTITY || op == BC_OP_PAG_SCHEDULER_STEP || op == BC_OP_BLEND_SCHEDULER_STEP || op == BC_OP_BLEND_MASK
                ? kNoFileVersion : op_min_version(op);
 }
 
@@ -211,6 +213,11 @@ int launch_rec(BcPlan* pl, Rec& r, hipStream_t* streams, int nstreams) {
         case BC_OP_PAG_SCHEDULER_STEP:
             return bc_pag_scheduler_step(CP(float, 0), MP(float, 1), CP(float, 2), MP(int, 3), MP(float, 4), CP(float, 5), I(6), I(7), I(8),
                                          CP(float, 9), I(10), I(11), I(12), MP(float, 13), I(14), s);
+        case BC_OP_BLEND_SCHEDULER_STEP:
+            return bc_blend_scheduler_step(CP(float, 0), MP(float, 1), CP(float, 2), MP(int, 3), MP(float, 4), CP(float, 5), CP(float, 6),
+                                           CP(float, 7), CP(float, 8), CP(float, 9), I(10), I(11), I(12), CP(float, 13), I(14), I(15), I(16),
+                                           MP(float, 17), I(18), s);
+        case BC_OP_BLEND_MASK: return bc_blend_mask(CP(unsigned char, 0), MP(float, 1), I(2), I(3), I(4), s);
         case BC_OP_ROWCHAIN:
             return bc_rowchain(I(0), I(1), I(2), I(3), CP(bc_half, 4), CP(float, 5), CP(unsigned long long, 6), CP(float, 7), CP(float, 8), I(9),
                                F(10), CP(bc_half, 11), CP(bc_half, 12), CP(bc_half, 13), I(14), I(15), I(16), CP(bc_half, 17), CP(float, 18),

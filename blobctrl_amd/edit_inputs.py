@@ -113,6 +113,25 @@ def ellipse_masks(ellipses, H, W, device="cuda:0", out=None):
 
 
 @torch.no_grad()
+def edit_region_masks(ops, start_ellipses, target_ellipses, H, W, device="cuda:0"):
+    """The region an edit may repaint, for `pipeline(..., mask_image=)`: per request the union of its start and its target ellipse cover
+    (`ellipse_masks`) -> uint8 [n][H][W], 255 / 0.  A move changes both places; a "remove" (or a request without a target) has only its
+    start."""
+    ops, starts = list(ops), list(start_ellipses)
+    targets = list(target_ellipses) if target_ellipses is not None else [None] * len(ops)
+    if not ops or not (len(starts) == len(targets) == len(ops)):
+        raise ValueError("edit_region_masks: ops, start_ellipses and target_ellipses must have one entry per request, at least one")
+    for op, target in zip(ops, targets):
+        if op != "remove" and op not in EDIT_OPS:
+            raise ValueError(f"unknown edit operation {op!r}")
+        if op != "remove" and target is None:
+            raise ValueError(f"{op} needs a target ellipse")
+    seconds = [s if (op == "remove" or t is None) else t for op, s, t in zip(ops, starts, targets)]
+    cover = ellipse_masks(starts + seconds, H, W, device)
+    return cover[: len(ops)] | cover[len(ops):]
+
+
+@torch.no_grad()
 def paint_ellipses(images, ellipses, colors):
     """bc_ellipse_paint, IN PLACE on `images` uint8 [n][H][W][3] (contiguous): image i takes `ellipses[i][j]` in `colors[i][j]` (r, g, b) for
     j = 0 .. k - 1 in that order - `composite_mask_and_image(ellipse_mask(e), image, color)` k times over - in one launch."""

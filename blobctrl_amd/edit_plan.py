@@ -67,6 +67,11 @@ class PlanSpec:
     buffer `pag_table` (fp32 [nsteps], refilled per edit).  The key holds the prefixes and never the scales: another pag_scale or
     pag_adaptive_scale replays the same plan and the same whole-edit graph.  No CFG-prefix sharing (it pairs images b and b + Bu / 2) and
     no BC_SPLIT_CFG; not with `requests`.  In-process only.
+    blend: a masked edit (pipeline_stable_diffusion_inpaint.py:1272-1285) - after every step the latents outside a mask are the original
+    image's latents noised to the next timestep.  The plan owns the named buffers `blend_image` / `blend_noise` [B][4][h][w], `blend_mask`
+    [B][h][w] and `blend_table` [nsteps][2] (all fp32, refilled per edit), and both step segments end in bc_blend_scheduler_step, which
+    takes `pag_table` too (NULL where the plan has none) and serves every step form.  The key gains "blend" and never the mask or the
+    image: another mask replays the same plan and the same whole-edit graph.  Not with `requests`.  In-process only.
 
     Read from those, once: Bi - images (fg / bg / score / feature sets) behind the batch.  Bu - images the UNet runs: the CFG pair of every
     sample, or the sample alone; with PAG the perturbed copy of the (conditional) sample behind them.  cfg_pairs - images b and b + Bu / 2
@@ -89,10 +94,11 @@ class PlanSpec:
     ip: tuple = ()
     ip_masked: bool = False
     pag: tuple = ()
+    blend: bool = False
 
     def __post_init__(self):
         put = lambda name, v: object.__setattr__(self, name, v)
-        for name in ("per_request", "stochastic", "third_order", "scaled", "single", "freeu", "requests"):
+        for name in ("per_request", "stochastic", "third_order", "scaled", "single", "freeu", "requests", "blend"):
             put(name, bool(getattr(self, name)))
         put("ip", tuple(self.ip or ()))
         put("ip_masked", bool(self.ip and self.ip_masked))
@@ -109,6 +115,9 @@ class PlanSpec:
         if self.pag and self.requests:
             raise NotImplementedError("perturbed-attention guidance with per-request schedules: bc_pag_scheduler_step reads ONE coefficient "
                                       "table and ONE pag_table; run the requests with shared steps, guidance scale, window and eta")
+        if self.blend and self.requests:
+            raise NotImplementedError("a masked edit (blend) with per-request schedules: bc_blend_scheduler_step reads ONE coefficient "
+                                      "table and ONE blend_table; run the requests with shared steps, guidance scale, window and eta")
         if self.stochastic and self.third_order:
             raise NotImplementedError("a third-order step has no noise term (the reference's third-order update has no SDE branch)")
 
@@ -120,14 +129,15 @@ class PlanSpec:
         masked = (("ip", "masked") + self.ip_images,) if self.ip_masked else ()
         pag = (("pag",) + self.pag,) if self.pag else ()
         return (self.B, self.h, self.w, self.T, self.ctx_dim, self.nsteps, self.per_request, self.stochastic) + \
-            tuple(name for name, on in switches if on) + ip + masked + pag
+            tuple(name for name, on in switches if on) + ip + masked + pag + (("blend",) if self.blend else ())
 
     def step_call(self):
         """The entry point a step segment ends in, and what it takes around (B, h, w): (name, arguments between `hist` and `B`, arguments
         between `w` and `eps_out`); a string names a buffer of the plan (NULL where the plan does not own it).  The first row that applies:
-        the PAG, requests and single entry points each serve every step form - noise (or NULL), nsteps, third[, single]."""
+        the blend, PAG, requests and single entry points each serve every step form - noise (or NULL), nsteps, third[, single]."""
         forms = ("variance_noise", self.nsteps, int(self.third_order), int(self.single))
-        calls = ((self.pag, "bc_pag_scheduler_step", ("pag_table",), forms), (self.requests, "bc_scheduler_step_requests", (), forms),
+        blend = ("pag_table", "blend_image", "blend_noise", "blend_mask", "blend_table")
+        calls = ((self.blend, "bc_blend_scheduler_step", blend, forms), (self.pag, "bc_pag_scheduler_step", ("pag_table",), forms), (self.requests, "bc_scheduler_step_requests", (), forms),
                  (self.single, "bc_scheduler_step_single", (), forms[:3]), (self.stochastic, "bc_cfg_scheduler_step_noise", (-1.0,), forms[:2]),
                  (self.third_order, "bc_cfg_scheduler_step3", (-1.0,), (self.nsteps,)), (True, "bc_cfg_scheduler_step", (-1.0,), ()))
         return next(tuple(call) for on, *call in calls if on)
@@ -162,6 +172,9 @@ class EditPlan:
         self.eps_guided = rec.zeros(B, 4, h, w, dtype=f32, name="eps_guided")
         self.variance_noise = rec.zeros(n, B, 4, h, w, dtype=f32, name="variance_noise") if s.stochastic else None
         self.freeu = rec.zeros(4, dtype=f32, name="freeu") if s.freeu else None
+        self.blend_image, self.blend_noise = (rec.zeros(B, 4, h, w, dtype=f32, name=name) if s.blend else None for name in ("blend_image", "blend_noise"))
+        self.blend_mask = rec.zeros(B, h, w, dtype=f32, name="blend_mask") if s.blend else None
+        self.blend_table = rec.zeros(n, 2, dtype=f32, name="blend_table") if s.blend else None
         # rank-1 collapse of the BlobNet feature channels (per-edit weight; round 6: per-IMAGE weights for a batch of independent requests -
         # conv_in then runs as one launch per image, engine.record_collapse)
         self.collapse = F > 3 and "conv_in.featmat" in eng.blob_w.h

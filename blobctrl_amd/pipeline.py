@@ -69,11 +69,11 @@ class EditSetup(namedtuple("EditSetup", "requests tables n stochastic third_orde
     def segments(self):
         return ["step_active" if a else "step_inactive" for a in self.active]
 
-    def plan_spec(self, B, h, w, T, ctx_dim, *, per_request, single, freeu=False, ip=(), ip_masked=False, pag=()):
+    def plan_spec(self, B, h, w, T, ctx_dim, *, per_request, single, freeu=False, ip=(), ip_masked=False, pag=(), blend=False):
         """The PlanSpec of this set-up: the loop length, the step form, the input scaling and the request form are the set-up's, the rest
         is the call's."""
         return PlanSpec(B, h, w, T, ctx_dim, self.n, per_request, self.stochastic, self.third_order, self.scaled, single, freeu,
-                        self.requests, ip, ip_masked, pag)
+                        self.requests, ip, ip_masked, pag, blend)
 
 
 class _PreviewVAE:
@@ -664,6 +664,58 @@ class BlobCtrlEngine(_PreviewVAE):
                                  f"such as 'mid' into prefixes such as 'mid_block.attentions.0.')")
         return layers
 
+    @staticmethod
+    def _blend_on(blend_image_latents, blend_mask, listed=False):
+        """Whether a call is a masked edit: both blend arguments, or neither."""
+        if (blend_image_latents is None) != (blend_mask is None):
+            raise ValueError("blend_image_latents and blend_mask go together: the latents to keep and where to keep them (pass both or neither)")
+        if blend_mask is not None and listed:
+            raise NotImplementedError("a masked edit (blend) with per-request schedules (a list for num_inference_steps, guidance_scale, the "
+                                      "control window, eta or timesteps): bc_blend_scheduler_step reads one coefficient table and one blend_table")
+        return blend_mask is not None
+
+    @staticmethod
+    def _check_blend(image, mask, B, h, w):
+        """The blend arguments of `denoise` against the edit's (B, h, w): image [1 or B][4][h][w]; mask float [1 or B][1 or none][h][w], or
+        uint8 on the device [1 or B][8h][8w].  Returns (image, mask with the optional channel axis dropped)."""
+        if not torch.is_tensor(image) or image.ndim != 4 or image.shape[0] not in (1, B) or tuple(image.shape[1:]) != (4, h, w):
+            raise ValueError(f"blend_image_latents must be a tensor [1 or {B}][4][{h}][{w}], got "
+                             f"{tuple(image.shape) if torch.is_tensor(image) else type(image).__name__}")
+        if not torch.is_tensor(mask):
+            raise ValueError(f"blend_mask must be a tensor, got {type(mask).__name__}")
+        if mask.dtype == torch.uint8:
+            if mask.device.type != "cuda":
+                raise _lib.BlobCtrlHipError("a uint8 blend_mask is reduced to latent resolution on the device (bc_blend_mask): there is no CPU "
+                                            "fallback - pass a device tensor, or a float mask at latent resolution")
+            if mask.ndim != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (8 * h, 8 * w):
+                raise ValueError(f"a uint8 blend_mask must be [1 or {B}][{8 * h}][{8 * w}], got {tuple(mask.shape)}")
+            return image, mask
+        if not mask.is_floating_point():
+            raise ValueError(f"blend_mask must be a float mask at latent resolution or a uint8 device mask at image resolution, not {mask.dtype}")
+        if mask.ndim == 4 and mask.shape[1] == 1:
+            mask = mask[:, 0]
+        if mask.ndim != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (h, w):
+            raise ValueError(f"a float blend_mask must be [1 or {B}][1 or none][{h}][{w}], got {tuple(mask.shape)}")
+        return image, mask
+
+    def _fill_blend(self, P, noise, image, mask, rows):
+        """The per-edit operands of a blend plan, on the engine's (current) stream; one image / mask entry is repeated over the batch."""
+        dev, f32 = self.device, torch.float32
+        P.blend_noise.copy_(noise.to(dev, f32))
+        P.blend_image.copy_(image.to(dev, f32).expand_as(P.blend_image))
+        if mask.dtype == torch.uint8:
+            m = mask.contiguous()
+            n, H, W = m.shape
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.bc_blend_mask(m.data_ptr(), P.blend_mask.data_ptr(), n, H, W, torch.cuda.current_stream(dev).cuda_stream),
+                           "bc_blend_mask")
+            m.record_stream(torch.cuda.current_stream(dev))
+            if n < P.blend_mask.shape[0]:
+                P.blend_mask[1:].copy_(P.blend_mask[:1].expand_as(P.blend_mask[1:]))
+        else:
+            P.blend_mask.copy_(mask.to(dev, f32).expand_as(P.blend_mask))
+        P.blend_table.copy_(rows)
+
     @torch.no_grad()
     def denoise(self, prompt_embeds: torch.Tensor, fg_image_latents: Optional[torch.Tensor] = None,
                  bg_image_latents: Optional[torch.Tensor] = None, gs_score: torch.Tensor = None, dino_feats: Optional[torch.Tensor] = None, num_inference_steps: int = 50,
@@ -677,7 +729,8 @@ class BlobCtrlEngine(_PreviewVAE):
                  variance_noise: Optional[torch.Tensor] = None, timesteps: Optional[List[int]] = None,
                  single_pass: Optional[bool] = None, timestep_cond: Optional[torch.Tensor] = None, freeu=None,
                  ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None, ip_adapter_masks: Optional[List[torch.Tensor]] = None,
-                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=None):
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=None,
+                 blend_image_latents: Optional[torch.Tensor] = None, blend_mask: Optional[torch.Tensor] = None):
         """prompt_embeds [2B, T, D] = cat(negative, positive) (pipe:937-949); fg/bg_image_latents [1,4,h,w] already scaled
         by 0.18215 (pipe:300-309); gs_score [1,2,h,w] = (bg, fg) scores (pipe:974); dino_feats [1,1,F] (pipe:982).
         Instead of the latents, `fg_image` / `bg_image` [1,3,8h,8w] in [-1,1] may be given when the pipeline has a VAE.
@@ -719,6 +772,15 @@ class BlobCtrlEngine(_PreviewVAE):
         [cond | perturbed].  pag_adaptive_scale > 0: the scale of a step at timestep t is max(0, pag_scale - pag_adaptive_scale * (1000 -
         t)).  The scales are per-edit data of the PAG plan.  One setting per call, in a request batch too (per-request schedules and
         lists for these arguments are refused); inactive, the call is the call without these arguments.
+        `blend_image_latents`, `blend_mask` (both or neither): a masked edit, the four-channel inpainting path of the reference stack
+        (pipeline_stable_diffusion_inpaint.py:1272-1285).  After every step the latents where the mask is 0 are replaced by
+        `blend_image_latents` noised to the next timestep with the edit's own start noise (the last step: by the image latents themselves),
+        inside the step launch, so a callback and `teacher_latents` see blended latents.  blend_image_latents [1 or B][4][h][w], scaled
+        like fg / bg_image_latents.  blend_mask: float [1 or B][1 or none][h][w] in [0, 1], 1 = repaint, used as it is (soft values
+        blend); or a uint8 DEVICE mask [1 or B][8h][8w], binarised at 128 and read at the top-left pixel of every 8 x 8 cell
+        (bc_blend_mask: the reference's mask_processor + prepare_mask_latents).  One entry is repeated over the batch, in a request batch
+        too.  Per-edit data of the blend plan: another mask or image replays the same plan and graph.  Refused with per-request schedules
+        and with the Heun scheduler.
         A list (one entry per request) for any of num_inference_steps, guidance_scale, the control window, eta or timesteps (a list of
         lists): the requests of a request batch run their own schedules, on the `requests` plan form.  Both kinds of call are one
         set-up (`_setup` -> EditSetup; a call without lists is "one table, shared by every image"), one plan, one run; `self.timesteps`
@@ -730,6 +792,7 @@ class BlobCtrlEngine(_PreviewVAE):
                               blobnet_control_guidance_start=blobnet_control_guidance_start,
                               blobnet_control_guidance_end=blobnet_control_guidance_end, eta=eta, timesteps=timesteps)
         pag = self._pag_layers(pag_scale, pag_adaptive_scale, pag_applied_layers, bool(listed))
+        blend = self._blend_on(blend_image_latents, blend_mask, bool(listed))
         if not listed:                                           # (a call without lists refuses its eta before anything else)
             self._check_eta(float(eta))
         if output_type not in ("latent", "pt", "np"):
@@ -768,8 +831,11 @@ class BlobCtrlEngine(_PreviewVAE):
                                              pag=bool(pag))
         if ip and ip_adapter_masks is not None:
             ip_adapter_masks = ip_masks.check_masks(ip_adapter_masks, [e if isinstance(e, int) else e[0] for e in ip])
+        if blend:                                                # (shapes, and Heun's refusal, before a plan is recorded)
+            blend_image_latents, blend_mask = self._check_blend(blend_image_latents, blend_mask, B, h, w)
+            blend_rows = S.tables[0].blend_rows()
         P = self._plan(S.plan_spec(B, h, w, T, Dc, per_request=per_request, single=single, freeu=freeu_enabled(freeu), ip=ip,
-                                   ip_masked=ip_adapter_masks is not None, pag=pag))
+                                   ip_masked=ip_adapter_masks is not None, pag=pag, blend=blend))
         dev = self.device
         self.timesteps = [t.timesteps for t in S.tables] if S.requests else S.tables[0].timesteps
         if latents is None:                                                          # pipe:438-453
@@ -790,6 +856,8 @@ class BlobCtrlEngine(_PreviewVAE):
                 ip_masks.fill_plan_masks(P.ip_adapters, ip_adapter_masks, dev)
             if S.stochastic:
                 P.variance_noise.copy_(variance_noise.to(dev, torch.float32))
+            if blend:                                            # (the noise BEFORE init_noise_sigma: prepare_latents' second value)
+                self._fill_blend(P, latents, blend_image_latents, blend_mask, blend_rows)
             P.step_idx.zero_()
             P.hist.zero_()
         if S.requests:
@@ -906,7 +974,8 @@ class BlobCtrlEngine(_PreviewVAE):
 
     def compile_plan(self, path, B, h, w, T, ctx_dim, num_inference_steps, guidance_scale=7.5, blobnet_conditioning_scale=1.0,
                      blobnet_control_guidance_start=0.0, blobnet_control_guidance_end=1.0, eta=0.0, variance_noise=None, timesteps=None,
-                     single_pass=None, freeu=None, pag_scale=0.0, pag_adaptive_scale=0.0, pag_applied_layers=None):
+                     single_pass=None, freeu=None, pag_scale=0.0, pag_adaptive_scale=0.0, pag_applied_layers=None,
+                     blend_image_latents=None, blend_mask=None):
         """Write the launch plan of one edit configuration as a relocatable `.bcplan` file for the C plan runtime
         (include/blobctrl_hip.h: bc_plan_load / bc_plan_buffer / bc_step / bc_plan_capture_loop): segments "prologue",
         "step_active", "step_inactive"; packed weights and the scheduler / guidance tables stored with their contents; the per-edit
@@ -934,6 +1003,9 @@ class BlobCtrlEngine(_PreviewVAE):
         if self._pag_layers(pag_scale, pag_adaptive_scale, pag_applied_layers):
             raise NotImplementedError("a plan with perturbed-attention guidance is recorded and replayed in-process only (bc_attention_identity "
                                       "and bc_pag_scheduler_step are not part of the .bcplan format): run `denoise`")
+        if blend_image_latents is not None or blend_mask is not None:    # (the two blend arguments of `denoise`, taken for the same reason)
+            raise NotImplementedError("a plan of a masked edit (blend) is recorded and replayed in-process only (bc_blend_scheduler_step is "
+                                      "not part of the .bcplan format): run `denoise`")
         if self.ip_adapters:
             raise NotImplementedError("a plan with IP-Adapters loaded is recorded and replayed in-process only (bc_attention_ip is not part of "
                                       "the .bcplan format): unload them, or run `denoise`")
@@ -1548,6 +1620,50 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
         lat = self.engine.encode_latents(image.to(self.device, torch.float32), generator)
         return lat if prompt_embeds is None else lat.repeat(prompt_embeds.shape[0], 1, 1, 1)
 
+    # ---- masked edits: the image and the mask of pipeline_stable_diffusion_inpaint.py (check_inputs, prepare_latents 709-712,
+    # prepare_mask_latents, the mask_processor of its constructor)
+    def _check_blend_inputs(self, image, mask_image, height, width):
+        if (image is None) != (mask_image is None):
+            raise ValueError("`image` and `mask_image` go together: the image to keep and where to keep it (white = repaint). Pass both or "
+                             "neither.")
+        if image is None:
+            return
+        if height % self.vae_scale_factor != 0 or width % self.vae_scale_factor != 0:
+            raise ValueError(f"`height` and `width` have to be divisible by {self.vae_scale_factor} but are {height} and {width}.")
+        if torch.is_tensor(mask_image):                            # (anything else: the mask processor's own type check)
+            if mask_image.dtype != torch.uint8 or mask_image.ndim not in (2, 3) or tuple(mask_image.shape[-2:]) != (height, width):
+                raise ValueError(f"a tensor `mask_image` is a uint8 device mask [H][W] or [n][H][W] of exactly (height, width) = "
+                                 f"{(height, width)}, got {mask_image.dtype} {tuple(mask_image.shape)}")
+        if torch.is_tensor(image) and not _is_device_image(image) and not (image.ndim == 4 and image.shape[1] == 4):
+            raise ValueError(f"a tensor `image` is a uint8 device image [H][W][3] or latents [n][4][h][w], got {image.dtype} {tuple(image.shape)}")
+
+    def prepare_blend_image_latents(self, image, height, width):
+        """The latents a masked edit keeps: a tensor with 4 channels is taken as latents (inpaint:709-712), everything else is encoded."""
+        if torch.is_tensor(image) and not _is_device_image(image):
+            h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+            if tuple(image.shape[2:]) != (h, w):
+                raise ValueError(f"`image` given as latents must be [n][4][{h}][{w}] for height {height} and width {width}, got {tuple(image.shape)}")
+            return image.to(self.device, torch.float32)
+        return self.encode_latents(image, height=height, width=width)
+
+    def prepare_blend_mask(self, mask_image, height, width, batch_size):
+        """`mask_image` as the engine takes it: a device mask as it is ([n][H][W] uint8; bc_blend_mask reduces it), a host mask through
+        the mask_processor and the nearest reduction of prepare_mask_latents -> fp32 [n][1][h][w], 1 = repaint."""
+        if torch.is_tensor(mask_image):
+            if mask_image.device.type != "cuda":
+                raise _lib.BlobCtrlHipError("a tensor `mask_image` is reduced on the device (bc_blend_mask): there is no CPU fallback - pass a "
+                                            "device tensor, a PIL image or a numpy array")
+            mask = mask_image[None] if mask_image.ndim == 2 else mask_image
+        else:
+            from .image_processor import IPAdapterMaskProcessor         # (the settings of the reference's mask_processor)
+            f = self.vae_scale_factor
+            mask = IPAdapterMaskProcessor(vae_scale_factor=f).preprocess(mask_image, height=height, width=width)
+            mask = mask[:, :, ::f, ::f].contiguous()                     # F.interpolate(size=(h, w)), nearest: the top-left pixel of a cell
+        if mask.shape[0] not in (1, batch_size):
+            raise ValueError("The passed mask and the required batch size don't match. Masks are supposed to be duplicated to"
+                             f" a total batch size of {batch_size}, but {mask.shape[0]} masks were passed. Pass one mask, or one per image.")
+        return mask
+
     # ---- pipe:690-703
     def encode_image_dinov2(self, image, device=None):
         if self.dinov2 is None:
@@ -1595,13 +1711,20 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
                  blobnet_control_guidance_start: Union[float, List[float]] = 0.0,
                  blobnet_control_guidance_end: Union[float, List[float]] = 1.0, clip_skip: Optional[int] = None,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: List[str] = ["latents"], return_sample: bool = False,
-                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, image=None, mask_image=None, **kwargs):
         """pipeline_blobnet.py:743-1166 with the same keyword names, defaults and error behaviour.  Returns
         StableDiffusionBlobNetPipelineOutput(images=..., nsfw_content_detected=None) or `(images, None)` for return_dict=False;
         `output_type` "pil" | "np" | "pt" | "latent".  Beyond the reference: `fg_image` / `bg_image` may be uint8 DEVICE tensors [H][W][3] of
         exactly (height, width), as `blobctrl_amd.edit_inputs` builds them; they give the latents the same pixels give as PIL images.
         `pag_scale` / `pag_adaptive_scale`: perturbed-attention guidance as in the reference's PAG pipelines, on the layers of
-        `set_pag_applied_layers` (default "mid"); pag_scale = 0, the default, is the call without it."""
+        `set_pag_applied_layers` (default "mid"); pag_scale = 0, the default, is the call without it.
+        `image` / `mask_image` (both or neither): a masked edit as the reference stack's four-channel inpainting pipeline runs it
+        (pipeline_stable_diffusion_inpaint.py:1272-1285) - where the mask is black the result keeps `image`: after every step those
+        latents are `image`'s latents noised to the next timestep, and at the end `image`'s latents themselves.  `image`: PIL, numpy, a
+        uint8 device tensor [H][W][3] (encoded through `encode_latents`, after fg_image and bg_image), or a tensor with 4 channels, taken
+        as latents (inpaint:709-712).  `mask_image`, white = repaint: PIL or numpy through the reference's mask_processor (resized to
+        (height, width), greyscale, binarised at 0.5) and prepare_mask_latents' nearest reduction; or a uint8 device tensor [H][W] or
+        [n][H][W] of exactly (height, width), reduced on the device (bc_blend_mask) to the same values.  One mask or one per image."""
         callback_steps = kwargs.pop("callback_steps", None)
         if kwargs.pop("callback", None) is not None:
             raise NotImplementedError("`callback` is deprecated in the reference (pipe:868-875): use callback_on_step_end")
@@ -1633,6 +1756,7 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
                           blobnet_control_guidance_end, callback_on_step_end_tensor_inputs)
         if gs_score is None:
             raise ValueError("gs_score is required (pipe:974)")
+        self._check_blend_inputs(image, mask_image, height, width)
         # 2. call parameters (pipe:912-922)
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
@@ -1669,6 +1793,11 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
         # 7. image latents (pipe:970-971): fg first, then bg - the order in which the reference consumes the global generator
         fg_lat = self.encode_latents(fg_image, height=height, width=width)
         bg_lat = self.encode_latents(bg_image, height=height, width=width)
+        # (the image a masked edit keeps is encoded last: every call without one consumes the generator as it always did)
+        blend_kw = {}
+        if mask_image is not None:
+            blend_kw = dict(blend_image_latents=self.prepare_blend_image_latents(image, height, width),
+                            blend_mask=self.prepare_blend_mask(mask_image, height, width, batch_size * num_images_per_prompt))
         # 9. DINOv2 feature of the foreground (pipe:982)
         dino = self.encode_image_dinov2(fg_image)
         # 12. loop (pipe:1025-1123) on the captured plans
@@ -1700,7 +1829,7 @@ class StableDiffusionBlobNetPipeline(_PreviewVAE):
                                     callback_on_step_end=cb, return_sample=return_sample, eta=eta, do_classifier_free_guidance=cfg,
                                     generator=generator, timesteps=timesteps, timestep_cond=timestep_cond,
                                     freeu=getattr(self.unet, "freeu", None), ip_adapter_image_embeds=ip_embeds,
-                                    ip_adapter_masks=ip_adapter_masks, **pag_kw)
+                                    ip_adapter_masks=ip_adapter_masks, **pag_kw, **blend_kw)
         # pipe:1132-1166
         if output_type != "latent":
             if self.vae is None:

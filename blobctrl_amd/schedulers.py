@@ -68,6 +68,22 @@ class _Base:
         alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
         return alpha_t, sigma * alpha_t
 
+    def _blend_pair(self, i):
+        """(a, s) of add_noise(., ., timesteps[i]): sqrt(abar), sqrt(1 - abar) (add_noise of scheduling_ddim.py / scheduling_lcm.py)."""
+        abar = self.alphas_cumprod[self.timesteps[i]]
+        return abar ** 0.5, (1 - abar) ** 0.5
+
+    def blend_rows(self) -> torch.Tensor:
+        """[num_steps, 2] float32 for a masked edit (`bc_blend_scheduler_step`'s blend_table): row i = (a, s) with
+        add_noise(image, noise, timesteps[i + 1]) = a * image + s * noise - what the kept region holds after step i - and the last row
+        (1, 0): the image itself (pipeline_stable_diffusion_inpaint.py:1272-1285)."""
+        n = len(self.timesteps)
+        rows = torch.zeros(n, 2, dtype=torch.float32)
+        for i in range(n - 1):
+            rows[i, 0], rows[i, 1] = self._blend_pair(i + 1)
+        rows[n - 1, 0] = 1.0
+        return rows
+
     def _lam(self, i):                                                    # lambda = log(alpha) - log(sigma) of self.sigmas[i]
         a, s = self._as(self.sigmas[i])
         return torch.log(a) - torch.log(s)
@@ -79,6 +95,9 @@ class UniPCTable(_Base):
     def __init__(self, solver_order=2, **kw):
         super().__init__(**kw)
         assert solver_order == 2, "the coefficient form is written for the reference's solver_order=2 / bh2"
+
+    def _blend_pair(self, i):                                             # (alpha_t, sigma_t) of the interpolated sigma, as its add_noise
+        return self._as(self.sigmas[i])
 
     def set_timesteps(self, n, device=None):
         ts = np.linspace(0, self.num_train - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
@@ -226,6 +245,9 @@ class DPMSolverMultistepTable(_Base):
         self.sde = o["algorithm_type"] == "sde-dpmsolver++"
         self.sigmas = None
         self.num_inference_steps = None
+
+    def _blend_pair(self, i):                                             # (alpha_t, sigma_t) of the interpolated sigma, as its add_noise
+        return self._as(self.sigmas[i])
 
     # ---- scheduling_dpmsolver_multistep.py:306-408
     def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None):
@@ -409,6 +431,9 @@ class _SigmaTable(_Base):
     def _train_sigmas(self):
         return (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy().copy()
 
+    def _blend_pair(self, i):                                             # the latents live in sigma space: image + sigma * noise
+        return 1.0, self.sigmas[i]                                        # (scheduling_euler_discrete.py add_noise)
+
     def _spaced(self, n):                                                 # scheduling_euler_discrete.py:357-381 (the same in all three)
         o = self.options
         if o["timestep_spacing"] == "linspace":
@@ -535,6 +560,12 @@ class HeunTable(_SigmaTable):
     The last evaluation (sigma_next = 0) is a lone first stage, as in the reference."""
     order = 2
     _option_defaults = HEUN_OPTIONS
+
+    def blend_rows(self):
+        raise NotImplementedError("a masked edit (blend) with the Heun scheduler: the reference's second stage takes eps as (sample - x0) / "
+                                  "sigma_next from its own state, independent of the blended sample, while this table expresses that stage "
+                                  "through the current latents (`last`), which the blend changes - use Euler, Euler-ancestral, DDIM, "
+                                  "DPM-Solver++, UniPC or LCM")
 
     def set_timesteps(self, num_inference_steps, device=None):
         n = num_inference_steps

@@ -26,7 +26,9 @@ target ellipses, padded by PAD and grown to the frame's ratio, is blown up to th
 frame, and the result is pasted back over the original through the ellipses' mask blurred with --blur F (`blur`, `apply_overlay`) - all
 on the device; pixels outside the blurred mask keep the original's bytes.
 With --pag-scale S [--pag-layers mid,up_blocks.1] [--pag-adaptive-scale A] the edit runs perturbed-attention guidance (blobctrl_amd.pag): the
-UNet takes a third copy of the sample whose self-attention in the named layers is the identity on V, and eps gains S (eps_cond - eps_perturbed)."""
+UNet takes a third copy of the sample whose self-attention in the named layers is the identity on V, and eps gains S (eps_cond - eps_perturbed).
+With --device-inputs --keep-background the edit is a masked one (include/blobctrl_blend.h): `edit_inputs.edit_region_masks` builds the union
+of the start and target ellipses on the device, and after every step the latents outside it are the untouched frame's, noised to that step."""
 import argparse
 import os
 import sys
@@ -114,6 +116,8 @@ def main():
     ap.add_argument("--ip-image", default=None, help="the image prompt (any file PIL opens); seeded noise without it")
     ap.add_argument("--ip-mask", default=None, metavar="blob|FILE",
                     help="confine the image prompt (with --ip-adapter): 'blob' = the edit's target ellipse, or a mask image of the frame")
+    ap.add_argument("--keep-background", action="store_true",
+                    help="a masked edit (with --device-inputs): only the start and target ellipses are repainted, the rest keeps the input")
     ap.add_argument("--pag-scale", type=float, default=0.0, metavar="S", help="perturbed-attention guidance scale (0 = off; the PAG pipelines use 3.0)")
     ap.add_argument("--pag-layers", default="mid", metavar="IDS", help="comma-separated layer ids as diffusers' set_pag_applied_layers takes them (with --pag-scale)")
     ap.add_argument("--pag-adaptive-scale", type=float, default=0.0, metavar="A", help="the scale falls by A per timestep below 1000 (with --pag-scale)")
@@ -131,6 +135,8 @@ def main():
         ap.error("--device-inputs needs --sam and a click prompt")
     if args.zoom is not None and not args.device_inputs:
         ap.error("--zoom needs --device-inputs")
+    if args.keep_background and not args.device_inputs:
+        ap.error("--keep-background needs --device-inputs (the mask is built from the edit's ellipses on the device)")
     if (args.click or args.sam_auto is not None) and not args.sam:
         ap.error("--click / --sam-auto need --sam")
     if args.click and args.sam_auto is not None:
@@ -276,6 +282,12 @@ def main():
         layers = pag.resolve_layers(pipe.unet_cfg, args.pag_layers.split(","))
         ip_kwargs.update(pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale, pag_applied_layers=layers)
         print(f"--pag-scale {args.pag_scale}: {len(layers)} self-attention layers perturbed, UNet batch 3")
+    if args.keep_background:
+        # a masked edit: only the start and the target ellipse may be repainted; everywhere else every step puts back the untouched
+        # frame's latents, noised to that step (with --zoom the frame is the zoomed one, and the paste-back below finishes the job)
+        region = edit_inputs.edit_region_masks(["move"], [start], [target], R, R)
+        ip_kwargs.update(blend_image_latents=pipe.encode_latents(edit_inputs.vae_input(frame)), blend_mask=region)
+        print(f"--keep-background: {100 * float((region > 127).float().mean()):.1f} % of the frame may be repainted, the rest keeps the input's latents")
     otype = "pt" if args.zoom is not None else "np"           # a zoomed edit's result stays on the device for the paste-back
     img = pipe(prompt, None, None, score, feats, num_inference_steps=args.steps, guidance_scale=7.5,
                generator=torch.Generator().manual_seed(0), blobnet_conditioning_scale=1.0, blobnet_control_guidance_end=0.9,

@@ -2996,6 +2996,108 @@ def golden_pipeline_call_pag():
     print("pipeline_call_pag.npz: %.1f KB" % (os.path.getsize(path) / 1024))
 
 
+# ------------------------------------------------------------------------------------------------ masked edits (latent blend)
+_BLEND_NOISE_MODULES = {"ddim": "diffusers.schedulers.scheduling_ddim", "sde": "diffusers.schedulers.scheduling_dpmsolver_multistep",
+                        "eulera": EULER_A_MODULE, "lcm": LCM_MODULE}
+
+
+def golden_pipeline_call_blend():
+    """tests/golden/pipeline_call_blend.npz: the reference's own `__call__` (pipe:743-1166) on the tiny pipeline of pipeline_call.npz (case
+    `ddim_neg2`, 64 x 64, 3 steps - 5 for DPM-Solver++ 3M, whose table has no third-order row below that - `latents=` given) as a masked edit and as a plain one, per case of tests/blend_common.py BLEND_CASES.  The
+    blend is the inpainting pipeline's (pipeline_stable_diffusion_inpaint.py:1272-1285) with the reference scheduler's own add_noise,
+    applied to what `scheduler.step` returns (pipe:1102).  That is where a callback_on_step_end would apply it - nothing stands between the
+    two - but the reference's callback branch reads names its `__call__` never binds (pipe:1115-1116) and cannot be entered.  Stored per
+    case: the final latents with and without the blend, the timesteps, and of the blended run the guided eps, the sample entering and the
+    blended latents leaving every step, the noise a stochastic step drew and the add_noise coefficients (a, s) of every step.
+    A second file, blend_mask.npz: the reference's mask_processor + prepare_mask_latents reduction of an odd uint8 mask holding bytes 127
+    and 128."""
+    import diffusers as ref_mod
+    from PIL import Image
+    from tests.common import FakeTokenizer, pipeline_cases
+    from tests import blend_common as bc
+    base = np.load(os.path.join(OUT, "pipeline_call.npz"))
+    kw0 = dict(pipeline_cases()["ddim_neg2"])
+    for k in ("scheduler", "seed", "rng_seed"):
+        kw0.pop(k)
+    kw0["num_inference_steps"] = bc.BLEND_STEPS
+    seed, rng_seed = bc.BLEND_SEEDS["seed"], bc.BLEND_SEEDS["rng_seed"]
+    out = {"seed": np.array(seed), "rng_seed": np.array(rng_seed), "num_inference_steps": np.array(bc.BLEND_STEPS), "mask": bc.BLEND_MASK}
+    assert 64 / 3 <= bc.BLEND_MASK.sum() <= 128 / 3 and not np.array_equal(bc.BLEND_MASK, bc.BLEND_MASK.T)
+    unet, blob, vae, te, proc, dino = _tiny_pipeline_components()
+    for case, extra in bc.BLEND_CASES.items():
+        kw = dict(kw0, **{k: v for k, v in extra.items() if k != "scheduler"})
+        batch = len(kw["prompt"]) * kw.get("num_images_per_prompt", 1)
+        lat, image, mask = bc.blend_inputs(batch)
+        for blended in (True, False):
+            sch = bc.make_scheduler(ref_mod, extra["scheduler"], SD_SCHED)
+            pipe = StableDiffusionBlobNetPipeline(vae=vae, unet=unet, tokenizer=FakeTokenizer(), text_encoder=te, blobnet=blob,
+                                                  scheduler=sch, safety_checker=None, dinov2_processor=proc, dinov2=dino,
+                                                  requires_safety_checker=False)
+            pipe.set_progress_bar_config(disable=True)
+            tap = dict(eps=[], x=[], out=[], coef=[])
+            step = sch.step
+
+            def blended_step(model_output, t, sample, *a, _step=step, _sch=sch, **k_):
+                i = len(tap["eps"])
+                prev = _step(model_output, t, sample, *a, **k_)[0]
+                ts = _sch.timesteps
+                proper, row = image, (1.0, 0.0)
+                if i < len(ts) - 1:                                        # inpaint:1272-1285
+                    t_next = ts[i + 1: i + 2]
+                    proper = _sch.add_noise(image, lat, t_next)
+                    one, zero = torch.ones(1, 1, 1, 1), torch.zeros(1, 1, 1, 1)
+                    row = (float(_sch.add_noise(one, zero, t_next)), float(_sch.add_noise(zero, one, t_next)))
+                prev = (1 - mask) * proper + mask * prev
+                for key, v in (("eps", model_output), ("x", sample), ("out", prev)):
+                    tap[key].append(v.detach().clone())
+                tap["coef"].append(row)
+                return (prev,)
+            blended_step.__wrapped__ = step                                # (prepare_extra_step_kwargs inspects the signature for eta / generator)
+            if blended:
+                sch.step = blended_step
+            torch.manual_seed(rng_seed)
+            kind = extra["scheduler"]
+            module = _BLEND_NOISE_MODULES.get(kind) if (kind != "ddim" or extra.get("eta")) else None
+            noise = _TapNoise(module) if module else None
+            if noise:
+                noise.__enter__()
+            try:
+                r = pipe(fg_image=Image.fromarray(base["fg"]), bg_image=Image.fromarray(base["bg"]), gs_score=torch.from_numpy(base["gs_score"]),
+                         height=64, width=64, latents=lat.clone(), generator=torch.Generator().manual_seed(seed), output_type="latent", **kw)
+            finally:
+                if noise:
+                    noise.__exit__()
+            tag = f"{case}_blend" if blended else f"{case}_plain"
+            out[f"{tag}_latents"] = r.images.numpy()
+            if blended:
+                assert len(tap["eps"]) == kw["num_inference_steps"]
+                out[f"{case}_timesteps"] = sch.timesteps.numpy()
+                out[f"{case}_step_eps"], out[f"{case}_step_in"], out[f"{case}_step_out"] = (torch.stack(tap[k_]).numpy() for k_ in ("eps", "x", "out"))
+                out[f"{case}_add_noise"] = np.array(tap["coef"], dtype=np.float32)
+                if noise:
+                    out[f"{case}_step_noise"] = torch.stack(noise.drawn).numpy()
+                keep = (mask == 0).expand_as(image).numpy()
+                assert np.array_equal(out[f"{tag}_latents"][keep], image.numpy()[keep]), case        # exactly the image outside the mask
+        a, b = out[f"{case}_blend_latents"], out[f"{case}_plain_latents"]
+        gap = float(np.abs(a - b).max() / np.abs(b).max()) / 1e-2
+        print(f"pipeline __call__ blend {case}: latents std {a.std():.4f}, blend vs plain {gap:.1f} bars")
+        assert gap >= 10.0, (case, gap)
+    # the mask path: mask_processor (no normalise, binarise, greyscale) + prepare_mask_latents' default-mode F.interpolate
+    from diffusers.image_processor import VaeImageProcessor
+    rng = np.random.Generator(np.random.PCG64(41))
+    m8 = rng.integers(0, 256, (48, 72)).astype(np.uint8)
+    m8[::8, ::8][0, :4] = (127, 128, 0, 255)
+    m8[8, 8], m8[16, 24] = 127, 128
+    proc_m = VaeImageProcessor(vae_scale_factor=8, do_normalize=False, do_binarize=True, do_convert_grayscale=True)
+    full = proc_m.preprocess(Image.fromarray(m8), height=48, width=72)
+    assert (m8[::8, ::8] == 127).any() and (m8[::8, ::8] == 128).any()
+    np.savez_compressed(os.path.join(OUT, "blend_mask.npz"), mask_u8=m8, mask_processed=full.numpy(),
+                        mask_latent=torch.nn.functional.interpolate(full, size=(6, 9)).numpy())
+    path = os.path.join(OUT, "pipeline_call_blend.npz")
+    np.savez_compressed(path, **out)
+    print("pipeline_call_blend.npz: %.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         if sys.argv[1] == "golden_fullsize_loop":             # python tools/make_golden.py golden_fullsize_loop [unipc:1.0 ...]
@@ -3055,6 +3157,7 @@ if __name__ == "__main__":
     golden_blocks_pag()
     golden_unet_pag()
     golden_pipeline_call_pag()
+    golden_pipeline_call_blend()
     print("golden fixtures written to", OUT)
     for f in sorted(os.listdir(OUT)):
         print("  %-24s %8.1f KB" % (f, os.path.getsize(os.path.join(OUT, f)) / 1024))
